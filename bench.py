@@ -14,8 +14,13 @@ environment), or -- when WORLD_SIZE is unset -- bench.py re-executes ITSELF unde
 time; for N > 1 the line carries `collective` (backend, ranks seen in the gathered answers, time of the one all-gather).
 `--dry` replaces the GPU work by a deterministic token pattern (real sharding, barriers, all-gather and JSON; gloo, no GPU):
 the CPU test of the N > 1 control flow.
-The line also carries `roofline` (dominant kernel family, measured with hipEvent pairs around every launch in a
-profiled pass on the launch stream) and, at N=1, `cpu_baseline` (the CPU oracle timed on a bounded sample).
+A plain run only sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the benchmark measures:
+`pcie_inclusive`, `latency_b1`, `runner`, `families` / `roofline` (dominant kernel family, measured with hipEvent pairs around every
+launch in a profiled pass on the launch stream), `side` (other dtypes and configurations) and, at N=1, `cpu_baseline` (the reference's
+modules timed on the host cores on a bounded sample).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32): `answer_tokens` [clips, new_tokens] (the
+greedy answers of all clips, in global clip order) for the full workload, `video_tokens` [clips, rows, 4096] (this rank's projected video
+tokens) for `--workload vision`.  Inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -80,10 +85,42 @@ def parse():
     ap.add_argument("--cpu-frames", type=int, default=4)
     ap.add_argument("--cpu-layers", type=int, default=2)
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the guarded side lines of the default run (`side.fp16`: the reference's dtype, the one the 1e-3 tolerance is stated in; "
+                    help="skip the guarded side lines of the --full run (`side.fp16`: the reference's dtype, the one the 1e-3 tolerance is stated in; "
                          "`side.cfg5_13b_fp8`: BASELINE configs[4] with its own roofline; `side.clips32` when the decoder batches that many)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also run every other measurement: pcie_inclusive, latency_b1, runner, the profiled pass "
+                         "(families, rooflines), the side lines and the CPU baseline (the --no-* switches above leave single ones out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)     # internal: the pinned CPU-baseline subprocess
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32 (token ids are exact: the vocabulary is far below 2^24).  An array larger than its
+    share of DUMP_BUDGET_BYTES is written as a fixed sample of its flattened elements (seed 0), with the flat indices of the sample in
+    DIR/<name>_index.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 12, replace=False))    # 4 bytes of value + 8 of index per element
+            np.save(os.path.join(dirname, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+
+
+def answers_array(answers):
+    """The collated answers (one token-id list per clip, global order) as one [clips, new_tokens] array."""
+    assert all(a is not None for a in answers) and len({len(a) for a in answers}) == 1, "answers of unequal length"
+    return np.asarray(answers, dtype=np.float32)
 
 
 def _interleave_host_memory():
@@ -413,6 +450,8 @@ def main_dry(args):
         elapsed = float(tt[0])
     for i in range(n_global):
         assert answers[i] == dry_pattern(i, NEW, vocab), f"rank {rank}: clip {i} collated wrongly"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"answer_tokens": answers_array(answers)})
     coll, _ = time_collective(parallel, toks, lens, n_global, rank, world, sync)
     coll.update(parallel.collective_identity(dev, rank, world, allow_shared_device=True))      # the same identity record the GPU run carries (no GPUs here: BDFs are null)
     if coll["world_seen"] != args.gpus or coll["ranks_answered"] != args.gpus:
@@ -460,6 +499,9 @@ def main():
     elapsed, vit_ms, own_elapsed = wl.timed(args.steps, args.warmup)
     ms_per_step = elapsed / args.steps * 1e3
     value = n_global * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        out = wl.last_out
+        dump_outputs(args.dump_outputs, {"answer_tokens": answers_array(out)} if args.workload == "full" else {"video_tokens": out.float().cpu().numpy()})
     rank_ms = None
     if world > 1:                                             # every rank's own ms per step: a straggler shows in the one JSON line
         tt = torch.zeros(world, dtype=torch.float64, device=dev)
@@ -467,7 +509,7 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.SUM)
         rank_ms = [float(x) for x in tt.cpu()]
     pcie = None
-    if not args.no_host_frames:                              # same steps, frames handed over as host buffers (the reference's boundary: PIL images on the host)
+    if args.full and not args.no_host_frames:                # same steps, frames handed over as host buffers (the reference's boundary: PIL images on the host)
         host = frames.cpu().pin_memory()
         keep = list(wl.vit_events)
         el, _, _ = wl.timed(args.steps, 1, host_frames=host)
@@ -475,9 +517,9 @@ def main():
         pcie = {"value": n_global * args.steps / el, "unit": "videos/sec", "ms_per_step": el / args.steps * 1e3,
                 "h2d_bytes_per_step_per_gpu": int(host.numel())}
         del host
-    latency = wl.latency_b1() if (not args.no_latency and args.workload == "full" and rank == 0) else None
+    latency = wl.latency_b1() if (args.full and not args.no_latency and args.workload == "full" and rank == 0) else None
     runner = None
-    if not args.no_runner and args.workload == "full" and world == 1:
+    if args.full and not args.no_runner and args.workload == "full" and world == 1:
         try:
             runner = runner_measurement(args, model, tower, video_rows, S, rank, world)
             runner["ratio_to_value"] = runner["videos_per_sec"] / value
@@ -513,7 +555,7 @@ def main():
 
     # ---- profiled pass: hipEvent pairs around every launch of each kernel family, on the launch stream -----------------
     fam, roofline = {}, None
-    if rank == 0 and not args.no_profile_pass:
+    if rank == 0 and args.full and not args.no_profile_pass:
         fam, roofline = wl.profile_pass(ms_per_step)
 
     if rank == 0:
@@ -552,7 +594,7 @@ def main():
             if getattr(wl, "roofline_gemv", None):
                 line["roofline_gemv"] = wl.roofline_gemv
         headline = (args.workload == "full" and args.llm == "7b" and args.weights == "16bit" and args.dtype == "bf16" and S == 224 and world == 1)
-        if headline and not args.no_side:
+        if headline and args.full and not args.no_side:
             # Guarded side lines: driver-timed numbers for the parity-grade dtype and for BASELINE configs[4]; a failure costs
             # only its own field.  The headline models are freed first.
             wl.free()
@@ -573,7 +615,7 @@ def main():
             if side["fp16"].get("value"):
                 side["fp16"]["ratio_to_headline"] = side["fp16"]["value"] / value
             line["side"] = side
-        if args.gpus == 1 and not args.no_cpu_baseline and args.workload == "full":
+        if args.gpus == 1 and args.full and not args.no_cpu_baseline and args.workload == "full":
             try:
                 line["cpu_baseline"] = cpu_baseline_reference(args)
                 line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]

@@ -1,14 +1,15 @@
 #!/bin/bash
-# Full GPU check: test-suite, bench line, rocprofv3 kernel trace of the same bench command (summary -> gpurun_out/full/).
+# Full GPU check: test-suite, the --full bench line, rocprofv3 kernel trace of the same bench command (summaries -> $PGV_OUT_DIR/full/, default out/full/).
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out/full
-timeout 1200 python -m pytest tests -m gpu -x -q > gpurun_out/full/pytest.log 2>&1
-tail -3 gpurun_out/full/pytest.log
-timeout 900 python bench.py --steps 2 --warmup 1 > gpurun_out/full/bench.json 2> gpurun_out/full/bench.err
-tail -c 600 gpurun_out/full/bench.err
-timeout 900 rocprofv3 --kernel-trace --stats -d gpurun_out/full/prof -o bench -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-host-frames --no-latency --no-runner --no-side > gpurun_out/full/bench_under_rocprof.json 2> gpurun_out/full/rocprof.err
-python scripts/rocprof_summary.py gpurun_out/full/prof/bench_results.db > gpurun_out/full/kernel_trace.txt 2>&1
-python scripts/trace_gaps.py gpurun_out/full/prof/bench_results.db > gpurun_out/full/gaps.txt 2>&1
-rm -rf gpurun_out/full/prof      # raw trace (tens of MB) stays on the box: gpurun merges at most 64 MiB back
-head -12 gpurun_out/full/kernel_trace.txt | cut -c1-150
+O="${PGV_OUT_DIR:-out}/full"
+mkdir -p "$O"
+timeout 1200 python -m pytest tests -m gpu -x -q > "$O/pytest.log" 2>&1
+tail -3 "$O/pytest.log"
+timeout 900 python bench.py --full --steps 2 --warmup 1 > "$O/bench.json" 2> "$O/bench.err"
+tail -c 600 "$O/bench.err"
+timeout 900 rocprofv3 --kernel-trace --stats -d "$O/prof" -o bench -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-host-frames --no-latency --no-runner --no-side > "$O/bench_under_rocprof.json" 2> "$O/rocprof.err"
+python scripts/rocprof_summary.py "$O/prof/bench_results.db" > "$O/kernel_trace.txt" 2>&1
+python scripts/trace_gaps.py "$O/prof/bench_results.db" > "$O/gaps.txt" 2>&1
+rm -rf "$O/prof"      # the raw trace is tens of MB: only the summaries are kept
+head -12 "$O/kernel_trace.txt" | cut -c1-150

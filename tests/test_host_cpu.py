@@ -349,6 +349,35 @@ def test_bench_launcher_dry_world_4_8(n):
     assert len(d["collective"].get("rank_ms_per_step", [0] * n)) == n
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs DIR: what the last timed step returned (here the collated answers of both ranks of a --dry run, in global clip order) as
+    float32 .npy; --steps is the number of timed steps the line reports.  An output over its share of the 64 MB budget is written as a fixed
+    seeded sample with its flat indices."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry", "--steps", "4", "--warmup", "0", "--clips-per-gpu", "3",
+           "--new-tokens", "5", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 4 and d["ms_per_step"] > 0
+    from video_llava_amd.benchlib import dry_pattern
+    got = np.load(tmp_path / "out" / "answer_tokens.npy")
+    assert got.dtype == np.float32 and got.tolist() == [dry_pattern(i, 5, 32003) for i in range(6)]
+
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1200)
+    big = np.arange(1000, dtype=np.float64).reshape(10, 100)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"x": big})
+    idx = np.load(tmp_path / "a" / "x_index.npy")
+    val = np.load(tmp_path / "a" / "x.npy")
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and val.dtype == np.float32 and np.array_equal(val, big.reshape(-1)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "x_index.npy"))
+
+
 def test_collective_identity_refuses_shared_devices_and_parses_the_rccl_log(tmp_path, monkeypatch):
     """parallel.collective_identity: two ranks of one host on one GPU are refused unless the caller allows it (bench.py: PGV_BENCH_SHARE_DEVICE=1);
     parallel.rccl_transport: the channel lines of an RCCL INFO log are counted into a P2P / SHM / NET verdict."""
