@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 310
+#define PGV_VERSION 320
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -155,6 +155,13 @@ int pgv_llm_vocab(const pgv_llm *llm);
  * has no quantised path); idempotent. */
 int pgv_llm_quantize_fp8(pgv_ctx *ctx, pgv_llm *llm, void *stream);
 int pgv_llm_is_fp8(const pgv_llm *llm);
+/* bf16 models: once every tensor is loaded, the decode GEMVs stream a lossless 12-bit copy of every decoder matrix and lm_head at batches of
+ * up to 16 sequences (pgv_encode_w12_blocked; a matrix whose exceptions do not fit keeps its 16-bit stream).  Every weight load or
+ * vocabulary resize rebuilds the copy; pgv_llm_quantize_fp8 drops it.  Tokens and logits are bitwise those of the 16-bit stream.
+ * pgv_llm_set_weight_stream(llm, 0) streams the 16-bit matrices, 1 (the default) the 12-bit copies where they exist.
+ * pgv_llm_weight_stream_bytes: the weight bytes one decode token step streams at `batch` sequences (matrices + lm_head + side data). */
+int pgv_llm_set_weight_stream(pgv_llm *llm, int use12);
+int64_t pgv_llm_weight_stream_bytes(const pgv_llm *llm, int batch);
 /* Read a decoder matrix ("model.layers.N.{self_attn.{q,k,v,o}_proj,mlp.{gate,up,down}_proj}.weight", "lm_head.weight") back as
  * row-major fp32 [rows, cols] in its HF orientation: the values the path computes with (after quantisation: dequantised). */
 int pgv_llm_get_weight(pgv_ctx *ctx, pgv_llm *llm, const char *name, float *d_out, void *stream);
@@ -257,6 +264,16 @@ int pgv_quantize_fp8_blocked(pgv_ctx *ctx, int dtype, void *d_w16_blocked, void 
 /* pgv_gemv on the fp8 copy: bit-identical to pgv_gemv on the dequantised 16-bit matrix, half the weight bytes.  modes 0..3. */
 int pgv_gemv_fp8(pgv_ctx *ctx, int dtype, int mode, const void *d_W8, const float *d_scales, const void *d_x, int ldx, void *d_out, int ldo,
                  int N, int K, int B, void *stream);
+/* Lossless 12-bit copy of a blocked bf16 matrix [N, K] (N % 16 == 0, K % 64 == 0) for the decode GEMVs: low byte of every weight kept, sign +
+ * 3-bit exponent offset below a per-row base as a 4-bit code, the weights that do not fit listed per 16-row block (at most 64 each) and
+ * patched back in registers.  d_w12 holds pgv_w12_bytes(N, K) bytes; d_counts [N / 16] receives the exception count of every row block --
+ * the copy is usable iff none exceeds 64.  Layout: video_llava_amd/csrc/w12.h. */
+size_t pgv_w12_bytes(int N, int K);
+int pgv_encode_w12_blocked(pgv_ctx *ctx, int dtype, const void *d_w16_blocked, void *d_w12, int *d_counts, int N, int K, void *stream);
+/* pgv_gemv on the 12-bit copy: bitwise equal to pgv_gemv on the bf16 matrix it was encoded from, 3/4 of the weight bytes.  modes 0..3, B <= 16;
+ * N = the encoded row count (or fewer, mode 3). */
+int pgv_gemv_w12(pgv_ctx *ctx, int dtype, int mode, const void *d_W12, const void *d_x, int ldx, void *d_out, int ldo, int N, int K, int B,
+                 void *stream);
 int pgv_layernorm(pgv_ctx *ctx, int dtype, const float *d_x, const float *d_gamma, const float *d_beta, float eps,
                   void *d_y, int rows, int cols, void *stream);
 int pgv_rmsnorm(pgv_ctx *ctx, int dtype, const float *d_x, const float *d_gamma, float eps, void *d_y, int rows, int cols,

@@ -332,9 +332,8 @@ class Workload:
         model, prompts, dev = self.model, self.prompts, self.dev
         cfg = model.config
         H, I, L, V = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, model.vocab_size
-        wb = 1.0 if model.is_fp8 else 2.0
-        n_w = L * (4.0 * H * H + 3.0 * H * I) + float((V + 15) // 16 * 16) * H
-        weight_bytes = n_w * wb + (L * (4.0 * H + 2.0 * I + H) + V) * 4.0 * (1.0 if model.is_fp8 else 0.0)      # + per-row fp32 scales of the fp8 copies
+        # the weight bytes the decode actually streams at this batch (16-bit, the lossless 12-bit copies of a bf16 model, or e4m3 + per-row scales)
+        weight_bytes = float(model.ctx.lib.pgv_llm_weight_stream_bytes(model.handle, len(prompts)))
         pooled = self.vision(self.frames)
         kv, nxt, _ = model.prefill(prompts, pooled, max(len(p) for p in prompts) + 3 * tokens + 16)
         model.decode_greedy(kv, nxt, 8)                              # eager warm-up, then graph capture

@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "llm_internal.h"
+#include "w12.h"
 
 namespace {
 
@@ -43,6 +44,8 @@ struct GemvArgs {
     // load path than its weights (512 KB against 393 KB for qkv); with row-major rows the loads alone took 26 us of the 38 us qkv launch
     // (x-only ablation, LAB.md), blocked 19.  xblk: x is blocked; xgblk: the producer writes xg blocked.
     int xblk, xgblk;
+    // W12 = true: W is the unit plane of the 12-bit copy (w12.h), with its row blocks' exception lists and row bases
+    const unsigned* w12exc; const unsigned char* w12base;
 #ifdef PGV_LAB
     int abl;           // lab builds only (PGV_GEMV_ABLATE; results are garbage): 1 = no x loads in the K loop, 2 = no MFMA, 4 = no weight loads
 #endif
@@ -99,17 +102,22 @@ __device__ __forceinline__ typename T::v8 fp8x8_to_v8(unsigned lo, unsigned hi) 
 // register-buffer depth (64-column groups per buffer): one row block per workgroup buffers 2 groups, 2 - 3 row blocks 1; an fp8 group is one 16-byte
 // load per lane and row block where a 16-bit group is two, so the fp8 variants buffer twice as many groups for the same bytes in flight; batches
 // beyond one MFMA tile keep one group per buffer (the x fragments of CT tiles fill the registers)
+// (12-bit weights: the 16-bit depths -- a group is 1.5 KiB instead of 2, a quarter fewer bytes in flight per buffer)
 constexpr int gemv_pu(int tl, bool w8, int ct) { return (ct > 1 || tl >= 6) ? 1 : (tl == 1 ? 2 : 1) * (w8 ? 2 : 1); }
 constexpr int kGemvWaves = 8;          // waves per workgroup = K phases of a row block (the arithmetic of every launch shape is defined on these 8 chains)
 
-template <typename T, int MODE, bool W8, int TL, bool X2, int CT = 1>
+// W12 (one column tile): the 12-bit copy (w12.h) -- per unit and row block one 16-byte load of low bytes and one 8-byte load of codes per lane,
+// the high bytes rebuilt with packed byte arithmetic, the rare exceptions patched in (wave-uniform branch), and the two 16-bit A fragments
+// assembled with v_perm_b32: the MFMAs see the 16-bit operands, so the result is bitwise the 16-bit kernel's.
+template <typename T, int MODE, bool W8, int TL, bool X2, int CT = 1, bool W12 = false>
 __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) {
     constexpr int NW = kGemvWaves, PU = gemv_pu(TL, W8, CT);
     constexpr int TILES = TL;
     static_assert(!X2 || CT == 1, "the merged x load uses the lanes of columns 8..15");
     // HS (six row blocks and more): the weight stream is pipelined in HALF groups (one 32-column k-block per register buffer) -- a whole group of
     // six row blocks x four column tiles would not fit the register file next to its 96 accumulator registers.  Same order of the MFMAs.
-    constexpr bool HS = (TL >= 6) && !W8;
+    static_assert(!W12 || (!W8 && CT == 1 && T::id == PGV_BF16), "12-bit weights: bf16, one column tile");
+    constexpr bool HS = (TL >= 6) && !W8 && !W12;
     static_assert(!HS || (!W8 && PU == 1 && !X2), "half-group pipelining: 16-bit weights, one group per buffer");
     // HS8: the same for fp8 weights.  An fp8 group (64 columns) is ONE 16-byte load per lane and row block, so the weights are buffered per group and
     // only the x fragments per k-block: 2 x (TL + CT) x 4 buffer registers instead of 2 x (TL + 2 CT) x 4.  Same order of the MFMAs.
@@ -329,11 +337,34 @@ __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) 
         constexpr int j_lo = 0;
         const int gpw = (j_end - j_lo + NW - 1) / NW;
         const int nb = (gpw + PU - 1) / PU;
-        using wreg_t = typename std::conditional<W8, u32x4_t, typename T::v8>::type;
-        constexpr int WH = W8 ? 1 : 2;                            // weight loads per group and row block
+        using wreg_t = typename std::conditional<W8 || W12, u32x4_t, typename T::v8>::type;
+        constexpr int WH = (W8 || W12) ? 1 : 2;                   // weight loads per group and row block (12-bit: + the code load)
         const char* wp[TILES];
 #pragma unroll
-        for (int t = 0; t < TILES; ++t) wp[t] = p.W + ((size_t)rb[t] * (W8 ? (p.K >> 6) : kblocks)) * 1024 + lane * 16;
+        for (int t = 0; t < TILES; ++t) wp[t] = p.W + ((size_t)rb[t] * (W8 ? (p.K >> 6) : kblocks)) * (W12 ? 768 : 1024) + lane * 16;
+        // 12-bit: row base (4 bytes), this lane's exception entry of each row block, its group index
+        unsigned b4[W12 ? TILES : 1], ex[W12 ? TILES : 1], exg[W12 ? TILES : 1];
+        u32x2_t ca[PU][W12 ? TILES : 1] = {}, cb[PU][W12 ? TILES : 1] = {};
+        if constexpr (W12) {
+#pragma unroll
+            for (int t = 0; t < TILES; ++t) {
+                b4[t] = (unsigned)p.w12base[rb[t] * 16 + l15] * 0x01010101u;
+                ex[t] = p.w12exc[(size_t)rb[t] * kW12MaxExc + lane];
+                exg[t] = ex[t] >> 18;
+            }
+        }
+        auto cload = [&](u32x2_t (&cf)[PU][W12 ? TILES : 1], int b) {
+            if constexpr (W12) {
+#pragma unroll
+                for (int u = 0; u < PU; ++u) {
+                    const int g = min(j_lo + w + NW * (b * PU + u), j_end - 1);
+                    if (!GV_ABL(p, 4)) {
+#pragma unroll
+                        for (int t = 0; t < TILES; ++t) cf[u][t] = __builtin_nontemporal_load((const u32x2_t*)(wp[t] + (size_t)g * 1536 + 1024 - lane * 8));
+                    }
+                }
+            }
+        };
         constexpr int XH = X2 ? 1 : 2;                            // x loads per group
         const unsigned xvo2 = (l15 & 7) < p.B ? (unsigned)(((size_t)(l15 & 7) * p.ldx + (l15 >> 3) * 32 + kg * 8) * 2) : 0x80000000u;
         auto load = [&](wreg_t (&wf)[PU][WH][TILES], typename T::v8 (&xf)[PU][XH][CT], int b) {
@@ -343,10 +374,10 @@ __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) 
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int kb = min(2 * g + h, kb_end - 1);
-                    if ((!W8 || h == 0) && !GV_ABL(p, 4)) {
+                    if ((WH == 2 || h == 0) && !GV_ABL(p, 4)) {
 #pragma unroll
                         for (int t = 0; t < TILES; ++t)
-                            wf[u][W8 ? 0 : h][t] = __builtin_nontemporal_load((const wreg_t*)(wp[t] + (size_t)(W8 ? min(g, j_end - 1) : kb) * 1024));
+                            wf[u][WH == 1 ? 0 : h][t] = __builtin_nontemporal_load((const wreg_t*)(wp[t] + (W12 ? (size_t)min(g, j_end - 1) * 1536 : (size_t)(W8 ? min(g, j_end - 1) : kb) * 1024)));
                     }
                     if (GV_ABL(p, 1)) continue;
                     if constexpr (!X2) {
@@ -357,7 +388,7 @@ __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) 
                 }
             }
         };
-        auto mma = [&](wreg_t (&wf)[PU][WH][TILES], typename T::v8 (&xf)[PU][XH][CT], int b, bool last) {
+        auto mma = [&](wreg_t (&wf)[PU][WH][TILES], u32x2_t (&cf)[PU][W12 ? TILES : 1], typename T::v8 (&xf)[PU][XH][CT], int b, bool last) {
 #pragma unroll
             for (int u = 0; u < PU; ++u) {
                 const int g = j_lo + w + NW * (b * PU + u);
@@ -382,11 +413,20 @@ __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) 
                         for (int ct = 0; ct < CT; ++ct) xv[h][ct] = (2 * g + h >= kb_end) ? z : xv[h][ct];
                 }
 #pragma unroll
-                for (int t = 0; t < TILES; ++t)
+                for (int t = 0; t < TILES; ++t) {
+                    unsigned hi[4] = {0u, 0u, 0u, 0u};
+                    if constexpr (W12) {
+                        const int gc = min(g, j_end - 1);
+                        w12_high_bytes(cf[u][t], b4[t], hi);
+                        w12_patch(ex[t], exg[t], (unsigned)gc, lane, hi);
+                        // a group past the end re-reads the last one: as the 16-bit kernel, against its second k-block twice
+                        if (last && g >= j_end) { hi[0] = hi[2]; hi[1] = hi[3]; wf[u][0][t][0] = wf[u][0][t][2]; wf[u][0][t][1] = wf[u][0][t][3]; }
+                    }
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         typename T::v8 wv;
                         if constexpr (W8) wv = fp8x8_to_v8<T>(wf[u][0][t][2 * h], wf[u][0][t][2 * h + 1]);      // widened once, used by every column tile
+                        else if constexpr (W12) wv = w12_kblock<typename T::v8>(wf[u][0][t], hi, h);
                         else wv = wf[u][h][t];
                         if (GV_ABL(p, 2)) {
 #pragma unroll
@@ -396,29 +436,30 @@ __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) 
 #pragma unroll
                         for (int ct = 0; ct < CT; ++ct) acc[t][ct] = T::mfma16(wv, xv[h][ct], acc[t][ct]);
                     }
+                }
             }
         };
         wreg_t wa[PU][WH][TILES] = {}, wb[PU][WH][TILES] = {};
         typename T::v8 xa[PU][XH][CT] = {}, xb[PU][XH][CT] = {};
-        load(wa, xa, 0);
+        load(wa, xa, 0); cload(ca, 0);
         int i = 0;
         for (; i + 2 < nb; i += 2) {
-            load(wb, xb, i + 1);
+            load(wb, xb, i + 1); cload(cb, i + 1);
             __builtin_amdgcn_sched_barrier(0);
-            mma(wa, xa, i, false);
+            mma(wa, ca, xa, i, false);
             __builtin_amdgcn_sched_barrier(0);
-            load(wa, xa, i + 2);
+            load(wa, xa, i + 2); cload(ca, i + 2);
             __builtin_amdgcn_sched_barrier(0);
-            mma(wb, xb, i + 1, false);
+            mma(wb, cb, xb, i + 1, false);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (nb - i == 2) {
-            load(wb, xb, i + 1);
+            load(wb, xb, i + 1); cload(cb, i + 1);
             __builtin_amdgcn_sched_barrier(0);
-            mma(wa, xa, i, false);
-            mma(wb, xb, i + 1, true);
+            mma(wa, ca, xa, i, false);
+            mma(wb, cb, xb, i + 1, true);
         } else {
-            mma(wa, xa, i, true);
+            mma(wa, ca, xa, i, true);
         }
     }
     if (SSQ_LATE && scaled) {
@@ -801,29 +842,44 @@ static int lab_switch(const char* name, int dflt) {
 
 using gemv_launch_fn = int (*)(int dtype, int grid, const GemvArgs& a, hipStream_t s);
 
-template <int MODE, bool W8, int TL, bool X2, int CT>
+template <int MODE, bool W8, int TL, bool X2, int CT, bool W12 = false>
 static int launch_variant(int dtype, int grid, const GemvArgs& a, hipStream_t s) {
-    PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gemv_mfma_kernel<T, MODE, W8, TL, X2, CT>), dim3(grid), dim3(kGemvWaves * 64), 0, s, a));
+    if constexpr (W12) {
+        PGV_CHECK(dtype == PGV_BF16, "gemv: the 12-bit weight stream is bf16 only");
+        hipLaunchKernelGGL((gemv_mfma_kernel<TBF16, MODE, false, TL, X2, CT, true>), dim3(grid), dim3(kGemvWaves * 64), 0, s, a);
+    } else {
+        PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gemv_mfma_kernel<T, MODE, W8, TL, X2, CT>), dim3(grid), dim3(kGemvWaves * 64), 0, s, a));
+    }
     return PGV_OK;
 }
 
-template <int MODE, bool W8, int TL, int CT>
+template <int MODE, bool W8, int TL, int CT, bool W12 = false>
 constexpr gemv_launch_fn x2_variant() {          // the merged x load (B <= 8) uses the lanes of batch columns 8..15: one column tile only, not the half-group pipeline
-    if constexpr (CT == 1 && TL < 6) return &launch_variant<MODE, W8, TL, true, 1>;
+    if constexpr (CT == 1 && TL < 6) return &launch_variant<MODE, W8, TL, true, 1, W12>;
     else return nullptr;
 }
 
+template <int MODE, int TL, int CT>
+constexpr gemv_launch_fn w12_variant() {
+    if constexpr (CT == 1) return &launch_variant<MODE, false, TL, false, 1, true>;
+    else return nullptr;
+}
+
+enum { WF_16 = 0, WF_FP8 = 1, WF_12 = 2 };      // weight formats of the decode GEMVs
 struct GemvShape {
     int mode, tl, ct;
-    gemv_launch_fn fn[2][2];                     // [fp8 weights][merged x load]
+    gemv_launch_fn fn[3][2];                     // [weight format][merged x load]
 };
 template <int MODE, int TL, int CT>
 constexpr GemvShape gemv_shape() {
+    // 12-bit weights: one column tile (the main loop of the 16-row kernel, also at six and more row blocks)
+    constexpr gemv_launch_fn w12 = w12_variant<MODE, TL, CT>();
     if constexpr (TL >= 6)                       // six row blocks and more: no merged x load (half-group pipelining for 16-bit weights; an fp8 group is ONE load per lane: whole groups)
-        return {MODE, TL, CT, {{&launch_variant<MODE, false, TL, false, CT>, nullptr}, {&launch_variant<MODE, true, TL, false, CT>, nullptr}}};
+        return {MODE, TL, CT, {{&launch_variant<MODE, false, TL, false, CT>, nullptr}, {&launch_variant<MODE, true, TL, false, CT>, nullptr}, {w12, nullptr}}};
     else
         return {MODE, TL, CT, {{&launch_variant<MODE, false, TL, false, CT>, x2_variant<MODE, false, TL, CT>()},
-                               {&launch_variant<MODE, true, TL, false, CT>, x2_variant<MODE, true, TL, CT>()}}};
+                               {&launch_variant<MODE, true, TL, false, CT>, x2_variant<MODE, true, TL, CT>()},
+                               {w12, x2_variant<MODE, false, TL, CT, true>()}}};
 }
 static const GemvShape kGemvShapes[] = {
     // one MFMA tile of sequences (B <= 16)
@@ -939,7 +995,7 @@ static GemvChoice choose_gemv(int mode, bool w8, int B, int grid, int K, int num
 }
 
 int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void* x, int ldx, void* out, int ldo, int N, int K, int B, hipStream_t s,
-                    const float* wscale, const GemvNorm* norm) {
+                    const float* wscale, const GemvNorm* norm, const W12Ref* w12) {
     PGV_CHECK(B >= 1 && B <= 64, "gemv: batch %d outside [1,64]", B);
     PGV_CHECK(K % 32 == 0, "gemv: K=%d must be a multiple of 32", K);
     PGV_CHECK(mode == GV_STORE16 || mode == GV_RESID || mode == GV_SWIGLU || mode == GV_F32 || mode == GV_RESIDNORM, "gemv: bad mode %d", mode);
@@ -947,7 +1003,7 @@ int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void
     GemvArgs a;
     a.W = (const char*)W; a.x = (const char*)x; a.out = (char*)out; a.N = N; a.K = K; a.B = B; a.ldx = ldx; a.ldo = ldo; a.wscale = wscale;
     a.ssq_in = nullptr; a.nparts_in = 0; a.inv_h = 0.f; a.eps = 0.f; a.gamma = nullptr; a.xg = nullptr; a.ssq_out = nullptr; a.amax_val = nullptr; a.amax_idx = nullptr;
-    a.ssq_ts = 0; a.amax_ts = 0; a.lds_bytes = 0; a.xblk = 0; a.xgblk = 0;
+    a.ssq_ts = 0; a.amax_ts = 0; a.lds_bytes = 0; a.xblk = 0; a.xgblk = 0; a.w12exc = nullptr; a.w12base = nullptr;
 #ifdef PGV_LAB
     a.abl = lab_switch("PGV_GEMV_ABLATE", 0);
     if (B > 16 && lab_switch("PGV_GEMV_XBLK", 0) != 0) a.xblk = 1;      // lab: the caller hands over x in the blocked layout (scripts/microbench.py gemvwide)
@@ -970,6 +1026,19 @@ int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void
     if (mode == GV_SWIGLU) { PGV_CHECK(N % 64 == 0, "gemv swiglu: N=%d must be a multiple of 64", N); grid = N / 32; }
     else { if (mode != GV_F32) PGV_CHECK(N % 16 == 0, "gemv: N=%d must be a multiple of 16", N); grid = (N + 15) / 16; }
     const GemvChoice c = choose_gemv(mode, w8, B, grid, K, ctx->num_cu, norm && norm->k8_part);
+    // the 12-bit copy replaces W at one column tile (w12.h); beyond, the 16-bit matrix is streamed (the same products in the same order)
+    const bool use12 = w12 && w12->buf && !w8 && c.ct == 1 && !c.k8;
+    if (w12 && w12->buf) {
+        PGV_CHECK(!w8 && dtype == PGV_BF16 && K % 64 == 0 && w12->rows % 16 == 0 && w12->rows >= ((N + 15) & ~15), "gemv: bad 12-bit weight copy (%lld rows for N = %d, K = %d)",
+                  w12->rows, N, K);
+        PGV_CHECK(use12 || W != nullptr, "gemv: %d sequences need the 16-bit matrix (the 12-bit copy serves one column tile)", B);
+    }
+    if (use12) {
+        a.W = (const char*)w12->buf;
+        a.w12exc = (const unsigned*)((const char*)w12->buf + pgv_w12_units_bytes(w12->rows, K));
+        a.w12base = (const unsigned char*)w12->buf + pgv_w12_units_bytes(w12->rows, K) + pgv_w12_exc_bytes(w12->rows);
+    }
+    const int wf = use12 ? WF_12 : (w8 ? WF_FP8 : WF_16);
     pgv_prof_begin(ctx, 3, s);
     if (c.k8) {
 #ifdef PGV_LAB
@@ -982,11 +1051,11 @@ int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void
             if (g.mode == mode && g.tl == c.tl && g.ct == c.ct) { shape = &g; break; }
         PGV_CHECK(shape != nullptr, "gemv: no kernel for mode %d with %d row blocks x %d column tiles", mode, c.tl, c.ct);
         const int tiles_per_wg = mode == GV_SWIGLU ? c.tl / 2 : c.tl;       // SwiGLU: the grid counts (gate, up) pairs
-        gemv_launch_fn fn = shape->fn[w8][c.x2 && c.ct == 1];
-        PGV_CHECK(fn != nullptr, "gemv: mode %d with %d row blocks x %d column tiles has no %s kernel", mode, c.tl, c.ct, w8 ? "fp8" : "16-bit");
+        gemv_launch_fn fn = shape->fn[wf][c.x2 && c.ct == 1];
+        PGV_CHECK(fn != nullptr, "gemv: mode %d with %d row blocks x %d column tiles has no %s kernel", mode, c.tl, c.ct, wf == WF_12 ? "12-bit" : (w8 ? "fp8" : "16-bit"));
         PGV_TRY(fn(dtype, (grid + tiles_per_wg - 1) / tiles_per_wg, a, s));     // (only the three-pair SwiGLU shape can leave a ragged last workgroup)
     }
-    pgv_prof_end(ctx, 3, s, 2.0 * B * (double)N * K, (w8 ? 1.0 : 2.0) * (double)N * K);
+    pgv_prof_end(ctx, 3, s, 2.0 * B * (double)N * K, (w8 ? 1.0 : (use12 ? 1.5 : 2.0)) * (double)N * K);
     return PGV_OK;
 }
 
@@ -1003,6 +1072,15 @@ extern "C" int pgv_pack_blocked(pgv_ctx* ctx, int dtype, const void* d_src, int 
     PackDst d;
     d.ptr = d_dst; d.dst_dtype = dtype; d.rows = rows; d.cols = cols; d.dst_stride = cols; d.blocked = true;
     return pgv_pack_tensor(d, d_src, dtype, 1, (hipStream_t)stream);
+}
+
+extern "C" int pgv_gemv_w12(pgv_ctx* ctx, int dtype, int mode, const void* d_W12, const void* d_x, int ldx, void* d_out, int ldo, int N, int K, int B,
+                            void* stream) {
+    PGV_CHECK(ctx && d_W12 && d_x && d_out, "pgv_gemv_w12: null argument");
+    PGV_CHECK(mode >= GV_STORE16 && mode <= GV_F32, "pgv_gemv_w12: mode %d outside [0,3]", mode);
+    PGV_CHECK(B >= 1 && B <= 16, "pgv_gemv_w12: batch %d outside [1,16]", B);
+    W12Ref r; r.buf = d_W12; r.rows = (N + 15) & ~15;
+    return pgv_launch_gemv(ctx, dtype, mode, nullptr, d_x, ldx, d_out, ldo, N, K, B, (hipStream_t)stream, nullptr, nullptr, &r);
 }
 
 extern "C" int pgv_gemv_fp8(pgv_ctx* ctx, int dtype, int mode, const void* d_W8, const float* d_scales, const void* d_x, int ldx, void* d_out, int ldo, int N,

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "llm_internal.h"
+#include "w12.h"
 #include "weights.h"
 
 constexpr int kMaxPos = 4096;   // max_position_embeddings of LLaVA-1.5 / Vicuna-1.5
@@ -16,6 +17,8 @@ struct LlmLayer {
     // fp8 decode copies (pgv_llm_quantize_fp8): e4m3 blocked matrices + per-row power-of-two scales; null until quantised
     void *q_wqkv = nullptr, *q_wo = nullptr, *q_wgu = nullptr, *q_wdown = nullptr;
     float *s_wqkv = nullptr, *s_wo = nullptr, *s_wgu = nullptr, *s_wdown = nullptr;
+    // lossless 12-bit decode copies of bf16 models (w12.h; buf null: none, or the matrix keeps its 16-bit stream)
+    W12Ref z_wqkv, z_wo, z_wgu, z_wdown;
 };
 
 struct pgv_llm {
@@ -34,6 +37,9 @@ struct pgv_llm {
     char* blob8 = nullptr;   // fp8 copies + scales (decode weight stream halves; the 16-bit copies hold the dequantised values)
     void* q_head = nullptr; float* s_head = nullptr;
     bool fp8 = false;
+    char* blob12 = nullptr;  // 12-bit copies (bf16 models): built once every tensor is loaded, rebuilt by every later weight write
+    W12Ref z_head;
+    bool use12 = true;       // pgv_llm_set_weight_stream
     int generation = 0;      // bumped by every call that changes what a captured decode graph baked in (vocabulary size, weight pointers)
 };
 
@@ -116,10 +122,99 @@ extern "C" void pgv_llm_destroy(pgv_llm* llm) {
     if (!llm) return;
     if (llm->blob) (void)hipFree(llm->blob);
     if (llm->blob8) (void)hipFree(llm->blob8);
+    if (llm->blob12) (void)hipFree(llm->blob12);
     delete llm;
 }
 
 extern "C" int pgv_llm_missing(const pgv_llm* llm) { return llm ? llm->expected - (int)llm->loaded.size() : -1; }
+
+// ---------------------------------------------------------------------------------------------
+// 12-bit decode copies (bf16 models, w12.h): what the decode GEMVs stream at batches of up to 16 sequences
+// ---------------------------------------------------------------------------------------------
+struct W12Slot { const void* w16; W12Ref* ref; long long N, K; size_t off; };
+static std::vector<W12Slot> w12_slots(pgv_llm* m, size_t* total) {
+    const long long H = m->cfg.hidden, I = m->cfg.inter, V = m->vocab_cap;
+    std::vector<W12Slot> v;
+    size_t off = 0;
+    auto add = [&](const void* w, W12Ref* r, long long N, long long K) { v.push_back({w, r, N, K, off}); off += pgv_align(pgv_w12_total_bytes(N, K)); };
+    add(m->lm_head, &m->z_head, V, H);
+    for (LlmLayer& l : m->layers) {
+        add(l.wqkv, &l.z_wqkv, 3 * H, H); add(l.wo, &l.z_wo, H, H); add(l.wgu, &l.z_wgu, 2 * I, H); add(l.wdown, &l.z_wdown, H, I);
+    }
+    *total = off;
+    return v;
+}
+
+// (Re)build the 12-bit copy of the matrix at `only` (the first time: of every matrix, once the model is complete; null later: nothing).  A matrix with
+// more than kW12MaxExc exceptions in a row block keeps its 16-bit stream.  Synchronous (model setup / weight loads, never inside a capture).
+static int w12_sync(pgv_llm* m, const void* only, hipStream_t s) {
+    if (m->dtype != PGV_BF16 || m->fp8 || pgv_llm_missing(m) != 0) return PGV_OK;
+    if (m->blob12) { if (!only) return PGV_OK; }
+    else only = nullptr;
+    size_t total = 0;
+    std::vector<W12Slot> slots = w12_slots(m, &total);
+    if (!m->blob12) {
+        hipError_t e = hipMalloc((void**)&m->blob12, total);
+        if (e != hipSuccess) { pgv_set_error("12-bit weight copies: hipMalloc(%zu MiB): %s", total >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
+    }
+    size_t nrb = 0;
+    for (const W12Slot& x : slots) nrb += x.N / 16;
+    int* d_counts = nullptr;
+    PGV_HIP(hipMalloc((void**)&d_counts, nrb * sizeof(int)));
+    std::vector<size_t> coff;
+    size_t c = 0;
+    int rc = PGV_OK;
+    for (const W12Slot& x : slots) {
+        coff.push_back(c);
+        if ((!only || x.w16 == only) && rc == PGV_OK) rc = pgv_launch_encode_w12(x.w16, m->blob12 + x.off, d_counts + c, x.N, x.K, s);
+        c += x.N / 16;
+    }
+    std::vector<int> counts(nrb, 0);
+    hipError_t e = rc == PGV_OK ? hipMemcpyAsync(counts.data(), d_counts, nrb * sizeof(int), hipMemcpyDeviceToHost, s) : hipSuccess;
+    if (e == hipSuccess && rc == PGV_OK) e = hipStreamSynchronize(s);
+    (void)hipFree(d_counts);
+    PGV_TRY(rc);
+    if (e != hipSuccess) { pgv_set_error("12-bit weight copies: %s", hipGetErrorString(e)); return PGV_EHIP; }
+    for (size_t i = 0; i < slots.size(); ++i) {
+        const W12Slot& x = slots[i];
+        if (only && x.w16 != only) continue;
+        int worst = 0;
+        for (long long r = 0; r < x.N / 16; ++r) worst = counts[coff[i] + r] > worst ? counts[coff[i] + r] : worst;
+        x.ref->buf = worst <= kW12MaxExc ? m->blob12 + x.off : nullptr;
+        x.ref->rows = x.N;
+    }
+    m->generation += 1;           // captured decode graphs stream the previous copies
+    return PGV_OK;
+}
+
+static void w12_drop(pgv_llm* m) {
+    if (m->blob12) (void)hipFree(m->blob12);
+    m->blob12 = nullptr;
+    m->z_head = W12Ref{};
+    for (LlmLayer& l : m->layers) l.z_wqkv = l.z_wo = l.z_wgu = l.z_wdown = W12Ref{};
+}
+
+// the copy a decode GEMV streams for a matrix (null: its 16-bit / fp8 matrix)
+static const W12Ref* z12(const pgv_llm* m, const W12Ref& r) { return (m->use12 && r.buf) ? &r : nullptr; }
+
+extern "C" int pgv_llm_set_weight_stream(pgv_llm* m, int use12) {
+    PGV_CHECK(m != nullptr && (use12 == 0 || use12 == 1), "pgv_llm_set_weight_stream: bad arguments");
+    if (m->use12 != (use12 == 1)) { m->use12 = use12 == 1; m->generation += 1; }
+    return PGV_OK;
+}
+
+extern "C" int64_t pgv_llm_weight_stream_bytes(const pgv_llm* m, int batch) {
+    if (!m || batch < 1) return -1;
+    const long long H = m->cfg.hidden, I = m->cfg.inter, V16 = (m->cfg.vocab + 15) / 16 * 16;
+    auto one = [&](const W12Ref& z, long long N, long long K) -> double {
+        if (m->fp8) return (double)N * K + 4.0 * N;                                     // e4m3 + per-row fp32 scales
+        if (batch <= 16 && z12(m, z)) return (double)pgv_w12_total_bytes(N, K);
+        return 2.0 * N * K;
+    };
+    double b = one(m->z_head, V16, H);
+    for (const LlmLayer& l : m->layers) b += one(l.z_wqkv, 3 * H, H) + one(l.z_wo, H, H) + one(l.z_wgu, 2 * I, H) + one(l.z_wdown, H, I);
+    return (int64_t)b;
+}
 extern "C" int pgv_llm_vocab(const pgv_llm* llm) { return llm ? llm->cfg.vocab : -1; }
 
 extern "C" int pgv_llm_resize_vocab(pgv_llm* m, int new_vocab, void* stream) {
@@ -136,6 +231,7 @@ extern "C" int pgv_llm_resize_vocab(pgv_llm* m, int new_vocab, void* stream) {
         PGV_TRY(pgv_zero_rows_blocked(m->lm_head, m->cfg.vocab, new_vocab - m->cfg.vocab, (long long)H, (hipStream_t)stream));
     }
     m->cfg.vocab = new_vocab;
+    PGV_TRY(w12_sync(m, m->lm_head, (hipStream_t)stream));
     m->generation += 1;           // captured decode graphs have the old vocabulary baked into lm_head / the token pick
     return PGV_OK;
 }
@@ -153,7 +249,7 @@ extern "C" int pgv_llm_load_rows(pgv_llm* m, const char* name, const void* data,
     else { pgv_set_error("pgv_llm_load_rows: '%s' is not a vocabulary matrix", name); return PGV_ENAME; }
     PGV_TRY(pgv_pack_tensor(d, data, src_dtype, on_device, (hipStream_t)stream));
     m->loaded.insert(name);
-    return PGV_OK;
+    return w12_sync(m, d.blocked ? d.ptr : nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pgv_llm_load_tensor(pgv_llm* m, const char* name_in, const void* data, int src_dtype, int on_device, int64_t numel, void* stream) {
@@ -191,7 +287,7 @@ extern "C" int pgv_llm_load_tensor(pgv_llm* m, const char* name_in, const void* 
               (long long)numel, d.rows, d.cols);
     PGV_TRY(pgv_pack_tensor(d, data, src_dtype, on_device, (hipStream_t)stream));
     m->loaded.insert(name);
-    return PGV_OK;
+    return w12_sync(m, d.blocked ? d.ptr : nullptr, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -228,6 +324,7 @@ extern "C" int pgv_llm_quantize_fp8(pgv_ctx* ctx, pgv_llm* m, void* stream) {
         PGV_TRY(pgv_launch_quantize_fp8(m->dtype, l.wdown, l.q_wdown, l.s_wdown, (long long)H, (long long)I, s));
     }
     PGV_HIP(hipStreamSynchronize(s));
+    w12_drop(m);                  // decode streams the fp8 copies
     m->fp8 = true;
     m->generation += 1;           // decode graphs captured before now stream the 16-bit matrices
     return PGV_OK;
@@ -339,7 +436,8 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
     const bool greedy = !(flags & AM_SAMPLE);
     if (greedy) { nm.amax_val = kv->amax_val; nm.amax_idx = kv->amax_idx; }
     if (m->fp8 && nparts > 0) PGV_TRY(gemv8(ctx, m, kv, GV_F32, m->q_head, m->s_head, kv->xn, H, kv->logits, V, V, B, s, &nm));
-    else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_F32, m->fp8 ? m->q_head : m->lm_head, kv->xn, H, kv->logits, V, V, H, B, s, m->fp8 ? m->s_head : nullptr, &nm));
+    else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_F32, m->fp8 ? m->q_head : m->lm_head, kv->xn, H, kv->logits, V, V, H, B, s, m->fp8 ? m->s_head : nullptr, &nm,
+                                 z12(m, m->z_head)));
     pgv_prof_begin(ctx, 6, s);
     if (flags & AM_SAMPLE)
         PGV_TRY(pgv_launch_sample(kv->logits, V, B, kv->s_temp, kv->s_topk, kv->d_u, B, 1, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
@@ -498,12 +596,12 @@ static int decode_enqueue_unfolded(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos
         const LlmLayer& l = m->layers[li];
         const bool q8 = m->fp8;
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.in_g, m->cfg.eps, kv->xn, B, H, s));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, q8 ? l.q_wqkv : l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, q8 ? l.s_wqkv : nullptr, nullptr));
+        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, q8 ? l.q_wqkv : l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, q8 ? l.s_wqkv : nullptr, nullptr, z12(m, l.z_wqkv)));
         PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESID, q8 ? l.q_wo : l.wo, kv->ao, H, kv->resid, H, H, H, B, s, q8 ? l.s_wo : nullptr, nullptr));
+        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESID, q8 ? l.q_wo : l.wo, kv->ao, H, kv->resid, H, H, H, B, s, q8 ? l.s_wo : nullptr, nullptr, z12(m, l.z_wo)));
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.post_g, m->cfg.eps, kv->xn, B, H, s));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_SWIGLU, q8 ? l.q_wgu : l.wgu, kv->xn, H, kv->act, I, 2 * I, H, B, s, q8 ? l.s_wgu : nullptr, nullptr));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESID, q8 ? l.q_wdown : l.wdown, kv->act, I, kv->resid, H, H, I, B, s, q8 ? l.s_wdown : nullptr, nullptr));
+        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_SWIGLU, q8 ? l.q_wgu : l.wgu, kv->xn, H, kv->act, I, 2 * I, H, B, s, q8 ? l.s_wgu : nullptr, nullptr, z12(m, l.z_wgu)));
+        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESID, q8 ? l.q_wdown : l.wdown, kv->act, I, kv->resid, H, H, I, B, s, q8 ? l.s_wdown : nullptr, nullptr, z12(m, l.z_wdown)));
     }
     PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
     PGV_TRY(lm_head_and_pick(ctx, m, kv, B, eos, flags, s, 0));
@@ -527,17 +625,17 @@ static int decode_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int fla
         const bool q8 = m->fp8;
         GemvNorm cons; cons.ssq_in = kv->ssq; cons.nparts_in = parts_in; cons.hidden = H; cons.eps = m->cfg.eps; cons.ssq_ts = kv->ssq_ts; cons.x_blocked = true;
         if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_STORE16, l.q_wqkv, l.s_wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, B, s, &cons));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, nullptr, &cons));
+        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, nullptr, &cons, z12(m, l.z_wqkv)));
         PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket));
         GemvNorm prod; prod.gamma = l.post_g; prod.xg = kv->xn; prod.ssq_out = kv->ssq; prod.ssq_ts = kv->ssq_ts; prod.k8_part = kv->k8_part; prod.x_blocked = true;
         if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_RESIDNORM, l.q_wo, l.s_wo, kv->ao, H, kv->resid, H, H, B, s, &prod));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESIDNORM, l.wo, kv->ao, H, kv->resid, H, H, H, B, s, nullptr, &prod));
+        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESIDNORM, l.wo, kv->ao, H, kv->resid, H, H, H, B, s, nullptr, &prod, z12(m, l.z_wo)));
         cons.nparts_in = nparts;
         if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_SWIGLU, l.q_wgu, l.s_wgu, kv->xn, H, kv->act, I, 2 * I, B, s, &cons));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_SWIGLU, l.wgu, kv->xn, H, kv->act, I, 2 * I, H, B, s, nullptr, &cons));
+        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_SWIGLU, l.wgu, kv->xn, H, kv->act, I, 2 * I, H, B, s, nullptr, &cons, z12(m, l.z_wgu)));
         prod.gamma = li + 1 < L ? m->layers[li + 1].in_g : m->norm_g;
         if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_RESIDNORM, l.q_wdown, l.s_wdown, kv->act, I, kv->resid, H, H, B, s, &prod));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESIDNORM, l.wdown, kv->act, I, kv->resid, H, H, I, B, s, nullptr, &prod));
+        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESIDNORM, l.wdown, kv->act, I, kv->resid, H, H, I, B, s, nullptr, &prod, z12(m, l.z_wdown)));
         parts_in = nparts;
     }
     PGV_TRY(lm_head_and_pick(ctx, m, kv, B, eos, flags, s, parts_in));

@@ -7,7 +7,9 @@ constexpr int kHD = 128;             // LLaMA head_dim
 constexpr int kMaxBatch = 64;        // decode GEMVs: up to 4 MFMA column tiles of 16 sequences per weight fragment
 enum { GV_STORE16 = 0, GV_RESID = 1, GV_SWIGLU = 2, GV_F32 = 3, GV_RESIDNORM = 5 };     // gemv.hip epilogues
 enum { AM_INC_POS = 1, AM_RECORD = 2, AM_SAMPLE = 4 };                                  // sampling.hip bookkeeping flags
-constexpr int kDattnSplitMax = 8, kDattnPart = kHD + 2;                                 // decode_attn.hip: context splits, floats per partial state
+constexpr int kDattnSplitMax = 8, kDattnPart = kHD + 2;                                 // w12.hip
+int pgv_launch_encode_w12(const void* w16_blocked, void* w12, int* counts, long long N, long long K, hipStream_t s);
+// decode_attn.hip: context splits, floats per partial state
 
 // vit_attn.hip
 int pgv_vit_attn_configure(pgv_ctx* ctx);  // per-device dynamic-LDS opt-in of the attention kernels: called once per context
@@ -21,8 +23,11 @@ int pgv_launch_rope_kv_write(int dtype, void* qkv, const int* row_b, const int* 
 int pgv_launch_prefill_attn(pgv_ctx* ctx, int dtype, const void* qkv, void* out, const void* Kc, const void* Vc, const int* cu, const int* koff, int B, int max_len,
                             int H, int heads, int max_seq, double flops, hipStream_t s);
 // gemv.hip
+// w12: the 12-bit copy of W (w12.h), streamed instead of W at batches of one column tile (B <= 16) -- bitwise the same result; W may be null
+// only when B <= 16.  rows = the row count it was encoded with (>= N).
+struct W12Ref { const void* buf = nullptr; long long rows = 0; };
 int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void* x, int ldx, void* out, int ldo, int N, int K, int B, hipStream_t s,
-                    const float* wscale = nullptr, const GemvNorm* norm = nullptr);
+                    const float* wscale = nullptr, const GemvNorm* norm = nullptr, const W12Ref* w12 = nullptr);
 int pgv_gemv_configure(pgv_ctx* ctx);      // per-device function attributes of the 8-phase producers: called once per context, outside graph capture
 int pgv_launch_embed_tok_norm(int dtype, const int* tok, const void* embed, float* resid, const float* gamma, void* xg, float* ssq, int B, int H, hipStream_t s, bool x_blocked);
 int pgv_launch_final_prep(int dtype, const float* resid, const float* gamma, void* xg, float* ssq, int B, int H, hipStream_t s, bool x_blocked);
