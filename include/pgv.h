@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 320
+#define PGV_VERSION 321
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -274,6 +274,20 @@ int pgv_encode_w12_blocked(pgv_ctx *ctx, int dtype, const void *d_w16_blocked, v
  * N = the encoded row count (or fewer, mode 3). */
 int pgv_gemv_w12(pgv_ctx *ctx, int dtype, int mode, const void *d_W12, const void *d_x, int ldx, void *d_out, int ldo, int N, int K, int B,
                  void *stream);
+/* LLaMA decode attention of one token step on caller buffers: the kernels and launcher pgv_llm_decode runs (RoPE on q and k at h_pos[b], append of
+ * the rotated k and of v at row h_pos[b], softmax over cache rows [0, h_pos[b]] with scale 128^-0.5).  `llm` supplies the dtype, head count and
+ * RoPE table (no weights need to be loaded).  d_qkv [B, 3H] 16-bit (q | k | v), d_Kc / d_Vc [B, heads, max_seq, 128], d_out [B, H]; rows at
+ * or past h_pos[b] are never read into the result.  Host-checked: 1 <= B <= 64, 1 <= max_seq <= 4096, 0 <= h_pos[b] < max_seq.  split: 0 = the
+ * model's choice (as pgv_llm_decode), 1 / 2 / 4 / 8 = that many workgroups per (sequence, head).  d_part (B * heads * 8 * 130 floats) and
+ * d_ticket (B * heads, zeroed by the caller; every launch leaves it zero) are the split merge's scratch.  Synchronises the stream once. */
+int pgv_decode_attention(pgv_ctx *ctx, pgv_llm *llm, const void *d_qkv, const int32_t *h_pos, void *d_Kc, void *d_Vc, void *d_out, int B, int max_seq,
+                         int split, float *d_part, uint32_t *d_ticket, void *stream);
+/* LLaMA prefill attention on caller buffers: the kernels pgv_llm_prefill / pgv_llm_prefill_append run.  Sequence b has h_seq_lens[b] rows,
+ * concatenated in d_qkv [M, 3H]; row i sits at position koff + i (h_koff[b], or 0 when h_koff is NULL).  q is rotated in place in d_qkv,
+ * the rotated k and v are written to cache rows koff + i, and row i attends to keys [0, koff + i].  d_out [M, H].  Host-checked:
+ * 1 <= B <= 64, 1 <= max_seq <= 4096, koff >= 0, koff + len <= max_seq.  Synchronises the stream once. */
+int pgv_prefill_attention(pgv_ctx *ctx, pgv_llm *llm, void *d_qkv, const int32_t *h_seq_lens, const int32_t *h_koff, void *d_Kc, void *d_Vc,
+                          void *d_out, int B, int max_seq, void *stream);
 int pgv_layernorm(pgv_ctx *ctx, int dtype, const float *d_x, const float *d_gamma, const float *d_beta, float eps,
                   void *d_y, int rows, int cols, void *stream);
 int pgv_rmsnorm(pgv_ctx *ctx, int dtype, const float *d_x, const float *d_gamma, float eps, void *d_y, int rows, int cols,

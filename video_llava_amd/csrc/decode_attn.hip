@@ -370,13 +370,14 @@ static int decode_attn_split(int heads, int num_cu) {
 }
 
 int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const void* rope, void* Kc, void* Vc, void* out, int B, int H,
-                           int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket) {
+                           int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket, int split_force) {
     const float sc = 0.08838834764831845f * 1.4426950408889634f;
     int nw = 8;                                          // 16-wave workgroups: a lab A/B switch (-DPGV_LAB), never the release default
 #ifdef PGV_LAB
     { const char* e = getenv("PGV_DATTN_WAVES"); if (e && atoi(e) == 16) nw = 16; }
 #endif
-    const int split = (part && ticket) ? decode_attn_split(heads, ctx->num_cu) : 1;
+    // split_force 1/2/4/8: that split (pgv_decode_attention, the building block of the tests); 0: the model's choice (the product path)
+    const int split = split_force ? split_force : (part && ticket) ? decode_attn_split(heads, ctx->num_cu) : 1;
     pgv_prof_begin(ctx, 4, s);
 #define PGV_DATTN_SPLIT_LAUNCH(S_) \
         PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_attn_split_kernel<T, S_>), dim3(heads, B, S_), dim3(512), 0, s, (const typename T::elem*)qkv, pos, \

@@ -597,7 +597,7 @@ static int decode_enqueue_unfolded(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos
         const bool q8 = m->fp8;
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.in_g, m->cfg.eps, kv->xn, B, H, s));
         PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, q8 ? l.q_wqkv : l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, q8 ? l.s_wqkv : nullptr, nullptr, z12(m, l.z_wqkv)));
-        PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket));
+        PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket, 0));
         PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESID, q8 ? l.q_wo : l.wo, kv->ao, H, kv->resid, H, H, H, B, s, q8 ? l.s_wo : nullptr, nullptr, z12(m, l.z_wo)));
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.post_g, m->cfg.eps, kv->xn, B, H, s));
         PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_SWIGLU, q8 ? l.q_wgu : l.wgu, kv->xn, H, kv->act, I, 2 * I, H, B, s, q8 ? l.s_wgu : nullptr, nullptr, z12(m, l.z_wgu)));
@@ -626,7 +626,7 @@ static int decode_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int fla
         GemvNorm cons; cons.ssq_in = kv->ssq; cons.nparts_in = parts_in; cons.hidden = H; cons.eps = m->cfg.eps; cons.ssq_ts = kv->ssq_ts; cons.x_blocked = true;
         if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_STORE16, l.q_wqkv, l.s_wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, B, s, &cons));
         else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, nullptr, &cons, z12(m, l.z_wqkv)));
-        PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket));
+        PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket, 0));
         GemvNorm prod; prod.gamma = l.post_g; prod.xg = kv->xn; prod.ssq_out = kv->ssq; prod.ssq_ts = kv->ssq_ts; prod.k8_part = kv->k8_part; prod.x_blocked = true;
         if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_RESIDNORM, l.q_wo, l.s_wo, kv->ao, H, kv->resid, H, H, B, s, &prod));
         else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESIDNORM, l.wo, kv->ao, H, kv->resid, H, H, H, B, s, nullptr, &prod, z12(m, l.z_wo)));
@@ -764,6 +764,80 @@ extern "C" int pgv_llm_decode_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | AM_SAMPLE, n, s));
     PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// attention building blocks (pgv.h): the launchers of prefill_impl / decode_enqueue* on caller buffers, for unit parity tests
+// ---------------------------------------------------------------------------------------------
+// Host values reach the device through the workspace arena; the stream is synchronised once after the upload so the host staging need not
+// outlive the call.  Every position is checked here, on the host: the kernels index the cache and the RoPE table with them unchecked.
+static int upload_ints(pgv_ctx* ctx, const std::vector<int>& h, int** d, hipStream_t s) {
+    const size_t bytes = pgv_align(h.size() * 4);
+    PGV_TRY(pgv_ws_reserve(ctx, bytes, s));
+    *d = (int*)pgv_ws_alloc(ctx, bytes);
+    PGV_CHECK(*d != nullptr, "attention building block: workspace exhausted");
+    PGV_HIP(hipMemcpyAsync(*d, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipStreamSynchronize(s));
+    return PGV_OK;
+}
+
+extern "C" int pgv_decode_attention(pgv_ctx* ctx, pgv_llm* m, const void* d_qkv, const int32_t* h_pos, void* d_Kc, void* d_Vc, void* d_out, int B,
+                                    int max_seq, int split, float* d_part, uint32_t* d_ticket, void* stream) {
+    PGV_CHECK(ctx && m && d_qkv && h_pos && d_Kc && d_Vc && d_out && d_part && d_ticket, "pgv_decode_attention: null argument");
+    PGV_CHECK(B >= 1 && B <= kMaxBatch, "pgv_decode_attention: batch %d outside [1,%d]", B, kMaxBatch);
+    PGV_CHECK(max_seq >= 1 && max_seq <= kMaxPos, "pgv_decode_attention: max_seq %d outside [1,%d]", max_seq, kMaxPos);
+    PGV_CHECK(split == 0 || split == 1 || split == 2 || split == 4 || split == 8, "pgv_decode_attention: split %d is not 0, 1, 2, 4 or 8", split);
+    std::vector<int> pos(h_pos, h_pos + B);
+    double bytes = 0;
+    for (int b = 0; b < B; ++b) {
+        PGV_CHECK(pos[b] >= 0 && pos[b] < max_seq, "pgv_decode_attention: position %d of sequence %d outside [0,%d)", pos[b], b, max_seq);
+        bytes += 2.0 * 2.0 * (pos[b] + 1.0) * m->cfg.hidden;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int* d_pos = nullptr;
+    PGV_TRY(upload_ints(ctx, pos, &d_pos, s));
+    PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, d_qkv, d_pos, m->rope, d_Kc, d_Vc, d_out, B, m->cfg.hidden, m->cfg.heads, max_seq, bytes, s, d_part,
+                                   d_ticket, split));
+    PGV_HIP(hipGetLastError());
+    PGV_TRY(pgv_ws_release(ctx, s));
+    return PGV_OK;
+}
+
+extern "C" int pgv_prefill_attention(pgv_ctx* ctx, pgv_llm* m, void* d_qkv, const int32_t* h_seq_lens, const int32_t* h_koff, void* d_Kc, void* d_Vc,
+                                     void* d_out, int B, int max_seq, void* stream) {
+    PGV_CHECK(ctx && m && d_qkv && h_seq_lens && d_Kc && d_Vc && d_out, "pgv_prefill_attention: null argument");
+    PGV_CHECK(B >= 1 && B <= kMaxBatch, "pgv_prefill_attention: batch %d outside [1,%d]", B, kMaxBatch);
+    PGV_CHECK(max_seq >= 1 && max_seq <= kMaxPos, "pgv_prefill_attention: max_seq %d outside [1,%d]", max_seq, kMaxPos);
+    const int H = m->cfg.hidden, heads = m->cfg.heads;
+    int M = 0, max_len = 0;
+    for (int b = 0; b < B; ++b) {
+        const int off = h_koff ? h_koff[b] : 0;
+        PGV_CHECK(h_seq_lens[b] >= 1 && off >= 0 && off <= max_seq - h_seq_lens[b], "pgv_prefill_attention: sequence %d has %d + %d tokens (cache holds %d)", b,
+                  off, h_seq_lens[b], max_seq);
+        M += h_seq_lens[b];
+        max_len = h_seq_lens[b] > max_len ? h_seq_lens[b] : max_len;
+    }
+    // row maps as prefill_impl builds them: [row_b | row_pos | cu (B+1) | offs (B)]
+    std::vector<int> meta((size_t)2 * M + 2 * B + 1, 0);
+    int* row_b = meta.data(); int* row_pos = row_b + M; int* cu = row_pos + M; int* offs = cu + B + 1;
+    int r = 0;
+    for (int b = 0; b < B; ++b) {
+        cu[b] = r;
+        offs[b] = h_koff ? h_koff[b] : 0;
+        for (int p = 0; p < h_seq_lens[b]; ++p, ++r) { row_b[r] = b; row_pos[r] = offs[b] + p; }
+    }
+    cu[B] = r;
+    hipStream_t s = (hipStream_t)stream;
+    int* d_meta = nullptr;
+    PGV_TRY(upload_ints(ctx, meta, &d_meta, s));
+    const int* d_cu = d_meta + 2 * M;
+    double flops = 0;
+    for (int b = 0; b < B; ++b) flops += 2.0 * (double)h_seq_lens[b] * (h_seq_lens[b] + 2.0 * offs[b]) * H;
+    PGV_TRY(pgv_launch_rope_kv_write(m->dtype, d_qkv, d_meta, d_meta + M, m->rope, d_Kc, d_Vc, M, H, heads, max_seq, s));
+    PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, d_qkv, d_out, d_Kc, d_Vc, d_cu, h_koff ? d_cu + B + 1 : nullptr, B, max_len, H, heads, max_seq, flops, s));
+    PGV_HIP(hipGetLastError());
+    PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
 }
 

@@ -38,7 +38,7 @@ int pgv_launch_unpack_blocked(int dtype, const void* src, float* dst, long long 
                               long long rows, hipStream_t s);
 // decode_attn.hip
 int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const void* rope, void* Kc, void* Vc, void* out, int B, int H,
-                           int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket);
+                           int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket, int split_force);
 // sampling.hip
 int pgv_launch_sample(const float* logits, int V, int B, float temperature, int top_k, const float* u, int u_stride, int u_by_step, int* next, int* pos,
                       int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s);
