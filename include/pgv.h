@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 321
+#define PGV_VERSION 322
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -195,6 +195,20 @@ int pgv_llm_prefill(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_ids
 int pgv_llm_prefill_append(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_ids, const int32_t *h_seq_lens, int B,
                            const void *d_video, int V, const int32_t *h_vid_pos, float *d_logits, int32_t *d_next, float *d_all_logits,
                            int ld_all, void *stream);
+/* Continuous batching: prefill n NEW prompts into slots h_slots[0..n) of a cache that holds a live group (the last pgv_llm_prefill of `kv`),
+ * while the other slots keep their state.  1 <= n, every slot < the width of that prefill, slots distinct.  h_ids / h_seq_lens / d_video [n, V, hidden]
+ * / h_vid_pos as pgv_llm_prefill, in slot-list order.  d_u == NULL: greedy first token; otherwise it is drawn exactly as pgv_llm_sample does, with
+ * d_u[i], `temperature` (> 0) and `top_k`.  d_logits [n, vocab] / d_next [n] (either may be NULL) receive the refilled sequences' logits / first tokens.
+ * A listed slot s: cache rows [0, len) hold the new prompt, pgv_kv_len(kv, s) == len, its current token is the pick, its done flag and step
+ * counter are cleared.  An unlisted slot: cache rows, length, current token and done flag are untouched; the group's width does not change and
+ * captured decode graphs stay valid (they read positions and tokens from device memory).  A refilled sequence's later tokens and logits are
+ * bitwise those of the same prompt run alone through pgv_llm_prefill + decode.  Refused (cache unchanged): no live group or a slot outside it
+ * (PGV_ESTATE / PGV_EINVAL), a duplicate slot, a prompt longer than the cache, a bad video run or token id (PGV_EINVAL).
+ * A slot with no task left is not released: rewind it with pgv_kv_truncate(kv, s, 1) before every decode chunk so that it neither outgrows
+ * max_seq nor keeps reading a long cache; its tokens are then meaningless and ignored by the caller. */
+int pgv_llm_prefill_slots(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_slots, int n, const int32_t *h_ids, const int32_t *h_seq_lens,
+                          const void *d_video, int V, const int32_t *h_vid_pos, float temperature, int top_k, const float *d_u, float *d_logits,
+                          int32_t *d_next, void *stream);
 /* Forget the cache entries of sequence b from position `len` on (1 <= len <= pgv_kv_len): the next append / decode call continues there.
  * Used when a new chat turn shares only a prefix with what the cache holds (surplus decode steps past a stop string,
  * video_chatgpt/model/utils.py:6-26). */

@@ -1,0 +1,280 @@
+"""Continuous batching: answer a stream of tasks through a fixed group of decode slots, refilling the slots whose answer has finished with
+queued tasks (pgv_llm_prefill_slots) instead of holding them until the longest answer of a static group is done.
+
+`model.generate` on a static group keeps stepping until its LONGEST answer ends: with the runners' max_new_tokens = 1024 and answers of
+5-60 tokens, one answer that runs to the cap keeps every other slot of its group decoding discarded tokens for ~1000 steps.  Here a slot
+whose task ended (EOS, stop string or its token budget) is refilled at the next chunk boundary, while the other slots keep their cache and
+state.  Every kernel on the path treats a sequence independently of the others (batch invariance is bitwise), so a task's ids are exactly
+those of `model.generate([ids], ...)` on its own -- greedy, or sampled with the task's own seeded uniform stream.
+"""
+from __future__ import annotations
+
+import time
+from dataclasses import dataclass
+from typing import Any, Callable, Iterable, Iterator, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+DEFAULT_CHUNK = 16          # decode steps between two host checks (EOS / stop strings / budgets) and refills
+
+
+@dataclass
+class Task:
+    """One prompt to answer.  feats: pooled video features [V, C] (None: text only).  stop: stop string (needs the tokenizer).
+    max_new_tokens: this task's token budget (None: the call's).  seed: seed of the task's uniform stream (do_sample)."""
+    task_id: Any
+    ids: List[int]
+    feats: Optional[torch.Tensor] = None
+    stop: Optional[str] = None
+    max_new_tokens: Optional[int] = None
+    seed: Optional[int] = None
+
+
+def task_uniforms(n: int, seed: int, device) -> torch.Tensor:
+    """The task's uniform stream: the [n, 1] draw `model.generate(do_sample=True, generator=Generator(device).manual_seed(seed))` makes for a
+    single prompt with max_new_tokens = n; value t picks new token t."""
+    g = torch.Generator(device=device).manual_seed(int(seed))
+    return torch.rand(n, 1, device=device, dtype=torch.float32, generator=g)[:, 0]
+
+
+class _Slot:
+    __slots__ = ("task", "new", "budget", "scanned", "u", "prefill_s", "decode_s", "steps", "group_size")
+
+    def __init__(self, task: Task, budget: int, u: Optional[torch.Tensor], prefill_s: float, group_size: int):
+        self.task, self.budget, self.u, self.group_size = task, budget, u, group_size
+        self.new: List[int] = []
+        self.scanned = 2            # stop strings: prefixes shorter than this are known not to fire (as in generate)
+        self.prefill_s, self.decode_s, self.steps = prefill_s, 0.0, 0
+
+
+def _default_on_error(task_id, exc):
+    print(f"Error processing task {task_id!r}: {exc}")
+
+
+def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens: int, *, do_sample: bool = False, temperature: float = 0.2,
+                        top_k: int = 50, tokenizer=None, chunk: int = DEFAULT_CHUNK, refill_min: Optional[int] = None, max_seq: Optional[int] = None,
+                        prompt_slack: int = 128, eos_token_id="config", seed: int = 0,
+                        on_error: Callable[[Any, Exception], None] = _default_on_error,
+                        timings: Optional[dict] = None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
+    """Yield (task_id, new_ids) as each task finishes; new_ids is None for a task that failed (`on_error(task_id, exc)` is told why) -- a failed
+    task costs only itself.
+
+    width: decode slots (<= 64).  The group opens with `model.prefill` over the first `width` tasks; every `chunk` decode steps the host applies
+    EOS, the stop-string cut (`first_stop_length`, scanned incrementally: exactly generate's rule) and the budgets, then refills the freed slots
+    with ONE `prefill_slots` call once at least `refill_min` slots are free (default: width // 8, at least 1) -- or sooner when waiting would
+    stall: no task left decoding, or the queue holds fewer tasks than that.  Slots without a task are rewound to one position every chunk
+    (pgv_kv_truncate) so that they neither outgrow the cache nor read a long one.
+    do_sample: task t draws from its own stream `task_uniforms(budget, task.seed, device)` (seed None: `seed` + the task's arrival index), so a
+    sampled answer equals generate(do_sample=True, generator=<that seeded generator>) whatever its slot and the group width.
+    max_seq: cache positions per slot (default: longest prompt of the first group + `prompt_slack` + max_new_tokens + chunk, rounded to 64);
+    a later task that does not fit fails alone.
+    timings (a dict): timings[task_id] = {prefill_s, decode_s, steps, group_size} of each finished task (host clock; the prefill call that
+    started it and the decode chunks it was live in)."""
+    if not 1 <= width <= 64:
+        raise ValueError(f"width {width} outside [1, 64]")
+    if do_sample and not float(temperature) > 0.0:
+        raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float; use do_sample=False for greedy decoding")
+    chunk = max(1, int(chunk))
+    k_min = max(1, int(refill_min) if refill_min is not None else width // 8)
+    eos = model.config.eos_token_id if eos_token_id == "config" else eos_token_id
+    eos_i = -1 if eos is None else int(eos)
+    dev = model.device_
+    from .model.utils import first_stop_length
+
+    source = iter(tasks)
+    pending: List[Tuple[int, Task]] = []
+    arrivals = [0]
+    exhausted = [False]
+
+    def pull(n: int):
+        while len(pending) < n and not exhausted[0]:
+            try:
+                t = next(source)
+            except StopIteration:
+                exhausted[0] = True
+                break
+            pending.append((arrivals[0], t))
+            arrivals[0] += 1
+
+    def budget_of(t: Task) -> int:
+        return int(t.max_new_tokens) if t.max_new_tokens is not None else int(max_new_tokens)
+
+    def check(t: Task, limit: int):
+        """Host-side checks of one task (the ones the library would refuse a whole call for): a bad task fails alone."""
+        if len(t.ids) < 1:
+            raise ValueError("empty prompt")
+        if budget_of(t) < 1:
+            raise ValueError(f"max_new_tokens {budget_of(t)} < 1")
+        if len(t.ids) + budget_of(t) + chunk > limit:
+            raise ValueError(f"prompt of {len(t.ids)} tokens + {budget_of(t)} new tokens does not fit the group's {limit} cache positions")
+        if t.stop and tokenizer is None:
+            raise ValueError("a stop string needs the tokenizer")
+        vp = model._video_positions([t.ids], t.feats.shape[-2])[0] if t.feats is not None else -1
+        a = np.asarray(t.ids)
+        vocab = model.vocab_size
+        keep = np.ones(len(a), dtype=bool)
+        if vp >= 0:
+            keep[vp + 1:vp + 1 + t.feats.shape[-2]] = False
+        if ((a[keep] < 0) | (a[keep] >= vocab)).any():
+            raise ValueError(f"token id outside the vocabulary ({vocab})")
+
+    def feats_for(group: List[Task]) -> Optional[torch.Tensor]:
+        shapes = {tuple(t.feats.shape) for t in group if t.feats is not None}
+        if not shapes:
+            return None
+        if len(shapes) > 1:
+            raise ValueError(f"video feature shapes differ inside one prefill call: {sorted(shapes)}")
+        ref = next(t.feats for t in group if t.feats is not None)
+        return torch.stack([(t.feats if t.feats is not None else torch.zeros_like(ref)).to(dev) for t in group])
+
+    def uniforms(arrival: int, t: Task) -> Optional[torch.Tensor]:
+        if not do_sample:
+            return None
+        return task_uniforms(budget_of(t), t.seed if t.seed is not None else seed + arrival, dev)
+
+    # ---- open the group ------------------------------------------------------------------------------------------
+    pull(width)
+    first: List[Tuple[int, Task]] = []
+    if max_seq is None:
+        if not pending:
+            return
+        longest = max(len(t.ids) for _, t in pending)
+        max_seq = longest + prompt_slack + int(max_new_tokens) + chunk
+        max_seq = min((max_seq + 63) // 64 * 64, int(getattr(model.config, "max_position_embeddings", 4096)), 4096)
+    while pending and len(first) < width:
+        a, t = pending.pop(0)
+        try:
+            check(t, max_seq)
+            first.append((a, t))
+        except Exception as e:                                     # noqa: BLE001 -- one bad task fails alone
+            on_error(t.task_id, e)
+            yield t.task_id, None
+        pull(width)
+    if not first:
+        return
+    W = len(first)
+    t0 = time.perf_counter()
+    kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq)
+    slots: List[Optional[_Slot]] = [None] * W
+    us = [uniforms(a, t) for a, t in first]
+    if do_sample:
+        nxt = model.sample_last(kv, torch.stack([u[0] for u in us]), temperature, top_k)
+    cur = nxt.clone()
+    first_tok = nxt.cpu().tolist()
+    dt = time.perf_counter() - t0
+    for s, (a, t) in enumerate(first):
+        slots[s] = _Slot(t, budget_of(t), us[s], dt, W)
+    finished: List[int] = []
+
+    def absorb(s: int, toks: List[int]) -> bool:
+        """Append a slot's tokens of this chunk (up to its budget and first EOS), apply the stop-string cut; True = the task is finished."""
+        sl = slots[s]
+        take = toks[:sl.budget - len(sl.new)]
+        done = False
+        if eos_i >= 0 and eos_i in take:
+            take = take[:take.index(eos_i) + 1]
+            done = True
+        sl.new.extend(take)
+        if len(sl.new) >= sl.budget:
+            done = True
+        if sl.task.stop and len(sl.new) >= 2:
+            n = first_stop_length(sl.new, tokenizer, [sl.task.stop], start=sl.scanned)
+            if n is not None:
+                del sl.new[n:]
+                return True
+            sl.scanned = len(sl.new) + 1
+        return done
+
+    def finish(s: int):
+        sl = slots[s]
+        slots[s] = None
+        finished.append(s)
+        if timings is not None:
+            timings[sl.task.task_id] = {"prefill_s": sl.prefill_s, "decode_s": sl.decode_s, "steps": sl.steps, "group_size": sl.group_size}
+        return sl.task.task_id, list(sl.new)
+
+    for s in range(W):
+        if absorb(s, [first_tok[s]]):
+            yield finish(s)
+
+    # ---- decode / refill loop --------------------------------------------------------------------------------------
+    while True:
+        free = [s for s in range(W) if slots[s] is None]
+        live = W - len(free)
+        pull(len(free) + width)
+        if free and pending and (len(free) >= k_min or live == 0 or (exhausted[0] and len(pending) <= len(free))):
+            group: List[Tuple[int, int, Task]] = []
+            for s in free:
+                while pending:
+                    a, t = pending.pop(0)
+                    try:
+                        check(t, max_seq)
+                        group.append((s, a, t))
+                        break
+                    except Exception as e:                         # noqa: BLE001
+                        on_error(t.task_id, e)
+                        yield t.task_id, None
+                if not pending:
+                    pull(1)
+                    if not pending:
+                        break
+            parts = [group]
+            ok: List[Tuple[int, int, Task, int, float]] = []
+            while parts:
+                part = parts.pop(0)
+                if not part:
+                    continue
+                t0 = time.perf_counter()
+                try:
+                    u_part = [uniforms(a, t) for _, a, t in part]
+                    u0 = torch.stack([u[0] for u in u_part]) if do_sample else None
+                    nx, _ = model.prefill_slots(kv, [s for s, _, _ in part], [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
+                                                u=u0, temperature=temperature, top_k=top_k)
+                    cur[[s for s, _, _ in part]] = nx
+                    firsts = nx.cpu().tolist()
+                    dt = time.perf_counter() - t0
+                    for (s, a, t), u, f in zip(part, u_part, firsts):
+                        slots[s] = _Slot(t, budget_of(t), u, dt, len(part))
+                        ok.append((s, a, t, f, dt))
+                except Exception as e:                             # noqa: BLE001 -- the call was refused as a whole: split it, isolate the bad task
+                    if len(part) > 1:
+                        parts[:0] = [part[:len(part) // 2], part[len(part) // 2:]]
+                    else:
+                        on_error(part[0][2].task_id, e)
+                        yield part[0][2].task_id, None
+            for s, _, _, f, _ in ok:
+                if absorb(s, [f]):
+                    yield finish(s)
+            continue                                                # re-evaluate: refilled slots may have finished at their first token
+        if live == 0:
+            if not pending and exhausted[0]:
+                break
+            continue
+        # one chunk of decode steps for the whole group; slots without a task are rewound first
+        for s in free:
+            if model.kv_len(kv, s) > 1:
+                model.kv_truncate(kv, s, 1)
+        n = min(chunk, max(slots[s].budget - len(slots[s].new) for s in range(W) if slots[s] is not None))
+        t0 = time.perf_counter()
+        if do_sample:
+            u = torch.full((n, W), 0.5, dtype=torch.float32, device=dev)
+            for s in range(W):
+                sl = slots[s]
+                if sl is not None:
+                    seg = sl.u[len(sl.new):len(sl.new) + n]
+                    u[:seg.numel(), s] = seg
+            toks = model.decode_sample(kv, cur, n, eos_i, temperature, top_k, u)
+        else:
+            toks = model.decode_greedy(kv, cur, n, eos_i)
+        cur = toks[:, n - 1].contiguous()
+        host = toks.cpu().tolist()
+        dt = time.perf_counter() - t0
+        for s in range(W):
+            sl = slots[s]
+            if sl is None:
+                continue
+            sl.decode_s += dt
+            sl.steps += n
+            if absorb(s, host[s]):
+                yield finish(s)

@@ -428,16 +428,22 @@ static int gemv8(pgv_ctx* ctx, pgv_llm* m, pgv_kv*, int mode, const void* w8, co
     return pgv_launch_gemv(ctx, m->dtype, mode, w8, x, K, out, ldo, N, K, B, s, ws, nm);
 }
 
-static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos, int flags, hipStream_t s, int nparts) {
+// lm_head GEMV on kv->xn (B rows) -> kv->logits and, for a greedy pick, the per-workgroup argmax candidates
+static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hipStream_t s, int nparts) {
     const int H = m->cfg.hidden, V = m->cfg.vocab;
     GemvNorm nm; nm.ssq_in = nparts > 0 ? kv->ssq : nullptr; nm.nparts_in = nparts; nm.hidden = H; nm.eps = m->cfg.eps;     // nparts 0: kv->xn is already normalised
     nm.ssq_ts = kv->ssq_ts; nm.amax_ts = kv->amax_ts;
     nm.x_blocked = nparts > 0;                       // the folded path hands kv->xn over blocked at batches beyond 16 (pgv_gemv_xblk_tiles)
-    const bool greedy = !(flags & AM_SAMPLE);
     if (greedy) { nm.amax_val = kv->amax_val; nm.amax_idx = kv->amax_idx; }
     if (m->fp8 && nparts > 0) PGV_TRY(gemv8(ctx, m, kv, GV_F32, m->q_head, m->s_head, kv->xn, H, kv->logits, V, V, B, s, &nm));
     else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_F32, m->fp8 ? m->q_head : m->lm_head, kv->xn, H, kv->logits, V, V, H, B, s, m->fp8 ? m->s_head : nullptr, &nm,
                                  z12(m, m->z_head)));
+    return PGV_OK;
+}
+
+static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos, int flags, hipStream_t s, int nparts) {
+    const int V = m->cfg.vocab;
+    PGV_TRY(lm_head(ctx, m, kv, B, !(flags & AM_SAMPLE), s, nparts));
     pgv_prof_begin(ctx, 6, s);
     if (flags & AM_SAMPLE)
         PGV_TRY(pgv_launch_sample(kv->logits, V, B, kv->s_temp, kv->s_topk, kv->d_u, B, 1, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
@@ -456,19 +462,31 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
 // prefix as well): VideoChatGPTLlamaForCausalLM.forward with past_key_values and input_ids.shape[1] > 1 (video_chatgpt/model/video_chatgpt.py:193-251;
 // the splice still runs when the new ids carry a placeholder run, :103).  Same kernels, same per-row arithmetic: an appended row is bitwise the
 // row of one full prefill over prefix + new tokens.
+// `h_slots` (pgv_llm_prefill_slots): sequence b of the call is a NEW prompt for cache slot h_slots[b] of the live group; the other slots keep their
+// cache rows, lengths, current tokens and flags.  The new rows run through the same kernels (the slot only redirects the cache rows they write and
+// read), the pick lands in rows [0, B) of the scratch and is scattered to the slots: d_u null = greedy, else sampled with d_u[b].
 static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video,
-                        int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream, bool append) {
-    const char* who = append ? "pgv_llm_prefill_append" : "pgv_llm_prefill";
+                        int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream, bool append,
+                        const int32_t* h_slots = nullptr, float temperature = 0.f, int top_k = 0, const float* d_u = nullptr) {
+    const bool slots = h_slots != nullptr;
+    const char* who = append ? "pgv_llm_prefill_append" : slots ? "pgv_llm_prefill_slots" : "pgv_llm_prefill";
     PGV_CHECK(ctx && m && kv && h_ids && h_seq_lens, "%s: null argument", who);
     PGV_CHECK(kv->llm == m, "%s: kv cache belongs to another model", who);
     PGV_CHECK(B >= 1 && B <= kv->B, "%s: batch %d outside [1,%d]", who, B, kv->B);
     if (pgv_llm_missing(m) != 0) { pgv_set_error("%s: %d weight tensors not loaded", who, pgv_llm_missing(m)); return PGV_ESTATE; }
     if (append && kv->active != B) { pgv_set_error("pgv_llm_prefill_append: %d sequences for a cache that holds %d prefilled ones", B, kv->active); return PGV_ESTATE; }
+    if (slots) {
+        if (kv->active < 1) { pgv_set_error("pgv_llm_prefill_slots: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
+        PGV_CHECK(B <= kv->active, "pgv_llm_prefill_slots: %d sequences for a group of %d", B, kv->active);
+        for (int b = 0; b < B; ++b) {
+            PGV_CHECK(h_slots[b] >= 0 && h_slots[b] < kv->active, "pgv_llm_prefill_slots: slot %d outside the %d of the live group", h_slots[b], kv->active);
+            for (int c = 0; c < b; ++c) PGV_CHECK(h_slots[c] != h_slots[b], "pgv_llm_prefill_slots: slot %d listed twice", h_slots[b]);
+        }
+        PGV_CHECK(d_u == nullptr || temperature > 0.f, "pgv_llm_prefill_slots: temperature must be positive (got %g)", (double)temperature);
+        PGV_CHECK(d_all_logits == nullptr, "pgv_llm_prefill_slots: no all-position logits");
+    }
     hipStream_t s = (hipStream_t)stream;
     const int H = m->cfg.hidden, I = m->cfg.inter, heads = m->cfg.heads, vocab = m->cfg.vocab;
-    // arrival tickets of the context-split decode attention: a launch re-arms its own, but an ABORTED decode launch (device fault, process kill
-    // between launches) would leave one non-zero for the next user of this cache -- every prefill starts from zeros (ADVICE r4)
-    PGV_HIP(hipMemsetAsync(kv->dattn_ticket, 0, (size_t)kv->B * heads * sizeof(unsigned), s));
     int M = 0, max_len = 0;
     for (int b = 0; b < B; ++b) {
         const int off = append ? kv->h_len[b] : 0;
@@ -476,10 +494,11 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
         M += h_seq_lens[b];
         if (h_seq_lens[b] > max_len) max_len = h_seq_lens[b];
     }
-    // ---- host-built row maps: [row_src | row_b | row_pos | cu (B+1) | last_rows (B) | lens (B) = positions after this call | offs (B)] ----
+    // ---- host-built row maps: [row_src | row_b | row_pos | cu (B+1) | last_rows (B) | lens (B) = positions after this call | offs (B) | slots (B)] ----
     std::vector<int>& meta = kv->h_meta;
-    meta.assign((size_t)3 * M + 4 * B + 1, 0);
+    meta.assign((size_t)3 * M + 5 * B + 1, 0);
     int* row_src = meta.data(); int* row_b = row_src + M; int* row_pos = row_b + M; int* cu = row_pos + M; int* last = cu + B + 1; int* lens = last + B; int* offs = lens + B;
+    int* slot = offs + B;
     int r = 0;
     for (int b = 0; b < B; ++b) {
         cu[b] = r;
@@ -491,27 +510,35 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
             const bool vid = vp >= 0 && p > vp && p <= vp + Vt;
             if (!vid) PGV_CHECK(id >= 0 && id < vocab, "%s: token id %d at row %d outside the vocabulary (%d)", who, id, r, vocab);
             row_src[r] = vid ? -(b * Vt + (p - vp - 1) + 1) : id;
-            row_b[r] = b; row_pos[r] = off + p;
+            row_b[r] = slots ? h_slots[b] : b; row_pos[r] = off + p;
         }
-        last[b] = r - 1; lens[b] = off + h_seq_lens[b]; offs[b] = off;
+        last[b] = r - 1; lens[b] = off + h_seq_lens[b]; offs[b] = off; slot[b] = slots ? h_slots[b] : b;
     }
     cu[B] = r;
+    // arrival tickets of the context-split decode attention: a launch re-arms its own, but an ABORTED decode launch (device fault, process kill
+    // between launches) would leave one non-zero for the next user of this cache -- every prefill starts from zeros (ADVICE r4)
+    PGV_HIP(hipMemsetAsync(kv->dattn_ticket, 0, (size_t)kv->B * heads * sizeof(unsigned), s));
 
     const size_t b_meta = pgv_align(meta.size() * 4), b_resid = pgv_align((size_t)M * H * 4), b_xn = pgv_align((size_t)M * H * 2),
                  b_qkv = pgv_align((size_t)M * 3 * H * 2), b_ao = pgv_align((size_t)M * H * 2), b_act = pgv_align((size_t)M * I * 2);
-    PGV_TRY(pgv_ws_reserve(ctx, b_meta + b_resid + b_xn + b_qkv + b_ao + b_act, s));
+    const size_t b_pick = slots ? pgv_align((size_t)B * 4) : 0;
+    PGV_TRY(pgv_ws_reserve(ctx, b_meta + b_resid + b_xn + b_qkv + b_ao + b_act + b_pick, s));
     int* d_meta = (int*)pgv_ws_alloc(ctx, b_meta);
     float* resid = (float*)pgv_ws_alloc(ctx, b_resid);
     char* xn = (char*)pgv_ws_alloc(ctx, b_xn);
     char* qkv = (char*)pgv_ws_alloc(ctx, b_qkv);
     char* ao = (char*)pgv_ws_alloc(ctx, b_ao);
     char* act = (char*)pgv_ws_alloc(ctx, b_act);
-    PGV_CHECK(d_meta && resid && xn && qkv && ao && act, "pgv_llm_prefill: workspace exhausted");
+    int* d_pick = slots ? (int*)pgv_ws_alloc(ctx, b_pick) : nullptr;       // the refilled sequences' first tokens, before they go to their slots
+    PGV_CHECK(d_meta && resid && xn && qkv && ao && act && (!slots || d_pick), "%s: workspace exhausted", who);
     PGV_HIP(hipMemcpyAsync(d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
     const int* d_row_src = d_meta; const int* d_row_b = d_meta + M; const int* d_row_pos = d_row_b + M; const int* d_cu = d_row_pos + M;
     const int* d_last = d_cu + B + 1; const int* d_lens = d_last + B; const int* d_offs = append ? d_lens + B : nullptr;
-    PGV_HIP(hipMemcpyAsync(kv->d_pos, d_lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
+    const int* d_slots = slots ? d_lens + 2 * B : nullptr;
+    if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
+        PGV_HIP(hipMemcpyAsync(kv->d_pos, d_lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+        PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
+    }
 
     PGV_TRY(pgv_launch_embed_splice(m->dtype, d_row_src, m->embed, d_video, resid, M, H, s));
     double attn_flops = 0;
@@ -523,7 +550,7 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
         g.A = xn; g.lda = H; g.W = l.wqkv; g.ldw = H; g.bias = nullptr; g.C = qkv; g.ldc = 3 * H; g.M = M; g.N = 3 * H; g.K = H; g.epi = PGV_EPI_NONE; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
         PGV_TRY(pgv_launch_rope_kv_write(m->dtype, qkv, d_row_b, d_row_pos, m->rope, kv->Kc[li], kv->Vc[li], M, H, heads, kv->max_seq, s));
-        PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, qkv, ao, kv->Kc[li], kv->Vc[li], d_cu, d_offs, B, max_len, H, heads, kv->max_seq, attn_flops, s));
+        PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, qkv, ao, kv->Kc[li], kv->Vc[li], d_cu, d_offs, B, max_len, H, heads, kv->max_seq, attn_flops, s, d_slots));
         g = GemmArgs{}; g.A = ao; g.lda = H; g.W = l.wo; g.ldw = H; g.C = resid; g.ldc = H; g.M = M; g.N = H; g.K = H; g.epi = PGV_EPI_RESID; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, l.post_g, m->cfg.eps, xn, M, H, s));
@@ -542,18 +569,29 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
     }
     // lm_head only on the last position of every sequence (the reference computes all S positions, video_chatgpt.py:226)
+    // (a refill runs this tail in rows [0, B) of the decode scratch: every decode step rebuilds resid / xn / ssq / logits / amax_* from d_cur)
     PGV_TRY(pgv_launch_gather_rows(resid, d_last, kv->resid, B, H, s));
-    if (norm_fold_enabled()) {
-        PGV_TRY(pgv_launch_final_prep(m->dtype, kv->resid, m->norm_g, kv->xn, kv->ssq, B, H, s, true));
-        PGV_TRY(lm_head_and_pick(ctx, m, kv, B, -1, 0, s, 1));
+    const int nparts = norm_fold_enabled() ? 1 : 0;
+    if (nparts) PGV_TRY(pgv_launch_final_prep(m->dtype, kv->resid, m->norm_g, kv->xn, kv->ssq, B, H, s, true));
+    else PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
+    if (!slots) {
+        PGV_TRY(lm_head_and_pick(ctx, m, kv, B, -1, 0, s, nparts));
     } else {
-        PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
-        PGV_TRY(lm_head_and_pick(ctx, m, kv, B, -1, 0, s, 0));
+        PGV_TRY(lm_head(ctx, m, kv, B, true, s, nparts));           // the greedy candidates too: the same launch as a plain prefill, same logits
+        pgv_prof_begin(ctx, 6, s);
+        if (d_u) PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, temperature, top_k, d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s));
+        else PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (vocab + 15) / 16, kv->amax_ts, vocab, B, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s));
+        PGV_TRY(pgv_launch_slot_scatter(d_slots, d_pick, d_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
+        pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
     if (d_logits) PGV_HIP(hipMemcpyAsync(d_logits, kv->logits, (size_t)B * vocab * 4, hipMemcpyDeviceToDevice, s));
-    if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    for (int b = 0; b < kv->B; ++b) kv->h_len[b] = b < B ? lens[b] : 0;
-    kv->active = B;
+    if (d_next) PGV_HIP(hipMemcpyAsync(d_next, slots ? d_pick : kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    if (slots) {
+        for (int b = 0; b < B; ++b) kv->h_len[h_slots[b]] = lens[b];
+    } else {
+        for (int b = 0; b < kv->B; ++b) kv->h_len[b] = b < B ? lens[b] : 0;
+        kv->active = B;
+    }
     PGV_HIP(hipGetLastError());
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
@@ -567,6 +605,13 @@ extern "C" int pgv_llm_prefill(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32
 extern "C" int pgv_llm_prefill_append(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video,
                                       int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream) {
     return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, B, d_video, Vt, h_vid_pos, d_logits, d_next, d_all_logits, ld_all, stream, true);
+}
+
+extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_slots, int n, const int32_t* h_ids, const int32_t* h_seq_lens,
+                                     const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k, const float* d_u, float* d_logits,
+                                     int32_t* d_next, void* stream) {
+    PGV_CHECK(h_slots, "pgv_llm_prefill_slots: null slot list");
+    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, n, d_video, Vt, h_vid_pos, d_logits, d_next, nullptr, 0, stream, false, h_slots, temperature, top_k, d_u);
 }
 
 // Drop the tail of sequence b: the next pgv_llm_prefill_append / decode call continues at position `len` (the entries beyond it are simply

@@ -20,8 +20,9 @@ int pgv_launch_embed_splice(int dtype, const int* row_src, const void* embed, co
 int pgv_launch_gather_rows(const float* src, const int* rows, float* dst, int B, int H, hipStream_t s);
 int pgv_launch_rope_kv_write(int dtype, void* qkv, const int* row_b, const int* row_pos, const void* rope, void* Kc, void* Vc, int M, int H,
                              int heads, int max_seq, hipStream_t s);
+// slot [B]: cache slot of sequence b (null: b; pgv_llm_prefill_slots)
 int pgv_launch_prefill_attn(pgv_ctx* ctx, int dtype, const void* qkv, void* out, const void* Kc, const void* Vc, const int* cu, const int* koff, int B, int max_len,
-                            int H, int heads, int max_seq, double flops, hipStream_t s);
+                            int H, int heads, int max_seq, double flops, hipStream_t s, const int* slot = nullptr);
 // gemv.hip
 // w12: the 12-bit copy of W (w12.h), streamed instead of W at batches of one column tile (B <= 16) -- bitwise the same result; W may be null
 // only when B <= 16.  rows = the row count it was encoded with (>= N).
@@ -44,6 +45,8 @@ int pgv_launch_sample(const float* logits, int V, int B, float temperature, int 
                       int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s);
 int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, int* next, int* pos, int* step, int* hist, int hist_stride, int* done,
                             int eos, int advance, hipStream_t s);
+// pgv_llm_prefill_slots: sequence i of the call becomes slot slots[i] -- cur = pick[i], pos = lens[i], step = done = 0
+int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, int n, int* cur, int* pos, int* step, int* done, hipStream_t s);
 
 #if defined(__HIPCC__)
 // sum over each aligned group of 16 lanes with DPP (VALU latency) instead of ds_bpermute shuffles (LDS crossbar latency):

@@ -79,6 +79,7 @@ struct PrefillAttnArgs {
     const char* Vc;
     const int* cu;        // [B+1] row offsets
     const int* koff;      // [B] tokens already in the cache in front of this call's rows (null: 0) -- query i sits at position koff + i
+    const int* slot;      // [B] cache slot sequence b reads and writes (null: b) -- pgv_llm_prefill_slots refills some slots of a live group
     int H, heads, max_seq;
     float scale_log2e;
 };
@@ -90,6 +91,7 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(PrefillAttnArgs p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.z, h = blockIdx.y;
+    const int cb = p.slot ? p.slot[b] : b;            // cache slot of this sequence
     const int r0 = p.cu[b], S = p.cu[b + 1] - r0;
     const int q0 = blockIdx.x * 128;
     if (q0 >= S) return;
@@ -99,8 +101,8 @@ __global__ __launch_bounds__(256) void prefill_attn_kernel(PrefillAttnArgs p) {
     const int qi = q0 + w * 32 + l31;                 // this lane's query index within this call's rows of the sequence
     const int qpos = off + qi;                        // ... and its position
     const int qrow = r0 + min(qi, S - 1);
-    const char* kbase = p.Kc + ((size_t)b * p.heads + h) * p.max_seq * HD * 2;
-    const char* vbase = p.Vc + ((size_t)b * p.heads + h) * p.max_seq * HD * 2;
+    const char* kbase = p.Kc + ((size_t)cb * p.heads + h) * p.max_seq * HD * 2;
+    const char* vbase = p.Vc + ((size_t)cb * p.heads + h) * p.max_seq * HD * 2;
 
     typename T::v8 qf[8];
 #pragma unroll
@@ -254,9 +256,9 @@ int pgv_launch_rope_kv_write(int dtype, void* qkv, const int* row_b, const int* 
     return PGV_OK;
 }
 int pgv_launch_prefill_attn(pgv_ctx* ctx, int dtype, const void* qkv, void* out, const void* Kc, const void* Vc, const int* cu, const int* koff, int B, int max_len,
-                            int H, int heads, int max_seq, double flops, hipStream_t s) {
+                            int H, int heads, int max_seq, double flops, hipStream_t s, const int* slot) {
     PrefillAttnArgs a;
-    a.qkv = (const char*)qkv; a.out = (char*)out; a.Kc = (const char*)Kc; a.Vc = (const char*)Vc; a.cu = cu; a.koff = koff;
+    a.qkv = (const char*)qkv; a.out = (char*)out; a.Kc = (const char*)Kc; a.Vc = (const char*)Vc; a.cu = cu; a.koff = koff; a.slot = slot;
     a.H = H; a.heads = heads; a.max_seq = max_seq;
     a.scale_log2e = 0.08838834764831845f * 1.4426950408889634f;    // 128^-0.5 * log2(e)
     dim3 grid((max_len + 127) / 128, heads, B);

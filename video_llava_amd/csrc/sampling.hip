@@ -203,7 +203,27 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// pgv_llm_prefill_slots: the picks of the n refilled sequences (computed in rows [0, n) of the cache's scratch) become the state of their slots;
+// every other slot's position, current token, step counter and done flag stays as it is.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void slot_scatter_kernel(const int* __restrict__ slots, const int* __restrict__ pick, const int* __restrict__ lens, int n,
+                                                          int* __restrict__ cur, int* __restrict__ pos, int* __restrict__ step, int* __restrict__ done) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int sl = slots[i];
+    cur[sl] = pick[i];
+    pos[sl] = lens[i];
+    step[sl] = 0;
+    done[sl] = 0;
+}
+
 }  // namespace
+
+int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, int n, int* cur, int* pos, int* step, int* done, hipStream_t s) {
+    hipLaunchKernelGGL(slot_scatter_kernel, dim3((n + 63) / 64), dim3(64), 0, s, slots, pick, lens, n, cur, pos, step, done);
+    return PGV_OK;
+}
 
 int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, int* next, int* pos, int* step, int* hist, int hist_stride, int* done,
                             int eos, int advance, hipStream_t s) {

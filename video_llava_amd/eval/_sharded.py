@@ -25,7 +25,15 @@ def add_runtime_arguments(parser):
                              "token step is shared by the whole group, so larger groups raise videos/s: 8.9 / 13.4 / 16.2 / 18.9 at 8 / 16 / 32 / 64 on MI355X). "
                              "auto (default): the largest of 8 / 16 / 32 / 64 whose KV cache + tower workspace fit the GPU's free memory (pick_batch)")
     parser.add_argument("--max_new_tokens", type=int, default=1024)
-    parser.add_argument("--do_sample", action="store_true", help="reference decoding: temperature-0.2 sampling, one clip at a time")
+    parser.add_argument("--do_sample", action="store_true", help="reference decoding: temperature-0.2 sampling, one clip at a time (with --schedule refill: "
+                                                                 "batched, every task drawing from its own seeded stream)")
+    parser.add_argument("--schedule", choices=("group", "refill"), default="group",
+                        help="group (default): answer the shard in static groups of --batch clips, each decoding until its longest answer ends; refill: keep "
+                             "--batch decode slots busy and refill a slot with the next task as soon as its answer ends (continuous batching, "
+                             "video_llava_amd/continuous.py) -- the same answers, fewer wasted decode steps when answer lengths differ")
+    parser.add_argument("--seed", type=int, default=0,
+                        help="--schedule refill --do_sample: task i samples from torch.Generator seeded with seed * 1000003 + i, so its answer does "
+                             "not depend on --batch or on the slot it lands in")
     parser.add_argument("--timings", default=None, metavar="OUT.jsonl",
                         help="append one JSON line per answered task (rank-local file `OUT.jsonl.rank<r>` when world > 1): frame load, upload + ingest, "
                              "tower + pool, prefill, decode seconds, generated tokens, group size, feature-cache hit (SURVEY 5: per-clip stage timings)")
@@ -283,6 +291,78 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
         group_no[0] += 1
         return toks, lens
 
+    def infer_refill(indices, clips=None):
+        """--schedule refill: the whole shard through generate_continuous.  The groups of --batch tasks still drive the host half -- prepare()
+        one group ahead on a background thread, one tower pass per group, the feature cache -- but decode slots are refilled task by task."""
+        from concurrent.futures import ThreadPoolExecutor
+        from ..continuous import Task, generate_continuous
+        W = max(1, int(args.batch))
+        groups = [indices[g0:g0 + W] for g0 in range(0, len(indices), W)]
+        toks = torch.zeros(len(indices), args.max_new_tokens, dtype=torch.int32)
+        lens = [0] * len(indices)
+        row = {idx: j for j, idx in enumerate(indices)}
+        info = {}
+        eos = model.config.eos_token_id
+
+        def stream():
+            pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="pgv-prefetch")
+            try:
+                fut = pool.submit(prepare, groups[0]) if groups else None
+                for gi, group in enumerate(groups):
+                    try:
+                        clips_g = fut.result()
+                    except Exception as e:                             # noqa: BLE001 -- the group's tasks fail, the others go on
+                        clips_g = {tasks[i]["path"]: e for i in group}
+                    fut = pool.submit(prepare, groups[gi + 1]) if gi + 1 < len(groups) else None
+                    load_s = clips_g.pop("__load_s__", {})
+                    tm_v = {} if tfile else None
+                    feat_of = features_for(clips_g, tm_v)
+                    n_fresh = sum(1 for f in clips_g.values() if not isinstance(f, (Exception, _Cached)))
+                    for idx in group:
+                        t = tasks[idx]
+                        info[idx] = {"group": gi, "load_s": load_s.get(t["path"], 0.0), "hit": isinstance(clips_g.get(t["path"]), _Cached),
+                                     "tm_v": tm_v or {}, "n_fresh": n_fresh}
+                        if t["path"] is None:
+                            print(f"Error processing video file '{t['name']}': not found")
+                            continue
+                        try:
+                            if t["path"] not in feat_of:
+                                raise clips_g[t["path"]]
+                            prompt, stop = build_prompt(t["question"], args.conv_mode, video_token_len, use_se)
+                            ids = tokenizer([prompt]).input_ids[0]
+                            stop_strs[idx] = stop
+                            yield Task(idx, ids, feat_of[t["path"]], stop=stop, seed=int(getattr(args, "seed", 0)) * 1000003 + idx)
+                        except Exception as e:                         # noqa: BLE001 -- the reference's print-and-continue
+                            print(f"Error processing video file '{t['name']}': {e}")
+            finally:
+                pool.shutdown(wait=True, cancel_futures=True)
+
+        def failed(task_id, e):
+            print(f"Error processing video file '{tasks[task_id]['name']}': {e}")
+
+        tm = {} if tfile else None
+        for idx, new in generate_continuous(model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
+                                            tokenizer=tokenizer, on_error=failed, timings=tm):
+            if new is None:
+                continue
+            if eos is not None and eos in new:
+                new = new[:new.index(eos)]
+            new = new[:args.max_new_tokens]
+            j = row[idx]
+            toks[j, :len(new)] = torch.tensor(new, dtype=torch.int32)
+            lens[j] = len(new) + 1
+        if tfile:
+            for j, idx in enumerate(indices):
+                t, inf, g = tasks[idx], info.get(idx, {}), (tm or {}).get(idx, {})
+                tfile.write(json.dumps({"task": idx, "video": t["name"], "rank": rank, "group": inf.get("group", -1), "group_size": g.get("group_size"),
+                                        "ok": lens[j] > 0, "tokens": max(lens[j] - 1, 0), "feature_cache_hit": inf.get("hit", False),
+                                        "load_s": inf.get("load_s", 0.0), "upload_ingest_s_group": inf.get("tm_v", {}).get("upload_ingest_s", 0.0),
+                                        "tower_pool_s_group": inf.get("tm_v", {}).get("tower_pool_s", 0.0), "clips_in_tower_pass": inf.get("n_fresh", 0),
+                                        "prefill_s_group": g.get("prefill_s"), "decode_s_group": g.get("decode_s"),
+                                        "decode_steps_group": g.get("steps")}) + "\n")
+            tfile.flush()
+        return toks, lens
+
     def infer_sampled(indices, clips=None):
         """--do_sample: the reference's temperature-0.2 sampling with its stopping criterion, one task at a time (video_chatgpt_infer's
         path up to the detokenisation); the ids travel through the same fixed-shape collation as the greedy answers."""
@@ -329,7 +409,11 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
     if spill:
         os.makedirs(args.output_dir, exist_ok=True)
     try:
-        if args.do_sample:
+        if getattr(args, "schedule", "group") == "refill":
+            # one infer call over the whole shard (it prefetches its own groups); the answers collate like the static groups'
+            answers = parallel.run_sharded(len(tasks), infer_refill, args.max_new_tokens, rank, world, device, per_gpu_batch=max(1, len(tasks)),
+                                           length_offset=1, spill_path=spill)
+        elif args.do_sample:
             answers = parallel.run_sharded(len(tasks), infer_sampled, args.max_new_tokens, rank, world, device, per_gpu_batch=1, length_offset=1, prepare=prepare,
                                            spill_path=spill)
         else:

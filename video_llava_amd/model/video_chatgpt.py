@@ -395,6 +395,49 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             return kv, nxt, logits, all_logits[:, :self.vocab_size]
         return kv, nxt, logits
 
+    def prefill_slots(self, kv, slots: Sequence[int], seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor],
+                      want_logits: bool = False, u: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 50):
+        """Prefill NEW prompts `seqs` into cache slots `slots` of the live group `kv` (a handle prefill() returned) while the other slots keep
+        their state (pgv_llm_prefill_slots: continuous batching).  `video_spatio_temporal_features` [n, V, C] (None: text only; a text-only
+        prompt next to video ones takes any [V, C] block, it is not read).  u [n] (optional): draw each first token as sample_last does,
+        else greedy.  Returns (first tokens [n] int32 on device, logits [n, vocab] or None)."""
+        n = len(seqs)
+        if len(slots) != n:
+            raise ValueError(f"{len(slots)} slots for {n} prompts")
+        lens = [len(s) for s in seqs]
+        feats = video_spatio_temporal_features
+        proj, V, vid_pos = None, 0, [-1] * n
+        if feats is not None:
+            if feats.dim() == 2:
+                feats = feats.unsqueeze(0)
+            proj = self.model.mm_projector(feats.to(self.device_))
+            if isinstance(self.model.mm_projector, IdentityMap):
+                proj = proj.to(self.dtype_)
+            proj = proj.contiguous()
+            V = proj.shape[1]
+            if proj.shape[0] != n:
+                raise ValueError(f"{proj.shape[0]} video feature sets for {n} prompts")
+            vid_pos = self._video_positions(seqs, V)
+        flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
+        nxt = torch.empty(n, dtype=torch.int32, device=self.device_)
+        logits = torch.empty(n, self.vocab_size, dtype=torch.float32, device=self.device_) if want_logits else None
+        if u is not None:
+            u = u.to(device=self.device_, dtype=torch.float32).contiguous()
+            assert u.numel() == n
+        _lib.check(self.ctx.lib.pgv_llm_prefill_slots(self.ctx.handle, self.handle, kv, (C.c_int32 * n)(*[int(s) for s in slots]), n,
+                                                      flat.ctypes.data_as(C.c_void_p), (C.c_int32 * n)(*lens),
+                                                      proj.data_ptr() if proj is not None else None, V, (C.c_int32 * n)(*vid_pos),
+                                                      float(temperature), int(top_k), u.data_ptr() if u is not None else None,
+                                                      logits.data_ptr() if logits is not None else None, nxt.data_ptr(),
+                                                      _lib.stream_ptr(self.device_)), "pgv_llm_prefill_slots")
+        return nxt, logits
+
+    def kv_len(self, kv, b: int) -> int:
+        return int(self.ctx.lib.pgv_kv_len(kv, int(b)))
+
+    def kv_truncate(self, kv, b: int, length: int):
+        _lib.check(self.ctx.lib.pgv_kv_truncate(kv, int(b), int(length), _lib.stream_ptr(self.device_)), "pgv_kv_truncate")
+
     def decode_step(self, kv, last: torch.Tensor, want_logits: bool = False):
         B = last.shape[0]
         nxt = torch.empty(B, dtype=torch.int32, device=self.device_)
