@@ -325,6 +325,49 @@ def test_vit_800_frames_benched_shape(ctx, dtype, tol):
     assert e < tol
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_vit_peaked_attention_tower_vs_oracle(ctx, dtype):
+    """A tower whose attention is sharply peaked, as real CLIP-L heads are: CLIP_TINY's width and depth at 224 px (257 tokens = 3 key chunks,
+    2 frames) with the q / k projections scaled by 4 (score std 6.8 instead of 0.4).  Asserted on the fp32 oracle: rows whose largest attention
+    weight exceeds 0.9 exist in some layer, and the float64 route model of tests/test_gpu_vit_attention.py, fed the oracle's q / k of that layer,
+    reports failed speculations -- synth.make_clip_weights alone (flat softmax) never leaves the speculative route of csrc/vit_attn.hip.
+    Tolerance: the oracle run in the same 16-bit dtype on the host is the yardstick, the HIP path stays within 1.25 x its distance
+    from the fp32 oracle.  Measured (path / yardstick): fp16 9.17e-4 / 2.16e-3, bf16 7.32e-3 / 1.70e-2."""
+    import dataclasses
+    import math
+
+    from test_gpu_vit_attention import S2, kernel_model
+    cfg = dataclasses.replace(synth.CLIP_TINY, image=224)
+    w = synth.make_clip_weights(cfg, seed=5)
+    for i in range(cfg.layers):
+        for name in ("q_proj", "k_proj"):
+            for part in ("weight", "bias"):
+                key = f"vision_model.encoder.layers.{i}.self_attn.{name}.{part}"
+                w[key] = w[key] * np.float32(4.0)
+    frames = synth.make_frames(2, 224, seed=6)
+    px = ovis.clip_preprocess(frames)
+    hs = ovis.clip_hidden_states(px, w, cfg, upto=cfg.layers - 1)
+    peaked_rows, failed = [], []
+    for i in range(cfg.layers - 1):
+        p = f"vision_model.encoder.layers.{i}."
+        h = ovis._layer_norm(hs[i], ovis._t(w, p + "layer_norm1.weight", torch.float32), ovis._t(w, p + "layer_norm1.bias", torch.float32), cfg.eps)
+        q, k = ((h @ ovis._t(w, p + f"self_attn.{n}.weight", torch.float32).t() + ovis._t(w, p + f"self_attn.{n}.bias", torch.float32))
+                .view(2, cfg.tokens, cfg.heads, 64).transpose(1, 2).reshape(2 * cfg.heads, cfg.tokens, 64).double() for n in ("q_proj", "k_proj"))
+        s2 = S2 * q @ k.transpose(1, 2)
+        peaked_rows.append(int((torch.softmax(s2 * math.log(2.0), -1).amax(-1) > 0.9).sum()))
+        failed.append(int((kernel_model(s2)["route"][:, :, 1:] >= 2).sum()))
+    print(f"peaked tower: rows with a weight > 0.9 per layer {peaked_rows}, failed speculations per layer {failed} of {2 * cfg.heads * 9 * 2} (block, chunk) pairs")
+    assert max(peaked_rows) >= 100 and max(failed) >= 20
+    tower = _tower(cfg, w, dtype)
+    got = tower(ctx.preprocess_u8(torch.from_numpy(frames).to(DEV), dtype), output_hidden_states=True).hidden_states
+    assert len(got) == cfg.layers + 1
+    ref = hs[-1]
+    yard = rel(ovis.clip_hidden_states(px.to(dtype), w, cfg, upto=cfg.layers - 1)[-1].float(), ref)
+    e = rel(got[-2], ref)
+    print(f"peaked tower {dtype}: HIP path vs fp32 oracle {e:.3e}; the oracle in {dtype} on the host vs fp32 oracle {yard:.3e}")
+    assert torch.isfinite(got[-2].float()).all() and e <= 1.25 * yard
+
+
 @pytest.mark.parametrize("dtype,tol", [(torch.float16, 1e-3), (torch.bfloat16, 8e-3)])
 def test_vit_336_even_row_count(ctx, dtype, tol):
     """336 px (N = 577): 14 frames in one lane = 8078 rows -> 32 tile rows (even -> W-resident order for qkv / fc1); the same frames in
