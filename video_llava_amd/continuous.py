@@ -16,6 +16,8 @@ from typing import Any, Callable, Iterable, Iterator, List, Optional, Tuple
 import numpy as np
 import torch
 
+from .model.utils import AnswerState
+
 DEFAULT_CHUNK = 16          # decode steps between two host checks (EOS / stop strings / budgets) and refills
 
 
@@ -39,13 +41,32 @@ def task_uniforms(n: int, seed: int, device) -> torch.Tensor:
 
 
 class _Slot:
-    __slots__ = ("task", "new", "budget", "scanned", "u", "prefill_s", "decode_s", "steps", "group_size")
+    """A decode slot's task: its answer state and what the scheduler keeps about it (uniform stream, timing counters)."""
+    __slots__ = ("task", "answer", "u", "prefill_s", "decode_s", "steps", "group_size")
 
-    def __init__(self, task: Task, budget: int, u: Optional[torch.Tensor], prefill_s: float, group_size: int):
-        self.task, self.budget, self.u, self.group_size = task, budget, u, group_size
-        self.new: List[int] = []
-        self.scanned = 2            # stop strings: prefixes shorter than this are known not to fire (as in generate)
+    def __init__(self, task: Task, answer: AnswerState, u: Optional[torch.Tensor], prefill_s: float, group_size: int):
+        self.task, self.answer, self.u, self.group_size = task, answer, u, group_size
         self.prefill_s, self.decode_s, self.steps = prefill_s, 0.0, 0
+
+
+def split_refused(parts: List[list], call: Callable[[list], Any]) -> Iterator[Tuple[list, Any, Optional[Exception]]]:
+    """`call(part)` for every part, in order.  A call that raises was refused as a whole (one bad item, or too much at once): its part is split
+    in halves and tried again, until the bad item is alone.  Yields (part, result, None) for a call that went through and (part of one item,
+    None, exception) for an item refused on its own."""
+    parts = list(parts)
+    while parts:
+        part = parts.pop(0)
+        if not part:
+            continue
+        try:
+            result = call(part)
+        except Exception as e:                                     # noqa: BLE001
+            if len(part) > 1:
+                parts[:0] = [part[:len(part) // 2], part[len(part) // 2:]]
+            else:
+                yield part, None, e
+            continue
+        yield part, result, None
 
 
 def _default_on_error(task_id, exc):
@@ -61,7 +82,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     task costs only itself.
 
     width: decode slots (<= 64).  The group opens with `model.prefill` over the first `width` tasks; every `chunk` decode steps the host applies
-    EOS, the stop-string cut (`first_stop_length`, scanned incrementally: exactly generate's rule) and the budgets, then refills the freed slots
+    EOS, the stop-string cut and the budgets (model.utils.AnswerState, the bookkeeping `generate` keeps per sequence), then refills the freed slots
     with ONE `prefill_slots` call once at least `refill_min` slots are free (default: width // 8, at least 1) -- or sooner when waiting would
     stall: no task left decoding, or the queue holds fewer tasks than that.  Slots without a task are rewound to one position every chunk
     (pgv_kv_truncate) so that they neither outgrow the cache nor read a long one.
@@ -80,7 +101,6 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     eos = model.config.eos_token_id if eos_token_id == "config" else eos_token_id
     eos_i = -1 if eos is None else int(eos)
     dev = model.device_
-    from .model.utils import first_stop_length
 
     source = iter(tasks)
     pending: List[Tuple[int, Task]] = []
@@ -161,41 +181,20 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     if do_sample:
         nxt = model.sample_last(kv, torch.stack([u[0] for u in us]), temperature, top_k)
     cur = nxt.clone()
-    first_tok = nxt.cpu().tolist()
+    first_tok = nxt.cpu().numpy()
     dt = time.perf_counter() - t0
     for s, (a, t) in enumerate(first):
-        slots[s] = _Slot(t, budget_of(t), us[s], dt, W)
-    finished: List[int] = []
-
-    def absorb(s: int, toks: List[int]) -> bool:
-        """Append a slot's tokens of this chunk (up to its budget and first EOS), apply the stop-string cut; True = the task is finished."""
-        sl = slots[s]
-        take = toks[:sl.budget - len(sl.new)]
-        done = False
-        if eos_i >= 0 and eos_i in take:
-            take = take[:take.index(eos_i) + 1]
-            done = True
-        sl.new.extend(take)
-        if len(sl.new) >= sl.budget:
-            done = True
-        if sl.task.stop and len(sl.new) >= 2:
-            n = first_stop_length(sl.new, tokenizer, [sl.task.stop], start=sl.scanned)
-            if n is not None:
-                del sl.new[n:]
-                return True
-            sl.scanned = len(sl.new) + 1
-        return done
+        slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), us[s], dt, W)
 
     def finish(s: int):
         sl = slots[s]
         slots[s] = None
-        finished.append(s)
         if timings is not None:
             timings[sl.task.task_id] = {"prefill_s": sl.prefill_s, "decode_s": sl.decode_s, "steps": sl.steps, "group_size": sl.group_size}
-        return sl.task.task_id, list(sl.new)
+        return sl.task.task_id, sl.answer.new
 
     for s in range(W):
-        if absorb(s, [first_tok[s]]):
+        if slots[s].answer.take(first_tok[s:s + 1]):
             yield finish(s)
 
     # ---- decode / refill loop --------------------------------------------------------------------------------------
@@ -219,32 +218,28 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                     pull(1)
                     if not pending:
                         break
-            parts = [group]
-            ok: List[Tuple[int, int, Task, int, float]] = []
-            while parts:
-                part = parts.pop(0)
-                if not part:
-                    continue
+
+            def prefill_part(part):
                 t0 = time.perf_counter()
-                try:
-                    u_part = [uniforms(a, t) for _, a, t in part]
-                    u0 = torch.stack([u[0] for u in u_part]) if do_sample else None
-                    nx, _ = model.prefill_slots(kv, [s for s, _, _ in part], [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
-                                                u=u0, temperature=temperature, top_k=top_k)
-                    cur[[s for s, _, _ in part]] = nx
-                    firsts = nx.cpu().tolist()
-                    dt = time.perf_counter() - t0
-                    for (s, a, t), u, f in zip(part, u_part, firsts):
-                        slots[s] = _Slot(t, budget_of(t), u, dt, len(part))
-                        ok.append((s, a, t, f, dt))
-                except Exception as e:                             # noqa: BLE001 -- the call was refused as a whole: split it, isolate the bad task
-                    if len(part) > 1:
-                        parts[:0] = [part[:len(part) // 2], part[len(part) // 2:]]
-                    else:
-                        on_error(part[0][2].task_id, e)
-                        yield part[0][2].task_id, None
-            for s, _, _, f, _ in ok:
-                if absorb(s, [f]):
+                u_part = [uniforms(a, t) for _, a, t in part]
+                u0 = torch.stack([u[0] for u in u_part]) if do_sample else None
+                nx, _ = model.prefill_slots(kv, [s for s, _, _ in part], [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
+                                            u=u0, temperature=temperature, top_k=top_k)
+                cur[[s for s, _, _ in part]] = nx
+                return u_part, nx.cpu().numpy(), time.perf_counter() - t0
+
+            ok: List[Tuple[int, np.ndarray]] = []
+            for part, res, e in split_refused([group], prefill_part):
+                if e is not None:                                  # the bad task, isolated
+                    on_error(part[0][2].task_id, e)
+                    yield part[0][2].task_id, None
+                    continue
+                u_part, firsts, dt = res
+                for i, (s, _, t) in enumerate(part):
+                    slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), u_part[i], dt, len(part))
+                    ok.append((s, firsts[i:i + 1]))
+            for s, f in ok:
+                if slots[s].answer.take(f):
                     yield finish(s)
             continue                                                # re-evaluate: refilled slots may have finished at their first token
         if live == 0:
@@ -255,20 +250,20 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         for s in free:
             if model.kv_len(kv, s) > 1:
                 model.kv_truncate(kv, s, 1)
-        n = min(chunk, max(slots[s].budget - len(slots[s].new) for s in range(W) if slots[s] is not None))
+        n = min(chunk, max(sl.answer.budget - len(sl.answer.new) for sl in slots if sl is not None))
         t0 = time.perf_counter()
         if do_sample:
             u = torch.full((n, W), 0.5, dtype=torch.float32, device=dev)
             for s in range(W):
                 sl = slots[s]
                 if sl is not None:
-                    seg = sl.u[len(sl.new):len(sl.new) + n]
+                    seg = sl.u[len(sl.answer.new):len(sl.answer.new) + n]
                     u[:seg.numel(), s] = seg
             toks = model.decode_sample(kv, cur, n, eos_i, temperature, top_k, u)
         else:
             toks = model.decode_greedy(kv, cur, n, eos_i)
         cur = toks[:, n - 1].contiguous()
-        host = toks.cpu().tolist()
+        host = toks.cpu().numpy()
         dt = time.perf_counter() - t0
         for s in range(W):
             sl = slots[s]
@@ -276,5 +271,5 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                 continue
             sl.decode_s += dt
             sl.steps += n
-            if absorb(s, host[s]):
+            if sl.answer.take(host[s]):
                 yield finish(s)

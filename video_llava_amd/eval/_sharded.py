@@ -8,7 +8,9 @@ the ranks (one process per GPU), each rank answers its shard in groups of `--bat
 (the launch shape bench.py measures), batched prefill + KV-cached greedy decode in libpgv, while a background thread decodes the next
 group's frames into pinned memory; the only collective is the final all-gather of the answer token ids (video_llava_amd/parallel.py).
 A task whose video is missing or fails yields None (the reference prints and leaves the sample out).
-`do_sample=True` restores the reference's temperature-0.2 sampling through `video_chatgpt_infer`, one task at a time.
+`--schedule refill` keeps the groups for the host half and the tower pass, but decodes through continuous.generate_continuous: a slot whose
+answer has ended takes the next task at once.  `--do_sample` restores the reference's temperature-0.2 sampling: through `video_chatgpt_infer`
+one task at a time, or batched with `--schedule refill`, every task drawing from its own seeded stream.  `_Runner` holds what the schedules share.
 """
 from __future__ import annotations
 
@@ -136,58 +138,57 @@ class _Cached:
         self.feat = feat
 
 
-def answer_tasks(args, tasks, components, load_frames, rank, world):
-    """tasks: [{"path": str | None, "name": str, "question": str}] -> [str | None] in task order, identical on every rank."""
-    import json
-    import time
-    from .. import parallel
-    from ..inference import build_prompt, video_chatgpt_infer_ids, video_features, video_features_batch
+class _Runner:
+    """What the schedules of `answer_tasks` share on one rank: the host half of a group (`prepare`), its pooled features, a task's inputs,
+    the answer collation (`toks`, `lens`) and the --timings lines; `infer_batch` / `infer_refill` / `infer_sampled` are the schedules.
+    Length encoding: lens[j] = 0 = the task failed (no prediction), k + 1 = an answer of k tokens (k = 0 is a legitimate empty answer: the
+    reference writes pred = '' when the first token is EOS)."""
 
-    model, vision_tower, tokenizer, image_processor, video_token_len = components
-    use_se = model.get_model().vision_config.use_vid_start_end
-    stop_strs = {}
-    cache = FeatureCache(getattr(args, "feature_cache", FEATURE_CACHE_CLIPS))
-    timings_path = getattr(args, "timings", None)
-    if timings_path and world > 1:
-        timings_path = f"{timings_path}.rank{rank}"
-    tfile = open(timings_path, "a") if timings_path else None
-    group_no = [0]
+    def __init__(self, args, tasks, components, load_frames, rank, tfile):
+        from ..feature_extraction import PinnedRing
+        self.args, self.tasks, self.load_frames, self.rank, self.tfile = args, tasks, load_frames, rank, tfile
+        self.model, self.vision_tower, self.tokenizer, self.image_processor, self.video_token_len = components
+        self.use_se = self.model.get_model().vision_config.use_vid_start_end
+        self.cache = FeatureCache(getattr(args, "feature_cache", FEATURE_CACHE_CLIPS))
+        self.ring = PinnedRing()
+        self.stop_strs = {}             # task -> the stop string of its prompt
+        self.group_no = 0
 
-    from ..feature_extraction import PinnedRing
-    ring = PinnedRing()
-
-    def prepare(indices):
+    def prepare(self, indices):
         """HOST half of a group, run one group ahead on the prefetch thread (parallel.run_sharded): decode / sample the frames of the group's
         distinct clips into pinned memory -- except clips whose pooled features are still cached from an earlier group.
         -> {path: frames | _Cached | Exception} (+ "__load_s__": {path: seconds})"""
+        import time
         from ..feature_extraction import pin_frames
-        ring.new_group()
+        self.ring.new_group()
         clips, load_s = {}, {}
         for idx in indices:
-            path = tasks[idx]["path"]
+            path = self.tasks[idx]["path"]
             if path is None or path in clips:
                 continue
-            hit = cache.get(path)
+            hit = self.cache.get(path)
             if hit is not None:
                 clips[path] = _Cached(hit)
                 continue
             t0 = time.perf_counter()
             try:
-                clips[path] = pin_frames(load_frames(path), ring)
+                clips[path] = pin_frames(self.load_frames(path), self.ring)
             except Exception as e:                                     # noqa: BLE001 -- reported per task below, like the reference's except
                 clips[path] = e
             load_s[path] = time.perf_counter() - t0
         clips["__load_s__"] = load_s
         return clips
 
-    def features_for(clips, tm):
-        """{path: pooled features} for every usable clip of a group: cached ones as they are, the others through ONE tower pass."""
+    def features_for(self, clips, tm):
+        """{path: pooled features} for every usable clip of a group: cached ones as they are, the others through ONE tower pass
+        (inference.video_features_batch; bitwise equal to per-clip passes)."""
+        from .. import inference
         feat_of = {p: f.feat for p, f in clips.items() if isinstance(f, _Cached)}
         good = []
         for p, f in clips.items():
             if isinstance(f, (Exception, _Cached)):
                 continue
-            hit = cache.get(p)               # the prefetch thread runs one group ahead: a clip it loaded may have been pooled by the group in between
+            hit = self.cache.get(p)          # the prefetch thread runs one group ahead: a clip it loaded may have been pooled by the group in between
             if hit is not None:
                 feat_of[p] = hit
                 clips[p] = _Cached(hit)
@@ -195,68 +196,95 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
                 good.append(p)
         if good:
             try:
-                fresh = dict(zip(good, video_features_batch([clips[p] for p in good], vision_tower, image_processor, timings=tm)))
+                fresh = dict(zip(good, inference.video_features_batch([clips[p] for p in good], self.vision_tower, self.image_processor, timings=tm)))
             except Exception as e:                                     # noqa: BLE001 -- one bad clip must not take the group down
                 print(f"batched feature extraction failed ({e}); retrying the {len(good)} clips one by one")
                 fresh = {}
                 for p in good:
                     try:
-                        fresh[p] = video_features(clips[p], vision_tower, image_processor)
+                        fresh[p] = inference.video_features(clips[p], self.vision_tower, self.image_processor)
                     except Exception as e1:                            # noqa: BLE001
                         clips[p] = e1
             for p, f in fresh.items():
-                cache.put(p, f)
+                self.cache.put(p, f)
             feat_of.update(fresh)
         return feat_of
 
-    def infer_batch(indices, clips=None):
-        """-> (tokens [n, <= max_new] int32, lengths).  Length encoding: 0 = the task failed (no prediction), k + 1 = an answer of k tokens
-        (k = 0 is a legitimate empty answer: the reference writes pred = '' when the first token is EOS).
-        DEVICE half of a group: ONE tower pass over the frames of all distinct uncached clips of the group (inference.video_features_batch;
-        bitwise equal to per-clip passes), then batched prefill + decode with the per-chunk stop-string check."""
-        if clips is None:
-            clips = prepare(indices)
+    def group_features(self, clips):
+        """Device half of a group, first part.  -> (feat_of, host): host is what the group's --timings lines say about that half."""
         load_s = clips.pop("__load_s__", {})
-        tm_v, tm_g = ({}, {}) if tfile else (None, None)
-        feat_of = features_for(clips, tm_v)
-        prompts, feats, keep, stops = [], [], [], []
-        for j, idx in enumerate(indices):
-            t = tasks[idx]
-            if t["path"] is None:
-                print(f"Error processing video file '{t['name']}': not found")
-                continue
-            try:
-                if t["path"] not in feat_of:
-                    raise clips[t["path"]]
-                prompt, stop = build_prompt(t["question"], args.conv_mode, video_token_len, use_se)
-                ids = tokenizer([prompt]).input_ids[0]
-                feats.append(feat_of[t["path"]])
-                stop_strs[idx] = stop
-                prompts.append(ids)
-                stops.append(stop)
-                keep.append(j)
-            except Exception as e:                                     # noqa: BLE001 -- the reference's print-and-continue
-                print(f"Error processing video file '{t['name']}': {e}")
-        toks = torch.zeros(len(indices), args.max_new_tokens, dtype=torch.int32)
-        lens = [0] * len(indices)
-        eos = model.config.eos_token_id
+        tm_v = {} if self.tfile else None
+        feat_of = self.features_for(clips, tm_v)
+        n_fresh = sum(1 for f in clips.values() if not isinstance(f, (Exception, _Cached)))
+        return feat_of, {"clips": clips, "load_s": load_s, "tm_v": tm_v or {}, "n_fresh": n_fresh}
 
-        def record(j, row, n_prompt):
-            new = row[n_prompt:].tolist()
-            if eos is not None and eos in new:
-                new = new[:new.index(eos)]
-            new = new[:args.max_new_tokens]
-            toks[j, :len(new)] = torch.tensor(new, dtype=torch.int32)
-            lens[j] = len(new) + 1
+    def failed(self, idx, why):
+        print(f"Error processing video file '{self.tasks[idx]['name']}': {why}")
+
+    def inputs(self, idx, clips, feat_of):
+        """Task idx -> (prompt ids, pooled features, stop string); None after the reference's print-and-continue for a missing video, a clip
+        that failed to load or pool, or a prompt that cannot be built."""
+        from ..inference import build_prompt
+        t = self.tasks[idx]
+        if t["path"] is None:
+            return self.failed(idx, "not found")
+        try:
+            if t["path"] not in feat_of:
+                raise clips[t["path"]]
+            prompt, stop = build_prompt(t["question"], self.args.conv_mode, self.video_token_len, self.use_se)
+            ids = self.tokenizer([prompt]).input_ids[0]
+            self.stop_strs[idx] = stop
+            return ids, feat_of[t["path"]], stop
+        except Exception as e:                                         # noqa: BLE001 -- the reference's print-and-continue
+            return self.failed(idx, e)
+
+    def record(self, toks, lens, j, new, strip_eos=True):
+        """Answer `new` (ids) of row j: stripped from its EOS on, cut at --max_new_tokens."""
+        eos = self.model.config.eos_token_id
+        if strip_eos and eos is not None and eos in new:
+            new = new[:new.index(eos)]
+        new = new[:self.args.max_new_tokens]
+        toks[j, :len(new)] = torch.tensor(new, dtype=torch.int32)
+        lens[j] = len(new) + 1
+
+    def write_timing(self, idx, length, group, host, tm_g, group_size):
+        """One --timings line.  host: group_features' second result; tm_g: prefill_s / decode_s / steps of the generation the task was in."""
+        import json
+        t = self.tasks[idx]
+        self.tfile.write(json.dumps({"task": idx, "video": t["name"], "rank": self.rank, "group": group, "group_size": group_size, "ok": length > 0,
+                                     "tokens": max(length - 1, 0), "feature_cache_hit": isinstance(host["clips"].get(t["path"]), _Cached),
+                                     "load_s": host["load_s"].get(t["path"], 0.0), "upload_ingest_s_group": host["tm_v"].get("upload_ingest_s", 0.0),
+                                     "tower_pool_s_group": host["tm_v"].get("tower_pool_s", 0.0), "clips_in_tower_pass": host["n_fresh"],
+                                     "prefill_s_group": tm_g.get("prefill_s"), "decode_s_group": tm_g.get("decode_s"),
+                                     "decode_steps_group": tm_g.get("steps")}) + "\n")
+
+    def infer_batch(self, indices, clips=None):
+        """--schedule group -> (tokens [n, <= max_new] int32, lengths).  DEVICE half of a group: ONE tower pass over the frames of all distinct
+        uncached clips of the group, then batched prefill + decode with the per-chunk stop-string check."""
+        from ..continuous import split_refused
+        feat_of, host = self.group_features(self.prepare(indices) if clips is None else clips)
+        tm_g = {} if self.tfile else None
+        toks, lens = torch.zeros(len(indices), self.args.max_new_tokens, dtype=torch.int32), [0] * len(indices)
+        keep = []                                                      # (row, prompt ids, features, stop string) of the tasks that can run
+        for j, idx in enumerate(indices):
+            inp = self.inputs(idx, host["clips"], feat_of)
+            if inp is not None:
+                keep.append((j,) + inp)
+
+        def generate(part, timings=None):
+            # a stop string that IS the EOS piece (pg-video-llava: "</s>") is already handled on the device by the EOS flag; the host check
+            # is for conv modes whose stop is ordinary text (default: "###") -- without it every group decodes max_new_tokens steps
+            return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
+                                       do_sample=False, max_new_tokens=self.args.max_new_tokens, stop_strings=[s for _, _, _, s in part],
+                                       tokenizer=self.tokenizer, timings=timings).cpu()
+
+        def record(part, out):
+            for row, (j, ids, _, _) in zip(out, part):
+                self.record(toks, lens, j, row[len(ids):].tolist())
 
         if keep:
-            # a stop string that IS the EOS piece (pg-video-llava: "</s>") is already handled on the device by the EOS flag; the host check
-            # is for conv modes whose stop is ordinary text (video-chatgpt_v1: "###") -- without it every group decodes max_new_tokens steps
             try:
-                out = model.generate(prompts, video_spatio_temporal_features=torch.stack(feats), do_sample=False,
-                                     max_new_tokens=args.max_new_tokens, stop_strings=stops, tokenizer=tokenizer, timings=tm_g).cpu()
-                for r, j in enumerate(keep):
-                    record(j, out[r], len(prompts[r]))
+                record(keep, generate(keep, tm_g))
             except Exception as e:                                     # noqa: BLE001
                 # one bad sample (e.g. an over-long prompt) must not take the whole group down: the reference loses only that sample.  Out of
                 # memory (the KV cache of the group did not fit next to whatever else lives on the device: ADVICE r5) is not a sample's fault:
@@ -264,133 +292,100 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
                 oom = isinstance(e, (MemoryError, torch.cuda.OutOfMemoryError))
                 size = max(1, len(keep) // 2) if oom and len(keep) > 1 else 1
                 print(f"batched generation failed ({type(e).__name__}: {e}); retrying the {len(keep)} samples in groups of {size}")
-                pending = [list(range(i, min(i + size, len(keep)))) for i in range(0, len(keep), size)]
-                while pending:
-                    rs = pending.pop(0)
-                    try:
-                        out = model.generate([prompts[r] for r in rs], video_spatio_temporal_features=torch.stack([feats[r] for r in rs]), do_sample=False,
-                                             max_new_tokens=args.max_new_tokens, stop_strings=[stops[r] for r in rs], tokenizer=tokenizer).cpu()
-                        for q, r in enumerate(rs):
-                            record(keep[r], out[q], len(prompts[r]))
-                    except Exception as e1:                            # noqa: BLE001
-                        if len(rs) > 1:                                # still too big (or one bad sample inside): split again
-                            pending[:0] = [rs[:len(rs) // 2], rs[len(rs) // 2:]]
-                        else:
-                            print(f"Error processing video file '{tasks[indices[keep[rs[0]]]]['name']}': {e1}")
-        if tfile:
-            n_fresh = sum(1 for f in clips.values() if not isinstance(f, (Exception, _Cached)))
+                for part, out, e1 in split_refused([keep[i:i + size] for i in range(0, len(keep), size)], generate):
+                    if e1 is None:
+                        record(part, out)
+                    else:
+                        self.failed(indices[part[0][0]], e1)
+        if self.tfile:
             for j, idx in enumerate(indices):
-                t = tasks[idx]
-                hit = isinstance(clips.get(t["path"]), _Cached)
-                tfile.write(json.dumps({"task": idx, "video": t["name"], "rank": rank, "group": group_no[0], "group_size": len(indices), "ok": lens[j] > 0,
-                                        "tokens": max(lens[j] - 1, 0), "feature_cache_hit": hit, "load_s": load_s.get(t["path"], 0.0),
-                                        "upload_ingest_s_group": (tm_v or {}).get("upload_ingest_s", 0.0), "tower_pool_s_group": (tm_v or {}).get("tower_pool_s", 0.0),
-                                        "clips_in_tower_pass": n_fresh, "prefill_s_group": (tm_g or {}).get("prefill_s"), "decode_s_group": (tm_g or {}).get("decode_s"),
-                                        "decode_steps_group": (tm_g or {}).get("steps")}) + "\n")
-            tfile.flush()
-        group_no[0] += 1
+                self.write_timing(idx, lens[j], self.group_no, host, tm_g, len(indices))
+            self.tfile.flush()
+        self.group_no += 1
         return toks, lens
 
-    def infer_refill(indices, clips=None):
+    def infer_refill(self, indices, clips=None):
         """--schedule refill: the whole shard through generate_continuous.  The groups of --batch tasks still drive the host half -- prepare()
         one group ahead on a background thread, one tower pass per group, the feature cache -- but decode slots are refilled task by task."""
         from concurrent.futures import ThreadPoolExecutor
         from ..continuous import Task, generate_continuous
+        args = self.args
         W = max(1, int(args.batch))
         groups = [indices[g0:g0 + W] for g0 in range(0, len(indices), W)]
-        toks = torch.zeros(len(indices), args.max_new_tokens, dtype=torch.int32)
-        lens = [0] * len(indices)
+        toks, lens = torch.zeros(len(indices), args.max_new_tokens, dtype=torch.int32), [0] * len(indices)
         row = {idx: j for j, idx in enumerate(indices)}
-        info = {}
-        eos = model.config.eos_token_id
+        info = {}                                                      # task -> (its group, the group's host half)
 
         def stream():
             pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="pgv-prefetch")
             try:
-                fut = pool.submit(prepare, groups[0]) if groups else None
+                fut = pool.submit(self.prepare, groups[0]) if groups else None
                 for gi, group in enumerate(groups):
                     try:
                         clips_g = fut.result()
                     except Exception as e:                             # noqa: BLE001 -- the group's tasks fail, the others go on
-                        clips_g = {tasks[i]["path"]: e for i in group}
-                    fut = pool.submit(prepare, groups[gi + 1]) if gi + 1 < len(groups) else None
-                    load_s = clips_g.pop("__load_s__", {})
-                    tm_v = {} if tfile else None
-                    feat_of = features_for(clips_g, tm_v)
-                    n_fresh = sum(1 for f in clips_g.values() if not isinstance(f, (Exception, _Cached)))
+                        clips_g = {self.tasks[i]["path"]: e for i in group}
+                    fut = pool.submit(self.prepare, groups[gi + 1]) if gi + 1 < len(groups) else None
+                    feat_of, host = self.group_features(clips_g)
                     for idx in group:
-                        t = tasks[idx]
-                        info[idx] = {"group": gi, "load_s": load_s.get(t["path"], 0.0), "hit": isinstance(clips_g.get(t["path"]), _Cached),
-                                     "tm_v": tm_v or {}, "n_fresh": n_fresh}
-                        if t["path"] is None:
-                            print(f"Error processing video file '{t['name']}': not found")
-                            continue
-                        try:
-                            if t["path"] not in feat_of:
-                                raise clips_g[t["path"]]
-                            prompt, stop = build_prompt(t["question"], args.conv_mode, video_token_len, use_se)
-                            ids = tokenizer([prompt]).input_ids[0]
-                            stop_strs[idx] = stop
-                            yield Task(idx, ids, feat_of[t["path"]], stop=stop, seed=int(getattr(args, "seed", 0)) * 1000003 + idx)
-                        except Exception as e:                         # noqa: BLE001 -- the reference's print-and-continue
-                            print(f"Error processing video file '{t['name']}': {e}")
+                        info[idx] = (gi, host)
+                        inp = self.inputs(idx, clips_g, feat_of)
+                        if inp is not None:
+                            yield Task(idx, inp[0], inp[1], stop=inp[2], seed=int(getattr(args, "seed", 0)) * 1000003 + idx)
             finally:
                 pool.shutdown(wait=True, cancel_futures=True)
 
-        def failed(task_id, e):
-            print(f"Error processing video file '{tasks[task_id]['name']}': {e}")
-
-        tm = {} if tfile else None
-        for idx, new in generate_continuous(model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
-                                            tokenizer=tokenizer, on_error=failed, timings=tm):
-            if new is None:
-                continue
-            if eos is not None and eos in new:
-                new = new[:new.index(eos)]
-            new = new[:args.max_new_tokens]
-            j = row[idx]
-            toks[j, :len(new)] = torch.tensor(new, dtype=torch.int32)
-            lens[j] = len(new) + 1
-        if tfile:
+        tm = {} if self.tfile else None
+        for idx, new in generate_continuous(self.model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
+                                            tokenizer=self.tokenizer, on_error=self.failed, timings=tm):
+            if new is not None:
+                self.record(toks, lens, row[idx], new)
+        if self.tfile:
             for j, idx in enumerate(indices):
-                t, inf, g = tasks[idx], info.get(idx, {}), (tm or {}).get(idx, {})
-                tfile.write(json.dumps({"task": idx, "video": t["name"], "rank": rank, "group": inf.get("group", -1), "group_size": g.get("group_size"),
-                                        "ok": lens[j] > 0, "tokens": max(lens[j] - 1, 0), "feature_cache_hit": inf.get("hit", False),
-                                        "load_s": inf.get("load_s", 0.0), "upload_ingest_s_group": inf.get("tm_v", {}).get("upload_ingest_s", 0.0),
-                                        "tower_pool_s_group": inf.get("tm_v", {}).get("tower_pool_s", 0.0), "clips_in_tower_pass": inf.get("n_fresh", 0),
-                                        "prefill_s_group": g.get("prefill_s"), "decode_s_group": g.get("decode_s"),
-                                        "decode_steps_group": g.get("steps")}) + "\n")
-            tfile.flush()
+                g = tm.get(idx, {})
+                self.write_timing(idx, lens[j], info[idx][0], info[idx][1], g, g.get("group_size"))
+            self.tfile.flush()
         return toks, lens
 
-    def infer_sampled(indices, clips=None):
-        """--do_sample: the reference's temperature-0.2 sampling with its stopping criterion, one task at a time (video_chatgpt_infer's
-        path up to the detokenisation); the ids travel through the same fixed-shape collation as the greedy answers."""
+    def infer_sampled(self, indices, clips=None):
+        """--do_sample (--schedule group): the reference's temperature-0.2 sampling with its stopping criterion, one task at a time
+        (video_chatgpt_infer's path up to the detokenisation); the ids travel through the same fixed-shape collation as the greedy answers."""
+        from ..inference import video_chatgpt_infer_ids
         if clips is None:
-            clips = prepare(indices)
+            clips = self.prepare(indices)
         clips.pop("__load_s__", None)
-        feat_of = features_for(clips, None)
-        toks = torch.zeros(len(indices), args.max_new_tokens, dtype=torch.int32)
-        lens = [0] * len(indices)
+        feat_of = self.features_for(clips, None)
+        toks, lens = torch.zeros(len(indices), self.args.max_new_tokens, dtype=torch.int32), [0] * len(indices)
         for j, idx in enumerate(indices):
-            t = tasks[idx]
+            t = self.tasks[idx]
             try:
                 if t["path"] is None:
                     raise FileNotFoundError(t["name"])
                 if t["path"] not in feat_of:
                     raise clips[t["path"]]
-                new, stop = video_chatgpt_infer_ids(None, t["question"], args.conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
-                                                    None, max_new_tokens=args.max_new_tokens, features=feat_of[t["path"]])
-                new = new[:args.max_new_tokens]
-                stop_strs[idx] = stop
-                toks[j, :len(new)] = torch.tensor(new, dtype=torch.int32)
-                lens[j] = len(new) + 1
+                new, stop = video_chatgpt_infer_ids(None, t["question"], self.args.conv_mode, self.model, self.vision_tower, self.tokenizer,
+                                                    self.image_processor, self.video_token_len, None, max_new_tokens=self.args.max_new_tokens,
+                                                    features=feat_of[t["path"]])
+                self.stop_strs[idx] = stop
+                self.record(toks, lens, j, new, strip_eos=False)       # the ids end where the reference's criterion stopped them
             except Exception as e:                                     # noqa: BLE001
-                print(f"Error processing video file '{t['name']}': {e}")
+                self.failed(idx, e)
         return toks, lens
 
-    device = vision_tower.device if hasattr(vision_tower, "device") else torch.device("cpu")
+
+def answer_tasks(args, tasks, components, load_frames, rank, world):
+    """tasks: [{"path": str | None, "name": str, "question": str}] -> [str | None] in task order, identical on every rank."""
     import os
+    from .. import parallel
+    from ..inference import build_prompt
+
+    model, vision_tower, tokenizer = components[:3]
+    timings_path = getattr(args, "timings", None)
+    if timings_path and world > 1:
+        timings_path = f"{timings_path}.rank{rank}"
+    tfile = open(timings_path, "a") if timings_path else None
+    run = _Runner(args, tasks, components, load_frames, rank, tfile)
+    device = vision_tower.device if hasattr(vision_tower, "device") else torch.device("cpu")
     if getattr(args, "batch", "auto") == "auto":
         free_b = torch.cuda.mem_get_info(device)[0] if device.type == "cuda" else 0
         # processes that share this device see the same free pool and would each claim 70 % of it (ADVICE r5): PGV_DEVICE_SHARERS (or, in a
@@ -411,14 +406,14 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
     try:
         if getattr(args, "schedule", "group") == "refill":
             # one infer call over the whole shard (it prefetches its own groups); the answers collate like the static groups'
-            answers = parallel.run_sharded(len(tasks), infer_refill, args.max_new_tokens, rank, world, device, per_gpu_batch=max(1, len(tasks)),
+            answers = parallel.run_sharded(len(tasks), run.infer_refill, args.max_new_tokens, rank, world, device, per_gpu_batch=max(1, len(tasks)),
                                            length_offset=1, spill_path=spill)
         elif args.do_sample:
-            answers = parallel.run_sharded(len(tasks), infer_sampled, args.max_new_tokens, rank, world, device, per_gpu_batch=1, length_offset=1, prepare=prepare,
+            answers = parallel.run_sharded(len(tasks), run.infer_sampled, args.max_new_tokens, rank, world, device, per_gpu_batch=1, length_offset=1, prepare=run.prepare,
                                            spill_path=spill)
         else:
-            answers = parallel.run_sharded(len(tasks), infer_batch, args.max_new_tokens, rank, world, device, per_gpu_batch=args.batch,
-                                           length_offset=1, prepare=prepare, spill_path=spill)
+            answers = parallel.run_sharded(len(tasks), run.infer_batch, args.max_new_tokens, rank, world, device, per_gpu_batch=args.batch,
+                                           length_offset=1, prepare=run.prepare, spill_path=spill)
     finally:
         if tfile:
             tfile.close()
@@ -428,7 +423,7 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
         if ids is None:
             preds.append(None)                                         # failed / missing: left out of the output like the reference's except
             continue
-        stop = stop_strs.get(idx) or build_prompt("", args.conv_mode, 1, use_se)[1]
+        stop = run.stop_strs.get(idx) or build_prompt("", args.conv_mode, 1, run.use_se)[1]
         if args.do_sample:
             # the ids already end where the reference's criterion stopped them; its own post-processing (inference.py:119-123)
             text = tokenizer.batch_decode([ids], skip_special_tokens=True)[0]

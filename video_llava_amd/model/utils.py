@@ -1,7 +1,9 @@
 """Stop-string criterion with the reference's semantics (video_chatgpt/model/utils.py:6-26): a keyword whose
 tokenisation is exactly one id is matched on the last generated id; otherwise the generated tail is decoded and
-searched for the keyword."""
+searched for the keyword.  `AnswerState` is the per-sequence answer bookkeeping of the chunked decode loops built on it."""
 from __future__ import annotations
+
+import numpy as np
 
 
 class KeywordsStoppingCriteria:
@@ -68,3 +70,39 @@ def first_stop_length(new_tokens, tokenizer, keywords, start: int = 2):
     if n_id is None:
         return n_txt
     return n_id if n_txt is None else min(n_id, n_txt)
+
+
+class AnswerState:
+    """The answer of ONE sequence while it is decoded in runs of tokens (model.generate keeps a list of these, generate_continuous one per
+    decode slot).  `new`: the ids kept so far.  The rule: a run is taken up to the token budget and up to and including its first EOS (one
+    numpy scan per run, not a Python loop per token: the GPU idles while the host does this); then the stop string is looked for with
+    `first_stop_length`, incrementally -- no prefix shorter than `scanned` fires -- and cuts the answer where the reference's per-token loop
+    would have stopped, so a stop string ahead of an EOS of the same run wins."""
+    __slots__ = ("new", "budget", "eos", "stop", "tokenizer", "scanned", "done", "taken")
+
+    def __init__(self, budget: int, eos: int = -1, stop=None, tokenizer=None):
+        self.new: list = []
+        self.budget, self.eos, self.stop, self.tokenizer = int(budget), int(eos), stop, tokenizer
+        self.scanned = 2
+        self.done = False
+        self.taken = 0              # tokens of the last run that were kept, before the stop cut (generate's `steps`)
+
+    def take(self, toks) -> bool:
+        """toks: the sequence's next tokens in generation order (1-D).  True = the answer is complete (EOS, stop string or budget)."""
+        a = np.asarray(toks)[:self.budget - len(self.new)]
+        if self.eos >= 0:
+            hit = np.flatnonzero(a == self.eos)
+            if hit.size:
+                a, self.done = a[:int(hit[0]) + 1], True
+        self.taken = len(a)
+        self.new.extend(a.tolist())
+        if len(self.new) >= self.budget:
+            self.done = True
+        if self.stop and len(self.new) >= 2:
+            n = first_stop_length(self.new, self.tokenizer, [self.stop], start=self.scanned)
+            if n is not None:
+                del self.new[n:]
+                self.done = True
+            else:
+                self.scanned = len(self.new) + 1
+        return self.done

@@ -22,6 +22,7 @@ import torch.nn as nn
 from .. import _lib
 from ..constants import CLIP_WIDTH
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
+from .utils import AnswerState
 
 DEFAULT_VIDEO_TOKEN = "<video>"
 DEFAULT_VIDEO_PATCH_TOKEN = "<vid_patch>"
@@ -582,8 +583,6 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 raise ValueError("stop_strings needs one entry per sequence and the tokenizer that decodes them")
             if not any(stops):
                 stops = None
-        scanned = [2] * B                                  # stop strings: prefixes shorter than this are known not to fire
-        final = [False] * B                                # ... and sequences whose stop check is complete
         import time as _time
         _t0 = _time.perf_counter()
 
@@ -602,47 +601,22 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         if do_sample and max_new_tokens >= 1:
             u = torch.rand(max_new_tokens, B, device=self.device_, dtype=torch.float32, generator=generator)
             nxt = self.sample_last(kv, u[0], temperature, top_k)
-        new = [[] for _ in range(B)]
-        done = [False] * B
-        prompt_t = [torch.tensor(s, dtype=torch.long) for s in seqs]
+        states = [AnswerState(max_new_tokens, eos_i, stops[b] if stops is not None else None, tokenizer) for b in range(B)]
+        prompt_t = torch.tensor(seqs[0], dtype=torch.long)
 
-        def absorb(tok_host) -> bool:
-            """Append one step's tokens; True = generation is over (HF: EOS on every sequence, or a criterion fires on the new ids)."""
-            for b in range(B):
-                if not done[b]:
-                    new[b].append(int(tok_host[b]))
-                    if eos_i >= 0 and int(tok_host[b]) == eos_i:
-                        done[b] = True
-            if all(done):
-                return True
-            if criteria:
-                cur = torch.cat([prompt_t[0], torch.tensor(new[0], dtype=torch.long)])[None]
-                if any(c(cur, None) for c in criteria):
-                    return True
-            return False
-
-        def check_stops() -> bool:
-            """Per-chunk stop-string check of the live sequences; True = every sequence has finished."""
-            from .utils import first_stop_length
-            for b in range(B):
-                if final[b] or not stops[b] or len(new[b]) < 2:
-                    continue
-                n = first_stop_length(new[b], tokenizer, [stops[b]], start=scanned[b])
-                if n is not None:
-                    del new[b][n:]                         # a stop string ahead of an EOS of the same chunk wins, as in the per-token loop
-                    done[b] = final[b] = True
-                elif done[b]:
-                    final[b] = True                        # finished by EOS, no stop string before it
-                else:
-                    scanned[b] = len(new[b]) + 1
-            return all(done)
+        def criterion_fires() -> bool:
+            """HF: a stopping criterion is asked after every appended token (B == 1)."""
+            cur = torch.cat([prompt_t, torch.tensor(states[0].new, dtype=torch.long)])[None]
+            return any(c(cur, None) for c in criteria)
 
         n_gen = 0
         _t1 = _t0
         if max_new_tokens >= 1:
-            first = nxt.cpu()
+            first = nxt.cpu().numpy()
             raw.append(int(first[0]))
-            stop = absorb(first)
+            for b, st in enumerate(states):
+                st.take(first[b:b + 1])
+            stop = all(st.done for st in states) or (bool(criteria) and criterion_fires())
             _t1 = _time.perf_counter()
             n_gen = 1
             while not stop and n_gen < max_new_tokens:
@@ -651,34 +625,26 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                     toks = self.decode_sample(kv, nxt, n, eos_i, temperature, top_k, u[n_gen:n_gen + n])
                 else:
                     toks = self.decode_greedy(kv, nxt, n, eos_i)
-                host = toks.cpu()
-                raw.extend(host[0].tolist())
+                h = toks.cpu().numpy()
+                raw.extend(h[0].tolist())
                 if criteria:
                     for i in range(n):
-                        stop = absorb(host[:, i])
+                        stop = states[0].take(h[0, i:i + 1]) or criterion_fires()
                         n_gen += 1
                         if stop:
                             break
                 else:
-                    # the same bookkeeping per SEQUENCE instead of per step (a chunk of 64 steps x 8 sequences cost ~0.6 ms of Python between two
-                    # decode launches, with the GPU idle): every live sequence takes its tokens up to and including its first EOS
-                    h = host.numpy()
+                    # per SEQUENCE, not per step (a chunk of 64 steps x 8 sequences cost ~0.6 ms of Python between two decode launches, with the
+                    # GPU idle): AnswerState.take absorbs a live sequence's whole run at once
                     last = 0
-                    for b in range(B):
-                        if done[b]:
-                            continue
-                        k = n
-                        if eos_i >= 0:
-                            hit = np.flatnonzero(h[b] == eos_i)
-                            if hit.size:
-                                k, done[b] = int(hit[0]) + 1, True
-                        new[b].extend(h[b, :k].tolist())
-                        last = max(last, k)
-                    stop = all(done)
+                    for b, st in enumerate(states):
+                        if not st.done:
+                            st.take(h[b])
+                            last = max(last, st.taken)
+                    stop = all(st.done for st in states)
                     n_gen += last if stop else n
-                if stops is not None:                   # also when the chunk ended with every sequence at EOS: a stop string AHEAD of that EOS still cuts
-                    stop = check_stops() or stop
                 nxt = toks[:, n - 1].contiguous()
+        new = [st.new for st in states]
         if timings is not None:
             _t2 = _time.perf_counter()
             timings.update(prefill_s=_t1 - _t0, decode_s=_t2 - _t1, steps=n_gen, batch=B, reused_tokens=reused)
