@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 322
+#define PGV_VERSION 323
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -239,6 +239,36 @@ int pgv_llm_decode_sample(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t 
 /* building block: the same pick on caller logits [B, V] fp32 (row stride V) */
 int pgv_sample_logits(pgv_ctx *ctx, const float *d_logits, int V, int B, float temperature, int top_k, const float *d_u, int32_t *d_next,
                       void *stream);
+
+/* The two further HF processors of a sampled run (HF generation/logits_process.py; HF's order, as GenerationMixin._get_logits_processor /
+ * _get_logits_warper build it: repetition penalty on the raw logits, then temperature, top-k, top-p, softmax, multinomial):
+ *  - RepetitionPenaltyLogitsProcessor(penalty) (`score = torch.where(score < 0, score * penalty, score / penalty)` gathered / scattered at
+ *    input_ids): for every token id in the sequence's seen-set, x = x < 0 ? x * penalty : x / penalty.
+ *  - TopPLogitsWarper(top_p, min_tokens_to_keep = 1) (`sorted_indices_to_remove = cumulative_probs <= (1 - top_p)` over the ASCENDING sort of
+ *    the softmax of what top-k left): a token stays iff the probability mass of the tokens ranked above it is < top_p; the largest always stays.
+ *    TIE RULE (HF's torch.sort leaves the order of equal logits unspecified): equal logits share one rank -- a value stays iff the mass of the
+ *    values STRICTLY greater is < top_p -- so equal logits are kept or removed together, exactly as the top-k mask `scores < kth` treats them.
+ * The sums that decide the nucleus are integer (64-bit fixed point, 2^-40 of the largest weight per entry) and every other reduction has a
+ * fixed order: same logits, same seen-set, same u -> same token on any launch, batch slot and group width.  top_p == 1 and
+ * repetition_penalty == 1 run the pick without the two processors: bit for bit the tokens of the calls above.
+ * Refused with PGV_EINVAL, in HF's words: top_p outside (0, 1] ("`top_p` has to be a float > 0 and <= 1"), repetition_penalty <= 0
+ * ("`penalty` has to be a strictly positive float").
+ *
+ * pgv_sample_logits_ex: pgv_sample_logits with both processors on caller buffers.  Seen-set of row b: the d_seen_lens[b] ids at
+ * d_seen_ids + b * seen_stride (both NULL: empty; ids outside [0, V) are ignored).  d_kept [B] (may be NULL) receives the number of
+ * vocabulary entries left with non-zero probability. */
+int pgv_sample_logits_ex(pgv_ctx *ctx, const float *d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                         const int32_t *d_seen_ids, int seen_stride, const int32_t *d_seen_lens, const float *d_u, int32_t *d_next, int32_t *d_kept,
+                         void *stream);
+/* Sampling state of a cache, default (1, 1): every later pick on it -- pgv_llm_sample, pgv_llm_decode_sample, the first-token draw of
+ * pgv_llm_prefill_slots, and with repetition_penalty != 1 also pgv_llm_decode_greedy and the greedy first token of pgv_llm_prefill_slots (the
+ * largest PENALISED logit, first index on ties; top_p plays no part in a greedy pick, as in HF) -- runs with these values.  The captured
+ * decode graph is rebuilt when they change.  A slot's seen-set (HF's `input_ids`): the ids of its prompt as handed to pgv_llm_prefill /
+ * _slots (placeholder ids included; a refill starts from an empty set, pgv_llm_prefill_append adds to it) plus every token one of those picks
+ * returned while a value differed from (1, 1).  Set the values before the prefill of the sequences they are meant for.  Not covered: the
+ * greedy d_next of pgv_llm_prefill / _append and plain pgv_llm_decode steps, which neither apply the penalty nor record a token -- a caller
+ * who wants the penalised first token draws it with pgv_llm_sample(temperature 1, top_k 1, u = 0). */
+int pgv_kv_set_warpers(pgv_kv *kv, float top_p, float repetition_penalty);
 
 /* current length (tokens in cache) of sequence b, host-side bookkeeping */
 int pgv_kv_len(const pgv_kv *kv, int b);

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgv.so")
 
-ABI_VERSION = 322          # PGV_VERSION of include/pgv.h this table was written against
+ABI_VERSION = 323          # PGV_VERSION of include/pgv.h this table was written against
 PGV_OK, PGV_EINVAL, PGV_EHIP, PGV_ENOMEM, PGV_ESTATE, PGV_ENAME = 0, 1, 2, 3, 4, 5
 PGV_F16, PGV_BF16, PGV_F32 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_GELU, EPI_RESID, EPI_BIAS_RESID, EPI_SWIGLU, EPI_F32 = range(8)
@@ -73,6 +73,8 @@ PROTOTYPES = {
     "pgv_llm_sample": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     "pgv_llm_decode_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
     "pgv_sample_logits": (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
+    "pgv_sample_logits_ex": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pgv_kv_set_warpers": (_i, [_vp, _f, _f]),
     "pgv_ingest_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pgv_gemm": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "pgv_vit_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
@@ -260,14 +262,42 @@ class Context:
                                      stream_ptr(frames.device)), "pgv_ingest_u8")
         return out
 
-    def sample_logits(self, logits: torch.Tensor, u: torch.Tensor, temperature: float, top_k: int = 50) -> torch.Tensor:
-        """Inverse-CDF pick from softmax(logits / temperature) restricted to the top_k logits (<= 0: all) with uniforms u [B] -> int32 [B]."""
+    def sample_logits(self, logits: torch.Tensor, u: torch.Tensor, temperature: float, top_k: int = 50, top_p: float = 1.0,
+                      repetition_penalty: float = 1.0, seen_ids: "torch.Tensor | None" = None) -> torch.Tensor:
+        """Inverse-CDF pick from softmax(logits / temperature) restricted to the top_k logits (<= 0: all) with uniforms u [B] -> int32 [B].
+        top_p / repetition_penalty (over seen_ids [B, n] int32) other than 1: sample_logits_ex."""
+        if float(top_p) != 1.0 or float(repetition_penalty) != 1.0:
+            return self.sample_logits_ex(logits, u, temperature, top_k, top_p, repetition_penalty, seen_ids)
         assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
         assert u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and u.numel() == logits.shape[0]
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
         check(self.lib.pgv_sample_logits(self.handle, logits.data_ptr(), logits.shape[1], logits.shape[0], float(temperature), int(top_k),
                                          u.data_ptr(), out.data_ptr(), stream_ptr(logits.device)), "pgv_sample_logits")
         return out
+
+    def sample_logits_ex(self, logits: torch.Tensor, u: torch.Tensor, temperature: float, top_k: int = 50, top_p: float = 1.0,
+                         repetition_penalty: float = 1.0, seen_ids: "torch.Tensor | None" = None, seen_lens: "torch.Tensor | None" = None,
+                         want_kept: bool = False):
+        """pgv_sample_logits_ex: the pick with HF's repetition penalty (over seen_ids [B, n] int32, the first seen_lens[b] of each row; None:
+        nothing seen) and nucleus filter.  Returns tokens int32 [B], or (tokens, kept [B]) with want_kept: the entries left with non-zero
+        probability per row."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+        assert u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and u.numel() == logits.shape[0]
+        B = logits.shape[0]
+        stride = 0
+        if seen_ids is not None:
+            assert seen_ids.is_cuda and seen_ids.dtype == torch.int32 and seen_ids.is_contiguous() and seen_ids.dim() == 2 and seen_ids.shape[0] == B
+            stride = seen_ids.shape[1]
+            if seen_lens is None:
+                seen_lens = torch.full((B,), stride, dtype=torch.int32, device=logits.device)
+            assert seen_lens.is_cuda and seen_lens.dtype == torch.int32 and seen_lens.numel() == B and int(seen_lens.max()) <= stride
+        out = torch.empty(B, dtype=torch.int32, device=logits.device)
+        kept = torch.empty(B, dtype=torch.int32, device=logits.device) if want_kept else None
+        check(self.lib.pgv_sample_logits_ex(self.handle, logits.data_ptr(), logits.shape[1], B, float(temperature), int(top_k), float(top_p),
+                                            float(repetition_penalty), seen_ids.data_ptr() if seen_ids is not None else None, stride,
+                                            seen_lens.data_ptr() if seen_ids is not None else None, u.data_ptr(), out.data_ptr(),
+                                            kept.data_ptr() if kept is not None else None, stream_ptr(logits.device)), "pgv_sample_logits_ex")
+        return (out, kept) if want_kept else out
 
     def preprocess_u8(self, frames: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         """uint8 [T, S, S, 3] on the device -> normalised [T, 3, S, S]."""

@@ -23,7 +23,7 @@ from .video_conversation import SeparatorStyle, conv_templates, default_conversa
 
 class VideoChatGPTInterface:
     def __init__(self, args_model_name, args_projection_path, use_asr=False, conv_mode="pg-video-llava", temperature=0.2,
-                 max_output_tokens=1024, components=None, do_sample=True, reuse_kv=True) -> None:
+                 max_output_tokens=1024, components=None, do_sample=True, reuse_kv=True, top_p=None, repetition_penalty=None) -> None:
         if use_asr:
             raise NotImplementedError("--use_asr needs the WhisperX transcript stack, which is outside this package's hot path")
         self.use_asr = use_asr
@@ -34,6 +34,7 @@ class VideoChatGPTInterface:
         model, vision_tower, tokenizer, image_processor, video_token_len = components
         self.tokenizer, self.image_processor, self.vision_tower, self.model = tokenizer, image_processor, vision_tower, model
         self.temperature = temperature
+        self.top_p, self.repetition_penalty = top_p, repetition_penalty      # None: the checkpoint's generation_config.json, else HF's default
         self.max_new_tokens = max_output_tokens
         self.do_sample = do_sample
         self.reuse_kv = reuse_kv
@@ -111,7 +112,8 @@ class VideoChatGPTInterface:
             output_ids = self.model.generate(input_ids, video_spatio_temporal_features=self.video_features.unsqueeze(0),
                                              do_sample=self.do_sample, temperature=float(self.temperature),
                                              max_new_tokens=min(int(self.max_new_tokens), 1536), stopping_criteria=[stopping_criteria],
-                                             kv_reuse_key=self.kv_key, timings=self.last_timings)
+                                             kv_reuse_key=self.kv_key, timings=self.last_timings, top_p=self.top_p,
+                                             repetition_penalty=self.repetition_penalty)
         n_in = input_ids.shape[1]
         n_diff = int((input_ids.to(output_ids.device) != output_ids[:, :n_in]).sum())
         if n_diff > 0:

@@ -77,7 +77,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                         top_k: int = 50, tokenizer=None, chunk: int = DEFAULT_CHUNK, refill_min: Optional[int] = None, max_seq: Optional[int] = None,
                         prompt_slack: int = 128, eos_token_id="config", seed: int = 0,
                         on_error: Callable[[Any, Exception], None] = _default_on_error,
-                        timings: Optional[dict] = None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
+                        timings: Optional[dict] = None, top_p: float = 1.0, repetition_penalty: float = 1.0) -> Iterator[Tuple[Any, Optional[List[int]]]]:
     """Yield (task_id, new_ids) as each task finishes; new_ids is None for a task that failed (`on_error(task_id, exc)` is told why) -- a failed
     task costs only itself.
 
@@ -88,6 +88,8 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     (pgv_kv_truncate) so that they neither outgrow the cache nor read a long one.
     do_sample: task t draws from its own stream `task_uniforms(budget, task.seed, device)` (seed None: `seed` + the task's arrival index), so a
     sampled answer equals generate(do_sample=True, generator=<that seeded generator>) whatever its slot and the group width.
+    top_p, repetition_penalty: HF's nucleus filter (sampling only) and repetition penalty (both modes) for every task of the call, as in
+    `generate`; a task's seen-set is its own prompt and answer -- a refilled slot starts clean (pgv_llm_prefill_slots).
     max_seq: cache positions per slot (default: longest prompt of the first group + `prompt_slack` + max_new_tokens + chunk, rounded to 64);
     a later task that does not fit fails alone.
     timings (a dict): timings[task_id] = {prefill_s, decode_s, steps, group_size} of each finished task (host clock; the prefill call that
@@ -96,6 +98,11 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         raise ValueError(f"width {width} outside [1, 64]")
     if do_sample and not float(temperature) > 0.0:
         raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float; use do_sample=False for greedy decoding")
+    from .generation import resolve_sampling
+    _, _, top_p, rep_pen = resolve_sampling(temperature if do_sample else 1.0, top_k, top_p, repetition_penalty)      # validates, HF's wording
+    # passed on only when they differ from the neutral values: the model calls below then keep the argument lists they have always had
+    warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
+    pen = {} if rep_pen == 1.0 else {"repetition_penalty": rep_pen}
     chunk = max(1, int(chunk))
     k_min = max(1, int(refill_min) if refill_min is not None else width // 8)
     eos = model.config.eos_token_id if eos_token_id == "config" else eos_token_id
@@ -179,7 +186,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     slots: List[Optional[_Slot]] = [None] * W
     us = [uniforms(a, t) for a, t in first]
     if do_sample:
-        nxt = model.sample_last(kv, torch.stack([u[0] for u in us]), temperature, top_k)
+        nxt = model.sample_last(kv, torch.stack([u[0] for u in us]), temperature, top_k, **warp)
+    elif rep_pen != 1.0:
+        nxt = model.sample_last(kv, torch.zeros(W, device=dev), 1.0, 1, **pen)      # greedy over the penalised logits (as generate does)
     cur = nxt.clone()
     first_tok = nxt.cpu().numpy()
     dt = time.perf_counter() - t0
@@ -224,7 +233,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                 u_part = [uniforms(a, t) for _, a, t in part]
                 u0 = torch.stack([u[0] for u in u_part]) if do_sample else None
                 nx, _ = model.prefill_slots(kv, [s for s, _, _ in part], [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
-                                            u=u0, temperature=temperature, top_k=top_k)
+                                            u=u0, temperature=temperature, top_k=top_k, **(warp if do_sample else pen))
                 cur[[s for s, _, _ in part]] = nx
                 return u_part, nx.cpu().numpy(), time.perf_counter() - t0
 
@@ -259,9 +268,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                 if sl is not None:
                     seg = sl.u[len(sl.answer.new):len(sl.answer.new) + n]
                     u[:seg.numel(), s] = seg
-            toks = model.decode_sample(kv, cur, n, eos_i, temperature, top_k, u)
+            toks = model.decode_sample(kv, cur, n, eos_i, temperature, top_k, u, **warp)
         else:
-            toks = model.decode_greedy(kv, cur, n, eos_i)
+            toks = model.decode_greedy(kv, cur, n, eos_i, **pen)
         cur = toks[:, n - 1].contiguous()
         host = toks.cpu().numpy()
         dt = time.perf_counter() - t0

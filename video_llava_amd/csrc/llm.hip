@@ -63,9 +63,13 @@ struct pgv_kv {
     // tokens and step counters live in device memory and are advanced by the argmax kernel)
     hipGraphExec_t gexec[2] = {nullptr, nullptr};      // [0]: one token step, [1]: kGraphSteps consecutive steps
     int g_B = 0, g_eos = 0, g_flags = 0, g_gen = -1, g_topk = 0;
-    float g_temp = 0.f;
+    float g_temp = 0.f, g_topp = 1.f, g_pen = 1.f;
     float* d_u = nullptr;               // uniforms of a sampled decode run: [max_seq][B], indexed by the device-side step counter
     float s_temp = 1.f; int s_topk = 0; // sampling parameters of the run in flight (AM_SAMPLE)
+    float s_topp = 1.f, s_pen = 1.f;
+    float w_topp = 1.f, w_pen = 1.f;    // pgv_kv_set_warpers: what every later pick on this cache runs with
+    unsigned* d_seen = nullptr;         // seen-set of every slot (repetition penalty): [B][seen_words] bitmaps over the vocabulary
+    int seen_words = 0;
     bool warmed = false;
 };
 
@@ -378,6 +382,9 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
                  o_logits = take(B * V * 4), o_ssq = take(CTn * H * 4), o_av = take(CTn * V * 4), o_ai = take(CTn * V * 4), o_ints = take((4 * B + B * (size_t)max_seq) * 4),
                  o_u = take(B * (size_t)max_seq * 4), o_dpart = take(B * llm->cfg.heads * (size_t)kDattnSplitMax * kDattnPart * 4), o_dtick = take(B * llm->cfg.heads * 4),
                  o_k8 = take((H / 16) * 8 * CTn * 64 * 16);
+    kv->seen_words = (int)(V / 32);                          // vocab_cap is a multiple of 16: round up
+    if ((size_t)kv->seen_words * 32 < V) kv->seen_words += 1;
+    const size_t o_seen = take(B * (size_t)kv->seen_words * 4);
     hipError_t e = hipMalloc((void**)&kv->blob, off);
     if (e != hipSuccess) { delete kv; pgv_set_error("pgv_kv_create: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
     char* b = kv->blob;
@@ -388,7 +395,9 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
     kv->d_u = (float*)(b + o_u);
     kv->dattn_part = (float*)(b + o_dpart); kv->dattn_ticket = (unsigned*)(b + o_dtick);
     kv->k8_part = (void*)(b + o_k8);
+    kv->d_seen = (unsigned*)(b + o_seen);
     e = hipMemset(ints, 0, (4 * B + B * (size_t)max_seq) * 4);
+    if (e == hipSuccess) e = hipMemset(kv->d_seen, 0, B * (size_t)kv->seen_words * 4);
     if (e == hipSuccess) e = hipMemset(kv->dattn_ticket, 0, B * llm->cfg.heads * 4);
     if (e == hipSuccess) e = hipMemset(kv->ssq, 0, CTn * H * 4);
     if (e == hipSuccess) e = hipMemset(kv->xn, 0, CTn * 16 * H * 2);            // the columns of absent sequences are read (never stored): finite
@@ -404,6 +413,21 @@ extern "C" void pgv_kv_destroy(pgv_kv* kv) {
     for (auto g : kv->gexec) if (g) (void)hipGraphExecDestroy(g);
     if (kv->blob) (void)hipFree(kv->blob);
     delete kv;
+}
+
+extern "C" int pgv_kv_set_warpers(pgv_kv* kv, float top_p, float repetition_penalty) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_set_warpers: null cache");
+    PGV_TRY(pgv_check_warpers("pgv_kv_set_warpers", top_p, repetition_penalty));
+    kv->w_topp = top_p; kv->w_pen = repetition_penalty;
+    return PGV_OK;
+}
+
+// the cache's warpers for a pick on its own slots (rows = slots unless `slot_map` says otherwise); greedy = argmax of the penalised logits
+static SampleWarp kv_warp(pgv_kv* kv, bool greedy, const int* slot_map = nullptr) {
+    SampleWarp w;
+    w.top_p = greedy ? 1.f : kv->w_topp; w.penalty = kv->w_pen;
+    w.seen_bits = kv->d_seen; w.seen_words = kv->seen_words; w.seen_slot = slot_map;
+    return w;
 }
 
 extern "C" int pgv_kv_len(const pgv_kv* kv, int b) { return (kv && b >= 0 && b < kv->B) ? kv->h_len[b] : -1; }
@@ -445,10 +469,12 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
     const int V = m->cfg.vocab;
     PGV_TRY(lm_head(ctx, m, kv, B, !(flags & AM_SAMPLE), s, nparts));
     pgv_prof_begin(ctx, 6, s);
-    if (flags & AM_SAMPLE)
+    if (flags & AM_SAMPLE) {
+        SampleWarp w = kv_warp(kv, false);
+        w.top_p = kv->s_topp; w.penalty = kv->s_pen;
         PGV_TRY(pgv_launch_sample(kv->logits, V, B, kv->s_temp, kv->s_topk, kv->d_u, B, 1, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
-                                  eos, flags & (AM_INC_POS | AM_RECORD), s));
-    else
+                                  eos, flags & (AM_INC_POS | AM_RECORD), s, &w));
+    } else
         PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (V + 15) / 16, kv->amax_ts, V, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, eos,
                                         flags, s));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
@@ -496,9 +522,10 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     }
     // ---- host-built row maps: [row_src | row_b | row_pos | cu (B+1) | last_rows (B) | lens (B) = positions after this call | offs (B) | slots (B)] ----
     std::vector<int>& meta = kv->h_meta;
-    meta.assign((size_t)3 * M + 5 * B + 1, 0);
+    meta.assign((size_t)4 * M + 5 * B + 1, 0);                  // + the ids as given [M], for the seen-set (pgv_launch_seen_mark)
     int* row_src = meta.data(); int* row_b = row_src + M; int* row_pos = row_b + M; int* cu = row_pos + M; int* last = cu + B + 1; int* lens = last + B; int* offs = lens + B;
     int* slot = offs + B;
+    int* raw_ids = slot + B;
     int r = 0;
     for (int b = 0; b < B; ++b) {
         cu[b] = r;
@@ -510,6 +537,7 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
             const bool vid = vp >= 0 && p > vp && p <= vp + Vt;
             if (!vid) PGV_CHECK(id >= 0 && id < vocab, "%s: token id %d at row %d outside the vocabulary (%d)", who, id, r, vocab);
             row_src[r] = vid ? -(b * Vt + (p - vp - 1) + 1) : id;
+            raw_ids[r] = id;
             row_b[r] = slots ? h_slots[b] : b; row_pos[r] = off + p;
         }
         last[b] = r - 1; lens[b] = off + h_seq_lens[b]; offs[b] = off; slot[b] = slots ? h_slots[b] : b;
@@ -535,6 +563,8 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     const int* d_row_src = d_meta; const int* d_row_b = d_meta + M; const int* d_row_pos = d_row_b + M; const int* d_cu = d_row_pos + M;
     const int* d_last = d_cu + B + 1; const int* d_lens = d_last + B; const int* d_offs = append ? d_lens + B : nullptr;
     const int* d_slots = slots ? d_lens + 2 * B : nullptr;
+    // HF's repetition penalty sees the prompt ids as given, placeholder ids included: a new prompt starts its slot's set, an appended turn adds to it
+    PGV_TRY(pgv_launch_seen_mark(d_lens + 3 * B, d_cu, d_slots, B, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s));
     if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
         PGV_HIP(hipMemcpyAsync(kv->d_pos, d_lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
         PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
@@ -579,8 +609,12 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     } else {
         PGV_TRY(lm_head(ctx, m, kv, B, true, s, nparts));           // the greedy candidates too: the same launch as a plain prefill, same logits
         pgv_prof_begin(ctx, 6, s);
-        if (d_u) PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, temperature, top_k, d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s));
-        else PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (vocab + 15) / 16, kv->amax_ts, vocab, B, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s));
+        const SampleWarp w = kv_warp(kv, d_u == nullptr, d_slots);
+        if (d_u) PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, temperature, top_k, d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w));
+        else if (kv->w_pen != 1.f) {        // greedy under a penalty: the pick over the penalised logits with top_k = 1, u = 0 (first index on ties, as the argmax)
+            PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)B * 4, s));
+            PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, 1.f, 1, kv->d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w));
+        } else PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (vocab + 15) / 16, kv->amax_ts, vocab, B, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s));
         PGV_TRY(pgv_launch_slot_scatter(d_slots, d_pick, d_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
         pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
@@ -702,9 +736,10 @@ constexpr int kGraphSteps = 8;
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s) {
     const int B = kv->active;
     if (kv->g_B != B || kv->g_eos != eos || kv->g_flags != flags || kv->g_gen != m->generation ||
-        ((flags & AM_SAMPLE) && (kv->g_temp != kv->s_temp || kv->g_topk != kv->s_topk))) {
+        ((flags & AM_SAMPLE) && (kv->g_temp != kv->s_temp || kv->g_topk != kv->s_topk || kv->g_topp != kv->s_topp || kv->g_pen != kv->s_pen))) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->g_B = B; kv->g_eos = eos; kv->g_flags = flags; kv->g_gen = m->generation; kv->g_temp = kv->s_temp; kv->g_topk = kv->s_topk;
+        kv->g_topp = kv->s_topp; kv->g_pen = kv->s_pen;
     }
     if (!kv->gexec[which]) {
         // capture on a library-owned stream (the caller's may be the legacy default stream, which cannot be
@@ -775,6 +810,13 @@ extern "C" int pgv_llm_decode_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     const int B = kv->active;
     if (d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
+    if (kv->w_pen != 1.f) {
+        // greedy under a repetition penalty (pgv_kv_set_warpers): the argmax candidates of lm_head know no penalty, so the steps run the sampled
+        // pick over the penalised logits with top_k = 1 and u = 0 -- the largest value, the first index on ties
+        PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)n * B * 4, s));
+        kv->s_temp = 1.f; kv->s_topk = 1; kv->s_topp = 1.f; kv->s_pen = kv->w_pen;
+        PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | AM_SAMPLE, n, s));
+    } else
     PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD, n, s));
     PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
@@ -787,8 +829,9 @@ extern "C" int pgv_llm_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, float temper
     if (kv->active < 1) { pgv_set_error("pgv_llm_sample: no prefilled sequences in this cache"); return PGV_ESTATE; }
     hipStream_t s = (hipStream_t)stream;
     const int B = kv->active;
+    const SampleWarp w = kv_warp(kv, false);
     PGV_TRY(pgv_launch_sample(kv->logits, m->cfg.vocab, B, temperature, top_k, d_u, B, 0, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
-                              -1, 0, s));
+                              -1, 0, s, &w));
     if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
@@ -805,7 +848,7 @@ extern "C" int pgv_llm_decode_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     if (d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
     PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)n * B * 4, hipMemcpyDeviceToDevice, s));     // n <= max_seq (check_decode)
-    kv->s_temp = temperature; kv->s_topk = top_k;
+    kv->s_temp = temperature; kv->s_topk = top_k; kv->s_topp = kv->w_topp; kv->s_pen = kv->w_pen;
     PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | AM_SAMPLE, n, s));
     PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());

@@ -41,8 +41,20 @@ int pgv_launch_unpack_blocked(int dtype, const void* src, float* dst, long long 
 int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const void* rope, void* Kc, void* Vc, void* out, int B, int H,
                            int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket, int split_force);
 // sampling.hip
+// The processors beyond temperature / top-k (null or neutral values: the pick runs without them).  Seen-set of row b: the bitmap of slot
+// seen_slot[b] (null: b) in seen_bits [slots][seen_words] -- the pick then sets the bit of the token it returns -- and / or the id list
+// seen_ids[b * seen_stride .. + seen_lens[b]).  kept [B] (optional): vocabulary entries left with non-zero probability.
+struct SampleWarp {
+    float top_p = 1.f, penalty = 1.f;
+    unsigned* seen_bits = nullptr; int seen_words = 0; const int* seen_slot = nullptr;
+    const int* seen_ids = nullptr; int seen_stride = 0; const int* seen_lens = nullptr;
+    int* kept = nullptr;
+};
+int pgv_check_warpers(const char* who, float top_p, float penalty);
 int pgv_launch_sample(const float* logits, int V, int B, float temperature, int top_k, const float* u, int u_stride, int u_by_step, int* next, int* pos,
-                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s);
+                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp = nullptr);
+// prefill: ids [M] of B sequences (row ranges cu [B + 1]) -> bitmap of slot slots[b] (null: b); clear = start from an empty set
+int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s);
 int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, int* next, int* pos, int* step, int* hist, int hist_stride, int* done,
                             int eos, int advance, hipStream_t s);
 // pgv_llm_prefill_slots: sequence i of the call becomes slot slots[i] -- cur = pick[i], pos = lens[i], step = done = 0

@@ -60,6 +60,21 @@ __global__ __launch_bounds__(256) void argmax_parts_kernel(const float* __restri
 // inside the selected wave -> an inclusive scan of the selected round.  Everything is a fixed-order reduction: same logits + same u ->
 // same token, on any launch.  The k-th largest logit comes from a 4-pass radix select on order-preserving integer keys (LDS histogram).
 // The logits (128 KB per sequence) are re-read from L2 per pass instead of living in registers.
+//
+// sample_kernel<true> adds the two HF processors around that chain (generation/logits_process.py, RepetitionPenaltyLogitsProcessor and
+// TopPLogitsWarper), in HF's order:
+//  * repetition penalty, on the raw logits: x = x < 0 ? x * penalty : x / penalty for every id of the row's seen-set.  The set is a
+//    bitmap in LDS (8 KB at the 65536-entry limit), loaded from the cache slot's bitmap or built from an id list with integer LDS atomics;
+//    every later pass reads the logits through it.  With a slot bitmap the pick sets the bit of the token it returns.
+//  * nucleus: HF sorts ascending and removes a token iff its cumulative probability is <= 1 - top_p, i.e. a token stays iff the mass of the
+//    tokens ranked above it is < top_p.  Tie rule: equal (penalised) logits share one rank -- a value v stays iff the mass of the values
+//    strictly greater than v is < top_p, so equal logits are kept or removed together (as `scores < kth` does for top-k) and the maximum
+//    always stays.  The smallest kept key comes from a second 4-pass radix select, over weight MASS instead of counts: a 256-bin LDS
+//    histogram of the summed weights per key byte.  The weights enter it as 64-bit fixed point (e * 2^40, e in (0, 1]; 65536 of them fit
+//    2^56) through integer LDS atomics, so the sums do not depend on the order in which lanes arrive.  With 0 < top_k the survivors of
+//    the top-k mask (k plus ties) are first compacted into LDS and the four passes walk that list; the whole-vocabulary case walks the
+//    logits, adding a wave's weights with ONE atomic when all its lanes fall into the same bin (the two leading bytes nearly always).
+// sample_kernel<false> is the kernel as it was: with top_p >= 1 and penalty == 1 that is the one launched.
 // ---------------------------------------------------------------------------------------------
 struct SampleArgs {
     const float* logits; int V;
@@ -67,6 +82,7 @@ struct SampleArgs {
     int top_k;
     const float* u; int u_stride; int u_by_step;     // uniform of sequence b: u[(u_by_step ? step[b] : 0) * u_stride + b]
     int* next; int* pos; int* step; int* hist; int hist_stride; int* done; int eos; int advance;
+    SampleWarp w;            // sample_kernel<true> only
 };
 
 __device__ __forceinline__ unsigned float_key(float x) {          // larger float <-> larger key; NaN -> 0 (below every number)
@@ -76,9 +92,21 @@ __device__ __forceinline__ unsigned float_key(float x) {          // larger floa
 }
 
 constexpr int SAMPLE_MAXR = 64;     // rounds of 64 per wave: V <= 16 * 64 * 64 = 65536
+constexpr int SAMPLE_CAND = 1024;   // top-k survivors the nucleus select compacts into LDS (more: it walks the logits instead)
+constexpr float SAMPLE_FX = 1099511627776.f;     // 2^40: fixed-point scale of a weight in the mass histogram
 
+__device__ __forceinline__ unsigned long long weight_fx(float e) { return e > 0.f ? (unsigned long long)(e * SAMPLE_FX) : 0ull; }     // NaN -> 0
+
+template <bool WARP>
 __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
     __shared__ int hist[256];
+    __shared__ unsigned sbits[WARP ? 16 * 64 * SAMPLE_MAXR / 32 : 1];      // seen-set of the row
+    __shared__ unsigned long long mass[WARP ? 256 : 1];
+    __shared__ unsigned ckey[WARP ? SAMPLE_CAND : 1];
+    __shared__ unsigned long long cfx[WARP ? SAMPLE_CAND : 1];
+    __shared__ int ccount[1];
+    __shared__ unsigned long long sel_q[2];
+    __shared__ int kc[16];
     __shared__ float R[16][SAMPLE_MAXR];
     __shared__ float Wt[16];
     __shared__ float red[16];
@@ -90,11 +118,38 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
     const float* lg = p.logits + (size_t)b * V;
     const int seg = (((V + 15) / 16) + 63) / 64 * 64, rounds = seg / 64;
     const int base = w * seg;
+    // ---- seen-set -> LDS; `load` = the logit every later pass sees (penalised when its id is in the set) ----------
+    const bool pen_on = WARP && p.w.penalty != 1.f;
+    const int slot = (WARP && p.w.seen_slot) ? p.w.seen_slot[b] : b;
+    if constexpr (WARP) {
+        if (pen_on) {
+            const int words = (V + 31) >> 5;
+            const unsigned* gb = p.w.seen_bits ? p.w.seen_bits + (size_t)slot * p.w.seen_words : nullptr;
+            for (int i = tid; i < words; i += 1024) sbits[i] = gb ? gb[i] : 0u;
+            __syncthreads();
+            if (p.w.seen_ids) {
+                const int* ids = p.w.seen_ids + (size_t)b * p.w.seen_stride;
+                const int n = p.w.seen_lens[b];
+                for (int j = tid; j < n; j += 1024) {
+                    const int id = ids[j];
+                    if (id >= 0 && id < V) atomicOr(&sbits[id >> 5], 1u << (id & 31));
+                }
+                __syncthreads();
+            }
+        }
+    }
+    auto load = [&](int i) -> float {
+        float x = lg[i];
+        if constexpr (WARP) {
+            if (pen_on && ((sbits[i >> 5] >> (i & 31)) & 1u)) x = x < 0.f ? __fmul_rn(x, p.w.penalty) : __fdiv_rn(x, p.w.penalty);
+        }
+        return x;
+    };
     // ---- pass 1: maximum over the finite entries --------------------------------------------------
     float mx = -INFINITY;
     for (int r = 0; r < rounds; ++r) {
         const int i = base + r * 64 + lane;
-        const float x = i < V ? lg[i] : -INFINITY;
+        const float x = i < V ? load(i) : -INFINITY;
         mx = fmaxf(mx, x);                       // fmaxf drops NaN operands
     }
     mx = wave_max(mx);
@@ -114,7 +169,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
             for (int r = 0; r < rounds; ++r) {
                 const int i = base + r * 64 + lane;
                 if (i < V) {
-                    const unsigned key = float_key(lg[i]);
+                    const unsigned key = float_key(load(i));
                     if ((key & mask) == prefix) atomicAdd(&hist[(key >> (8 * pass)) & 255u], 1);
                 }
             }
@@ -136,18 +191,100 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
         }
         thr = prefix;
     }
+    // ---- nucleus: the smallest key whose strictly-greater weight mass is < top_p * total (radix select over fixed-point mass) ----
+    if constexpr (WARP) {
+        if (p.w.top_p < 1.f) {
+            auto cand_fx = [&](int i, unsigned& key) -> unsigned long long {      // fixed-point weight of a top-k survivor, 0 for everything else
+                if (i >= V) return 0ull;
+                const float x = load(i);
+                key = float_key(x);
+                return (key >= thr && key != 0u) ? weight_fx(__builtin_amdgcn_exp2f((x - M) * p.c)) : 0ull;
+            };
+            bool compact = false;
+            if (p.top_k > 0 && p.top_k < V) {
+                if (tid == 0) ccount[0] = 0;
+                __syncthreads();
+                for (int r = 0; r < rounds; ++r) {
+                    unsigned key = 0u;
+                    const unsigned long long q = cand_fx(base + r * 64 + lane, key);
+                    if (q != 0ull) {
+                        const int at = atomicAdd(&ccount[0], 1);       // the list's order is arbitrary: only order-free integer sums read it
+                        if (at < SAMPLE_CAND) { ckey[at] = key; cfx[at] = q; }
+                    }
+                }
+                __syncthreads();
+                compact = ccount[0] <= SAMPLE_CAND;
+            }
+            unsigned prefix = 0u, mask = 0u;
+            if (tid == 0) { sel_q[0] = 0ull; sel_q[1] = 0ull; }          // mass above the prefix; the limit top_p * total (set in the first pass)
+            for (int pass = 3; pass >= 0; --pass) {
+                if (tid < 256) mass[tid] = 0ull;
+                __syncthreads();
+                if (compact) {
+                    if (tid < ccount[0] && (ckey[tid] & mask) == prefix) atomicAdd(&mass[(ckey[tid] >> (8 * pass)) & 255u], cfx[tid]);
+                } else {
+                    for (int r = 0; r < rounds; ++r) {
+                        unsigned key = 0u;
+                        unsigned long long q = cand_fx(base + r * 64 + lane, key);
+                        if ((key & mask) != prefix) q = 0ull;
+                        const int bin = (int)((key >> (8 * pass)) & 255u);
+                        const unsigned long long act = __ballot(q != 0ull);
+                        if (act == 0ull) continue;
+                        const int bin0 = __shfl(bin, __builtin_ctzll(act), 64);
+                        if (__ballot(q != 0ull && bin != bin0) == 0ull) {   // one bin for the whole wave: one atomic (integer adds: any order, same sum)
+#pragma unroll
+                            for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+                            if (lane == 0) atomicAdd(&mass[bin0], q);
+                        } else if (q != 0ull) {
+                            atomicAdd(&mass[bin], q);
+                        }
+                    }
+                }
+                __syncthreads();
+                if (tid == 0) {
+                    if (pass == 3) {
+                        unsigned long long S = 0ull;
+                        for (int q = 0; q < 256; ++q) S += mass[q];
+                        sel_q[1] = (unsigned long long)ceil((double)p.w.top_p * (double)S);     // integer D: D < top_p * S  <=>  D < ceil(top_p * S)
+                    }
+                    // the lowest non-empty bin whose LARGEST key is kept (mass above it < limit): the boundary key lies in it
+                    const unsigned long long limit = sel_q[1];
+                    unsigned long long cum = sel_q[0];
+                    int bin = -1;
+                    for (int q = 255; q >= 0; --q) {
+                        const unsigned long long h = mass[q];
+                        if (h == 0ull) continue;
+                        if (cum >= limit) break;
+                        bin = q; sel_q[0] = cum;
+                        cum += h;
+                    }
+                    sel_i[0] = bin;
+                }
+                __syncthreads();
+                const int bin = sel_i[0];
+                __syncthreads();
+                if (bin < 0) { mask = 0u; break; }                        // no finite weight in the row: keep what top-k kept
+                prefix |= (unsigned)bin << (8 * pass);
+                mask |= 0xffu << (8 * pass);
+            }
+            if (mask == 0xffffffffu) thr = prefix;                        // >= the top-k threshold: every candidate passed it
+        }
+    }
     // ---- weights e_i = exp2((x_i - M) c) of the kept entries; round and wave totals -------------------------
     auto weight = [&](int i) -> float {
         if (i >= V) return 0.f;
-        const float x = lg[i];
+        const float x = load(i);
         const unsigned key = float_key(x);
         return (key >= thr && key != 0u) ? __builtin_amdgcn_exp2f((x - M) * p.c) : 0.f;
     };
+    int nkept = 0;
     for (int r = 0; r < rounds; ++r) {
         const float e = weight(base + r * 64 + lane);
         const float t = wave_sum(e);
         if (lane == 0) R[w][r] = t;
+        if constexpr (WARP) nkept += __popcll(__ballot(e > 0.f));
     }
+    if constexpr (WARP) { if (lane == 0) kc[w] = nkept; }
     __syncthreads();
     if (tid < 16) {
         float t = 0.f;
@@ -158,6 +295,9 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
     if (tid == 0) {
         float S = 0.f;
         for (int i = 0; i < 16; ++i) S += Wt[i];
+        if constexpr (WARP) {
+            if (p.w.kept) { int n = 0; for (int i = 0; i < 16; ++i) n += kc[i]; p.w.kept[b] = n; }
+        }
         const float uu = p.u[(size_t)(p.u_by_step ? p.step[b] : 0) * p.u_stride + b];
         float T = uu * S;
         int ws = -1, last = 0; float acc = 0.f;
@@ -200,6 +340,27 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
         }
         if (p.advance & 1) p.pos[b] += 1;
         p.next[b] = tok;
+        if constexpr (WARP) {                                 // the returned token joins the slot's seen-set (one workgroup per slot: a plain update)
+            if (p.w.seen_bits && tok >= 0 && tok < V) p.w.seen_bits[(size_t)slot * p.w.seen_words + (tok >> 5)] |= 1u << (tok & 31);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Seen-set of a prefill: sequence b's ids (placeholder ids included, ids outside the vocabulary ignored) are set in the bitmap of its slot;
+// `clear` first empties it (a new prompt; an appended turn keeps what the slot has seen).  One workgroup per sequence.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void seen_mark_kernel(const int* __restrict__ ids, const int* __restrict__ cu, const int* __restrict__ slots, int V,
+                                                        unsigned* __restrict__ bits, int words, int clear) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    unsigned* row = bits + (size_t)(slots ? slots[b] : b) * words;
+    if (clear) {
+        for (int i = tid; i < words; i += 256) row[i] = 0u;
+        __syncthreads();
+    }
+    for (int r = cu[b] + tid; r < cu[b + 1]; r += 256) {
+        const int id = ids[r];
+        if (id >= 0 && id < V) atomicOr(&row[id >> 5], 1u << (id & 31));
     }
 }
 
@@ -231,14 +392,48 @@ int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax
     return PGV_OK;
 }
 
+int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s) {
+    hipLaunchKernelGGL(seen_mark_kernel, dim3(B), dim3(256), 0, s, ids, cu, slots, V, bits, words, clear);
+    return PGV_OK;
+}
+
+int pgv_check_warpers(const char* who, float top_p, float penalty) {
+    // HF's wording: generation/logits_process.py, TopPLogitsWarper / RepetitionPenaltyLogitsProcessor constructors (top_p == 0 is refused here:
+    // an empty nucleus has no meaning beyond min_tokens_to_keep)
+    PGV_CHECK(top_p > 0.f && top_p <= 1.f, "%s: `top_p` has to be a float > 0 and <= 1, but is %g", who, (double)top_p);
+    PGV_CHECK(penalty > 0.f, "%s: `penalty` has to be a strictly positive float, but is %g", who, (double)penalty);
+    return PGV_OK;
+}
+
 int pgv_launch_sample(const float* logits, int V, int B, float temperature, int top_k, const float* u, int u_stride, int u_by_step, int* next, int* pos,
-                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s) {
+                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp) {
     PGV_CHECK(V >= 1 && V <= 16 * 64 * SAMPLE_MAXR, "sample: vocabulary %d outside [1, %d]", V, 16 * 64 * SAMPLE_MAXR);
     PGV_CHECK(temperature > 0.f, "sample: temperature must be positive (got %g); use the greedy path for temperature 0", (double)temperature);
     SampleArgs a;
     a.logits = logits; a.V = V; a.c = 1.4426950408889634f / temperature; a.top_k = top_k; a.u = u; a.u_stride = u_stride; a.u_by_step = u_by_step;
     a.next = next; a.pos = pos; a.step = step; a.hist = hist; a.hist_stride = hist_stride; a.done = done; a.eos = eos; a.advance = advance;
-    hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(1024), 0, s, a);
+    a.w = warp ? *warp : SampleWarp{};
+    // the neutral values run the kernel without the two extra processors: bit for bit the tokens of the temperature / top-k chain alone
+    if (warp && (warp->top_p < 1.f || warp->penalty != 1.f || warp->kept)) {
+        PGV_TRY(pgv_check_warpers("sample", warp->top_p, warp->penalty));
+        PGV_CHECK(warp->seen_bits == nullptr || warp->seen_words * 32 >= V, "sample: seen-set bitmap of %d words for a vocabulary of %d", warp->seen_words, V);
+        hipLaunchKernelGGL(sample_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(sample_kernel<false>, dim3(B), dim3(1024), 0, s, a);
+    }
+    return PGV_OK;
+}
+
+extern "C" int pgv_sample_logits_ex(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                                    const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u, int32_t* d_next, int32_t* d_kept,
+                                    void* stream) {
+    PGV_CHECK(ctx && d_logits && d_u && d_next && B >= 1, "pgv_sample_logits_ex: bad arguments");
+    PGV_CHECK((d_seen_ids == nullptr) == (d_seen_lens == nullptr) && seen_stride >= 0, "pgv_sample_logits_ex: d_seen_ids and d_seen_lens go together");
+    PGV_TRY(pgv_check_warpers("pgv_sample_logits_ex", top_p, repetition_penalty));
+    SampleWarp w;
+    w.top_p = top_p; w.penalty = repetition_penalty; w.seen_ids = d_seen_ids; w.seen_stride = seen_stride; w.seen_lens = d_seen_lens; w.kept = d_kept;
+    PGV_TRY(pgv_launch_sample(d_logits, V, B, temperature, top_k, d_u, B, 0, d_next, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, (hipStream_t)stream, &w));
+    PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 

@@ -29,6 +29,11 @@ def add_runtime_arguments(parser):
     parser.add_argument("--max_new_tokens", type=int, default=1024)
     parser.add_argument("--do_sample", action="store_true", help="reference decoding: temperature-0.2 sampling, one clip at a time (with --schedule refill: "
                                                                  "batched, every task drawing from its own seeded stream)")
+    parser.add_argument("--top_p", type=float, default=None,
+                        help="nucleus filter of --do_sample (HF TopPLogitsWarper); default: the checkpoint's generation_config.json, else 1.0")
+    parser.add_argument("--repetition_penalty", type=float, default=None,
+                        help="HF RepetitionPenaltyLogitsProcessor over prompt + answer, greedy and sampled; default: the checkpoint's "
+                             "generation_config.json, else 1.0")
     parser.add_argument("--schedule", choices=("group", "refill"), default="group",
                         help="group (default): answer the shard in static groups of --batch clips, each decoding until its longest answer ends; refill: keep "
                              "--batch decode slots busy and refill a slot with the next task as soon as its answer ends (continuous batching, "
@@ -258,6 +263,11 @@ class _Runner:
                                      "prefill_s_group": tm_g.get("prefill_s"), "decode_s_group": tm_g.get("decode_s"),
                                      "decode_steps_group": tm_g.get("steps")}) + "\n")
 
+    def warpers(self):
+        """--top_p / --repetition_penalty as generate() arguments: only the ones given, so the rest comes from the model's generation config."""
+        given = {"top_p": getattr(self.args, "top_p", None), "repetition_penalty": getattr(self.args, "repetition_penalty", None)}
+        return {k: v for k, v in given.items() if v is not None}
+
     def infer_batch(self, indices, clips=None):
         """--schedule group -> (tokens [n, <= max_new] int32, lengths).  DEVICE half of a group: ONE tower pass over the frames of all distinct
         uncached clips of the group, then batched prefill + decode with the per-chunk stop-string check."""
@@ -276,7 +286,7 @@ class _Runner:
             # is for conv modes whose stop is ordinary text (default: "###") -- without it every group decodes max_new_tokens steps
             return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
                                        do_sample=False, max_new_tokens=self.args.max_new_tokens, stop_strings=[s for _, _, _, s in part],
-                                       tokenizer=self.tokenizer, timings=timings).cpu()
+                                       tokenizer=self.tokenizer, timings=timings, **self.warpers()).cpu()
 
         def record(part, out):
             for row, (j, ids, _, _) in zip(out, part):
@@ -336,8 +346,12 @@ class _Runner:
                 pool.shutdown(wait=True, cancel_futures=True)
 
         tm = {} if self.tfile else None
+        # temperature 0.2, top_k 50: the reference's call (inference.py:106-112 + HF's default); the two warpers by generate()'s precedence
+        from ..generation import resolve_sampling
+        _, _, top_p, rep_pen = resolve_sampling(0.2, 50, generation_config=getattr(self.model, "generation_config", None), **self.warpers())
+        warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
         for idx, new in generate_continuous(self.model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
-                                            tokenizer=self.tokenizer, on_error=self.failed, timings=tm):
+                                            tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp):
             if new is not None:
                 self.record(toks, lens, row[idx], new)
         if self.tfile:
@@ -365,7 +379,7 @@ class _Runner:
                     raise clips[t["path"]]
                 new, stop = video_chatgpt_infer_ids(None, t["question"], self.args.conv_mode, self.model, self.vision_tower, self.tokenizer,
                                                     self.image_processor, self.video_token_len, None, max_new_tokens=self.args.max_new_tokens,
-                                                    features=feat_of[t["path"]])
+                                                    features=feat_of[t["path"]], **self.warpers())
                 self.stop_strs[idx] = stop
                 self.record(toks, lens, j, new, strip_eos=False)       # the ids end where the reference's criterion stopped them
             except Exception as e:                                     # noqa: BLE001

@@ -1,0 +1,117 @@
+"""Which sampling parameters a `generate()` call runs with, and which HF `generate()` arguments it refuses.
+
+The reference calls HF's `model.generate(...)` (video_chatgpt/inference.py:105-112, chat.py:148-154).  HF merges the checkpoint's
+`generation_config.json` into every call: an argument given in the call wins, else the file's value, else HF's own default
+(GenerationMixin._prepare_generation_config: `generation_config = copy(self.generation_config); generation_config.update(**kwargs)`).
+This module is that precedence for the four parameters the device pick implements, plus the list of arguments that would change HF's
+result and have no counterpart here -- those raise instead of being ignored.  Pure host code: importable without a GPU.
+"""
+from __future__ import annotations
+
+import json
+import os
+from typing import Any, Dict, Optional, Tuple
+
+GENERATION_CONFIG_NAME = "generation_config.json"
+
+# HF's GenerationConfig defaults (generation/configuration_utils.py) of the parameters the pick implements
+HF_DEFAULTS = {"temperature": 1.0, "top_k": 50, "top_p": 1.0, "repetition_penalty": 1.0}
+
+
+def _positive(v) -> bool:
+    return v is not None and v > 0
+
+
+# argument -> True when the value asks HF for something this package does not compute (HF's neutral default passes)
+REFUSED = {
+    "num_beams": lambda v: v is not None and v > 1,
+    "num_beam_groups": lambda v: v is not None and v > 1,
+    "num_return_sequences": lambda v: v is not None and v > 1,
+    "min_p": lambda v: v is not None,
+    "typical_p": lambda v: v is not None and v < 1.0,
+    "penalty_alpha": lambda v: v is not None and v != 0,
+    "no_repeat_ngram_size": _positive,
+    "encoder_no_repeat_ngram_size": _positive,
+    "bad_words_ids": lambda v: v is not None,
+    "min_length": _positive,
+    "min_new_tokens": _positive,
+    "epsilon_cutoff": _positive,
+    "eta_cutoff": _positive,
+    "encoder_repetition_penalty": lambda v: v is not None and v != 1.0,
+}
+
+
+class GenerationDefaults:
+    """The fields of a checkpoint's generation_config.json, as attributes (`model.generation_config`).  An absent field reads as None."""
+
+    def __init__(self, **fields):
+        self._fields = dict(fields)
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        return self._fields.get(name)
+
+    def to_dict(self) -> Dict[str, Any]:
+        return dict(self._fields)
+
+    def __repr__(self):
+        return f"GenerationDefaults({self._fields})"
+
+
+def load_generation_config(path: str) -> Optional[GenerationDefaults]:
+    """`path`/generation_config.json -> GenerationDefaults; None when the checkpoint directory has no such file."""
+    f = os.path.join(path, GENERATION_CONFIG_NAME)
+    if not os.path.isfile(f):
+        return None
+    with open(f) as fh:
+        return GenerationDefaults(**json.load(fh))
+
+
+def _config_get(generation_config, name):
+    if generation_config is None:
+        return None
+    if isinstance(generation_config, dict):
+        return generation_config.get(name)
+    return getattr(generation_config, name, None)
+
+
+def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: str = "generate()") -> None:
+    """Raise ValueError naming the first argument -- of the call, else of the model's generation config -- that changes what HF's generate()
+    returns and that this package does not implement.  Everything else in `kwargs` is inert here (use_cache, pad_token_id, an all-ones
+    attention_mask, output_scores=False, ...) and stays ignored."""
+    for name, asks in REFUSED.items():
+        if name in kwargs:
+            v, where = kwargs[name], "argument"
+        else:
+            v, where = _config_get(generation_config, name), "generation_config field"
+        if asks(v):
+            raise ValueError(f"{who}: {where} `{name}`={v!r} is not implemented by this package (it would change the result of HF's generate()); "
+                             f"implemented: temperature, top_k, top_p, repetition_penalty")
+    for name in ("output_scores", "output_attentions", "output_hidden_states", "return_dict_in_generate"):
+        if kwargs.get(name):
+            raise ValueError(f"{who}: argument `{name}`={kwargs[name]!r} is not implemented by this package (generate() returns the ids only)")
+    mask = kwargs.get("attention_mask")
+    if mask is not None:
+        import torch
+        if not bool(torch.as_tensor(mask).to(torch.bool).all()):
+            raise ValueError(f"{who}: argument `attention_mask` with padding is not implemented; pass a list of prompts for a ragged batch")
+
+
+def resolve_sampling(temperature=None, top_k=None, top_p=None, repetition_penalty=None, generation_config=None) -> Tuple[float, int, float, float]:
+    """(temperature, top_k, top_p, repetition_penalty) of a call: each from the call if given (not None), else from the model's
+    generation config, else HF's default -- HF's own precedence.  top_p / repetition_penalty are validated with HF's wording."""
+    given = {"temperature": temperature, "top_k": top_k, "top_p": top_p, "repetition_penalty": repetition_penalty}
+    out = {}
+    for name, v in given.items():
+        if v is None:
+            v = _config_get(generation_config, name)
+        if v is None:
+            v = HF_DEFAULTS[name]
+        out[name] = v
+    t, k, p, r = float(out["temperature"]), int(out["top_k"]), float(out["top_p"]), float(out["repetition_penalty"])
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"`top_p` has to be a float > 0 and <= 1, but is {p}")
+    if not r > 0.0:
+        raise ValueError(f"`penalty` has to be a strictly positive float, but is {r}")
+    return t, k, p, r

@@ -141,10 +141,11 @@ def video_features_batch(clips, vision_tower, image_processor, timings=None):
 
 
 def video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
-                            transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None):
+                            transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, **generate_kwargs):
     """`video_chatgpt_infer` up to (not including) the detokenisation: -> (generated token ids [n] as a list, stop string).  The runners'
     sampling path collates these ids through the same fixed-shape all-gather as the greedy path (parallel.gather_answers) and decodes them
-    on every rank.  `features`: pooled [100 + P, 1024] features computed earlier for this clip (skips the tower)."""
+    on every rank.  `features`: pooled [100 + P, 1024] features computed earlier for this clip (skips the tower).  `generate_kwargs`
+    (top_p, repetition_penalty, ...) go to model.generate as they are."""
     prompt, stop_str = build_prompt(question, conv_mode, video_token_len, model.get_model().vision_config.use_vid_start_end, transcript)
     inputs = tokenizer([prompt])
     feats = features if features is not None else video_features(video_frames, vision_tower, image_processor)
@@ -152,7 +153,7 @@ def video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tow
     stopping_criteria = KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)
     with torch.inference_mode():
         output_ids = model.generate(input_ids, video_spatio_temporal_features=feats.unsqueeze(0), do_sample=do_sample,
-                                    temperature=temperature, max_new_tokens=max_new_tokens, stopping_criteria=[stopping_criteria])
+                                    temperature=temperature, max_new_tokens=max_new_tokens, stopping_criteria=[stopping_criteria], **generate_kwargs)
     n_in = input_ids.shape[1]
     n_diff = int((input_ids.to(output_ids.device) != output_ids[:, :n_in]).sum())
     if n_diff > 0:

@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..constants import CLIP_WIDTH
+from ..generation import check_generate_kwargs, load_generation_config, resolve_sampling
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
 from .utils import AnswerState
 
@@ -113,6 +114,8 @@ class CausalLMOutputWithPast:
 
 
 class VideoChatGPTLlamaForCausalLM(nn.Module):
+    generation_config = None        # the checkpoint's generation_config.json (from_pretrained; generation.GenerationDefaults): HF's per-model generate() defaults
+
     def __init__(self, config: VideoChatGPTConfig, vision_config: Optional[VisionConfig] = None,
                  torch_dtype: torch.dtype = torch.float16, device=None):
         super().__init__()
@@ -291,6 +294,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 model.load_state_dict(torch.load(os.path.join(path, f), map_location="cpu"), strict=False)
         if model.ctx.lib.pgv_llm_missing(model.handle):
             raise RuntimeError(f"{path}: decoder checkpoint is incomplete")
+        model.generation_config = load_generation_config(path)     # HF's from_pretrained reads it the same way; absent: None
         return model
 
     # ---- prompt validation (host): same checks and messages as model/video_chatgpt.py:113-128,150-157 ----
@@ -397,12 +401,15 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         return kv, nxt, logits
 
     def prefill_slots(self, kv, slots: Sequence[int], seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor],
-                      want_logits: bool = False, u: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 50):
+                      want_logits: bool = False, u: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 50,
+                      top_p: float = 1.0, repetition_penalty: float = 1.0):
         """Prefill NEW prompts `seqs` into cache slots `slots` of the live group `kv` (a handle prefill() returned) while the other slots keep
         their state (pgv_llm_prefill_slots: continuous batching).  `video_spatio_temporal_features` [n, V, C] (None: text only; a text-only
         prompt next to video ones takes any [V, C] block, it is not read).  u [n] (optional): draw each first token as sample_last does,
-        else greedy.  Returns (first tokens [n] int32 on device, logits [n, vocab] or None)."""
+        else greedy.  top_p / repetition_penalty: the cache's warpers from this call on (set_warpers); the refilled slots start from a seen-set
+        of their own prompt only.  Returns (first tokens [n] int32 on device, logits [n, vocab] or None)."""
         n = len(seqs)
+        self.set_warpers(kv, top_p, repetition_penalty)
         if len(slots) != n:
             raise ValueError(f"{len(slots)} slots for {n} prompts")
         lens = [len(s) for s in seqs]
@@ -433,6 +440,10 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                                                       _lib.stream_ptr(self.device_)), "pgv_llm_prefill_slots")
         return nxt, logits
 
+    def set_warpers(self, kv, top_p: float = 1.0, repetition_penalty: float = 1.0):
+        """pgv_kv_set_warpers: HF's TopPLogitsWarper / RepetitionPenaltyLogitsProcessor values for every later pick on this cache."""
+        _lib.check(self.ctx.lib.pgv_kv_set_warpers(kv, float(top_p), float(repetition_penalty)), "pgv_kv_set_warpers")
+
     def kv_len(self, kv, b: int) -> int:
         return int(self.ctx.lib.pgv_kv_len(kv, int(b)))
 
@@ -448,24 +459,29 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                                                _lib.stream_ptr(self.device_)), "pgv_llm_decode")
         return nxt, logits
 
-    def decode_greedy(self, kv, first: torch.Tensor, n: int, eos_id: int = -1) -> torch.Tensor:
+    def decode_greedy(self, kv, first: torch.Tensor, n: int, eos_id: int = -1, repetition_penalty: float = 1.0) -> torch.Tensor:
+        """n greedy steps on the device; repetition_penalty != 1: the argmax of the penalised logits (the cache's seen-set)."""
         B = first.shape[0]
+        self.set_warpers(kv, 1.0, repetition_penalty)
         toks = torch.empty(B, n, dtype=torch.int32, device=self.device_)
         _lib.check(self.ctx.lib.pgv_llm_decode_greedy(self.ctx.handle, self.handle, kv, first.data_ptr(), n, eos_id, toks.data_ptr(),
                                                       _lib.stream_ptr(self.device_)), "pgv_llm_decode_greedy")
         return toks
 
-    def sample_last(self, kv, u: torch.Tensor, temperature: float, top_k: int = 50) -> torch.Tensor:
+    def sample_last(self, kv, u: torch.Tensor, temperature: float, top_k: int = 50, top_p: float = 1.0, repetition_penalty: float = 1.0) -> torch.Tensor:
         """Draw the next token of every sequence from the logits of the last prefill / decode call (pgv_llm_sample): u [B] uniforms."""
+        self.set_warpers(kv, top_p, repetition_penalty)
         u = u.to(device=self.device_, dtype=torch.float32).contiguous()
         nxt = torch.empty(u.numel(), dtype=torch.int32, device=self.device_)
         _lib.check(self.ctx.lib.pgv_llm_sample(self.ctx.handle, self.handle, kv, float(temperature), int(top_k), u.data_ptr(), nxt.data_ptr(),
                                                _lib.stream_ptr(self.device_)), "pgv_llm_sample")
         return nxt
 
-    def decode_sample(self, kv, first: torch.Tensor, n: int, eos_id: int, temperature: float, top_k: int, u: torch.Tensor) -> torch.Tensor:
+    def decode_sample(self, kv, first: torch.Tensor, n: int, eos_id: int, temperature: float, top_k: int, u: torch.Tensor, top_p: float = 1.0,
+                      repetition_penalty: float = 1.0) -> torch.Tensor:
         """n sampled steps on the device (pgv_llm_decode_sample): u [n, B] uniforms, step i draws with u[i]."""
         B = first.shape[0]
+        self.set_warpers(kv, top_p, repetition_penalty)
         u = u.to(device=self.device_, dtype=torch.float32).contiguous()
         assert u.shape == (n, B)
         toks = torch.empty(B, n, dtype=torch.int32, device=self.device_)
@@ -529,10 +545,10 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
     # ---- generate ---------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, input_ids, video_spatio_temporal_features: Optional[torch.Tensor] = None, do_sample: bool = False,
-                 temperature: float = 1.0, max_new_tokens: int = 1024, stopping_criteria=None, eos_token_id="config",
-                 chunk: int = 32, generator: Optional[torch.Generator] = None, top_k: int = 50,
+                 temperature: Optional[float] = None, max_new_tokens: int = 1024, stopping_criteria=None, eos_token_id="config",
+                 chunk: int = 32, generator: Optional[torch.Generator] = None, top_k: Optional[int] = None,
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
-                 kv_reuse_key=None, **_unused):
+                 kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
 
         input_ids: LongTensor [B, S] (equal-length prompts, the reference's case) or a list of id lists (ragged batch).
@@ -543,6 +559,12 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             multinomial draw is an inverse-CDF pick in a HIP kernel (pgv_llm_decode_sample) fed with uniforms drawn up front from
             `generator` (a device torch.Generator; one uniform per sequence and step, so a run is reproducible from the seed and
             independent of the chunk size).
+        `temperature`, `top_k`, `top_p`, `repetition_penalty`: each from the call if given, else from `self.generation_config` (the checkpoint's
+        generation_config.json), else HF's default (1.0, 50, 1.0, 1.0) -- HF's own precedence (generation.resolve_sampling).  top_p and the
+        repetition penalty are HF's TopPLogitsWarper / RepetitionPenaltyLogitsProcessor inside the same device pick (pgv.h: pgv_kv_set_warpers);
+        the penalty sees the prompt ids as given plus every generated token and also applies to greedy decoding, top_p to sampling only.
+        Any other argument that would change HF's result (num_beams > 1, min_p, typical_p < 1, no_repeat_ngram_size > 0, ...:
+        generation.REFUSED), in the call or in the generation config, raises ValueError naming it; inert ones stay ignored.
         Stopping criteria (B == 1, as in the reference) are evaluated on the host after each chunk, token by token in generation
         order, and the output is cut at the first hit: the same ids as a per-token loop, the surplus steps of the chunk are discarded.
         `stop_strings` (one per sequence, None = no stop string; needs `tokenizer`): the BATCHED form of the reference's
@@ -557,6 +579,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         appended rows are bitwise what one prefill over the same cache contents computes; cache entries that DECODE steps wrote (the previous
         answer) carry the decode path's 16-bit rounding instead of the prefill path's -- as with any KV cache that is kept across calls.
         `timings["reused_tokens"]` reports the prefix."""
+        check_generate_kwargs(_unused, self.generation_config)
+        temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
         if torch.is_tensor(input_ids):
             seqs = [row.tolist() for row in input_ids.cpu()]
         else:
@@ -586,8 +610,13 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         import time as _time
         _t0 = _time.perf_counter()
 
+        # passed on only when they differ from the neutral values (the step methods default to them)
+        warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
+        pen = {} if rep_pen == 1.0 else {"repetition_penalty": rep_pen}
         reused = 0
-        if kv_reuse_key is not None and B == 1:
+        if kv_reuse_key is not None and B == 1 and rep_pen == 1.0:
+            # (under a repetition penalty the slot's seen-set has to be exactly prompt + answer: the surplus steps a kept cache carries past a
+            # stop string would stay in it, so such a turn runs the full prefill)
             reused = self._reusable_prefix(kv_reuse_key, seqs[0], max_new_tokens)
         if reused:
             kv = self._reuse[1]
@@ -600,7 +629,10 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         u = None
         if do_sample and max_new_tokens >= 1:
             u = torch.rand(max_new_tokens, B, device=self.device_, dtype=torch.float32, generator=generator)
-            nxt = self.sample_last(kv, u[0], temperature, top_k)
+            nxt = self.sample_last(kv, u[0], temperature, top_k, **warp)
+        elif rep_pen != 1.0 and max_new_tokens >= 1:
+            # greedy under a penalty: the prefill's argmax knows no penalty -- re-pick over the penalised logits (top_k = 1, u = 0: first index on ties)
+            nxt = self.sample_last(kv, torch.zeros(B, device=self.device_), 1.0, 1, **pen)
         states = [AnswerState(max_new_tokens, eos_i, stops[b] if stops is not None else None, tokenizer) for b in range(B)]
         prompt_t = torch.tensor(seqs[0], dtype=torch.long)
 
@@ -622,9 +654,9 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             while not stop and n_gen < max_new_tokens:
                 n = min(chunk, max_new_tokens - n_gen)
                 if do_sample:
-                    toks = self.decode_sample(kv, nxt, n, eos_i, temperature, top_k, u[n_gen:n_gen + n])
+                    toks = self.decode_sample(kv, nxt, n, eos_i, temperature, top_k, u[n_gen:n_gen + n], **warp)
                 else:
-                    toks = self.decode_greedy(kv, nxt, n, eos_i)
+                    toks = self.decode_greedy(kv, nxt, n, eos_i, **pen)
                 h = toks.cpu().numpy()
                 raw.extend(h[0].tolist())
                 if criteria:

@@ -196,6 +196,10 @@ class CLIPVisionTower:
     def __call__(self, pixel_values: torch.Tensor, output_hidden_states: bool = True, **_kw) -> VisionTowerOutput:
         if not output_hidden_states:
             raise ValueError("the PG-Video-LLaVA path always reads hidden_states; call with output_hidden_states=True")
+        # arguments that change what HF's CLIPVisionModel returns and have no counterpart here raise; inert ones stay ignored
+        for name, asks in (("output_attentions", bool), ("interpolate_pos_encoding", bool), ("return_dict", lambda v: v is False)):
+            if name in _kw and asks(_kw[name]):
+                raise ValueError(f"vision_tower(): argument `{name}`={_kw[name]!r} is not implemented by this package")
         return VisionTowerOutput(_LazyHiddenStates(self, pixel_values))
 
     forward = __call__
