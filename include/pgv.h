@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 323
+#define PGV_VERSION 324
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -287,6 +287,32 @@ enum pgv_epi {
 };
 int pgv_gemm(pgv_ctx *ctx, int dtype, int epi, const void *d_A, int lda, const void *d_W, int ldw, const float *d_bias,
              void *d_C, int ldc, int M, int N, int K, void *stream);
+/* pgv_gemm with every argument of the internal launcher, as the CLIP tower and the decoder fill it: W in the pgv_pack_blocked layout
+ * (w_blocked != 0: N % 16 == 0, ldw ignored; every prefill GEMM of the decoder) and the three epilogues of the folded LayerNorm, which the
+ * public enum does not list.  Same kernels, same host checks; unused pointers are NULL.
+ *  consumer  (PGV_EPI_LN_BIAS, PGV_EPI_LN_BIAS_QGELU): C16 = [quick_gelu] (rstd_m (acc - mean_m colsum_n) + bias_n) with d_rowstat [M][2] =
+ *            (mean, rstd) per row, d_colsum [N], d_bias [N] (all required).
+ *  producer  (PGV_EPI_BIAS_RESID_LNOUT): R32 = d_C += acc + bias (read-modify-write, fp32, ldc); d_x16 [M][ldx16] = round16((R32 - c_m) gnext_n)
+ *            with the centre c_m = d_rowmean[m] + *d_cshift (d_rowmean NULL: c = 0 and d_cshift is ignored; d_cshift NULL: 0);
+ *            d_stats_part [N / 64][M][2] = (sum, sum of squares) of R32 - c_m over each 64-column piece.  N % 64 == 0, ldx16 % 4 == 0.
+ * All three need row-major W and K >= 128. */
+enum { PGV_EPI_LN_BIAS = 8, PGV_EPI_LN_BIAS_QGELU = 9, PGV_EPI_BIAS_RESID_LNOUT = 10 };
+typedef struct {
+    const void *d_A; int lda;
+    const void *d_W; int ldw; int w_blocked;
+    const float *d_bias;
+    void *d_C; int ldc;
+    int M, N, K;
+    int epi;
+    const float *d_rowstat, *d_colsum;                                    /* consumer */
+    const float *d_gnext; void *d_x16; int ldx16; float *d_stats_part;    /* producer */
+    const float *d_rowmean, *d_cshift;
+} pgv_gemm_desc;
+int pgv_gemm_ex(pgv_ctx *ctx, int dtype, const pgv_gemm_desc *desc, void *stream);
+/* The kernel between producer and consumer: d_part [np][rows][2] -> d_rowstat [rows][2] = (delta, rsqrt(var + eps)) with delta = sum / cols,
+ * var = max(sumsq / cols - delta^2, 0), and d_rowmean[row] += delta + *d_cshift (d_cshift NULL: 0). */
+int pgv_ln_stats(pgv_ctx *ctx, const float *d_part, float *d_rowstat, float *d_rowmean, const float *d_cshift, int rows, int np, int cols,
+                 float eps, void *stream);
 /* CLIP self-attention on a fused qkv buffer [T*N, 3C] (q | k | v column blocks) -> [T*N, C]; head_dim 64, no mask
  * (HF CLIPAttention eager math, HF:clip/modeling_clip.py:259-277). */
 int pgv_vit_attention(pgv_ctx *ctx, int dtype, const void *d_qkv, void *d_out, int T, int N, int C, int heads, void *stream);

@@ -15,10 +15,11 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgv.so")
 
-ABI_VERSION = 323          # PGV_VERSION of include/pgv.h this table was written against
+ABI_VERSION = 324          # PGV_VERSION of include/pgv.h this table was written against
 PGV_OK, PGV_EINVAL, PGV_EHIP, PGV_ENOMEM, PGV_ESTATE, PGV_ENAME = 0, 1, 2, 3, 4, 5
 PGV_F16, PGV_BF16, PGV_F32 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_GELU, EPI_RESID, EPI_BIAS_RESID, EPI_SWIGLU, EPI_F32 = range(8)
+EPI_LN_BIAS, EPI_LN_BIAS_QGELU, EPI_BIAS_RESID_LNOUT = 8, 9, 10      # folded LayerNorm (pgv_gemm_ex only)
 FAMILIES = ("gemm", "vit_attn", "llm_prefill_attn", "decode_gemv", "decode_attn", "other", "decode_small")
 
 
@@ -33,6 +34,14 @@ class LlmConfig(C.Structure):
 
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+
+
+class GemmDesc(C.Structure):
+    """pgv_gemm_desc of include/pgv.h (pgv_gemm_ex)."""
+    _fields_ = [("d_A", _vp), ("lda", _i), ("d_W", _vp), ("ldw", _i), ("w_blocked", _i), ("d_bias", _vp), ("d_C", _vp), ("ldc", _i),
+                ("M", _i), ("N", _i), ("K", _i), ("epi", _i), ("d_rowstat", _vp), ("d_colsum", _vp), ("d_gnext", _vp), ("d_x16", _vp),
+                ("ldx16", _i), ("d_stats_part", _vp), ("d_rowmean", _vp), ("d_cshift", _vp)]
+
 
 # name -> (restype, argtypes); every symbol declared in include/pgv.h
 PROTOTYPES = {
@@ -77,6 +86,8 @@ PROTOTYPES = {
     "pgv_kv_set_warpers": (_i, [_vp, _f, _f]),
     "pgv_ingest_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pgv_gemm": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "pgv_gemm_ex": (_i, [_vp, _i, C.POINTER(GemmDesc), _vp]),
+    "pgv_ln_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "pgv_vit_attention": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "pgv_gemv": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "pgv_pack_blocked": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp]),

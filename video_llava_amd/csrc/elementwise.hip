@@ -342,6 +342,11 @@ extern "C" int pgv_rmsnorm(pgv_ctx* ctx, int dtype, const float* d_x, const floa
     PGV_CHECK(ctx && d_x && d_gamma && d_y && rows > 0, "pgv_rmsnorm: bad arguments");
     return pgv_launch_rmsnorm(dtype, d_x, d_gamma, eps, d_y, rows, cols, (hipStream_t)stream);
 }
+extern "C" int pgv_ln_stats(pgv_ctx* ctx, const float* d_part, float* d_rowstat, float* d_rowmean, const float* d_cshift, int rows, int np, int cols, float eps,
+                            void* stream) {
+    PGV_CHECK(ctx && d_part && d_rowstat && d_rowmean && rows > 0 && np > 0 && cols > 0, "pgv_ln_stats: bad arguments");
+    return pgv_launch_ln_stats(d_part, d_rowstat, d_rowmean, d_cshift, rows, np, cols, eps, (hipStream_t)stream);
+}
 
 extern "C" int pgv_ingest_u8(pgv_ctx* ctx, const uint8_t* d_frames, int T, int H, int W, int image, int dtype, void* d_pixels, void* stream) {
     PGV_CHECK(ctx && d_frames && d_pixels && T > 0 && H > 0 && W > 0 && image > 0, "pgv_ingest_u8: bad arguments");

@@ -727,3 +727,14 @@ extern "C" int pgv_gemm(pgv_ctx* ctx, int dtype, int epi, const void* d_A, int l
     a.M = M; a.N = N; a.K = K; a.epi = epi;
     return pgv_launch_gemm(ctx, dtype, a, (hipStream_t)stream);
 }
+
+// Building block for the unit tests: the launcher with every argument, filled exactly as vit.hip / llm.hip fill it.
+extern "C" int pgv_gemm_ex(pgv_ctx* ctx, int dtype, const pgv_gemm_desc* d, void* stream) {
+    PGV_CHECK(ctx != nullptr && d != nullptr, "pgv_gemm_ex: null argument");
+    GemmArgs a{};
+    a.A = d->d_A; a.lda = d->lda; a.W = d->d_W; a.ldw = d->ldw; a.bias = d->d_bias; a.C = d->d_C; a.ldc = d->ldc;
+    a.M = d->M; a.N = d->N; a.K = d->K; a.epi = d->epi; a.w_blocked = d->w_blocked != 0;
+    a.rowstat = d->d_rowstat; a.colsum = d->d_colsum; a.gnext = d->d_gnext; a.x16 = d->d_x16; a.ldx16 = d->ldx16; a.stats_part = d->d_stats_part;
+    a.rowmean = d->d_rowmean; a.cshift = d->d_cshift;
+    return pgv_launch_gemm(ctx, dtype, a, (hipStream_t)stream);
+}

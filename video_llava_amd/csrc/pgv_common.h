@@ -172,7 +172,7 @@ struct GemmArgs {
     const float* rowmean = nullptr;      // producer: per-row mean before the sublayer (null: centre 0)
     const float* cshift = nullptr;       // producer: device scalar mean(bias), added to rowmean to form the centre
 };
-enum { PGV_EPI_LN_BIAS = 8, PGV_EPI_LN_BIAS_QGELU = 9, PGV_EPI_BIAS_RESID_LNOUT = 10 };     // internal epilogues (gemm.hip)
+// the folded-LayerNorm epilogues PGV_EPI_LN_BIAS / _QGELU / PGV_EPI_BIAS_RESID_LNOUT (gemm.hip) are declared in pgv.h next to pgv_gemm_ex
 int pgv_launch_gemm(pgv_ctx* ctx, int dtype, const GemmArgs& a, hipStream_t s);
 
 // Folded-RMSNorm arguments of the decode GEMVs (gemv.hip, GemvArgs).  Consumer modes (store16 / swiglu / f32): ssq_in [nparts_in][16]
