@@ -556,10 +556,17 @@ def test_gemv_batch_columns_are_independent(ctx, dtype, mode, N, K):
 def test_llm_fp8_weights_vs_oracle(ctx, golden_dir, dtype, tol):
     cfg = synth.LlamaCfg(**{**synth.LLAMA_TINY.__dict__, "projector": "linear"})
     w = synth.make_llama_weights(cfg, seed=78, head_std=0.08)   # seed searched on the CPU: margins of all 8 steps > 0.3 in fp16 and bf16
-    m = _model(cfg, w, dtype).quantize_weights_fp8()
+    m = _model(cfg, w, dtype)
+    # every matrix key of both layers + lm_head: the q / k / v row offsets and the gate / up interleave of each layer, read back through the same table
+    mat_keys = [f"model.layers.{li}.{sfx}.weight" for li in range(cfg.layers) for sfx in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj",
+                                                                                          "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")] + ["lm_head.weight"]
+    assert cfg.layers == 2 and len(mat_keys) == 15
+    for key in mat_keys:            # before quantisation: the 16-bit copy is the loaded tensor rounded to dtype
+        assert torch.equal(m.get_weight(key).cpu(), torch.as_tensor(w[key], dtype=torch.float32).to(dtype).float()), key
+    m.quantize_weights_fp8()
     assert m.is_fp8
     wq = ollm.quantize_llama_weights_fp8(w, round16=dtype)
-    for key in ("model.layers.0.self_attn.k_proj.weight", "model.layers.1.mlp.up_proj.weight", "model.layers.1.mlp.down_proj.weight", "lm_head.weight"):
+    for key in mat_keys:
         assert torch.equal(m.get_weight(key).cpu(), torch.from_numpy(wq[key])), key
     V = 100 + 4
     rng = np.random.default_rng(5)

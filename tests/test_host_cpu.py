@@ -654,6 +654,115 @@ int main(int argc, char** argv) {
     assert (402, 12) in grids and (804, 16) in grids                           # the two grids bench.py times
 
 
+def test_llm_weight_table_layouts_and_keys(tmp_path):
+    """csrc/llm_weights.h is the one description of the decoder's matrices: compiled on its own with g++ (it must need no HIP header), it has to
+    give (1) the byte offset of every item and the total of the 16-bit, fp8 and 12-bit blobs exactly as the hand-written layouts it replaced
+    did -- restated below from those formulas, the 12-bit size as in w12_numpy.nbytes -- for the tiny test model, 7B and 13B (the totals decide
+    what `--batch auto` fits next to a replica); (2) for each of the seven matrix keys, at the first and the last layer, the matrix, its shape,
+    row offset, row count and gate / up interleave that pgv_llm_load_tensor / pgv_llm_get_weight used; (3) a status, not a crash, for malformed
+    keys.  Where g++ has the sanitizer runtimes the same stand-alone program runs a second time under ASan + UBSan."""
+    import shutil
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    csrc = os.path.join(ROOT, "video_llava_amd", "csrc")
+    prog = r"""#include <cstdio>
+#include "llm_weights.h"
+int main(int argc, char** argv) {
+    const LlmDims d{atoll(argv[1]), atoll(argv[2]), atoll(argv[3]), atoi(argv[4])};
+    const LlmLayout lo = llm_layout(d);
+    printf("mat16"); for (const LlmMatSlot& x : lo.mat) printf(" %zu", x.w16);
+    printf("\naux16 %zu %zu %zu", lo.embed, lo.norm_g, lo.rope); for (int l = 0; l < d.L; ++l) printf(" %zu %zu", lo.in_g[l], lo.post_g[l]);
+    printf("\nmat8"); for (const LlmMatSlot& x : lo.mat) printf(" %zu", x.w8);
+    printf("\naux8"); for (const LlmMatSlot& x : lo.mat) printf(" %zu", x.scale);
+    printf("\nmat12"); for (const LlmMatSlot& x : lo.mat) printf(" %zu", x.w12);
+    printf("\ntotal16 %zu\ntotal8 %zu\ntotal12 %zu\n", lo.total16, lo.total8, lo.total12);
+    for (int i = 5; i < argc; ++i) {
+        const LlmLayerKey k = llm_parse_layer_key(argv[i], d.L);
+        printf("key %d %d", (int)k.status, k.layer);
+        if (k.status == LLM_KEY_MATRIX) {
+            const LlmMatSlot& s = lo.mat[llm_mat_index(k.layer, k.mat->kind)];
+            printf(" %d %lld %lld %lld %lld %d %d", k.mat->kind, s.N, s.K, llm_dim(k.mat->row_off, d.H, d.I), llm_dim(k.mat->rows, d.H, d.I), k.mat->row_blk, k.mat->blk_stride);
+        } else if (k.status == LLM_KEY_OTHER) printf(" rest=%zu", strlen(k.rest));
+        printf("\n");
+    }
+    return 0;
+}
+"""
+    cpp, exe, exe_san = tmp_path / "weights.cpp", tmp_path / "weights", tmp_path / "weights_san"
+    cpp.write_text(prog)
+    base = [gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", csrc, str(cpp)]
+    subprocess.run([*base, "-o", str(exe)], check=True)
+    exes = [exe]
+    san = subprocess.run([*base, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe_san)], capture_output=True, text=True)
+    if san.returncode == 0:
+        exes.append(exe_san)
+    else:
+        assert "asan" in san.stderr or "ubsan" in san.stderr, san.stderr        # only a missing sanitizer runtime excuses the second build
+        print("g++ has no sanitizer runtimes here: plain build only")
+
+    def align(x):
+        return (x + 255) // 256 * 256
+
+    def expected(H, I, V, L):
+        """The layouts of pgv_llm_create / pgv_llm_quantize_fp8 / w12_slots before the table, item by item in their order."""
+        shapes = [(3 * H, H), (H, H), (2 * I, H), (H, I)]
+        off, mat16, aux16 = 0, [], []
+        for dst, nbytes in [(aux16, V * H * 2), (mat16, V * H * 2), (aux16, H * 4), (aux16, 4096 * 64 * 8)]:
+            dst.append(off); off += align(nbytes)
+        for _ in range(L):
+            for _g in range(2):
+                aux16.append(off); off += align(H * 4)
+            for N, K in shapes:
+                mat16.append(off); off += align(N * K * 2)
+        total16 = off
+        off, mat8, aux8 = 0, [], []
+        for group in [[(V, H)]] + [shapes] * L:
+            for N, K in group:
+                mat8.append(off); off += align(N * K)
+            for N, K in group:
+                aux8.append(off); off += align(N * 4)
+        total8 = off
+        off, mat12 = 0, []
+        for N, K in [(V, H)] + shapes * L:
+            mat12.append(off); off += align(N * K * 3 // 2 + (N // 16) * 64 * 4 + N)
+        return {"mat16": mat16, "aux16": aux16, "total16": [total16], "mat8": mat8, "aux8": aux8, "total8": [total8], "mat12": mat12, "total12": [off]}
+
+    suffixes = ["self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight", "mlp.gate_proj.weight",
+                "mlp.up_proj.weight", "mlp.down_proj.weight"]
+    NOT_LAYER, BAD_INDEX, OTHER, MATRIX = 0, 1, 2, 3
+    for H, I, V, L in [(512, 768, 592, 2), (4096, 11008, 32080, 32), (5120, 13824, 32080, 40)]:
+        # (kind, N, K, row_off, rows, row_blk, blk_stride) as the if-ladders of pgv_llm_load_tensor and pgv_llm_get_weight had them
+        want_mat = [(0, 3 * H, H, 0, H, 0, 0), (0, 3 * H, H, H, H, 0, 0), (0, 3 * H, H, 2 * H, H, 0, 0), (1, H, H, 0, H, 0, 0),
+                    (2, 2 * I, H, 0, I, 32, 64), (2, 2 * I, H, 32, I, 32, 64), (3, H, I, 0, H, 0, 0)]
+        keys, want = [], []
+        for layer in (0, L - 1):
+            for sfx, t in zip(suffixes, want_mat):
+                keys.append(f"model.layers.{layer}.{sfx}"); want.append([MATRIX, layer, *t])
+        for key, status in [("model.layers..x", BAD_INDEX), ("model.layers.-1.mlp.up_proj.weight", BAD_INDEX), (f"model.layers.{L}.mlp.up_proj.weight", BAD_INDEX),
+                            ("model.layers.1", BAD_INDEX), ("model.layers.", BAD_INDEX), ("model.layers." + "9" * 4096 + ".mlp.up_proj.weight", BAD_INDEX),
+                            ("model.layers.1.", OTHER), ("model.layers.1.self_attn.q_proj.weightX", OTHER), ("model.layers.1.self_attn.q_proj.weigh", OTHER),
+                            ("model.layers.1." + "a" * 4096, OTHER), ("model.layers.0.input_layernorm.weight", OTHER),
+                            ("model.layers.0.self_attn.rotary_emb.inv_freq", OTHER), ("x" * 4096, NOT_LAYER), ("", NOT_LAYER), ("lm_head.weight", NOT_LAYER),
+                            ("model.layers", NOT_LAYER), ("xmodel.layers.0.mlp.up_proj.weight", NOT_LAYER)]:
+            keys.append(key)
+            want.append([status, 1 if key.startswith("model.layers.1.") else 0 if status == OTHER else -1])
+        exp = expected(H, I, V, L)
+        for x in exes:
+            r = subprocess.run([str(x), str(H), str(I), str(V), str(L), *keys], capture_output=True, text=True)
+            assert r.returncode == 0 and not r.stderr, (x, r.returncode, r.stderr[-2000:])
+            lines = [ln.split() for ln in r.stdout.splitlines()]
+            got = {ln[0]: [int(v) for v in ln[1:]] for ln in lines if ln[0] != "key"}
+            assert got == exp, [(k, got.get(k), exp[k]) for k in exp if got.get(k) != exp[k]][:1]
+            got_keys = [[int(v) for v in ln[1:] if not v.startswith("rest=")] for ln in lines if ln[0] == "key"]
+            assert got_keys == want, [(k, g, w) for k, g, w in zip(keys, got_keys, want) if g != w][:3]
+            rests = [int(ln[-1][5:]) for ln in lines if ln[0] == "key" and ln[-1].startswith("rest=")]
+            assert rests == [len(k.split(".", 3)[3]) for k, w in zip(keys, want) if w[0] == OTHER]       # `rest` points at the suffix behind the index
+    assert expected(512, 768, 592, 2)["mat8"][1] == align(592 * 512) + align(592 * 4)                # the head's scales sit between its codes and layer 0's
+    # nothing but llm.hip reads the table
+    users = [f for f in sorted(os.listdir(csrc)) if '#include "llm_weights.h"' in open(os.path.join(csrc, f)).read()]
+    assert users == ["llm.hip"], users
+
+
 # --------------------------------------------------------------------------------------------------
 # offline feature extraction (scripts/save_spatio_temporal_clip_features.py) and the QA runner: host logic
 # --------------------------------------------------------------------------------------------------

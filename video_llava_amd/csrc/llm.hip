@@ -6,20 +6,21 @@
 #include <string.h>
 
 #include "llm_internal.h"
+#include "llm_weights.h"
 #include "w12.h"
 #include "weights.h"
 
-constexpr int kMaxPos = 4096;   // max_position_embeddings of LLaVA-1.5 / Vicuna-1.5
-
-struct LlmLayer {
-    float *in_g, *post_g;
-    void *wqkv, *wo, *wgu, *wdown;
-    // fp8 decode copies (pgv_llm_quantize_fp8): e4m3 blocked matrices + per-row power-of-two scales; null until quantised
-    void *q_wqkv = nullptr, *q_wo = nullptr, *q_wgu = nullptr, *q_wdown = nullptr;
-    float *s_wqkv = nullptr, *s_wo = nullptr, *s_wgu = nullptr, *s_wdown = nullptr;
-    // lossless 12-bit decode copies of bf16 models (w12.h; buf null: none, or the matrix keeps its 16-bit stream)
-    W12Ref z_wqkv, z_wo, z_wgu, z_wdown;
+// One decoder matrix (shapes, HF keys and blob offsets: llm_weights.h) and its copies.
+struct LlmMat {
+    long long N, K;          // rows a GEMV computes / get_weight reads, columns.  lm_head: N = cfg.vocab, the live vocabulary (pgv_llm_resize_vocab)
+    long long cap;           // allocated rows (LlmMatSlot::N): what the blobs, the 12-bit encoder and the fp8 quantiser cover (lm_head: vocab_cap, else N)
+    void* w16;               // fragment-blocked 16-bit matrix: prefill reads it, decode streams it unless one of the copies below exists
+    // fp8 decode copy (pgv_llm_quantize_fp8): e4m3 blocked matrix + per-row power-of-two scales; null until quantised
+    void* w8 = nullptr; float* scale = nullptr;
+    // lossless 12-bit decode copy of bf16 models (w12.h; buf null: none, or the matrix keeps its 16-bit stream)
+    W12Ref z;
 };
+struct LlmLayer { float *in_g, *post_g; };
 
 struct pgv_llm {
     pgv_ctx* ctx;
@@ -27,21 +28,22 @@ struct pgv_llm {
     int dtype;
     char* blob = nullptr;
     size_t blob_bytes = 0;
-    void *embed, *lm_head;
+    void* embed;
     float* norm_g;
     float* rope;   // float2 [kMaxPos][64]
     std::vector<LlmLayer> layers;
+    std::vector<LlmMat> mats;   // lm_head, then qkv, o, gate/up, down of every layer (llm_mat_index)
+    LlmLayout lo;               // byte offset of every item in blob / blob8 / blob12
     std::set<std::string> loaded;
     int expected = 0;
     int vocab_cap = 0;   // allocated rows of embed / lm_head (cfg.vocab at creation + 64 spare)
     char* blob8 = nullptr;   // fp8 copies + scales (decode weight stream halves; the 16-bit copies hold the dequantised values)
-    void* q_head = nullptr; float* s_head = nullptr;
     bool fp8 = false;
     char* blob12 = nullptr;  // 12-bit copies (bf16 models): built once every tensor is loaded, rebuilt by every later weight write
-    W12Ref z_head;
     bool use12 = true;       // pgv_llm_set_weight_stream
     int generation = 0;      // bumped by every call that changes what a captured decode graph baked in (vocabulary size, weight pointers)
 };
+static const LlmMat& layer_mat(const pgv_llm* m, int layer, int kind) { return m->mats[llm_mat_index(layer, kind)]; }
 
 struct pgv_kv {
     pgv_llm* llm;
@@ -83,28 +85,17 @@ extern "C" int pgv_llm_create(pgv_ctx* ctx, const pgv_llm_config* cfg, int dtype
     pgv_llm* m = new pgv_llm();
     m->ctx = ctx; m->cfg = *cfg; m->dtype = dtype;
     m->vocab_cap = (cfg->vocab + 64 + 15) / 16 * 16;   // lm_head is fragment-blocked: rows padded to 16 (zero rows)
-    const size_t H = cfg->hidden, I = cfg->inter, V = m->vocab_cap, L = cfg->layers;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
-    const size_t o_embed = take(V * H * 2), o_head = take(V * H * 2), o_norm = take(H * 4), o_rope = take((size_t)kMaxPos * 64 * 8);
-    struct LO { size_t in_g, post_g, wqkv, wo, wgu, wdown; };
-    std::vector<LO> lo(L);
-    for (size_t i = 0; i < L; ++i) {
-        lo[i].in_g = take(H * 4); lo[i].post_g = take(H * 4);
-        lo[i].wqkv = take(3 * H * H * 2); lo[i].wo = take(H * H * 2); lo[i].wgu = take(2 * I * H * 2); lo[i].wdown = take(H * I * 2);
-    }
-    hipError_t e = hipMalloc((void**)&m->blob, off);
-    if (e != hipSuccess) { delete m; pgv_set_error("pgv_llm_create: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
-    m->blob_bytes = off;
-    (void)hipMemset(m->blob + o_head, 0, V * H * 2);     // padded lm_head rows must be finite
+    const size_t H = cfg->hidden, V = m->vocab_cap, L = cfg->layers;
+    const LlmLayout& lo = m->lo = llm_layout({cfg->hidden, cfg->inter, m->vocab_cap, cfg->layers});
+    hipError_t e = hipMalloc((void**)&m->blob, lo.total16);
+    if (e != hipSuccess) { delete m; pgv_set_error("pgv_llm_create: hipMalloc(%zu MiB): %s", lo.total16 >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
+    m->blob_bytes = lo.total16;
+    (void)hipMemset(m->blob + lo.mat[0].w16, 0, V * H * 2);     // padded lm_head rows must be finite
     char* b = m->blob;
-    m->embed = b + o_embed; m->lm_head = b + o_head; m->norm_g = (float*)(b + o_norm); m->rope = (float*)(b + o_rope);
-    m->layers.resize(L);
-    for (size_t i = 0; i < L; ++i) {
-        LlmLayer& l = m->layers[i];
-        l.in_g = (float*)(b + lo[i].in_g); l.post_g = (float*)(b + lo[i].post_g);
-        l.wqkv = b + lo[i].wqkv; l.wo = b + lo[i].wo; l.wgu = b + lo[i].wgu; l.wdown = b + lo[i].wdown;
-    }
+    m->embed = b + lo.embed; m->norm_g = (float*)(b + lo.norm_g); m->rope = (float*)(b + lo.rope);
+    for (size_t i = 0; i < L; ++i) m->layers.push_back({(float*)(b + lo.in_g[i]), (float*)(b + lo.post_g[i])});
+    for (const LlmMatSlot& x : lo.mat) m->mats.push_back({x.N, x.K, x.N, b + x.w16});
+    m->mats[0].N = cfg->vocab;
     // RoPE table exactly as LlamaRotaryEmbedding (HF:llama/modeling_llama.py:96-126): fp32 inv_freq, fp32 angle, fp32 cos/sin
     std::vector<float> tab((size_t)kMaxPos * 64 * 2);
     for (int j = 0; j < 64; ++j) {
@@ -135,43 +126,25 @@ extern "C" int pgv_llm_missing(const pgv_llm* llm) { return llm ? llm->expected 
 // ---------------------------------------------------------------------------------------------
 // 12-bit decode copies (bf16 models, w12.h): what the decode GEMVs stream at batches of up to 16 sequences
 // ---------------------------------------------------------------------------------------------
-struct W12Slot { const void* w16; W12Ref* ref; long long N, K; size_t off; };
-static std::vector<W12Slot> w12_slots(pgv_llm* m, size_t* total) {
-    const long long H = m->cfg.hidden, I = m->cfg.inter, V = m->vocab_cap;
-    std::vector<W12Slot> v;
-    size_t off = 0;
-    auto add = [&](const void* w, W12Ref* r, long long N, long long K) { v.push_back({w, r, N, K, off}); off += pgv_align(pgv_w12_total_bytes(N, K)); };
-    add(m->lm_head, &m->z_head, V, H);
-    for (LlmLayer& l : m->layers) {
-        add(l.wqkv, &l.z_wqkv, 3 * H, H); add(l.wo, &l.z_wo, H, H); add(l.wgu, &l.z_wgu, 2 * I, H); add(l.wdown, &l.z_wdown, H, I);
-    }
-    *total = off;
-    return v;
-}
-
-// (Re)build the 12-bit copy of the matrix at `only` (the first time: of every matrix, once the model is complete; null later: nothing).  A matrix with
-// more than kW12MaxExc exceptions in a row block keeps its 16-bit stream.  Synchronous (model setup / weight loads, never inside a capture).
-static int w12_sync(pgv_llm* m, const void* only, hipStream_t s) {
+// (Re)build the 12-bit copy of matrix `only` of m->mats (the first time: of every matrix, once the model is complete; negative later: nothing).  A matrix
+// with more than kW12MaxExc exceptions in a row block keeps its 16-bit stream.  Synchronous (model setup / weight loads, never inside a capture).
+static int w12_sync(pgv_llm* m, int only, hipStream_t s) {
     if (m->dtype != PGV_BF16 || m->fp8 || pgv_llm_missing(m) != 0) return PGV_OK;
-    if (m->blob12) { if (!only) return PGV_OK; }
-    else only = nullptr;
-    size_t total = 0;
-    std::vector<W12Slot> slots = w12_slots(m, &total);
+    if (m->blob12 && only < 0) return PGV_OK;
     if (!m->blob12) {
-        hipError_t e = hipMalloc((void**)&m->blob12, total);
-        if (e != hipSuccess) { pgv_set_error("12-bit weight copies: hipMalloc(%zu MiB): %s", total >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
+        only = -1;
+        hipError_t e = hipMalloc((void**)&m->blob12, m->lo.total12);
+        if (e != hipSuccess) { pgv_set_error("12-bit weight copies: hipMalloc(%zu MiB): %s", m->lo.total12 >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
     }
+    std::vector<size_t> coff;     // first row block of every matrix in the exception counts
     size_t nrb = 0;
-    for (const W12Slot& x : slots) nrb += x.N / 16;
+    for (const LlmMat& x : m->mats) { coff.push_back(nrb); nrb += x.cap / 16; }
     int* d_counts = nullptr;
     PGV_HIP(hipMalloc((void**)&d_counts, nrb * sizeof(int)));
-    std::vector<size_t> coff;
-    size_t c = 0;
     int rc = PGV_OK;
-    for (const W12Slot& x : slots) {
-        coff.push_back(c);
-        if ((!only || x.w16 == only) && rc == PGV_OK) rc = pgv_launch_encode_w12(x.w16, m->blob12 + x.off, d_counts + c, x.N, x.K, s);
-        c += x.N / 16;
+    for (size_t i = 0; i < m->mats.size(); ++i) {
+        const LlmMat& x = m->mats[i];
+        if ((only < 0 || (int)i == only) && rc == PGV_OK) rc = pgv_launch_encode_w12(x.w16, m->blob12 + m->lo.mat[i].w12, d_counts + coff[i], x.cap, x.K, s);
     }
     std::vector<int> counts(nrb, 0);
     hipError_t e = rc == PGV_OK ? hipMemcpyAsync(counts.data(), d_counts, nrb * sizeof(int), hipMemcpyDeviceToHost, s) : hipSuccess;
@@ -179,13 +152,12 @@ static int w12_sync(pgv_llm* m, const void* only, hipStream_t s) {
     (void)hipFree(d_counts);
     PGV_TRY(rc);
     if (e != hipSuccess) { pgv_set_error("12-bit weight copies: %s", hipGetErrorString(e)); return PGV_EHIP; }
-    for (size_t i = 0; i < slots.size(); ++i) {
-        const W12Slot& x = slots[i];
-        if (only && x.w16 != only) continue;
+    for (size_t i = 0; i < m->mats.size(); ++i) {
+        LlmMat& x = m->mats[i];
+        if (only >= 0 && (int)i != only) continue;
         int worst = 0;
-        for (long long r = 0; r < x.N / 16; ++r) worst = counts[coff[i] + r] > worst ? counts[coff[i] + r] : worst;
-        x.ref->buf = worst <= kW12MaxExc ? m->blob12 + x.off : nullptr;
-        x.ref->rows = x.N;
+        for (long long r = 0; r < x.cap / 16; ++r) worst = counts[coff[i] + r] > worst ? counts[coff[i] + r] : worst;
+        x.z = {worst <= kW12MaxExc ? m->blob12 + m->lo.mat[i].w12 : nullptr, x.cap};
     }
     m->generation += 1;           // captured decode graphs stream the previous copies
     return PGV_OK;
@@ -194,8 +166,7 @@ static int w12_sync(pgv_llm* m, const void* only, hipStream_t s) {
 static void w12_drop(pgv_llm* m) {
     if (m->blob12) (void)hipFree(m->blob12);
     m->blob12 = nullptr;
-    m->z_head = W12Ref{};
-    for (LlmLayer& l : m->layers) l.z_wqkv = l.z_wo = l.z_wgu = l.z_wdown = W12Ref{};
+    for (LlmMat& x : m->mats) x.z = W12Ref{};
 }
 
 // the copy a decode GEMV streams for a matrix (null: its 16-bit / fp8 matrix)
@@ -209,14 +180,13 @@ extern "C" int pgv_llm_set_weight_stream(pgv_llm* m, int use12) {
 
 extern "C" int64_t pgv_llm_weight_stream_bytes(const pgv_llm* m, int batch) {
     if (!m || batch < 1) return -1;
-    const long long H = m->cfg.hidden, I = m->cfg.inter, V16 = (m->cfg.vocab + 15) / 16 * 16;
-    auto one = [&](const W12Ref& z, long long N, long long K) -> double {
-        if (m->fp8) return (double)N * K + 4.0 * N;                                     // e4m3 + per-row fp32 scales
-        if (batch <= 16 && z12(m, z)) return (double)pgv_w12_total_bytes(N, K);
-        return 2.0 * N * K;
-    };
-    double b = one(m->z_head, V16, H);
-    for (const LlmLayer& l : m->layers) b += one(l.z_wqkv, 3 * H, H) + one(l.z_wo, H, H) + one(l.z_wgu, 2 * I, H) + one(l.z_wdown, H, I);
+    double b = 0;
+    for (const LlmMat& x : m->mats) {
+        const long long N = (x.N + 15) / 16 * 16, K = x.K;        // the GEMVs stream whole 16-row blocks (only the lm_head's N is no multiple of 16)
+        if (m->fp8) b += (double)N * K + 4.0 * N;                                       // e4m3 + per-row fp32 scales
+        else if (batch <= 16 && z12(m, x.z)) b += (double)pgv_w12_total_bytes(N, K);
+        else b += 2.0 * N * K;
+    }
     return (int64_t)b;
 }
 extern "C" int pgv_llm_vocab(const pgv_llm* llm) { return llm ? llm->cfg.vocab : -1; }
@@ -232,10 +202,10 @@ extern "C" int pgv_llm_resize_vocab(pgv_llm* m, int new_vocab, void* stream) {
         PGV_HIP(hipMemsetAsync((char*)m->embed + off, 0, bytes, (hipStream_t)stream));
         // lm_head is fragment-blocked (rows interleaved inside 1 KiB blocks): zero the new rows in place (a shrink followed by a
         // grow must not resurrect old rows)
-        PGV_TRY(pgv_zero_rows_blocked(m->lm_head, m->cfg.vocab, new_vocab - m->cfg.vocab, (long long)H, (hipStream_t)stream));
+        PGV_TRY(pgv_zero_rows_blocked(m->mats[0].w16, m->cfg.vocab, new_vocab - m->cfg.vocab, (long long)H, (hipStream_t)stream));
     }
-    m->cfg.vocab = new_vocab;
-    PGV_TRY(w12_sync(m, m->lm_head, (hipStream_t)stream));
+    m->cfg.vocab = new_vocab; m->mats[0].N = new_vocab;
+    PGV_TRY(w12_sync(m, 0, (hipStream_t)stream));
     m->generation += 1;           // captured decode graphs have the old vocabulary baked into lm_head / the token pick
     return PGV_OK;
 }
@@ -249,49 +219,41 @@ extern "C" int pgv_llm_load_rows(pgv_llm* m, const char* name, const void* data,
     PackDst d;
     d.dst_dtype = m->dtype; d.rows = nrows; d.cols = m->cfg.hidden; d.dst_stride = d.cols; d.row_off = row0;
     if (!strcmp(name, "model.embed_tokens.weight")) d.ptr = m->embed;
-    else if (!strcmp(name, "lm_head.weight")) { d.ptr = m->lm_head; d.blocked = true; }
+    else if (!strcmp(name, "lm_head.weight")) { d.ptr = m->mats[0].w16; d.blocked = true; }
     else { pgv_set_error("pgv_llm_load_rows: '%s' is not a vocabulary matrix", name); return PGV_ENAME; }
     PGV_TRY(pgv_pack_tensor(d, data, src_dtype, on_device, (hipStream_t)stream));
     m->loaded.insert(name);
-    return w12_sync(m, d.blocked ? d.ptr : nullptr, (hipStream_t)stream);
+    return w12_sync(m, d.blocked ? 0 : -1, (hipStream_t)stream);
 }
 
 extern "C" int pgv_llm_load_tensor(pgv_llm* m, const char* name_in, const void* data, int src_dtype, int on_device, int64_t numel, void* stream) {
     PGV_CHECK(m && name_in && data, "pgv_llm_load_tensor: null argument");
     if (m->fp8) { pgv_set_error("pgv_llm_load_tensor: the weights are quantised to fp8 (the fp8 copies would go stale); load into a fresh model"); return PGV_ESTATE; }
-    std::string name(name_in);
     const long long H = m->cfg.hidden, I = m->cfg.inter, V = m->cfg.vocab;
     PackDst d;
+    int idx = -1;            // the matrix of m->mats the tensor lands in (none: embed and the norm vectors)
     auto vec = [&](float* ptr, long long n) { d.ptr = ptr; d.rows = 1; d.cols = n; };
     auto mat = [&](void* ptr, long long r, long long c, long long roff) { d.ptr = ptr; d.dst_dtype = m->dtype; d.rows = r; d.cols = c; d.row_off = roff; };
-    if (name == "model.embed_tokens.weight") mat(m->embed, V, H, 0);
-    else if (name == "lm_head.weight") { mat(m->lm_head, V, H, 0); d.blocked = true; }
-    else if (name == "model.norm.weight") vec(m->norm_g, H);
-    else if (name.rfind("model.layers.", 0) == 0) {
-        const char* p = name.c_str() + 13;
-        char* end = nullptr;
-        long li = strtol(p, &end, 10);
-        if (end == p || *end != '.' || li < 0 || li >= m->cfg.layers) { pgv_set_error("pgv_llm_load_tensor: bad layer index in '%s'", name_in); return PGV_ENAME; }
-        std::string rest(end + 1);
-        LlmLayer& l = m->layers[li];
-        if (rest == "self_attn.q_proj.weight") { mat(l.wqkv, H, H, 0); d.blocked = true; }
-        else if (rest == "self_attn.k_proj.weight") { mat(l.wqkv, H, H, H); d.blocked = true; }
-        else if (rest == "self_attn.v_proj.weight") { mat(l.wqkv, H, H, 2 * H); d.blocked = true; }
-        else if (rest == "self_attn.o_proj.weight") { mat(l.wo, H, H, 0); d.blocked = true; }
-        else if (rest == "mlp.gate_proj.weight") { mat(l.wgu, I, H, 0); d.row_blk = 32; d.blk_stride = 64; d.blocked = true; }       // [32 gate | 32 up] per 64 rows
-        else if (rest == "mlp.up_proj.weight") { mat(l.wgu, I, H, 32); d.row_blk = 32; d.blk_stride = 64; d.blocked = true; }
-        else if (rest == "mlp.down_proj.weight") { mat(l.wdown, H, I, 0); d.blocked = true; }
-        else if (rest == "input_layernorm.weight") vec(l.in_g, H);
-        else if (rest == "post_attention_layernorm.weight") vec(l.post_g, H);
-        else if (rest == "self_attn.rotary_emb.inv_freq") return PGV_OK;
-        else { pgv_set_error("pgv_llm_load_tensor: unexpected key '%s'", name_in); return PGV_ENAME; }
-    } else { pgv_set_error("pgv_llm_load_tensor: unexpected key '%s'", name_in); return PGV_ENAME; }
+    const LlmLayerKey k = llm_parse_layer_key(name_in, m->cfg.layers);
+    if (!strcmp(name_in, "model.embed_tokens.weight")) mat(m->embed, V, H, 0);
+    else if (!strcmp(name_in, "lm_head.weight")) { idx = 0; mat(m->mats[0].w16, V, H, 0); }
+    else if (!strcmp(name_in, "model.norm.weight")) vec(m->norm_g, H);
+    else if (k.status == LLM_KEY_BAD_INDEX) { pgv_set_error("pgv_llm_load_tensor: bad layer index in '%s'", name_in); return PGV_ENAME; }
+    else if (k.status == LLM_KEY_MATRIX) {
+        idx = llm_mat_index(k.layer, k.mat->kind);
+        mat(m->mats[idx].w16, llm_dim(k.mat->rows, H, I), m->mats[idx].K, llm_dim(k.mat->row_off, H, I));
+        d.row_blk = k.mat->row_blk; d.blk_stride = k.mat->blk_stride;
+    } else if (!strcmp(k.rest, "input_layernorm.weight")) vec(m->layers[k.layer].in_g, H);
+    else if (!strcmp(k.rest, "post_attention_layernorm.weight")) vec(m->layers[k.layer].post_g, H);
+    else if (!strcmp(k.rest, "self_attn.rotary_emb.inv_freq")) return PGV_OK;
+    else { pgv_set_error("pgv_llm_load_tensor: unexpected key '%s'", name_in); return PGV_ENAME; }
+    d.blocked = idx >= 0;
     d.dst_stride = d.cols;
     PGV_CHECK(numel == d.rows * d.cols, "pgv_llm_load_tensor: size mismatch for '%s': %lld elements given, the model expects %lld x %lld", name_in,
               (long long)numel, d.rows, d.cols);
     PGV_TRY(pgv_pack_tensor(d, data, src_dtype, on_device, (hipStream_t)stream));
-    m->loaded.insert(name);
-    return w12_sync(m, d.blocked ? d.ptr : nullptr, (hipStream_t)stream);
+    m->loaded.insert(name_in);
+    return w12_sync(m, idx, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -303,29 +265,12 @@ extern "C" int pgv_llm_quantize_fp8(pgv_ctx* ctx, pgv_llm* m, void* stream) {
     if (m->fp8) return PGV_OK;
     PGV_CHECK(m->cfg.hidden % 64 == 0 && m->cfg.inter % 64 == 0, "pgv_llm_quantize_fp8: hidden and intermediate sizes must be multiples of 64");
     hipStream_t s = (hipStream_t)stream;
-    const size_t H = m->cfg.hidden, I = m->cfg.inter, V = m->vocab_cap, L = m->cfg.layers;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
-    struct LO { size_t qkv, o, gu, down, sqkv, so, sgu, sdown; };
-    std::vector<LO> lo(L);
-    const size_t o_head = take(V * H), o_shead = take(V * 4);
-    for (size_t i = 0; i < L; ++i) {
-        lo[i].qkv = take(3 * H * H); lo[i].o = take(H * H); lo[i].gu = take(2 * I * H); lo[i].down = take(H * I);
-        lo[i].sqkv = take(3 * H * 4); lo[i].so = take(H * 4); lo[i].sgu = take(2 * I * 4); lo[i].sdown = take(H * 4);
-    }
-    hipError_t e = hipMalloc((void**)&m->blob8, off);
-    if (e != hipSuccess) { pgv_set_error("pgv_llm_quantize_fp8: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
-    char* b = m->blob8;
-    m->q_head = b + o_head; m->s_head = (float*)(b + o_shead);
-    PGV_TRY(pgv_launch_quantize_fp8(m->dtype, m->lm_head, m->q_head, m->s_head, (long long)V, (long long)H, s));
-    for (size_t i = 0; i < L; ++i) {
-        LlmLayer& l = m->layers[i];
-        l.q_wqkv = b + lo[i].qkv; l.q_wo = b + lo[i].o; l.q_wgu = b + lo[i].gu; l.q_wdown = b + lo[i].down;
-        l.s_wqkv = (float*)(b + lo[i].sqkv); l.s_wo = (float*)(b + lo[i].so); l.s_wgu = (float*)(b + lo[i].sgu); l.s_wdown = (float*)(b + lo[i].sdown);
-        PGV_TRY(pgv_launch_quantize_fp8(m->dtype, l.wqkv, l.q_wqkv, l.s_wqkv, 3 * (long long)H, (long long)H, s));
-        PGV_TRY(pgv_launch_quantize_fp8(m->dtype, l.wo, l.q_wo, l.s_wo, (long long)H, (long long)H, s));
-        PGV_TRY(pgv_launch_quantize_fp8(m->dtype, l.wgu, l.q_wgu, l.s_wgu, 2 * (long long)I, (long long)H, s));
-        PGV_TRY(pgv_launch_quantize_fp8(m->dtype, l.wdown, l.q_wdown, l.s_wdown, (long long)H, (long long)I, s));
+    hipError_t e = hipMalloc((void**)&m->blob8, m->lo.total8);
+    if (e != hipSuccess) { pgv_set_error("pgv_llm_quantize_fp8: hipMalloc(%zu MiB): %s", m->lo.total8 >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
+    for (size_t i = 0; i < m->mats.size(); ++i) {
+        LlmMat& x = m->mats[i];
+        x.w8 = m->blob8 + m->lo.mat[i].w8; x.scale = (float*)(m->blob8 + m->lo.mat[i].scale);
+        PGV_TRY(pgv_launch_quantize_fp8(m->dtype, x.w16, x.w8, x.scale, x.cap, x.K, s));
     }
     PGV_HIP(hipStreamSynchronize(s));
     w12_drop(m);                  // decode streams the fp8 copies
@@ -340,26 +285,16 @@ extern "C" int pgv_llm_is_fp8(const pgv_llm* m) { return (m && m->fp8) ? 1 : 0; 
 // whole path computes with) -- what a parity test or a checkpoint writer needs.
 extern "C" int pgv_llm_get_weight(pgv_ctx* ctx, pgv_llm* m, const char* name_in, float* d_out, void* stream) {
     PGV_CHECK(ctx && m && name_in && d_out, "pgv_llm_get_weight: null argument");
-    std::string name(name_in);
-    const long long H = m->cfg.hidden, I = m->cfg.inter, V = m->cfg.vocab;
+    const long long H = m->cfg.hidden, I = m->cfg.inter;
     hipStream_t s = (hipStream_t)stream;
-    if (name == "lm_head.weight") return pgv_launch_unpack_blocked(m->dtype, m->lm_head, d_out, m->vocab_cap, H, 0, 0, 0, V, s);
-    if (name.rfind("model.layers.", 0) != 0) { pgv_set_error("pgv_llm_get_weight: unsupported key '%s'", name_in); return PGV_ENAME; }
-    const char* p = name.c_str() + 13;
-    char* end = nullptr;
-    long li = strtol(p, &end, 10);
-    if (end == p || *end != '.' || li < 0 || li >= m->cfg.layers) { pgv_set_error("pgv_llm_get_weight: bad layer index in '%s'", name_in); return PGV_ENAME; }
-    std::string rest(end + 1);
-    const LlmLayer& l = m->layers[li];
-    if (rest == "self_attn.q_proj.weight") return pgv_launch_unpack_blocked(m->dtype, l.wqkv, d_out, 3 * H, H, 0, 0, 0, H, s);
-    if (rest == "self_attn.k_proj.weight") return pgv_launch_unpack_blocked(m->dtype, l.wqkv, d_out, 3 * H, H, 0, 0, H, H, s);
-    if (rest == "self_attn.v_proj.weight") return pgv_launch_unpack_blocked(m->dtype, l.wqkv, d_out, 3 * H, H, 0, 0, 2 * H, H, s);
-    if (rest == "self_attn.o_proj.weight") return pgv_launch_unpack_blocked(m->dtype, l.wo, d_out, H, H, 0, 0, 0, H, s);
-    if (rest == "mlp.gate_proj.weight") return pgv_launch_unpack_blocked(m->dtype, l.wgu, d_out, 2 * I, H, 32, 64, 0, I, s);
-    if (rest == "mlp.up_proj.weight") return pgv_launch_unpack_blocked(m->dtype, l.wgu, d_out, 2 * I, H, 32, 64, 32, I, s);
-    if (rest == "mlp.down_proj.weight") return pgv_launch_unpack_blocked(m->dtype, l.wdown, d_out, H, I, 0, 0, 0, H, s);
-    pgv_set_error("pgv_llm_get_weight: unsupported key '%s'", name_in);
-    return PGV_ENAME;
+    const LlmMat& head = m->mats[0];        // its live rows of the allocated ones
+    if (!strcmp(name_in, "lm_head.weight")) return pgv_launch_unpack_blocked(m->dtype, head.w16, d_out, head.cap, head.K, 0, 0, 0, head.N, s);
+    const LlmLayerKey k = llm_parse_layer_key(name_in, m->cfg.layers);
+    if (k.status == LLM_KEY_BAD_INDEX) { pgv_set_error("pgv_llm_get_weight: bad layer index in '%s'", name_in); return PGV_ENAME; }
+    if (k.status != LLM_KEY_MATRIX) { pgv_set_error("pgv_llm_get_weight: unsupported key '%s'", name_in); return PGV_ENAME; }
+    const LlmMat& x = layer_mat(m, k.layer, k.mat->kind);
+    return pgv_launch_unpack_blocked(m->dtype, x.w16, d_out, x.N, x.K, k.mat->row_blk, k.mat->blk_stride, llm_dim(k.mat->row_off, H, I),
+                                     llm_dim(k.mat->rows, H, I), s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -446,10 +381,10 @@ static bool norm_fold_enabled() {
     return v == 1;
 }
 
-// One decode GEMV on the fp8 weights (weight-only form: 16-bit x, e4m3 codes widened in registers; gemv.hip).
-static int gemv8(pgv_ctx* ctx, pgv_llm* m, pgv_kv*, int mode, const void* w8, const float* ws, const void* x, int K, void* out, int ldo, int N, int B,
-                 hipStream_t s, const GemvNorm* nm) {
-    return pgv_launch_gemv(ctx, m->dtype, mode, w8, x, K, out, ldo, N, K, B, s, ws, nm);
+// One decode GEMV over a matrix, streaming the copy decode reads: the fp8 codes once quantised (weight-only form: 16-bit x, e4m3 codes
+// widened in registers; gemv.hip), else the 12-bit copy where there is one, else the 16-bit matrix.  x is [B][K].
+static int gemv_mat(pgv_ctx* ctx, const pgv_llm* m, int mode, const LlmMat& w, const void* x, void* out, int ldo, int B, hipStream_t s, const GemvNorm* nm) {
+    return pgv_launch_gemv(ctx, m->dtype, mode, m->fp8 ? w.w8 : w.w16, x, (int)w.K, out, ldo, (int)w.N, (int)w.K, B, s, m->fp8 ? w.scale : nullptr, nm, z12(m, w.z));
 }
 
 // lm_head GEMV on kv->xn (B rows) -> kv->logits and, for a greedy pick, the per-workgroup argmax candidates
@@ -459,10 +394,7 @@ static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hip
     nm.ssq_ts = kv->ssq_ts; nm.amax_ts = kv->amax_ts;
     nm.x_blocked = nparts > 0;                       // the folded path hands kv->xn over blocked at batches beyond 16 (pgv_gemv_xblk_tiles)
     if (greedy) { nm.amax_val = kv->amax_val; nm.amax_idx = kv->amax_idx; }
-    if (m->fp8 && nparts > 0) PGV_TRY(gemv8(ctx, m, kv, GV_F32, m->q_head, m->s_head, kv->xn, H, kv->logits, V, V, B, s, &nm));
-    else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_F32, m->fp8 ? m->q_head : m->lm_head, kv->xn, H, kv->logits, V, V, H, B, s, m->fp8 ? m->s_head : nullptr, &nm,
-                                 z12(m, m->z_head)));
-    return PGV_OK;
+    return gemv_mat(ctx, m, GV_F32, m->mats[0], kv->xn, kv->logits, V, B, s, &nm);
 }
 
 static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos, int flags, hipStream_t s, int nparts) {
@@ -575,18 +507,19 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     for (int b = 0; b < B; ++b) attn_flops += 2.0 * (double)h_seq_lens[b] * (h_seq_lens[b] + 2.0 * offs[b]) * H;   // causal: 4 * S * (S / 2 + prefix) * H
     for (int li = 0; li < m->cfg.layers; ++li) {
         const LlmLayer& l = m->layers[li];
+        const LlmMat &wqkv = layer_mat(m, li, MAT_QKV), &wo = layer_mat(m, li, MAT_O), &wgu = layer_mat(m, li, MAT_GU), &wdown = layer_mat(m, li, MAT_DOWN);
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, l.in_g, m->cfg.eps, xn, M, H, s));
         GemmArgs g{};
-        g.A = xn; g.lda = H; g.W = l.wqkv; g.ldw = H; g.bias = nullptr; g.C = qkv; g.ldc = 3 * H; g.M = M; g.N = 3 * H; g.K = H; g.epi = PGV_EPI_NONE; g.w_blocked = true;
+        g.A = xn; g.lda = H; g.W = wqkv.w16; g.ldw = H; g.bias = nullptr; g.C = qkv; g.ldc = 3 * H; g.M = M; g.N = (int)wqkv.N; g.K = (int)wqkv.K; g.epi = PGV_EPI_NONE; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
         PGV_TRY(pgv_launch_rope_kv_write(m->dtype, qkv, d_row_b, d_row_pos, m->rope, kv->Kc[li], kv->Vc[li], M, H, heads, kv->max_seq, s));
         PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, qkv, ao, kv->Kc[li], kv->Vc[li], d_cu, d_offs, B, max_len, H, heads, kv->max_seq, attn_flops, s, d_slots));
-        g = GemmArgs{}; g.A = ao; g.lda = H; g.W = l.wo; g.ldw = H; g.C = resid; g.ldc = H; g.M = M; g.N = H; g.K = H; g.epi = PGV_EPI_RESID; g.w_blocked = true;
+        g = GemmArgs{}; g.A = ao; g.lda = H; g.W = wo.w16; g.ldw = H; g.C = resid; g.ldc = H; g.M = M; g.N = (int)wo.N; g.K = (int)wo.K; g.epi = PGV_EPI_RESID; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, l.post_g, m->cfg.eps, xn, M, H, s));
-        g = GemmArgs{}; g.A = xn; g.lda = H; g.W = l.wgu; g.ldw = H; g.C = act; g.ldc = I; g.M = M; g.N = 2 * I; g.K = H; g.epi = PGV_EPI_SWIGLU; g.w_blocked = true;
+        g = GemmArgs{}; g.A = xn; g.lda = H; g.W = wgu.w16; g.ldw = H; g.C = act; g.ldc = I; g.M = M; g.N = (int)wgu.N; g.K = (int)wgu.K; g.epi = PGV_EPI_SWIGLU; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
-        g = GemmArgs{}; g.A = act; g.lda = I; g.W = l.wdown; g.ldw = I; g.C = resid; g.ldc = H; g.M = M; g.N = H; g.K = I; g.epi = PGV_EPI_RESID; g.w_blocked = true;
+        g = GemmArgs{}; g.A = act; g.lda = I; g.W = wdown.w16; g.ldw = I; g.C = resid; g.ldc = H; g.M = M; g.N = (int)wdown.N; g.K = (int)wdown.K; g.epi = PGV_EPI_RESID; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
     }
     if (d_all_logits) {
@@ -595,7 +528,7 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
         PGV_CHECK(ld_all >= n16 && ld_all % 4 == 0 && n16 <= m->vocab_cap, "%s: ld_all %d must be a multiple of 4 and at least %d", who, ld_all, n16);
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, m->norm_g, m->cfg.eps, xn, M, H, s));
         GemmArgs g{};
-        g.A = xn; g.lda = H; g.W = m->lm_head; g.ldw = H; g.C = d_all_logits; g.ldc = ld_all; g.M = M; g.N = n16; g.K = H; g.epi = PGV_EPI_F32; g.w_blocked = true;
+        g.A = xn; g.lda = H; g.W = m->mats[0].w16; g.ldw = H; g.C = d_all_logits; g.ldc = ld_all; g.M = M; g.N = n16; g.K = H; g.epi = PGV_EPI_F32; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
     }
     // lm_head only on the last position of every sequence (the reference computes all S positions, video_chatgpt.py:226)
@@ -673,14 +606,13 @@ static int decode_enqueue_unfolded(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos
     for (int b = 0; b < B; ++b) kv_bytes += 2.0 * 2.0 * (double)(kv->h_len[b] + 1) * H;
     for (int li = 0; li < L; ++li) {
         const LlmLayer& l = m->layers[li];
-        const bool q8 = m->fp8;
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.in_g, m->cfg.eps, kv->xn, B, H, s));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, q8 ? l.q_wqkv : l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, q8 ? l.s_wqkv : nullptr, nullptr, z12(m, l.z_wqkv)));
+        PGV_TRY(gemv_mat(ctx, m, GV_STORE16, layer_mat(m, li, MAT_QKV), kv->xn, kv->qkv, 3 * H, B, s, nullptr));
         PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket, 0));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESID, q8 ? l.q_wo : l.wo, kv->ao, H, kv->resid, H, H, H, B, s, q8 ? l.s_wo : nullptr, nullptr, z12(m, l.z_wo)));
+        PGV_TRY(gemv_mat(ctx, m, GV_RESID, layer_mat(m, li, MAT_O), kv->ao, kv->resid, H, B, s, nullptr));
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.post_g, m->cfg.eps, kv->xn, B, H, s));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_SWIGLU, q8 ? l.q_wgu : l.wgu, kv->xn, H, kv->act, I, 2 * I, H, B, s, q8 ? l.s_wgu : nullptr, nullptr, z12(m, l.z_wgu)));
-        PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESID, q8 ? l.q_wdown : l.wdown, kv->act, I, kv->resid, H, H, I, B, s, q8 ? l.s_wdown : nullptr, nullptr, z12(m, l.z_wdown)));
+        PGV_TRY(gemv_mat(ctx, m, GV_SWIGLU, layer_mat(m, li, MAT_GU), kv->xn, kv->act, I, B, s, nullptr));
+        PGV_TRY(gemv_mat(ctx, m, GV_RESID, layer_mat(m, li, MAT_DOWN), kv->act, kv->resid, H, B, s, nullptr));
     }
     PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
     PGV_TRY(lm_head_and_pick(ctx, m, kv, B, eos, flags, s, 0));
@@ -701,20 +633,15 @@ static int decode_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int fla
     int parts_in = 1;                              // the embedding kernel leaves one partial per sequence
     for (int li = 0; li < L; ++li) {
         const LlmLayer& l = m->layers[li];
-        const bool q8 = m->fp8;
         GemvNorm cons; cons.ssq_in = kv->ssq; cons.nparts_in = parts_in; cons.hidden = H; cons.eps = m->cfg.eps; cons.ssq_ts = kv->ssq_ts; cons.x_blocked = true;
-        if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_STORE16, l.q_wqkv, l.s_wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, B, s, &cons));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_STORE16, l.wqkv, kv->xn, H, kv->qkv, 3 * H, 3 * H, H, B, s, nullptr, &cons, z12(m, l.z_wqkv)));
+        PGV_TRY(gemv_mat(ctx, m, GV_STORE16, layer_mat(m, li, MAT_QKV), kv->xn, kv->qkv, 3 * H, B, s, &cons));
         PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket, 0));
         GemvNorm prod; prod.gamma = l.post_g; prod.xg = kv->xn; prod.ssq_out = kv->ssq; prod.ssq_ts = kv->ssq_ts; prod.k8_part = kv->k8_part; prod.x_blocked = true;
-        if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_RESIDNORM, l.q_wo, l.s_wo, kv->ao, H, kv->resid, H, H, B, s, &prod));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESIDNORM, l.wo, kv->ao, H, kv->resid, H, H, H, B, s, nullptr, &prod, z12(m, l.z_wo)));
+        PGV_TRY(gemv_mat(ctx, m, GV_RESIDNORM, layer_mat(m, li, MAT_O), kv->ao, kv->resid, H, B, s, &prod));
         cons.nparts_in = nparts;
-        if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_SWIGLU, l.q_wgu, l.s_wgu, kv->xn, H, kv->act, I, 2 * I, B, s, &cons));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_SWIGLU, l.wgu, kv->xn, H, kv->act, I, 2 * I, H, B, s, nullptr, &cons, z12(m, l.z_wgu)));
+        PGV_TRY(gemv_mat(ctx, m, GV_SWIGLU, layer_mat(m, li, MAT_GU), kv->xn, kv->act, I, B, s, &cons));
         prod.gamma = li + 1 < L ? m->layers[li + 1].in_g : m->norm_g;
-        if (q8) PGV_TRY(gemv8(ctx, m, kv, GV_RESIDNORM, l.q_wdown, l.s_wdown, kv->act, I, kv->resid, H, H, B, s, &prod));
-        else PGV_TRY(pgv_launch_gemv(ctx, m->dtype, GV_RESIDNORM, l.wdown, kv->act, I, kv->resid, H, H, I, B, s, nullptr, &prod, z12(m, l.z_wdown)));
+        PGV_TRY(gemv_mat(ctx, m, GV_RESIDNORM, layer_mat(m, li, MAT_DOWN), kv->act, kv->resid, H, B, s, &prod));
         parts_in = nparts;
     }
     PGV_TRY(lm_head_and_pick(ctx, m, kv, B, eos, flags, s, parts_in));

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/pgv.h"
+#include "pgv_sizes.h"   // pgv_align
 
 // ---------------------------------------------------------------------------------------------
 // error plumbing
@@ -74,7 +75,6 @@ int pgv_ws_release(pgv_ctx* ctx, hipStream_t s);
 // Bump allocate (256-B aligned) from the reserved arena; nullptr if exhausted.
 void* pgv_ws_alloc(pgv_ctx* ctx, size_t bytes);
 inline void pgv_ws_reset(pgv_ctx* ctx) { ctx->ws_off = 0; }
-inline size_t pgv_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // RAII-free profiling scope helpers
 void pgv_prof_begin(pgv_ctx* ctx, int family, hipStream_t s);

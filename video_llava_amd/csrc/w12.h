@@ -17,12 +17,7 @@
 #pragma once
 #include "pgv_common.h"
 
-constexpr int kW12MaxExc = 64;               // exceptions per row block: one entry per lane of a wave
-constexpr unsigned kW12NoExc = 0xffffffffu;
-
-inline __host__ __device__ size_t pgv_w12_units_bytes(long long N, long long K) { return (size_t)N * (size_t)K / 2 * 3; }
-inline __host__ __device__ size_t pgv_w12_exc_bytes(long long N) { return (size_t)(N / 16) * kW12MaxExc * 4; }
-inline __host__ __device__ size_t pgv_w12_total_bytes(long long N, long long K) { return pgv_w12_units_bytes(N, K) + pgv_w12_exc_bytes(N) + (size_t)N; }
+constexpr unsigned kW12NoExc = 0xffffffffu;   // kW12MaxExc and the pgv_w12_*_bytes sizes: pgv_sizes.h
 
 #if defined(__HIPCC__)
 // High bytes of the 16 weights of a lane in one unit from its two code dwords and the row base replicated in four bytes (b4):

@@ -182,16 +182,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
 
     def get_weight(self, key: str) -> torch.Tensor:
         """fp32 [out, in] copy of a decoder matrix / lm_head under its HF key, as the kernels see it (dequantised after fp8)."""
-        c = self.config
-        H, I = c.hidden_size, c.intermediate_size
-        if key == "lm_head.weight":
-            shape = (self.vocab_size, H)
-        elif key.endswith(("gate_proj.weight", "up_proj.weight")):
-            shape = (I, H)
-        elif key.endswith("down_proj.weight"):
-            shape = (H, I)
-        else:
-            shape = (H, H)
+        shape = self._expected_shape(key) or (1,)       # not a decoder key: the library rejects it (as it does the norm vectors and embed_tokens)
         out = torch.empty(shape, dtype=torch.float32, device=self.device_)
         _lib.check(self.ctx.lib.pgv_llm_get_weight(self.ctx.handle, self.handle, key.encode(), out.data_ptr(), _lib.stream_ptr(self.device_)),
                    "pgv_llm_get_weight")
