@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 324
+#define PGV_VERSION 325
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -49,7 +49,7 @@ size_t pgv_ctx_workspace_bytes(const pgv_ctx *ctx);
 
 /* Per-kernel-family device timers (hipEvent pairs around every launch of the family on the
  * caller's stream).  family: 0 = MFMA GEMM, 1 = ViT attention, 2 = LLM prefill attention,
- * 3 = decode GEMV, 4 = decode attention, 5 = pooling, 6 = the short decode kernels (residual+RMSNorm, embedding, argmax).
+ * 3 = decode GEMV, 4 = decode attention, 5 = pooling, 6 = the short decode kernels (residual+RMSNorm, embedding, argmax) and logprob_rows.
  * Off by default. */
 #define PGV_NFAMILY 7
 int pgv_prof_enable(pgv_ctx *ctx, int on);
@@ -209,6 +209,26 @@ int pgv_llm_prefill_append(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t
 int pgv_llm_prefill_slots(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_slots, int n, const int32_t *h_ids, const int32_t *h_seq_lens,
                           const void *d_video, int V, const int32_t *h_vid_pos, float temperature, int top_k, const float *d_u, float *d_logits,
                           int32_t *d_next, void *stream);
+/* Teacher-forced scoring: the log-probability of GIVEN tokens -- the per-token terms of the loss the reference's forward(labels=...) computes
+ * (video_chatgpt/model/video_chatgpt.py:228-239: shift logits and labels by one, flatten, CrossEntropyLoss) -- without materialising the
+ * logits of every position.
+ * pgv_logprob_rows (building block, caller buffers): d_logits [R, ld] fp32 (16-byte aligned, ld % 4 == 0, ld >= V), d_targets [R].  Per row
+ * (each output pointer may be NULL): d_logprob[r] = x[t] - logsumexp(x[0:V]), d_lse[r] = logsumexp(x[0:V]), d_argmax[r] = the first index
+ * of the largest entry (the greedy pick's tie rule).  The reduction covers exactly columns [0, V) -- never the spare columns [V, ld) that the
+ * lm_head GEMM fills with logit 0.  d_targets[r] < 0: d_logprob[r] = 0, the other two are still written; a target at or beyond V (it cannot be
+ * checked on the host) gives NaN.  -inf entries contribute 0, a target on -inf gives -inf.  Every reduction has a fixed order: a row's result
+ * does not depend on R, on the row's index or on the launch.
+ * pgv_llm_score = pgv_llm_prefill + score: h_targets[r] (r = row of the concatenated batch) is the id whose probability row r's logits are
+ * asked for (the caller has done the shift of :234-235: usually the id of row r + 1), or < 0 = row not scored.  d_logprob / d_lse / d_argmax
+ * (each may be NULL): [sum of h_seq_lens], unscored rows 0 / 0 / -1.  The scored rows take the final norm and lm_head in chunks of at most
+ * PGV_SCORE_CHUNK_ROWS rows through a workspace buffer; their logits are bit for bit those of d_all_logits.  The cache is left a live group
+ * exactly as pgv_llm_prefill leaves it.  A target >= the vocabulary is refused with PGV_EINVAL like a bad token id, the cache unchanged. */
+#define PGV_SCORE_CHUNK_ROWS 1024
+int pgv_logprob_rows(pgv_ctx *ctx, const float *d_logits, int ld, int V, int R, const int32_t *d_targets, float *d_logprob, float *d_lse,
+                     int32_t *d_argmax, void *stream);
+int pgv_llm_score(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_ids, const int32_t *h_seq_lens, int B, const void *d_video, int V,
+                  const int32_t *h_vid_pos, const int32_t *h_targets, float *d_logprob, float *d_lse, int32_t *d_argmax, void *stream);
+
 /* Forget the cache entries of sequence b from position `len` on (1 <= len <= pgv_kv_len): the next append / decode call continues there.
  * Used when a new chat turn shares only a prefix with what the cache holds (surplus decode steps past a stop string,
  * video_chatgpt/model/utils.py:6-26). */

@@ -15,11 +15,12 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgv.so")
 
-ABI_VERSION = 324          # PGV_VERSION of include/pgv.h this table was written against
+ABI_VERSION = 325          # PGV_VERSION of include/pgv.h this table was written against
 PGV_OK, PGV_EINVAL, PGV_EHIP, PGV_ENOMEM, PGV_ESTATE, PGV_ENAME = 0, 1, 2, 3, 4, 5
 PGV_F16, PGV_BF16, PGV_F32 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_GELU, EPI_RESID, EPI_BIAS_RESID, EPI_SWIGLU, EPI_F32 = range(8)
 EPI_LN_BIAS, EPI_LN_BIAS_QGELU, EPI_BIAS_RESID_LNOUT = 8, 9, 10      # folded LayerNorm (pgv_gemm_ex only)
+SCORE_CHUNK_ROWS = 1024    # PGV_SCORE_CHUNK_ROWS: scored rows pgv_llm_score sends through lm_head at a time
 FAMILIES = ("gemm", "vit_attn", "llm_prefill_attn", "decode_gemv", "decode_attn", "other", "decode_small")
 
 
@@ -76,6 +77,8 @@ PROTOTYPES = {
     "pgv_llm_prefill_append": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _i, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
     "pgv_llm_prefill_slots": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, _vp, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), _f, _i, _vp, _vp,
                                    _vp, _vp]),
+    "pgv_logprob_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "pgv_llm_score": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _i, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp]),
     "pgv_kv_truncate": (_i, [_vp, _i, _i, _vp]),
     "pgv_llm_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pgv_llm_decode_greedy": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
@@ -309,6 +312,20 @@ class Context:
                                             seen_lens.data_ptr() if seen_ids is not None else None, u.data_ptr(), out.data_ptr(),
                                             kept.data_ptr() if kept is not None else None, stream_ptr(logits.device)), "pgv_sample_logits_ex")
         return (out, kept) if want_kept else out
+
+    def logprob_rows(self, logits: torch.Tensor, targets: torch.Tensor, V: "int | None" = None):
+        """pgv_logprob_rows on fp32 logits [R, ld] (unit column stride, ld % 4 == 0) over columns [0, V) (default: all): -> (logprob [R] fp32,
+        logsumexp [R] fp32, argmax [R] int32).  targets int32 [R]; a negative target gives logprob 0."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+        assert targets.is_cuda and targets.dtype == torch.int32 and targets.is_contiguous() and targets.numel() == logits.shape[0]
+        R, ld = logits.shape[0], max(logits.stride(0), logits.shape[1])       # a [:, :V] view of a wider buffer keeps the buffer's row stride
+        V = logits.shape[1] if V is None else int(V)
+        lp = torch.empty(R, dtype=torch.float32, device=logits.device)
+        lse = torch.empty(R, dtype=torch.float32, device=logits.device)
+        am = torch.empty(R, dtype=torch.int32, device=logits.device)
+        check(self.lib.pgv_logprob_rows(self.handle, logits.data_ptr(), ld, V, R, targets.data_ptr(), lp.data_ptr(), lse.data_ptr(), am.data_ptr(),
+                                        stream_ptr(logits.device)), "pgv_logprob_rows")
+        return lp, lse, am
 
     def preprocess_u8(self, frames: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
         """uint8 [T, S, S, 3] on the device -> normalised [T, 3, S, S]."""

@@ -423,11 +423,15 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
 // `h_slots` (pgv_llm_prefill_slots): sequence b of the call is a NEW prompt for cache slot h_slots[b] of the live group; the other slots keep their
 // cache rows, lengths, current tokens and flags.  The new rows run through the same kernels (the slot only redirects the cache rows they write and
 // read), the pick lands in rows [0, B) of the scratch and is scattered to the slots: d_u null = greedy, else sampled with d_u[b].
+// `score` (pgv_llm_score): a plain prefill with a scoring tail.  The rows with a target go, PGV_SCORE_CHUNK_ROWS at a time, through the final norm
+// and the lm_head GEMM of the d_all_logits branch into a workspace buffer (so their logits are bit for bit that branch's: the GEMM has one tile
+// shape and no split-K, a row does not depend on M), and logprob_rows (score.hip) reduces every row to (log-probability, logsumexp, argmax).
+struct ScoreReq { const int32_t* h_targets; float* d_logprob; float* d_lse; int32_t* d_argmax; };
 static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video,
                         int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream, bool append,
-                        const int32_t* h_slots = nullptr, float temperature = 0.f, int top_k = 0, const float* d_u = nullptr) {
+                        const int32_t* h_slots = nullptr, float temperature = 0.f, int top_k = 0, const float* d_u = nullptr, const ScoreReq* score = nullptr) {
     const bool slots = h_slots != nullptr;
-    const char* who = append ? "pgv_llm_prefill_append" : slots ? "pgv_llm_prefill_slots" : "pgv_llm_prefill";
+    const char* who = score ? "pgv_llm_score" : append ? "pgv_llm_prefill_append" : slots ? "pgv_llm_prefill_slots" : "pgv_llm_prefill";
     PGV_CHECK(ctx && m && kv && h_ids && h_seq_lens, "%s: null argument", who);
     PGV_CHECK(kv->llm == m, "%s: kv cache belongs to another model", who);
     PGV_CHECK(B >= 1 && B <= kv->B, "%s: batch %d outside [1,%d]", who, B, kv->B);
@@ -452,12 +456,22 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
         M += h_seq_lens[b];
         if (h_seq_lens[b] > max_len) max_len = h_seq_lens[b];
     }
+    int nscore = 0;                                             // rows with a target (pgv_llm_score)
+    if (score) PGV_CHECK(((vocab + 15) & ~15) <= m->vocab_cap, "%s: vocabulary %d beyond the %d allocated lm_head rows", who, vocab, m->vocab_cap);
+    if (score)
+        for (int r = 0; r < M; ++r) {
+            PGV_CHECK(score->h_targets[r] < vocab, "%s: target %d of row %d outside the vocabulary (%d)", who, score->h_targets[r], r, vocab);
+            nscore += score->h_targets[r] >= 0;
+        }
     // ---- host-built row maps: [row_src | row_b | row_pos | cu (B+1) | last_rows (B) | lens (B) = positions after this call | offs (B) | slots (B)] ----
     std::vector<int>& meta = kv->h_meta;
-    meta.assign((size_t)4 * M + 5 * B + 1, 0);                  // + the ids as given [M], for the seen-set (pgv_launch_seen_mark)
+    meta.assign((size_t)4 * M + 5 * B + 1 + 2 * nscore, 0);     // + the ids as given [M], for the seen-set (pgv_launch_seen_mark); + scored rows, their targets
     int* row_src = meta.data(); int* row_b = row_src + M; int* row_pos = row_b + M; int* cu = row_pos + M; int* last = cu + B + 1; int* lens = last + B; int* offs = lens + B;
     int* slot = offs + B;
     int* raw_ids = slot + B;
+    int* srows = raw_ids + M; int* stgts = srows + nscore;
+    for (int i = 0, k = 0; score && i < M; ++i)
+        if (score->h_targets[i] >= 0) { srows[k] = i; stgts[k++] = score->h_targets[i]; }
     int r = 0;
     for (int b = 0; b < B; ++b) {
         cu[b] = r;
@@ -482,7 +496,11 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     const size_t b_meta = pgv_align(meta.size() * 4), b_resid = pgv_align((size_t)M * H * 4), b_xn = pgv_align((size_t)M * H * 2),
                  b_qkv = pgv_align((size_t)M * 3 * H * 2), b_ao = pgv_align((size_t)M * H * 2), b_act = pgv_align((size_t)M * I * 2);
     const size_t b_pick = slots ? pgv_align((size_t)B * 4) : 0;
-    PGV_TRY(pgv_ws_reserve(ctx, b_meta + b_resid + b_xn + b_qkv + b_ao + b_act + b_pick, s));
+    // scoring tail: gathered residual rows, their normalised 16-bit form and the fp32 logits of one chunk
+    const int n16 = (vocab + 15) & ~15;
+    const int schunk = nscore < PGV_SCORE_CHUNK_ROWS ? nscore : PGV_SCORE_CHUNK_ROWS;
+    const size_t b_sres = pgv_align((size_t)schunk * H * 4), b_sxn = pgv_align((size_t)schunk * H * 2), b_slog = pgv_align((size_t)schunk * n16 * 4);
+    PGV_TRY(pgv_ws_reserve(ctx, b_meta + b_resid + b_xn + b_qkv + b_ao + b_act + b_pick + b_sres + b_sxn + b_slog, s));
     int* d_meta = (int*)pgv_ws_alloc(ctx, b_meta);
     float* resid = (float*)pgv_ws_alloc(ctx, b_resid);
     char* xn = (char*)pgv_ws_alloc(ctx, b_xn);
@@ -490,7 +508,10 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     char* ao = (char*)pgv_ws_alloc(ctx, b_ao);
     char* act = (char*)pgv_ws_alloc(ctx, b_act);
     int* d_pick = slots ? (int*)pgv_ws_alloc(ctx, b_pick) : nullptr;       // the refilled sequences' first tokens, before they go to their slots
-    PGV_CHECK(d_meta && resid && xn && qkv && ao && act && (!slots || d_pick), "%s: workspace exhausted", who);
+    float* sres = schunk ? (float*)pgv_ws_alloc(ctx, b_sres) : nullptr;
+    char* sxn = schunk ? (char*)pgv_ws_alloc(ctx, b_sxn) : nullptr;
+    float* slog = schunk ? (float*)pgv_ws_alloc(ctx, b_slog) : nullptr;
+    PGV_CHECK(d_meta && resid && xn && qkv && ao && act && (!slots || d_pick) && (!schunk || (sres && sxn && slog)), "%s: workspace exhausted", who);
     PGV_HIP(hipMemcpyAsync(d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
     const int* d_row_src = d_meta; const int* d_row_b = d_meta + M; const int* d_row_pos = d_row_b + M; const int* d_cu = d_row_pos + M;
     const int* d_last = d_cu + B + 1; const int* d_lens = d_last + B; const int* d_offs = append ? d_lens + B : nullptr;
@@ -524,12 +545,27 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     }
     if (d_all_logits) {
         // the reference's forward output: final norm + lm_head over ALL positions (video_chatgpt.py:225-226) -- on request only
-        const int n16 = (vocab + 15) & ~15;
         PGV_CHECK(ld_all >= n16 && ld_all % 4 == 0 && n16 <= m->vocab_cap, "%s: ld_all %d must be a multiple of 4 and at least %d", who, ld_all, n16);
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, m->norm_g, m->cfg.eps, xn, M, H, s));
         GemmArgs g{};
         g.A = xn; g.lda = H; g.W = m->mats[0].w16; g.ldw = H; g.C = d_all_logits; g.ldc = ld_all; g.M = M; g.N = n16; g.K = H; g.epi = PGV_EPI_F32; g.w_blocked = true;
         PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
+    }
+    if (score) {
+        // what the reference's loss reads (video_chatgpt.py:228-239), for the rows that have a target only; unscored rows: 0 / 0 / -1
+        if (score->d_logprob) PGV_HIP(hipMemsetAsync(score->d_logprob, 0, (size_t)M * 4, s));
+        if (score->d_lse) PGV_HIP(hipMemsetAsync(score->d_lse, 0, (size_t)M * 4, s));
+        if (score->d_argmax) PGV_HIP(hipMemsetAsync(score->d_argmax, 0xff, (size_t)M * 4, s));
+        const int* d_srows = d_lens + 3 * B + M; const int* d_stgts = d_srows + nscore;
+        for (int c0 = 0; c0 < nscore; c0 += schunk) {
+            const int n = nscore - c0 < schunk ? nscore - c0 : schunk;
+            PGV_TRY(pgv_launch_gather_rows(resid, d_srows + c0, sres, n, H, s));
+            PGV_TRY(pgv_launch_rmsnorm(m->dtype, sres, m->norm_g, m->cfg.eps, sxn, n, H, s));
+            GemmArgs g{};
+            g.A = sxn; g.lda = H; g.W = m->mats[0].w16; g.ldw = H; g.C = slog; g.ldc = n16; g.M = n; g.N = n16; g.K = H; g.epi = PGV_EPI_F32; g.w_blocked = true;
+            PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
+            PGV_TRY(pgv_launch_logprob_rows(ctx, slog, n16, vocab, n, d_stgts + c0, d_srows + c0, score->d_logprob, score->d_lse, score->d_argmax, s));
+        }
     }
     // lm_head only on the last position of every sequence (the reference computes all S positions, video_chatgpt.py:226)
     // (a refill runs this tail in rows [0, B) of the decode scratch: every decode step rebuilds resid / xn / ssq / logits / amax_* from d_cur)
@@ -579,6 +615,13 @@ extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
                                      int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots, "pgv_llm_prefill_slots: null slot list");
     return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, n, d_video, Vt, h_vid_pos, d_logits, d_next, nullptr, 0, stream, false, h_slots, temperature, top_k, d_u);
+}
+
+extern "C" int pgv_llm_score(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video, int Vt,
+                             const int32_t* h_vid_pos, const int32_t* h_targets, float* d_logprob, float* d_lse, int32_t* d_argmax, void* stream) {
+    PGV_CHECK(h_targets, "pgv_llm_score: null target list");
+    const ScoreReq sc{h_targets, d_logprob, d_lse, d_argmax};
+    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, B, d_video, Vt, h_vid_pos, nullptr, nullptr, nullptr, 0, stream, false, nullptr, 0.f, 0, nullptr, &sc);
 }
 
 // Drop the tail of sequence b: the next pgv_llm_prefill_append / decode call continues at position `len` (the entries beyond it are simply

@@ -60,6 +60,11 @@ int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax
 // pgv_llm_prefill_slots: sequence i of the call becomes slot slots[i] -- cur = pick[i], pos = lens[i], step = done = 0
 int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, int n, int* cur, int* pos, int* step, int* done, hipStream_t s);
 
+// score.hip: per-row log-probability of targets[r] / logsumexp / argmax over columns [0, V) of fp32 logits [R, ld]; row r writes at index
+// out_rows[r] (null: r).  Timed under family 6.
+int pgv_launch_logprob_rows(pgv_ctx* ctx, const float* logits, int ld, int V, int R, const int* targets, const int* out_rows, float* logprob, float* lse,
+                            int* argmax, hipStream_t s);
+
 #if defined(__HIPCC__)
 // sum over each aligned group of 16 lanes with DPP (VALU latency) instead of ds_bpermute shuffles (LDS crossbar latency):
 // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_ror:4, row_ror:8 -> every lane of the row ends up with the row total.

@@ -13,6 +13,7 @@ from . import _lib
 from .constants import (DEFAULT_TRANSCRIPT_START, DEFAULT_VID_END_TOKEN, DEFAULT_VID_START_TOKEN, DEFAULT_VIDEO_PATCH_TOKEN,
                         DEFAULT_VIDEO_TOKEN, NUM_TEMPORAL_TOKENS)
 from .model.utils import KeywordsStoppingCriteria
+from .scoring import continuation_labels
 from .video_conversation import SeparatorStyle, conv_templates
 
 
@@ -170,3 +171,28 @@ def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, 
                                                 transcript, do_sample, temperature, max_new_tokens)
     outputs = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0]
     return outputs.strip().rstrip(stop_str).strip()
+
+
+def video_chatgpt_score(video_frames, question, answers, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
+                        transcript=None, features=None):
+    """How likely is each of `answers` (a list of candidate strings) as the reply to `question` about one clip: the prompt of
+    `video_chatgpt_infer`, each candidate teacher-forced behind it.  CLIP runs once (`features`: pooled features computed earlier skip it) and
+    all candidates go through ONE model.score call as B sequences.  A candidate's ids are tokenizer(prompt + answer + stop_str) cut at the
+    prompt's length (the usual context / continuation split; a tokenizer that merges across the boundary raises in continuation_labels), so
+    the scored span includes the stop token(s).  Returns one dict per candidate, in order: "logprob" (sum over the span), "tokens" (its
+    length), "mean_logprob", "greedy" (every scored position's argmax is its target: greedy decoding would have produced this candidate)."""
+    prompt, stop_str = build_prompt(question, conv_mode, video_token_len, model.get_model().vision_config.use_vid_start_end, transcript)
+    prompt_ids = tokenizer([prompt]).input_ids[0]
+    feats = features if features is not None else video_features(video_frames, vision_tower, image_processor)
+    full = [list(tokenizer([prompt + a + stop_str]).input_ids[0]) for a in answers]
+    labels = [continuation_labels(prompt_ids, f) for f in full]
+    with torch.inference_mode():
+        out = model.score(full, labels, video_spatio_temporal_features=feats.unsqueeze(0))
+    res = []
+    for b in range(len(full)):
+        m = out.scored[b]
+        n = int(out.counts[b])
+        lp = float(out.sequence_logprob[b])
+        greedy = bool((out.argmax[b][m].long() == torch.tensor(labels[b], dtype=torch.long)[m]).all())
+        res.append({"logprob": lp, "tokens": n, "mean_logprob": lp / n if n else float("nan"), "greedy": greedy})
+    return res

@@ -22,6 +22,7 @@ import torch.nn as nn
 from .. import _lib
 from ..constants import CLIP_WIDTH
 from ..generation import check_generate_kwargs, load_generation_config, resolve_sampling
+from ..scoring import ScoreOutput, id_rows, shift_labels
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
 from .utils import AnswerState
 
@@ -346,6 +347,22 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         return L
 
     # ---- low-level steps (used by generate and by the parity tests) -------------------------------------
+    def _project_video(self, feats: torch.Tensor, seqs, broadcast: bool = False):
+        """Pooled features [n, V, C] (or [V, C]) of the prompts `seqs` -> (mm_projector output [n, V, hidden] contiguous (:105), V, the
+        placeholder positions).  broadcast: one feature set stands for all prompts (projected once)."""
+        n = len(seqs)
+        if feats.dim() == 2:
+            feats = feats.unsqueeze(0)
+        proj = self.model.mm_projector(feats.to(self.device_))
+        if isinstance(self.model.mm_projector, IdentityMap):
+            proj = proj.to(self.dtype_)
+        if broadcast and proj.shape[0] == 1 and n > 1:
+            proj = proj.expand(n, -1, -1)
+        if proj.shape[0] != n:
+            raise ValueError(f"{proj.shape[0]} video feature sets for {n} prompts")
+        proj = proj.contiguous()
+        return proj, proj.shape[1], self._video_positions(seqs, proj.shape[1])
+
     def prefill(self, seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor], max_seq: int,
                 want_logits: bool = False, want_all_logits: bool = False, append_to=None):
         """Run the prompt(s); returns (kv handle, next-token ids [B] int32 on device, logits [B, vocab] or None) -- with want_all_logits a fourth
@@ -358,16 +375,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         V = 0
         vid_pos = [-1] * B
         if feats is not None and not (max(lens) == 1):     # the reference skips the splice when input_ids.shape[1]==1 (:103)
-            if feats.dim() == 2:
-                feats = feats.unsqueeze(0)
-            proj = self.model.mm_projector(feats.to(self.device_))         # [B, V, hidden]  (:105)
-            if isinstance(self.model.mm_projector, IdentityMap):
-                proj = proj.to(self.dtype_)
-            proj = proj.contiguous()
-            V = proj.shape[1]
-            if proj.shape[0] != B:
-                raise ValueError(f"{proj.shape[0]} video feature sets for {B} prompts")
-            vid_pos = self._video_positions(seqs, V)
+            proj, V, vid_pos = self._project_video(feats, seqs)
         if append_to is None:
             kv = self._get_kv(max(B, 1), max_seq)
             self._kv_epoch += 1
@@ -391,6 +399,43 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             return kv, nxt, logits, all_logits[:, :self.vocab_size]
         return kv, nxt, logits
 
+    # ---- score: the per-token terms of the reference's forward(labels=...) loss (model/video_chatgpt.py:228-239) ------------------------
+    @torch.no_grad()
+    def score(self, input_ids, labels, video_spatio_temporal_features: Optional[torch.Tensor] = None) -> ScoreOutput:
+        """Teacher-forced log-probabilities of given tokens: one prefill of `input_ids` ([B, S] tensor or a ragged list of id lists) and, for every
+        position p whose `labels[p]` is not -100, log P(labels[p] | ids[:p]) from the logits of row p - 1 (HF's shift) -- computed on the device
+        row by row (pgv_llm_score), never as a [rows, vocab] tensor.  `labels` has the shape of `input_ids`; scoring.continuation_labels builds the
+        usual prompt / answer split.  `video_spatio_temporal_features`: [B, V, C], or one clip ([V, C] / [1, V, C]) for all B sequences (projected
+        once).  Returns scoring.ScoreOutput; `.loss` is the number the reference's forward(labels=) returns as `loss` (forward(labels=) itself
+        stays refused).  The KV cache (capacity: the longest sequence rounded up to 64) is refilled as by any prefill: earlier past_key_values
+        go stale, and `.kv` is a live group that decode_step / decode_greedy continue from."""
+        seqs = id_rows(input_ids)
+        B = len(seqs)
+        lens = [len(s_) for s_ in seqs]
+        if B < 1 or min(lens) < 1:
+            raise ValueError("score(): needs at least one non-empty sequence")
+        targets = shift_labels(seqs, labels)
+        limit = min(int(self.config.max_position_embeddings), 4096)
+        if max(lens) > limit:
+            raise ValueError(f"sequence of {max(lens)} tokens exceeds max_position_embeddings {limit}")
+        max_seq = min(limit, (max(lens) + 63) // 64 * 64)
+        feats = video_spatio_temporal_features
+        proj, V, vid_pos = None, 0, [-1] * B
+        if feats is not None:
+            proj, V, vid_pos = self._project_video(feats, seqs, broadcast=True)
+        kv = self._get_kv(B, max_seq)
+        self._kv_epoch += 1
+        self._reuse = None
+        flat = np.concatenate([np.asarray(s_, dtype=np.int32) for s_ in seqs])
+        M = int(flat.size)
+        out = torch.empty(3, M, dtype=torch.float32, device=self.device_)         # logprob | lse | argmax (int32 bits)
+        _lib.check(self.ctx.lib.pgv_llm_score(self.ctx.handle, self.handle, kv, flat.ctypes.data_as(C.c_void_p), (C.c_int32 * B)(*lens), B,
+                                              proj.data_ptr() if proj is not None else None, V, (C.c_int32 * B)(*vid_pos),
+                                              targets.ctypes.data_as(C.c_void_p), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                              _lib.stream_ptr(self.device_)), "pgv_llm_score")
+        host = out.cpu()
+        return ScoreOutput.from_rows(lens, targets, host[0].numpy(), host[2].view(torch.int32).numpy(), kv=kv)
+
     def prefill_slots(self, kv, slots: Sequence[int], seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor],
                       want_logits: bool = False, u: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 50,
                       top_p: float = 1.0, repetition_penalty: float = 1.0):
@@ -407,16 +452,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         feats = video_spatio_temporal_features
         proj, V, vid_pos = None, 0, [-1] * n
         if feats is not None:
-            if feats.dim() == 2:
-                feats = feats.unsqueeze(0)
-            proj = self.model.mm_projector(feats.to(self.device_))
-            if isinstance(self.model.mm_projector, IdentityMap):
-                proj = proj.to(self.dtype_)
-            proj = proj.contiguous()
-            V = proj.shape[1]
-            if proj.shape[0] != n:
-                raise ValueError(f"{proj.shape[0]} video feature sets for {n} prompts")
-            vid_pos = self._video_positions(seqs, V)
+            proj, V, vid_pos = self._project_video(feats, seqs)
         flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
         nxt = torch.empty(n, dtype=torch.int32, device=self.device_)
         logits = torch.empty(n, self.vocab_size, dtype=torch.float32, device=self.device_) if want_logits else None
