@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 325
+#define PGV_VERSION 326
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -287,8 +287,45 @@ int pgv_sample_logits_ex(pgv_ctx *ctx, const float *d_logits, int V, int B, floa
  * _slots (placeholder ids included; a refill starts from an empty set, pgv_llm_prefill_append adds to it) plus every token one of those picks
  * returned while a value differed from (1, 1).  Set the values before the prefill of the sequences they are meant for.  Not covered: the
  * greedy d_next of pgv_llm_prefill / _append and plain pgv_llm_decode steps, which neither apply the penalty nor record a token -- a caller
- * who wants the penalised first token draws it with pgv_llm_sample(temperature 1, top_k 1, u = 0). */
+ * who wants the penalised first token draws it with pgv_llm_pick_greedy (the token of pgv_llm_sample(temperature 1, top_k 1, u = 0)). */
 int pgv_kv_set_warpers(pgv_kv *kv, float top_p, float repetition_penalty);
+
+/* Log-probabilities of the tokens the picks RETURN (the mirror image of pgv_llm_score, which scores GIVEN tokens): two floats per pick, recorded
+ * on the device next to the token, inside the captured decode graphs -- no logits leave the device.  For the token t a pick returns for a
+ * sequence at one step, x the fp32 logits of that step over columns [0, vocab):
+ *  - `model` = x[t] - logsumexp(x): the model's own distribution, no processor.  HF: compute_transition_scores(sequences, logits,
+ *    normalize_logits=True) on output_logits=True.  Same reduction order as pgv_logprob_rows: for the same row and token it is the same float, and
+ *    its NaN / -inf rules hold (a NaN in the row poisons the sum; a token on -inf gives -inf).
+ *  - `pick` = the log of the probability the pick used.  HF: compute_transition_scores(sequences, scores, normalize_logits=True), `scores` the
+ *    processed scores of output_scores=True.  Sampling: log-softmax over the scores after repetition penalty -> temperature -> top-k -> top-p
+ *    (HF's order, the tie rules above), computed as (x'[t] - M) / T - ln sum_kept exp((x' - M) / T) from the logit itself; a NaN logit has
+ *    weight 0, as in the pick.  Greedy without a penalty: `model`, the same float bit for bit -- hence NaN, like `model`, on a row that holds a NaN
+ *    (the penalty-free greedy value IS the model's; the weight-0 rule applies wherever a processor is at work).  Greedy under a penalty (pgv_kv_set_warpers with
+ *    repetition_penalty != 1): the log-softmax of the PENALISED logits over the whole vocabulary at temperature 1, as HF's greedy loop has it
+ *    -- not the degenerate top-1 value 0.  The seen-set is the one the pick itself read (the returned token joins it afterwards).
+ *  - finished sequences: the step that emits eos_id carries its real values, the sticky steps after it 0.0 for both -- a row sum over the
+ *    history is the answer's log-probability.
+ * pgv_kv_set_logprobs(kv, on), default off: off, every launch, captured graph and token is exactly what it is without this switch; on, every
+ * pick that sets the cache's current token also stores the two values of its slot -- the greedy d_next of pgv_llm_prefill / _append, the first
+ * token of pgv_llm_prefill_slots (at the SLOT, not at the scratch row the pick ran in), pgv_llm_sample, pgv_llm_pick_greedy, pgv_llm_decode, and
+ * every step of pgv_llm_decode_greedy / _sample, which also append them to a per-slot history parallel to the token history (same index, same
+ * per-call reset).  The tokens do not change.  The captured decode graphs are rebuilt when the switch changes.
+ * pgv_kv_logprobs_last: d_model / d_pick [width of the live group] (either may be NULL), by slot: the values of each slot's most recent pick.
+ * pgv_kv_logprobs_steps: d_model / d_pick [B, n] (either may be NULL), laid out like d_tokens: the first n steps of the last
+ * pgv_llm_decode_greedy / _sample call.  PGV_ESTATE when the switch was off during that call (both calls: when it is off now).
+ * pgv_llm_pick_greedy: the greedy pick from the logits of the last prefill / decode call under the cache's repetition penalty -- the token of
+ * pgv_llm_sample(temperature 1, top_k 1, u = 0), recorded with the GREEDY `pick` value (pgv_llm_sample with top_k = 1 records a sampled pick: 0).
+ * It replaces the cache's current token and is written to d_next [B] (may be NULL).
+ * pgv_sample_logits_lp (building block, same kernels): pgv_sample_logits_ex plus d_lp_model / d_lp_pick [B] (either may be NULL).  greedy != 0:
+ * the arg-max of the penalised logits; temperature, top_k, top_p and d_u (may be NULL) are ignored.  Tokens and d_kept are bit for bit those of
+ * pgv_sample_logits_ex (greedy: of temperature 1, top_k 1, top_p 1, u = 0). */
+int pgv_kv_set_logprobs(pgv_kv *kv, int on);
+int pgv_kv_logprobs_last(pgv_kv *kv, float *d_model, float *d_pick, void *stream);
+int pgv_kv_logprobs_steps(pgv_kv *kv, int n, float *d_model, float *d_pick, void *stream);
+int pgv_llm_pick_greedy(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, int32_t *d_next, void *stream);
+int pgv_sample_logits_lp(pgv_ctx *ctx, const float *d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                         const int32_t *d_seen_ids, int seen_stride, const int32_t *d_seen_lens, const float *d_u, int32_t *d_next, int32_t *d_kept,
+                         int greedy, float *d_lp_model, float *d_lp_pick, void *stream);
 
 /* current length (tokens in cache) of sequence b, host-side bookkeeping */
 int pgv_kv_len(const pgv_kv *kv, int b);

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgv.so")
 
-ABI_VERSION = 325          # PGV_VERSION of include/pgv.h this table was written against
+ABI_VERSION = 326          # PGV_VERSION of include/pgv.h this table was written against
 PGV_OK, PGV_EINVAL, PGV_EHIP, PGV_ENOMEM, PGV_ESTATE, PGV_ENAME = 0, 1, 2, 3, 4, 5
 PGV_F16, PGV_BF16, PGV_F32 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_GELU, EPI_RESID, EPI_BIAS_RESID, EPI_SWIGLU, EPI_F32 = range(8)
@@ -87,6 +87,11 @@ PROTOTYPES = {
     "pgv_sample_logits": (_i, [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
     "pgv_sample_logits_ex": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "pgv_kv_set_warpers": (_i, [_vp, _f, _f]),
+    "pgv_kv_set_logprobs": (_i, [_vp, _i]),
+    "pgv_kv_logprobs_last": (_i, [_vp, _vp, _vp, _vp]),
+    "pgv_kv_logprobs_steps": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "pgv_llm_pick_greedy": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "pgv_sample_logits_lp": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "pgv_ingest_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pgv_gemm": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "pgv_gemm_ex": (_i, [_vp, _i, C.POINTER(GemmDesc), _vp]),
@@ -312,6 +317,32 @@ class Context:
                                             seen_lens.data_ptr() if seen_ids is not None else None, u.data_ptr(), out.data_ptr(),
                                             kept.data_ptr() if kept is not None else None, stream_ptr(logits.device)), "pgv_sample_logits_ex")
         return (out, kept) if want_kept else out
+
+    def sample_logits_lp(self, logits: torch.Tensor, u: "torch.Tensor | None", temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
+                         repetition_penalty: float = 1.0, seen_ids: "torch.Tensor | None" = None, seen_lens: "torch.Tensor | None" = None,
+                         greedy: bool = False):
+        """pgv_sample_logits_lp: sample_logits_ex plus the two log-probabilities of the returned token.  greedy: the arg-max of the penalised
+        logits (temperature / top_k / top_p / u ignored).  Returns (tokens int32 [B], kept int32 [B], model fp32 [B], pick fp32 [B])."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+        B = logits.shape[0]
+        if not greedy:
+            assert u is not None and u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and u.numel() == B
+        stride = 0
+        if seen_ids is not None:
+            assert seen_ids.is_cuda and seen_ids.dtype == torch.int32 and seen_ids.is_contiguous() and seen_ids.dim() == 2 and seen_ids.shape[0] == B
+            stride = seen_ids.shape[1]
+            if seen_lens is None:
+                seen_lens = torch.full((B,), stride, dtype=torch.int32, device=logits.device)
+            assert seen_lens.is_cuda and seen_lens.dtype == torch.int32 and seen_lens.numel() == B and int(seen_lens.max()) <= stride
+        out = torch.empty(B, dtype=torch.int32, device=logits.device)
+        kept = torch.empty(B, dtype=torch.int32, device=logits.device)
+        lp = torch.empty(2, B, dtype=torch.float32, device=logits.device)
+        check(self.lib.pgv_sample_logits_lp(self.handle, logits.data_ptr(), logits.shape[1], B, float(temperature), int(top_k), float(top_p),
+                                            float(repetition_penalty), seen_ids.data_ptr() if seen_ids is not None else None, stride,
+                                            seen_lens.data_ptr() if seen_ids is not None else None, u.data_ptr() if u is not None else None,
+                                            out.data_ptr(), kept.data_ptr(), 1 if greedy else 0, lp[0].data_ptr(), lp[1].data_ptr(),
+                                            stream_ptr(logits.device)), "pgv_sample_logits_lp")
+        return out, kept, lp[0], lp[1]
 
     def logprob_rows(self, logits: torch.Tensor, targets: torch.Tensor, V: "int | None" = None):
         """pgv_logprob_rows on fp32 logits [R, ld] (unit column stride, ld % 4 == 0) over columns [0, V) (default: all): -> (logprob [R] fp32,

@@ -42,11 +42,12 @@ def task_uniforms(n: int, seed: int, device) -> torch.Tensor:
 
 class _Slot:
     """A decode slot's task: its answer state and what the scheduler keeps about it (uniform stream, timing counters)."""
-    __slots__ = ("task", "answer", "u", "prefill_s", "decode_s", "steps", "group_size")
+    __slots__ = ("task", "answer", "u", "prefill_s", "decode_s", "steps", "group_size", "lp")
 
     def __init__(self, task: Task, answer: AnswerState, u: Optional[torch.Tensor], prefill_s: float, group_size: int):
         self.task, self.answer, self.u, self.group_size = task, answer, u, group_size
         self.prefill_s, self.decode_s, self.steps = prefill_s, 0.0, 0
+        self.lp: List[np.ndarray] = []      # logprobs: [2, steps] blocks (model | pick) of every token the device emitted for the task, in order
 
 
 def split_refused(parts: List[list], call: Callable[[list], Any]) -> Iterator[Tuple[list, Any, Optional[Exception]]]:
@@ -77,7 +78,8 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                         top_k: int = 50, tokenizer=None, chunk: int = DEFAULT_CHUNK, refill_min: Optional[int] = None, max_seq: Optional[int] = None,
                         prompt_slack: int = 128, eos_token_id="config", seed: int = 0,
                         on_error: Callable[[Any, Exception], None] = _default_on_error,
-                        timings: Optional[dict] = None, top_p: float = 1.0, repetition_penalty: float = 1.0) -> Iterator[Tuple[Any, Optional[List[int]]]]:
+                        timings: Optional[dict] = None, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                        logprobs: Optional[dict] = None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
     """Yield (task_id, new_ids) as each task finishes; new_ids is None for a task that failed (`on_error(task_id, exc)` is told why) -- a failed
     task costs only itself.
 
@@ -93,7 +95,10 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     max_seq: cache positions per slot (default: longest prompt of the first group + `prompt_slack` + max_new_tokens + chunk, rounded to 64);
     a later task that does not fit fails alone.
     timings (a dict): timings[task_id] = {prefill_s, decode_s, steps, group_size} of each finished task (host clock; the prefill call that
-    started it and the decode chunks it was live in)."""
+    started it and the decode chunks it was live in).
+    logprobs (a dict): logprobs[task_id] = {"token_logprobs": [...], "transition_scores": [...]} of each finished task, one entry per new id --
+    what `generate(output_logprobs=True)` returns for the task on its own, bit for bit, whatever its slot and the group width (the values are
+    recorded on the device at pick time: pgv_kv_set_logprobs)."""
     if not 1 <= width <= 64:
         raise ValueError(f"width {width} outside [1, 64]")
     if do_sample and not float(temperature) > 0.0:
@@ -182,103 +187,121 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         return
     W = len(first)
     t0 = time.perf_counter()
-    kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq)
-    slots: List[Optional[_Slot]] = [None] * W
-    us = [uniforms(a, t) for a, t in first]
-    if do_sample:
-        nxt = model.sample_last(kv, torch.stack([u[0] for u in us]), temperature, top_k, **warp)
-    elif rep_pen != 1.0:
-        nxt = model.sample_last(kv, torch.zeros(W, device=dev), 1.0, 1, **pen)      # greedy over the penalised logits (as generate does)
-    cur = nxt.clone()
-    first_tok = nxt.cpu().numpy()
-    dt = time.perf_counter() - t0
-    for s, (a, t) in enumerate(first):
-        slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), us[s], dt, W)
-
-    def finish(s: int):
-        sl = slots[s]
-        slots[s] = None
-        if timings is not None:
-            timings[sl.task.task_id] = {"prefill_s": sl.prefill_s, "decode_s": sl.decode_s, "steps": sl.steps, "group_size": sl.group_size}
-        return sl.task.task_id, sl.answer.new
-
-    for s in range(W):
-        if slots[s].answer.take(first_tok[s:s + 1]):
-            yield finish(s)
-
-    # ---- decode / refill loop --------------------------------------------------------------------------------------
-    while True:
-        free = [s for s in range(W) if slots[s] is None]
-        live = W - len(free)
-        pull(len(free) + width)
-        if free and pending and (len(free) >= k_min or live == 0 or (exhausted[0] and len(pending) <= len(free))):
-            group: List[Tuple[int, int, Task]] = []
-            for s in free:
-                while pending:
-                    a, t = pending.pop(0)
-                    try:
-                        check(t, max_seq)
-                        group.append((s, a, t))
-                        break
-                    except Exception as e:                         # noqa: BLE001
-                        on_error(t.task_id, e)
-                        yield t.task_id, None
-                if not pending:
-                    pull(1)
-                    if not pending:
-                        break
-
-            def prefill_part(part):
-                t0 = time.perf_counter()
-                u_part = [uniforms(a, t) for _, a, t in part]
-                u0 = torch.stack([u[0] for u in u_part]) if do_sample else None
-                nx, _ = model.prefill_slots(kv, [s for s, _, _ in part], [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
-                                            u=u0, temperature=temperature, top_k=top_k, **(warp if do_sample else pen))
-                cur[[s for s, _, _ in part]] = nx
-                return u_part, nx.cpu().numpy(), time.perf_counter() - t0
-
-            ok: List[Tuple[int, np.ndarray]] = []
-            for part, res, e in split_refused([group], prefill_part):
-                if e is not None:                                  # the bad task, isolated
-                    on_error(part[0][2].task_id, e)
-                    yield part[0][2].task_id, None
-                    continue
-                u_part, firsts, dt = res
-                for i, (s, _, t) in enumerate(part):
-                    slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), u_part[i], dt, len(part))
-                    ok.append((s, firsts[i:i + 1]))
-            for s, f in ok:
-                if slots[s].answer.take(f):
-                    yield finish(s)
-            continue                                                # re-evaluate: refilled slots may have finished at their first token
-        if live == 0:
-            if not pending and exhausted[0]:
-                break
-            continue
-        # one chunk of decode steps for the whole group; slots without a task are rewound first
-        for s in free:
-            if model.kv_len(kv, s) > 1:
-                model.kv_truncate(kv, s, 1)
-        n = min(chunk, max(sl.answer.budget - len(sl.answer.new) for sl in slots if sl is not None))
-        t0 = time.perf_counter()
+    want_lp = logprobs is not None
+    kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq, **({"logprobs": True} if want_lp else {}))
+    try:
+        slots: List[Optional[_Slot]] = [None] * W
+        us = [uniforms(a, t) for a, t in first]
         if do_sample:
-            u = torch.full((n, W), 0.5, dtype=torch.float32, device=dev)
+            nxt = model.sample_last(kv, torch.stack([u[0] for u in us]), temperature, top_k, **warp)
+        elif rep_pen != 1.0:
+            nxt = model.greedy_last(kv, W, **pen)                  # greedy over the penalised logits (as generate does)
+        cur = nxt.clone()
+        first_lp = model.logprobs_last(kv, W).cpu().numpy() if want_lp else None
+        first_tok = nxt.cpu().numpy()
+        dt = time.perf_counter() - t0
+        for s, (a, t) in enumerate(first):
+            slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), us[s], dt, W)
+            if want_lp:
+                slots[s].lp.append(first_lp[:, s:s + 1])
+
+        def finish(s: int):
+            sl = slots[s]
+            slots[s] = None
+            if timings is not None:
+                timings[sl.task.task_id] = {"prefill_s": sl.prefill_s, "decode_s": sl.decode_s, "steps": sl.steps, "group_size": sl.group_size}
+            if want_lp:
+                # the kept ids are a prefix of what the device emitted for the task: the same cut applies to the values
+                lp = np.concatenate(sl.lp, axis=1)[:, :len(sl.answer.new)]
+                logprobs[sl.task.task_id] = {"token_logprobs": lp[0].tolist(), "transition_scores": lp[1].tolist()}
+            return sl.task.task_id, sl.answer.new
+
+        for s in range(W):
+            if slots[s].answer.take(first_tok[s:s + 1]):
+                yield finish(s)
+
+        # ---- decode / refill loop --------------------------------------------------------------------------------------
+        while True:
+            free = [s for s in range(W) if slots[s] is None]
+            live = W - len(free)
+            pull(len(free) + width)
+            if free and pending and (len(free) >= k_min or live == 0 or (exhausted[0] and len(pending) <= len(free))):
+                group: List[Tuple[int, int, Task]] = []
+                for s in free:
+                    while pending:
+                        a, t = pending.pop(0)
+                        try:
+                            check(t, max_seq)
+                            group.append((s, a, t))
+                            break
+                        except Exception as e:                         # noqa: BLE001
+                            on_error(t.task_id, e)
+                            yield t.task_id, None
+                    if not pending:
+                        pull(1)
+                        if not pending:
+                            break
+
+                def prefill_part(part):
+                    t0 = time.perf_counter()
+                    u_part = [uniforms(a, t) for _, a, t in part]
+                    u0 = torch.stack([u[0] for u in u_part]) if do_sample else None
+                    nx, _ = model.prefill_slots(kv, [s for s, _, _ in part], [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
+                                                u=u0, temperature=temperature, top_k=top_k, **(warp if do_sample else pen))
+                    cur[[s for s, _, _ in part]] = nx
+                    lp_part = model.logprobs_last(kv, W).cpu().numpy() if want_lp else None
+                    return u_part, nx.cpu().numpy(), lp_part, time.perf_counter() - t0
+
+                ok: List[Tuple[int, np.ndarray]] = []
+                for part, res, e in split_refused([group], prefill_part):
+                    if e is not None:                                  # the bad task, isolated
+                        on_error(part[0][2].task_id, e)
+                        yield part[0][2].task_id, None
+                        continue
+                    u_part, firsts, lp_part, dt = res
+                    for i, (s, _, t) in enumerate(part):
+                        slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), u_part[i], dt, len(part))
+                        if want_lp:
+                            slots[s].lp.append(lp_part[:, s:s + 1])
+                        ok.append((s, firsts[i:i + 1]))
+                for s, f in ok:
+                    if slots[s].answer.take(f):
+                        yield finish(s)
+                continue                                                # re-evaluate: refilled slots may have finished at their first token
+            if live == 0:
+                if not pending and exhausted[0]:
+                    break
+                continue
+            # one chunk of decode steps for the whole group; slots without a task are rewound first
+            for s in free:
+                if model.kv_len(kv, s) > 1:
+                    model.kv_truncate(kv, s, 1)
+            n = min(chunk, max(sl.answer.budget - len(sl.answer.new) for sl in slots if sl is not None))
+            t0 = time.perf_counter()
+            if do_sample:
+                u = torch.full((n, W), 0.5, dtype=torch.float32, device=dev)
+                for s in range(W):
+                    sl = slots[s]
+                    if sl is not None:
+                        seg = sl.u[len(sl.answer.new):len(sl.answer.new) + n]
+                        u[:seg.numel(), s] = seg
+                toks = model.decode_sample(kv, cur, n, eos_i, temperature, top_k, u, **warp)
+            else:
+                toks = model.decode_greedy(kv, cur, n, eos_i, **pen)
+            cur = toks[:, n - 1].contiguous()
+            lp_chunk = model.logprobs_steps(kv, W, n).cpu().numpy() if want_lp else None
+            host = toks.cpu().numpy()
+            dt = time.perf_counter() - t0
             for s in range(W):
                 sl = slots[s]
-                if sl is not None:
-                    seg = sl.u[len(sl.answer.new):len(sl.answer.new) + n]
-                    u[:seg.numel(), s] = seg
-            toks = model.decode_sample(kv, cur, n, eos_i, temperature, top_k, u, **warp)
-        else:
-            toks = model.decode_greedy(kv, cur, n, eos_i, **pen)
-        cur = toks[:, n - 1].contiguous()
-        host = toks.cpu().numpy()
-        dt = time.perf_counter() - t0
-        for s in range(W):
-            sl = slots[s]
-            if sl is None:
-                continue
-            sl.decode_s += dt
-            sl.steps += n
-            if sl.answer.take(host[s]):
-                yield finish(s)
+                if sl is None:
+                    continue
+                sl.decode_s += dt
+                sl.steps += n
+                if want_lp:
+                    sl.lp.append(lp_chunk[:, s])
+                if sl.answer.take(host[s]):
+                    yield finish(s)
+    finally:
+        if want_lp:
+            model.set_logprobs(kv, False)                           # the switch was on for this call only: also when the generator is closed early

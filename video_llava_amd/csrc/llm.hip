@@ -72,6 +72,12 @@ struct pgv_kv {
     float w_topp = 1.f, w_pen = 1.f;    // pgv_kv_set_warpers: what every later pick on this cache runs with
     unsigned* d_seen = nullptr;         // seen-set of every slot (repetition penalty): [B][seen_words] bitmaps over the vocabulary
     int seen_words = 0;
+    // pgv_kv_set_logprobs: the two log-probabilities of every pick.  lp_stat [B][2] row statistics (row_lse_kernel), lp_last [2][B] the values of each
+    // slot's latest pick (model | pick), lp_hist [2][B][max_seq] those of the stepping calls, parallel to d_hist
+    bool lp_on = false; int g_lp = 0;
+    float *lp_stat = nullptr, *lp_last = nullptr, *lp_hist = nullptr;
+    int lp_steps = -1;                  // steps of the last pgv_llm_decode_greedy / _sample call that ran with the switch on (-1: it was off)
+    bool s_greedy = false; int g_greedy = 0;     // the run in flight picks the arg-max of the penalised logits (decode_greedy under a penalty)
     bool warmed = false;
 };
 
@@ -320,6 +326,7 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
     kv->seen_words = (int)(V / 32);                          // vocab_cap is a multiple of 16: round up
     if ((size_t)kv->seen_words * 32 < V) kv->seen_words += 1;
     const size_t o_seen = take(B * (size_t)kv->seen_words * 4);
+    const size_t n_lp = 4 * B + 2 * B * (size_t)max_seq, o_lp = take(n_lp * 4);
     hipError_t e = hipMalloc((void**)&kv->blob, off);
     if (e != hipSuccess) { delete kv; pgv_set_error("pgv_kv_create: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
     char* b = kv->blob;
@@ -331,8 +338,10 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
     kv->dattn_part = (float*)(b + o_dpart); kv->dattn_ticket = (unsigned*)(b + o_dtick);
     kv->k8_part = (void*)(b + o_k8);
     kv->d_seen = (unsigned*)(b + o_seen);
+    kv->lp_stat = (float*)(b + o_lp); kv->lp_last = kv->lp_stat + 2 * B; kv->lp_hist = kv->lp_last + 2 * B;
     e = hipMemset(ints, 0, (4 * B + B * (size_t)max_seq) * 4);
     if (e == hipSuccess) e = hipMemset(kv->d_seen, 0, B * (size_t)kv->seen_words * 4);
+    if (e == hipSuccess) e = hipMemset(kv->lp_stat, 0, n_lp * 4);
     if (e == hipSuccess) e = hipMemset(kv->dattn_ticket, 0, B * llm->cfg.heads * 4);
     if (e == hipSuccess) e = hipMemset(kv->ssq, 0, CTn * H * 4);
     if (e == hipSuccess) e = hipMemset(kv->xn, 0, CTn * 16 * H * 2);            // the columns of absent sequences are read (never stored): finite
@@ -363,6 +372,40 @@ static SampleWarp kv_warp(pgv_kv* kv, bool greedy, const int* slot_map = nullptr
     w.top_p = greedy ? 1.f : kv->w_topp; w.penalty = kv->w_pen;
     w.seen_bits = kv->d_seen; w.seen_words = kv->seen_words; w.seen_slot = slot_map;
     return w;
+}
+
+extern "C" int pgv_kv_set_logprobs(pgv_kv* kv, int on) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_set_logprobs: null cache");
+    if (kv->lp_on != (on != 0)) { kv->lp_on = on != 0; kv->lp_steps = -1; }
+    return PGV_OK;
+}
+
+// what a pick on the cache's own rows records (rows = slots unless `slot_map` says otherwise); switch off: nothing
+static PickLp kv_lp(pgv_kv* kv, int flags, bool greedy, const int* slot_map = nullptr) {
+    PickLp lp;
+    if (!kv->lp_on) return lp;
+    lp.stat = kv->lp_stat; lp.last_model = kv->lp_last; lp.last_pick = kv->lp_last + kv->B; lp.slot = slot_map; lp.greedy = greedy;
+    if (flags & AM_RECORD) { lp.hist_model = kv->lp_hist; lp.hist_pick = kv->lp_hist + (size_t)kv->B * kv->max_seq; lp.hist_stride = kv->max_seq; }
+    return lp;
+}
+
+extern "C" int pgv_kv_logprobs_last(pgv_kv* kv, float* d_model, float* d_pick, void* stream) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_logprobs_last: null cache");
+    if (!kv->lp_on || kv->active < 1) { pgv_set_error("pgv_kv_logprobs_last: %s", kv->lp_on ? "no prefilled sequences in this cache" : "pgv_kv_set_logprobs is off"); return PGV_ESTATE; }
+    if (d_model) PGV_HIP(hipMemcpyAsync(d_model, kv->lp_last, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_pick) PGV_HIP(hipMemcpyAsync(d_pick, kv->lp_last + kv->B, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PGV_OK;
+}
+
+extern "C" int pgv_kv_logprobs_steps(pgv_kv* kv, int n, float* d_model, float* d_pick, void* stream) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_logprobs_steps: null cache");
+    if (!kv->lp_on || kv->lp_steps < 0) { pgv_set_error("pgv_kv_logprobs_steps: pgv_kv_set_logprobs was off during the last pgv_llm_decode_greedy / _sample call"); return PGV_ESTATE; }
+    PGV_CHECK(n >= 1 && n <= kv->lp_steps, "pgv_kv_logprobs_steps: %d steps asked for, the last call ran %d", n, kv->lp_steps);
+    const size_t row = (size_t)kv->max_seq * 4;
+    if (d_model) PGV_HIP(hipMemcpy2DAsync(d_model, (size_t)n * 4, kv->lp_hist, row, (size_t)n * 4, kv->active, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_pick)
+        PGV_HIP(hipMemcpy2DAsync(d_pick, (size_t)n * 4, kv->lp_hist + (size_t)kv->B * kv->max_seq, row, (size_t)n * 4, kv->active, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PGV_OK;
 }
 
 extern "C" int pgv_kv_len(const pgv_kv* kv, int b) { return (kv && b >= 0 && b < kv->B) ? kv->h_len[b] : -1; }
@@ -401,14 +444,16 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
     const int V = m->cfg.vocab;
     PGV_TRY(lm_head(ctx, m, kv, B, !(flags & AM_SAMPLE), s, nparts));
     pgv_prof_begin(ctx, 6, s);
+    const PickLp lp = kv_lp(kv, flags, (flags & AM_SAMPLE) && kv->s_greedy);
+    if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, V, V, B, kv->lp_stat, s));
     if (flags & AM_SAMPLE) {
         SampleWarp w = kv_warp(kv, false);
         w.top_p = kv->s_topp; w.penalty = kv->s_pen;
         PGV_TRY(pgv_launch_sample(kv->logits, V, B, kv->s_temp, kv->s_topk, kv->d_u, B, 1, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
-                                  eos, flags & (AM_INC_POS | AM_RECORD), s, &w));
+                                  eos, flags & (AM_INC_POS | AM_RECORD), s, &w, &lp));
     } else
         PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (V + 15) / 16, kv->amax_ts, V, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, eos,
-                                        flags, s));
+                                        flags, s, kv->logits, &lp));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     return PGV_OK;
 }
@@ -579,11 +624,14 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
         PGV_TRY(lm_head(ctx, m, kv, B, true, s, nparts));           // the greedy candidates too: the same launch as a plain prefill, same logits
         pgv_prof_begin(ctx, 6, s);
         const SampleWarp w = kv_warp(kv, d_u == nullptr, d_slots);
-        if (d_u) PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, temperature, top_k, d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w));
+        const PickLp lp = kv_lp(kv, 0, d_u == nullptr, d_slots);      // the pick runs in scratch rows [0, B): its values land at the slots
+        if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, vocab, vocab, B, kv->lp_stat, s));
+        if (d_u) PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, temperature, top_k, d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w, &lp));
         else if (kv->w_pen != 1.f) {        // greedy under a penalty: the pick over the penalised logits with top_k = 1, u = 0 (first index on ties, as the argmax)
             PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)B * 4, s));
-            PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, 1.f, 1, kv->d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w));
-        } else PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (vocab + 15) / 16, kv->amax_ts, vocab, B, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s));
+            PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, 1.f, 1, kv->d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w, &lp));
+        } else PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (vocab + 15) / 16, kv->amax_ts, vocab, B, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s,
+                                               kv->logits, &lp));
         PGV_TRY(pgv_launch_slot_scatter(d_slots, d_pick, d_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
         pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
@@ -705,11 +753,11 @@ constexpr int kGraphSteps = 8;
 
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s) {
     const int B = kv->active;
-    if (kv->g_B != B || kv->g_eos != eos || kv->g_flags != flags || kv->g_gen != m->generation ||
-        ((flags & AM_SAMPLE) && (kv->g_temp != kv->s_temp || kv->g_topk != kv->s_topk || kv->g_topp != kv->s_topp || kv->g_pen != kv->s_pen))) {
+    if (kv->g_B != B || kv->g_eos != eos || kv->g_flags != flags || kv->g_lp != (int)kv->lp_on || kv->g_gen != m->generation ||
+        ((flags & AM_SAMPLE) && (kv->g_temp != kv->s_temp || kv->g_topk != kv->s_topk || kv->g_topp != kv->s_topp || kv->g_pen != kv->s_pen || kv->g_greedy != (int)kv->s_greedy))) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->g_B = B; kv->g_eos = eos; kv->g_flags = flags; kv->g_gen = m->generation; kv->g_temp = kv->s_temp; kv->g_topk = kv->s_topk;
-        kv->g_topp = kv->s_topp; kv->g_pen = kv->s_pen;
+        kv->g_topp = kv->s_topp; kv->g_pen = kv->s_pen; kv->g_lp = kv->lp_on; kv->g_greedy = kv->s_greedy;
     }
     if (!kv->gexec[which]) {
         // capture on a library-owned stream (the caller's may be the legacy default stream, which cannot be
@@ -784,10 +832,11 @@ extern "C" int pgv_llm_decode_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
         // greedy under a repetition penalty (pgv_kv_set_warpers): the argmax candidates of lm_head know no penalty, so the steps run the sampled
         // pick over the penalised logits with top_k = 1 and u = 0 -- the largest value, the first index on ties
         PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)n * B * 4, s));
-        kv->s_temp = 1.f; kv->s_topk = 1; kv->s_topp = 1.f; kv->s_pen = kv->w_pen;
+        kv->s_temp = 1.f; kv->s_topk = 1; kv->s_topp = 1.f; kv->s_pen = kv->w_pen; kv->s_greedy = true;
         PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | AM_SAMPLE, n, s));
     } else
     PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD, n, s));
+    kv->lp_steps = kv->lp_on ? n : -1;
     PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
@@ -800,8 +849,27 @@ extern "C" int pgv_llm_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, float temper
     hipStream_t s = (hipStream_t)stream;
     const int B = kv->active;
     const SampleWarp w = kv_warp(kv, false);
+    const PickLp lp = kv_lp(kv, 0, false);
+    if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, m->cfg.vocab, m->cfg.vocab, B, kv->lp_stat, s));
     PGV_TRY(pgv_launch_sample(kv->logits, m->cfg.vocab, B, temperature, top_k, d_u, B, 0, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
-                              -1, 0, s, &w));
+                              -1, 0, s, &w, &lp));
+    if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+extern "C" int pgv_llm_pick_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int32_t* d_next, void* stream) {
+    PGV_CHECK(ctx != nullptr, "pgv_llm_pick_greedy: null argument");
+    PGV_CHECK(m && kv && kv->llm == m, "pgv_llm_pick_greedy: bad model / cache");
+    if (kv->active < 1) { pgv_set_error("pgv_llm_pick_greedy: no prefilled sequences in this cache"); return PGV_ESTATE; }
+    hipStream_t s = (hipStream_t)stream;
+    const int B = kv->active;
+    // the pick over the penalised logits with top_k = 1 and u = 0: the largest value, the first index on ties (as pgv_llm_decode_greedy steps)
+    PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)B * 4, s));
+    const SampleWarp w = kv_warp(kv, true);
+    const PickLp lp = kv_lp(kv, 0, true);
+    if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, m->cfg.vocab, m->cfg.vocab, B, kv->lp_stat, s));
+    PGV_TRY(pgv_launch_sample(kv->logits, m->cfg.vocab, B, 1.f, 1, kv->d_u, B, 0, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, -1, 0, s, &w, &lp));
     if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
@@ -818,8 +886,9 @@ extern "C" int pgv_llm_decode_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     if (d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
     PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)n * B * 4, hipMemcpyDeviceToDevice, s));     // n <= max_seq (check_decode)
-    kv->s_temp = temperature; kv->s_topk = top_k; kv->s_topp = kv->w_topp; kv->s_pen = kv->w_pen;
+    kv->s_temp = temperature; kv->s_topk = top_k; kv->s_topp = kv->w_topp; kv->s_pen = kv->w_pen; kv->s_greedy = false;
     PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | AM_SAMPLE, n, s));
+    kv->lp_steps = kv->lp_on ? n : -1;
     PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;

@@ -50,13 +50,28 @@ struct SampleWarp {
     const int* seen_ids = nullptr; int seen_stride = 0; const int* seen_lens = nullptr;
     int* kept = nullptr;
 };
+// Log-probabilities of the token a pick returns (pgv_kv_set_logprobs; null `stat`: none).  stat [B][2] = (maximum, ln of the sum of exp(x - maximum))
+// of every raw logit row, written by pgv_launch_row_lse in front of the pick.  Row b's two values -- `model`: x[t] - logsumexp(x); `pick`: the log of
+// the probability the pick used -- go to index slot[b] (null: b) of last_model / last_pick (each may be null) and, when the pick records
+// (AM_RECORD), to hist_model / hist_pick [b * hist_stride + step[b]], next to the token history.  A sticky EOS step (the done flag was set before
+// the pick) stores 0 for both.  greedy: the pick is the arg-max of the penalised logits (top_k = 1, u = 0, temperature 1) and its value their
+// log-softmax over the WHOLE vocabulary, as HF's greedy loop has it -- without a penalty that is `model`, the same float.
+struct PickLp {
+    const float* stat = nullptr;
+    float *last_model = nullptr, *last_pick = nullptr;
+    float *hist_model = nullptr, *hist_pick = nullptr; int hist_stride = 0;
+    const int* slot = nullptr;
+    int greedy = 0;
+};
 int pgv_check_warpers(const char* who, float top_p, float penalty);
 int pgv_launch_sample(const float* logits, int V, int B, float temperature, int top_k, const float* u, int u_stride, int u_by_step, int* next, int* pos,
-                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp = nullptr);
+                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp = nullptr,
+                      const PickLp* lp = nullptr);
 // prefill: ids [M] of B sequences (row ranges cu [B + 1]) -> bitmap of slot slots[b] (null: b); clear = start from an empty set
 int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s);
+// logits [B, V] (row stride V) + lp: also store the log-probability of the pick (both values are `model`: a plain arg-max has no processor)
 int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, int* next, int* pos, int* step, int* hist, int hist_stride, int* done,
-                            int eos, int advance, hipStream_t s);
+                            int eos, int advance, hipStream_t s, const float* logits = nullptr, const PickLp* lp = nullptr);
 // pgv_llm_prefill_slots: sequence i of the call becomes slot slots[i] -- cur = pick[i], pos = lens[i], step = done = 0
 int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, int n, int* cur, int* pos, int* step, int* done, hipStream_t s);
 
@@ -64,6 +79,9 @@ int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, 
 // out_rows[r] (null: r).  Timed under family 6.
 int pgv_launch_logprob_rows(pgv_ctx* ctx, const float* logits, int ld, int V, int R, const int* targets, const int* out_rows, float* logprob, float* lse,
                             int* argmax, hipStream_t s);
+// its sibling in front of a pick (PickLp::stat): stat[r] = (maximum, ln sum exp(x - maximum)) over columns [0, V) of row r, in logprob_rows' reduction
+// order -- (x[t] - stat[r][0]) - stat[r][1] is bit for bit its logprob.  Any ld >= V and any 4-byte alignment (the decode logits are vocab floats apart).
+int pgv_launch_row_lse(const float* logits, int ld, int V, int R, float* stat, hipStream_t s);
 
 #if defined(__HIPCC__)
 // sum over each aligned group of 16 lanes with DPP (VALU latency) instead of ds_bpermute shuffles (LDS crossbar latency):

@@ -1,9 +1,21 @@
 // LLaMA decoder, token pick on the device: greedy (argmax over the lm_head GEMV's per-workgroup candidates) and the reference's sampling mode
 // (temperature, top-k 50, multinomial: video_chatgpt/inference.py:106-112 -> HF generation/logits_process.py:238-302,542-593), plus the
 // per-sequence bookkeeping (position, step, token history, EOS stickiness) that keeps a token step's kernel arguments constant.
+#include <type_traits>
+
 #include "llm_internal.h"
 
 namespace {
+
+__device__ __forceinline__ void lp_store(const PickLp& lp, int b, int step, int advance, float model, float pick) {
+    const int o = lp.slot ? lp.slot[b] : b;
+    if (lp.last_model) lp.last_model[o] = model;
+    if (lp.last_pick) lp.last_pick[o] = pick;
+    if (advance & 2) {
+        lp.hist_model[(size_t)b * lp.hist_stride + step] = model;
+        lp.hist_pick[(size_t)b * lp.hist_stride + step] = pick;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // greedy pick (first index wins ties, like torch.argmax on CPU) + bookkeeping: advance bit 0 does pos[b]++, bit 1 does
@@ -11,9 +23,12 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // greedy pick from the lm_head GEMV's per-workgroup candidates (GemvArgs::amax_*): same result as a scan of the full logits
 // (largest value, smallest index on ties, NaN never), 16x fewer values to scan.
-__global__ __launch_bounds__(256) void argmax_parts_kernel(const float* __restrict__ val, const int* __restrict__ idx, int nblk, int amax_ts, int V, int* __restrict__ next,
-                                                           int* __restrict__ pos, int* __restrict__ step, int* __restrict__ hist, int hist_stride,
-                                                           int* __restrict__ done, int eos, int advance) {
+// LP (pgv_kv_set_logprobs, argmax_parts_lp_kernel): thread 0 also stores x[tok] - logsumexp(x) from the row statistics of row_lse_kernel (PickLp), as
+// both values.  argmax_parts_kernel keeps the argument record and the code it has always had.
+template <bool LP>
+__device__ __forceinline__ void argmax_parts_body(const float* __restrict__ val, const int* __restrict__ idx, int nblk, int amax_ts, int V, int* __restrict__ next,
+                                                  int* __restrict__ pos, int* __restrict__ step, int* __restrict__ hist, int hist_stride,
+                                                  int* __restrict__ done, int eos, int advance, const float* __restrict__ logits, const PickLp& lp) {
     __shared__ float sv[4];
     __shared__ int si[4];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -37,6 +52,11 @@ __global__ __launch_bounds__(256) void argmax_parts_kernel(const float* __restri
         for (int i = 1; i < 4; ++i)
             if (sv[i] > best || (sv[i] == best && si[i] < bi)) { best = sv[i]; bi = si[i]; }
         int tok = bi < V ? bi : 0;
+        [[maybe_unused]] int lp_step = 0;
+        [[maybe_unused]] bool lp_sticky = false;               // the state BEFORE this pick: the step that emits EOS still carries its values
+        if constexpr (LP) {
+            if (advance & 2) { lp_step = step[b]; lp_sticky = done[b] != 0; }
+        }
         // flags (llm.hip AM_*): 1 = advance the position, 2 = record (token history + EOS stickiness).  A plain pgv_llm_decode step passes 1
         // only: it must neither append to the history nor look at a `done` flag a previous decode_greedy / decode_sample run left set
         // (tok = eos = -1 would index embed[-H] on the next step).
@@ -48,7 +68,23 @@ __global__ __launch_bounds__(256) void argmax_parts_kernel(const float* __restri
         }
         if (advance & 1) pos[b] += 1;
         next[b] = tok;
+        if constexpr (LP) {
+            const float v = lp_sticky ? 0.f : (logits[(size_t)b * V + tok] - lp.stat[2 * b]) - lp.stat[2 * b + 1];
+            lp_store(lp, b, lp_step, advance, v, v);
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void argmax_parts_kernel(const float* __restrict__ val, const int* __restrict__ idx, int nblk, int amax_ts, int V, int* __restrict__ next,
+                                                           int* __restrict__ pos, int* __restrict__ step, int* __restrict__ hist, int hist_stride,
+                                                           int* __restrict__ done, int eos, int advance) {
+    argmax_parts_body<false>(val, idx, nblk, amax_ts, V, next, pos, step, hist, hist_stride, done, eos, advance, nullptr, PickLp{});
+}
+
+__global__ __launch_bounds__(256) void argmax_parts_lp_kernel(const float* __restrict__ val, const int* __restrict__ idx, int nblk, int amax_ts, int V, int* __restrict__ next,
+                                                              int* __restrict__ pos, int* __restrict__ step, int* __restrict__ hist, int hist_stride,
+                                                              int* __restrict__ done, int eos, int advance, const float* __restrict__ logits, PickLp lp) {
+    argmax_parts_body<true>(val, idx, nblk, amax_ts, V, next, pos, step, hist, hist_stride, done, eos, advance, logits, lp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -75,6 +111,14 @@ __global__ __launch_bounds__(256) void argmax_parts_kernel(const float* __restri
 //    the top-k mask (k plus ties) are first compacted into LDS and the four passes walk that list; the whole-vocabulary case walks the
 //    logits, adding a wave's weights with ONE atomic when all its lanes fall into the same bin (the two leading bytes nearly always).
 // sample_kernel<false> is the kernel as it was: with top_p >= 1 and penalty == 1 that is the one launched.
+//
+// sample_kernel<true, true> (pgv_kv_set_logprobs) also stores the two log-probabilities of the token it returns (PickLp):
+//  * pick = (x'[t] - M) / T - ln S: the lane that holds the chosen entry has its (penalised) logit x', thread 0 publishes the total S of the kept
+//    weights through LDS.  From the logit, not as the log of the rounded weight.
+//  * greedy under a penalty: S is the sum over the WHOLE vocabulary of the penalised weights instead (one more pass, fixed order), not the sum
+//    above the top-1 threshold -- HF's greedy loop normalises the processed scores over everything.  Without a penalty the value is `model`.
+//  * model = (x[t] - max x) - ln sum exp(x - max x) on the raw logits, the two statistics taken from row_lse_kernel (score.hip).
+// The seen-set it reads is the LDS copy made before the pick; the bit of the returned token is set in global memory afterwards.
 // ---------------------------------------------------------------------------------------------
 struct SampleArgs {
     const float* logits; int V;
@@ -84,6 +128,7 @@ struct SampleArgs {
     int* next; int* pos; int* step; int* hist; int hist_stride; int* done; int eos; int advance;
     SampleWarp w;            // sample_kernel<true> only
 };
+struct SampleArgsLp : SampleArgs { PickLp lp; };     // sample_kernel<true, true>: the other two keep the argument record they have always had
 
 __device__ __forceinline__ unsigned float_key(float x) {          // larger float <-> larger key; NaN -> 0 (below every number)
     if (x != x) return 0u;
@@ -97,8 +142,10 @@ constexpr float SAMPLE_FX = 1099511627776.f;     // 2^40: fixed-point scale of a
 
 __device__ __forceinline__ unsigned long long weight_fx(float e) { return e > 0.f ? (unsigned long long)(e * SAMPLE_FX) : 0ull; }     // NaN -> 0
 
-template <bool WARP>
-__global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
+template <bool WARP, bool LP = false>
+__global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, SampleArgsLp, SampleArgs> p) {
+    static_assert(WARP || !LP, "the log-probability form is built on the kernel with both processors");
+    __shared__ float lp_red[LP ? 17 : 1];      // LP: the 16 wave totals of the whole-vocabulary sum, then the total the pick value is normalised by
     __shared__ int hist[256];
     __shared__ unsigned sbits[WARP ? 16 * 64 * SAMPLE_MAXR / 32 : 1];      // seen-set of the row
     __shared__ unsigned long long mass[WARP ? 256 : 1];
@@ -277,6 +324,22 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
         const unsigned key = float_key(x);
         return (key >= thr && key != 0u) ? __builtin_amdgcn_exp2f((x - M) * p.c) : 0.f;
     };
+    [[maybe_unused]] bool lp_whole = false;
+    if constexpr (LP) {
+        lp_whole = p.lp.greedy && pen_on;
+        if (lp_whole) {        // whole-vocabulary sum of the penalised weights (NaN: weight 0): lane, wave, then the 16 wave totals in order
+            float a = 0.f;
+            for (int r = 0; r < rounds; ++r) {
+                const int i = base + r * 64 + lane;
+                if (i < V) {
+                    const float x = load(i);
+                    a += x == x ? __builtin_amdgcn_exp2f((x - M) * p.c) : 0.f;
+                }
+            }
+            a = wave_sum(a);
+            if (lane == 0) lp_red[w] = a;
+        }
+    }
     int nkept = 0;
     for (int r = 0; r < rounds; ++r) {
         const float e = weight(base + r * 64 + lane);
@@ -297,6 +360,11 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
         for (int i = 0; i < 16; ++i) S += Wt[i];
         if constexpr (WARP) {
             if (p.w.kept) { int n = 0; for (int i = 0; i < 16; ++i) n += kc[i]; p.w.kept[b] = n; }
+        }
+        if constexpr (LP) {
+            float G = S;
+            if (lp_whole) { G = 0.f; for (int i = 0; i < 16; ++i) G += lp_red[i]; }
+            lp_red[16] = G;
         }
         const float uu = p.u[(size_t)(p.u_by_step ? p.step[b] : 0) * p.u_stride + b];
         float T = uu * S;
@@ -330,8 +398,15 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
     int sl = 0;
     if (hit != 0ull && !sel_i[3]) sl = __builtin_ctzll(hit);
     else if (any != 0ull) sl = 63 - __builtin_clzll(any);
+    [[maybe_unused]] float lp_x = 0.f;                       // the (penalised) logit of the chosen entry
+    if constexpr (LP) lp_x = __shfl(i0 + lane < V ? load(i0 + lane) : 0.f, sl, 64);
     if (lane == 0) {
         int tok = (any != 0ull) ? i0 + sl : 0;               // all-NaN / empty rows: token 0 rather than an out-of-range id
+        [[maybe_unused]] int lp_step = 0;
+        [[maybe_unused]] bool lp_sticky = false;              // the state BEFORE this pick: the step that emits EOS still carries its values
+        if constexpr (LP) {
+            if (p.advance & 2) { lp_step = p.step[b]; lp_sticky = p.done[b] != 0; }
+        }
         if (p.advance & 2) {                                  // AM_RECORD (see argmax_parts_kernel)
             if (p.done[b]) tok = p.eos;
             else if (p.eos >= 0 && tok == p.eos) p.done[b] = 1;
@@ -340,6 +415,15 @@ __global__ __launch_bounds__(1024) void sample_kernel(SampleArgs p) {
         }
         if (p.advance & 1) p.pos[b] += 1;
         p.next[b] = tok;
+        if constexpr (LP) {
+            float model = 0.f, pick = 0.f;
+            if (!lp_sticky) {
+                model = (lg[tok] - p.lp.stat[2 * b]) - p.lp.stat[2 * b + 1];
+                pick = ((lp_x - M) * p.c - __builtin_amdgcn_logf(lp_red[16])) * 0.6931471805599453f;        // v_log_f32 is log2; c = log2(e) / T
+                if (p.lp.greedy && !pen_on) pick = model;
+            }
+            lp_store(p.lp, b, lp_step, p.advance, model, pick);
+        }
         if constexpr (WARP) {                                 // the returned token joins the slot's seen-set (one workgroup per slot: a plain update)
             if (p.w.seen_bits && tok >= 0 && tok < V) p.w.seen_bits[(size_t)slot * p.w.seen_words + (tok >> 5)] |= 1u << (tok & 31);
         }
@@ -386,9 +470,19 @@ int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, 
     return PGV_OK;
 }
 
+static int check_lp(const char* who, const PickLp& lp, int advance) {
+    PGV_CHECK(!(advance & AM_RECORD) || (lp.hist_model && lp.hist_pick && lp.hist_stride > 0), "%s: a recording pick needs the log-probability history", who);
+    return PGV_OK;
+}
+
 int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, int* next, int* pos, int* step, int* hist, int hist_stride, int* done,
-                            int eos, int advance, hipStream_t s) {
-    hipLaunchKernelGGL(argmax_parts_kernel, dim3(B), dim3(256), 0, s, val, idx, nblk, amax_ts, V, next, pos, step, hist, hist_stride, done, eos, advance);
+                            int eos, int advance, hipStream_t s, const float* logits, const PickLp* lp) {
+    if (lp && lp->stat) {
+        PGV_CHECK(logits != nullptr, "argmax: the log-probabilities need the logits");
+        PGV_TRY(check_lp("argmax", *lp, advance));
+        hipLaunchKernelGGL(argmax_parts_lp_kernel, dim3(B), dim3(256), 0, s, val, idx, nblk, amax_ts, V, next, pos, step, hist, hist_stride, done, eos, advance, logits, *lp);
+    } else
+        hipLaunchKernelGGL(argmax_parts_kernel, dim3(B), dim3(256), 0, s, val, idx, nblk, amax_ts, V, next, pos, step, hist, hist_stride, done, eos, advance);
     return PGV_OK;
 }
 
@@ -406,20 +500,26 @@ int pgv_check_warpers(const char* who, float top_p, float penalty) {
 }
 
 int pgv_launch_sample(const float* logits, int V, int B, float temperature, int top_k, const float* u, int u_stride, int u_by_step, int* next, int* pos,
-                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp) {
+                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp, const PickLp* lp) {
     PGV_CHECK(V >= 1 && V <= 16 * 64 * SAMPLE_MAXR, "sample: vocabulary %d outside [1, %d]", V, 16 * 64 * SAMPLE_MAXR);
     PGV_CHECK(temperature > 0.f, "sample: temperature must be positive (got %g); use the greedy path for temperature 0", (double)temperature);
-    SampleArgs a;
+    SampleArgsLp a;
+    const SampleArgs& plain = a;      // what the two kernels without log-probabilities take
     a.logits = logits; a.V = V; a.c = 1.4426950408889634f / temperature; a.top_k = top_k; a.u = u; a.u_stride = u_stride; a.u_by_step = u_by_step;
     a.next = next; a.pos = pos; a.step = step; a.hist = hist; a.hist_stride = hist_stride; a.done = done; a.eos = eos; a.advance = advance;
     a.w = warp ? *warp : SampleWarp{};
+    a.lp = (lp && lp->stat) ? *lp : PickLp{};
+    if (a.lp.stat) PGV_TRY(check_lp("sample", a.lp, advance));
     // the neutral values run the kernel without the two extra processors: bit for bit the tokens of the temperature / top-k chain alone
     if (warp && (warp->top_p < 1.f || warp->penalty != 1.f || warp->kept)) {
         PGV_TRY(pgv_check_warpers("sample", warp->top_p, warp->penalty));
         PGV_CHECK(warp->seen_bits == nullptr || warp->seen_words * 32 >= V, "sample: seen-set bitmap of %d words for a vocabulary of %d", warp->seen_words, V);
-        hipLaunchKernelGGL(sample_kernel<true>, dim3(B), dim3(1024), 0, s, a);
+        if (a.lp.stat) hipLaunchKernelGGL((sample_kernel<true, true>), dim3(B), dim3(1024), 0, s, a);
+        else hipLaunchKernelGGL(sample_kernel<true>, dim3(B), dim3(1024), 0, s, plain);
+    } else if (a.lp.stat) {        // neutral processors: the same weights, total and token as sample_kernel<false>
+        hipLaunchKernelGGL((sample_kernel<true, true>), dim3(B), dim3(1024), 0, s, a);
     } else {
-        hipLaunchKernelGGL(sample_kernel<false>, dim3(B), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL(sample_kernel<false>, dim3(B), dim3(1024), 0, s, plain);
     }
     return PGV_OK;
 }
@@ -434,6 +534,31 @@ extern "C" int pgv_sample_logits_ex(pgv_ctx* ctx, const float* d_logits, int V, 
     w.top_p = top_p; w.penalty = repetition_penalty; w.seen_ids = d_seen_ids; w.seen_stride = seen_stride; w.seen_lens = d_seen_lens; w.kept = d_kept;
     PGV_TRY(pgv_launch_sample(d_logits, V, B, temperature, top_k, d_u, B, 0, d_next, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, (hipStream_t)stream, &w));
     PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+extern "C" int pgv_sample_logits_lp(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                                    const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u, int32_t* d_next, int32_t* d_kept,
+                                    int greedy, float* d_lp_model, float* d_lp_pick, void* stream) {
+    PGV_CHECK(ctx && d_logits && (d_u || greedy) && d_next && B >= 1, "pgv_sample_logits_lp: bad arguments");
+    PGV_CHECK((d_seen_ids == nullptr) == (d_seen_lens == nullptr) && seen_stride >= 0, "pgv_sample_logits_lp: d_seen_ids and d_seen_lens go together");
+    if (greedy) { temperature = 1.f; top_k = 1; top_p = 1.f; }
+    PGV_TRY(pgv_check_warpers("pgv_sample_logits_lp", top_p, repetition_penalty));
+    hipStream_t s = (hipStream_t)stream;
+    // row statistics [B][2] and, for the greedy form, B uniforms of 0 (top_k = 1, u = 0: the first index of the largest penalised logit)
+    PGV_TRY(pgv_ws_reserve(ctx, 2 * pgv_align((size_t)B * 8), s));
+    float* stat = (float*)pgv_ws_alloc(ctx, (size_t)B * 8);
+    float* zero = (float*)pgv_ws_alloc(ctx, (size_t)B * 4);
+    PGV_CHECK(stat && zero, "pgv_sample_logits_lp: workspace exhausted");
+    if (greedy) PGV_HIP(hipMemsetAsync(zero, 0, (size_t)B * 4, s));
+    PGV_TRY(pgv_launch_row_lse(d_logits, V, V, B, stat, s));
+    SampleWarp w;
+    w.top_p = top_p; w.penalty = repetition_penalty; w.seen_ids = d_seen_ids; w.seen_stride = seen_stride; w.seen_lens = d_seen_lens; w.kept = d_kept;
+    PickLp lp;
+    lp.stat = stat; lp.last_model = d_lp_model; lp.last_pick = d_lp_pick; lp.greedy = greedy != 0;
+    PGV_TRY(pgv_launch_sample(d_logits, V, B, temperature, top_k, greedy ? zero : d_u, B, 0, d_next, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w, &lp));
+    PGV_HIP(hipGetLastError());
+    PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
 }
 

@@ -82,7 +82,63 @@ __global__ __launch_bounds__(256) void logprob_rows_kernel(LogprobArgs p) {
     }
 }
 
+// The sibling that runs in front of a token pick (pgv_kv_set_logprobs): the row's maximum and ln sum exp(x - maximum), for the pick kernel to turn
+// into x[t] - logsumexp(x) once it knows t.  Same two passes, same lane -> column map and the same reduction trees as logprob_rows_kernel, so the value
+// is bit for bit what that kernel gives for the same row and token; but the rows of the decode logits are `vocab` floats apart (32003: odd), so
+// every column is one guarded 4-byte load (a lane's four loads hit the same 16 bytes; the row is served from L2 right behind the lm_head GEMV).
+__global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ logits, int ld, int V, float* __restrict__ stat) {
+    __shared__ float s_val[4];
+    __shared__ float s_sum[4];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nv = (V + 3) >> 2;
+    const float* lg = logits + (size_t)r * ld;
+    float best = -INFINITY;
+    for (int q = tid; q < nv; q += 256) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * q + e;
+            const float x = c < V ? lg[c] : -INFINITY;
+            if (x > best) best = x;                        // NaN never wins
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        if (ov > best) best = ov;
+    }
+    if (lane == 0) s_val[w] = best;
+    __syncthreads();
+    float M = s_val[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (s_val[i] > M) M = s_val[i];
+    float sum = 0.f;
+    for (int q = tid; q < nv; q += 256) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = 4 * q + e;
+            const float t = __builtin_amdgcn_exp2f(((c < V ? lg[c] : 0.f) - M) * 1.4426950408889634f);
+            sum += c < V ? t : 0.f;
+        }
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) s_sum[w] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        const float total = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
+        stat[2 * r] = M;
+        stat[2 * r + 1] = __builtin_amdgcn_logf(total) * 0.6931471805599453f;
+    }
+}
+
 }  // namespace
+
+int pgv_launch_row_lse(const float* logits, int ld, int V, int R, float* stat, hipStream_t s) {
+    PGV_CHECK(logits && stat && V >= 1 && ld >= V && R >= 1, "row_lse: bad arguments");
+    hipLaunchKernelGGL(row_lse_kernel, dim3(R), dim3(256), 0, s, logits, ld, V, stat);
+    return PGV_OK;
+}
 
 int pgv_launch_logprob_rows(pgv_ctx* ctx, const float* logits, int ld, int V, int R, const int* targets, const int* out_rows, float* logprob, float* lse,
                             int* argmax, hipStream_t s) {

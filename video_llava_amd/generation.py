@@ -10,7 +10,8 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Any, Dict, Optional, Tuple
+from dataclasses import dataclass
+from typing import Any, Dict, Optional, Sequence, Tuple
 
 GENERATION_CONFIG_NAME = "generation_config.json"
 
@@ -90,7 +91,8 @@ def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: s
                              f"implemented: temperature, top_k, top_p, repetition_penalty")
     for name in ("output_scores", "output_attentions", "output_hidden_states", "return_dict_in_generate"):
         if kwargs.get(name):
-            raise ValueError(f"{who}: argument `{name}`={kwargs[name]!r} is not implemented by this package (generate() returns the ids only)")
+            raise ValueError(f"{who}: argument `{name}`={kwargs[name]!r} is not implemented by this package (generate() returns the ids only; "
+                             f"`output_logprobs=True` adds the per-token log-probabilities, HF's compute_transition_scores)")
     mask = kwargs.get("attention_mask")
     if mask is not None:
         import torch
@@ -115,3 +117,32 @@ def resolve_sampling(temperature=None, top_k=None, top_p=None, repetition_penalt
     if not r > 0.0:
         raise ValueError(f"`penalty` has to be a strictly positive float, but is {r}")
     return t, k, p, r
+
+
+@dataclass
+class GenerateLogprobsOutput:
+    """What `generate(..., output_logprobs=True)` returns.  sequences: exactly what generate() returns without the keyword.  token_logprobs /
+    transition_scores: fp32 [B, n_new] on the host, entry i belongs to new token i of the sequence -- the `model` / `pick` values of pgv.h
+    (pgv_kv_set_logprobs): HF's compute_transition_scores(sequences, logits / scores, normalize_logits=True).  Both are cut exactly where the ids
+    are cut (EOS, stop strings, stopping criteria, budget) and are 0 beyond a sequence's end.  sequence_logprob: fp64 [B], the sums of
+    token_logprobs."""
+    sequences: Any
+    token_logprobs: Any
+    transition_scores: Any
+    sequence_logprob: Any
+
+    @classmethod
+    def assemble(cls, sequences, n_kept: Sequence[int], model_rows: Sequence, pick_rows: Sequence) -> "GenerateLogprobsOutput":
+        """n_kept[b]: new tokens sequence b kept; model_rows[b] / pick_rows[b]: the values of every token the device emitted for it, in
+        generation order (at least n_kept[b] of them; the surplus past a cut is dropped)."""
+        import numpy as np
+        import torch
+        B, width = len(n_kept), max([int(n) for n in n_kept], default=0)
+        out = np.zeros((2, B, width), dtype=np.float32)
+        for b, n in enumerate(n_kept):
+            for k, rows in enumerate((model_rows, pick_rows)):
+                row = np.asarray(rows[b], dtype=np.float32).reshape(-1)
+                if row.size < n:
+                    raise ValueError(f"sequence {b} kept {n} tokens but has {row.size} log-probabilities")
+                out[k, b, :n] = row[:n]
+        return cls(sequences, torch.from_numpy(out[0]), torch.from_numpy(out[1]), torch.from_numpy(out[0].astype(np.float64).sum(axis=1)))

@@ -141,24 +141,33 @@ def video_features_batch(clips, vision_tower, image_processor, timings=None):
     return out
 
 
-def video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
-                            transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, **generate_kwargs):
-    """`video_chatgpt_infer` up to (not including) the detokenisation: -> (generated token ids [n] as a list, stop string).  The runners'
-    sampling path collates these ids through the same fixed-shape all-gather as the greedy path (parallel.gather_answers) and decodes them
-    on every rank.  `features`: pooled [100 + P, 1024] features computed earlier for this clip (skips the tower).  `generate_kwargs`
-    (top_p, repetition_penalty, ...) go to model.generate as they are."""
+def _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len, transcript, do_sample,
+                    temperature, max_new_tokens, features, generate_kwargs):
+    """The generate() call of `video_chatgpt_infer` -> (what generate returned, its sequences, prompt length, stop string)."""
     prompt, stop_str = build_prompt(question, conv_mode, video_token_len, model.get_model().vision_config.use_vid_start_end, transcript)
     inputs = tokenizer([prompt])
     feats = features if features is not None else video_features(video_frames, vision_tower, image_processor)
     input_ids = torch.as_tensor(inputs.input_ids)
     stopping_criteria = KeywordsStoppingCriteria([stop_str], tokenizer, input_ids)
     with torch.inference_mode():
-        output_ids = model.generate(input_ids, video_spatio_temporal_features=feats.unsqueeze(0), do_sample=do_sample,
-                                    temperature=temperature, max_new_tokens=max_new_tokens, stopping_criteria=[stopping_criteria], **generate_kwargs)
+        out = model.generate(input_ids, video_spatio_temporal_features=feats.unsqueeze(0), do_sample=do_sample,
+                             temperature=temperature, max_new_tokens=max_new_tokens, stopping_criteria=[stopping_criteria], **generate_kwargs)
+    output_ids = out if torch.is_tensor(out) else out.sequences
     n_in = input_ids.shape[1]
     n_diff = int((input_ids.to(output_ids.device) != output_ids[:, :n_in]).sum())
     if n_diff > 0:
         print(f"[Warning] {n_diff} output_ids are not the same as the input_ids")
+    return out, output_ids, n_in, stop_str
+
+
+def video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
+                            transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, **generate_kwargs):
+    """`video_chatgpt_infer` up to (not including) the detokenisation: -> (generated token ids [n] as a list, stop string).  The runners'
+    sampling path collates these ids through the same fixed-shape all-gather as the greedy path (parallel.gather_answers) and decodes them
+    on every rank.  `features`: pooled [100 + P, 1024] features computed earlier for this clip (skips the tower).  `generate_kwargs`
+    (top_p, repetition_penalty, ...) go to model.generate as they are."""
+    _out, output_ids, n_in, stop_str = _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
+                                                       transcript, do_sample, temperature, max_new_tokens, features, generate_kwargs)
     return output_ids[0, n_in:].tolist(), stop_str
 
 
@@ -171,6 +180,22 @@ def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, 
                                                 transcript, do_sample, temperature, max_new_tokens)
     outputs = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0]
     return outputs.strip().rstrip(stop_str).strip()
+
+
+def video_chatgpt_infer_logprobs(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
+                                 transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, **generate_kwargs):
+    """`video_chatgpt_infer` that also says how probable the answer it produced was (model.generate(output_logprobs=True): recorded on the device
+    at pick time, no second prefill).  Returns a dict: "text" (what video_chatgpt_infer returns), "ids" (the generated token ids),
+    "token_logprobs" (per id, the model's own log-probability: HF's compute_transition_scores on the raw logits -- what video_chatgpt_score
+    gives for the same ids), "transition_scores" (per id, the log of the probability the pick used, after repetition penalty / temperature /
+    top-k / top-p) and "logprob" (the fp64 sum of token_logprobs)."""
+    out, output_ids, n_in, stop_str = _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
+                                                      transcript, do_sample, temperature, max_new_tokens, features, dict(generate_kwargs, output_logprobs=True))
+    new_ids = output_ids[0, n_in:].tolist()
+    text = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0].strip().rstrip(stop_str).strip()
+    n = len(new_ids)
+    return {"text": text, "ids": new_ids, "token_logprobs": out.token_logprobs[0, :n].tolist(), "transition_scores": out.transition_scores[0, :n].tolist(),
+            "logprob": float(out.sequence_logprob[0])}
 
 
 def video_chatgpt_score(video_frames, question, answers, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,

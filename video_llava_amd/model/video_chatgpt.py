@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..constants import CLIP_WIDTH
-from ..generation import check_generate_kwargs, load_generation_config, resolve_sampling
+from ..generation import GenerateLogprobsOutput, check_generate_kwargs, load_generation_config, resolve_sampling
 from ..scoring import ScoreOutput, id_rows, shift_labels
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
 from .utils import AnswerState
@@ -364,10 +364,12 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         return proj, proj.shape[1], self._video_positions(seqs, proj.shape[1])
 
     def prefill(self, seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor], max_seq: int,
-                want_logits: bool = False, want_all_logits: bool = False, append_to=None):
+                want_logits: bool = False, want_all_logits: bool = False, append_to=None, logprobs: Optional[bool] = None):
         """Run the prompt(s); returns (kv handle, next-token ids [B] int32 on device, logits [B, vocab] or None) -- with want_all_logits a fourth
         entry: the logits of EVERY position, [sum of lengths, vocab] fp32 (what the reference's forward returns, model/video_chatgpt.py:225-226).
-        `append_to` = a kv handle this model filled before: the rows continue its sequences (pgv_llm_prefill_append; `max_seq` is ignored)."""
+        `append_to` = a kv handle this model filled before: the rows continue its sequences (pgv_llm_prefill_append; `max_seq` is ignored).
+        `logprobs` (True / False): set the cache's log-probability switch (set_logprobs) before the prompt runs, so that the greedy first token is
+        recorded too; None leaves the switch as it is."""
         B = len(seqs)
         lens = [len(s) for s in seqs]
         feats = video_spatio_temporal_features
@@ -382,6 +384,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             self._reuse = None
         else:
             kv = append_to
+        if logprobs is not None:
+            self.set_logprobs(kv, logprobs)
         flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
         h_lens = (C.c_int32 * B)(*lens)
         h_pos = (C.c_int32 * B)(*vid_pos)
@@ -390,11 +394,16 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         ld_all = (self.vocab_size + 15) // 16 * 16
         all_logits = torch.empty(int(flat.size), ld_all, dtype=torch.float32, device=self.device_) if want_all_logits else None
         fn, who = (self.ctx.lib.pgv_llm_prefill, "pgv_llm_prefill") if append_to is None else (self.ctx.lib.pgv_llm_prefill_append, "pgv_llm_prefill_append")
-        _lib.check(fn(self.ctx.handle, self.handle, kv, flat.ctypes.data_as(C.c_void_p), h_lens, B,
-                      proj.data_ptr() if proj is not None else None, V, h_pos,
-                      logits.data_ptr() if logits is not None else None, nxt.data_ptr(),
-                      all_logits.data_ptr() if all_logits is not None else None, ld_all,
-                      _lib.stream_ptr(self.device_)), who)
+        try:
+            _lib.check(fn(self.ctx.handle, self.handle, kv, flat.ctypes.data_as(C.c_void_p), h_lens, B,
+                          proj.data_ptr() if proj is not None else None, V, h_pos,
+                          logits.data_ptr() if logits is not None else None, nxt.data_ptr(),
+                          all_logits.data_ptr() if all_logits is not None else None, ld_all,
+                          _lib.stream_ptr(self.device_)), who)
+        except Exception:
+            if logprobs:
+                self.set_logprobs(kv, False)               # a refused prompt never reaches the caller who would turn the switch off again
+            raise
         if want_all_logits:
             return kv, nxt, logits, all_logits[:, :self.vocab_size]
         return kv, nxt, logits
@@ -470,6 +479,31 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
     def set_warpers(self, kv, top_p: float = 1.0, repetition_penalty: float = 1.0):
         """pgv_kv_set_warpers: HF's TopPLogitsWarper / RepetitionPenaltyLogitsProcessor values for every later pick on this cache."""
         _lib.check(self.ctx.lib.pgv_kv_set_warpers(kv, float(top_p), float(repetition_penalty)), "pgv_kv_set_warpers")
+
+    def set_logprobs(self, kv, on: bool = True):
+        """pgv_kv_set_logprobs: record the two log-probabilities (`model`, `pick`: include/pgv.h) of every later pick on this cache."""
+        _lib.check(self.ctx.lib.pgv_kv_set_logprobs(kv, 1 if on else 0), "pgv_kv_set_logprobs")
+
+    def logprobs_last(self, kv, width: int) -> torch.Tensor:
+        """pgv_kv_logprobs_last: fp32 [2, width] on the device -- row 0 `model`, row 1 `pick` of each slot's most recent pick."""
+        out = torch.empty(2, int(width), dtype=torch.float32, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_kv_logprobs_last(kv, out[0].data_ptr(), out[1].data_ptr(), _lib.stream_ptr(self.device_)), "pgv_kv_logprobs_last")
+        return out
+
+    def logprobs_steps(self, kv, width: int, n: int) -> torch.Tensor:
+        """pgv_kv_logprobs_steps: fp32 [2, width, n] on the device -- the `model` / `pick` values of the n steps of the last decode_greedy /
+        decode_sample call, laid out like its tokens."""
+        out = torch.empty(2, int(width), int(n), dtype=torch.float32, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_kv_logprobs_steps(kv, int(n), out[0].data_ptr(), out[1].data_ptr(), _lib.stream_ptr(self.device_)), "pgv_kv_logprobs_steps")
+        return out
+
+    def greedy_last(self, kv, width: int, repetition_penalty: float = 1.0) -> torch.Tensor:
+        """The greedy pick of every sequence from the logits of the last prefill / decode call, under the repetition penalty
+        (pgv_llm_pick_greedy): what the prefill's own argmax, which knows no penalty, has to be replaced with."""
+        self.set_warpers(kv, 1.0, repetition_penalty)
+        nxt = torch.empty(int(width), dtype=torch.int32, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_llm_pick_greedy(self.ctx.handle, self.handle, kv, nxt.data_ptr(), _lib.stream_ptr(self.device_)), "pgv_llm_pick_greedy")
+        return nxt
 
     def kv_len(self, kv, b: int) -> int:
         return int(self.ctx.lib.pgv_kv_len(kv, int(b)))
@@ -575,8 +609,14 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  temperature: Optional[float] = None, max_new_tokens: int = 1024, stopping_criteria=None, eos_token_id="config",
                  chunk: int = 32, generator: Optional[torch.Generator] = None, top_k: Optional[int] = None,
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
-                 kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, **_unused):
+                 kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
+                 **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
+        `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
+        `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
+        distribution / under the distribution the pick used (HF's compute_transition_scores on `logits` / `scores`, normalize_logits=True), cut
+        where the ids are cut and 0 beyond a sequence's end; `.sequence_logprob` [B] fp64 sums the former.  The values are recorded on the device
+        by the pick kernels inside the decode chunks (pgv_kv_set_logprobs); the ids are those of the call without the keyword, whatever `chunk`.
 
         input_ids: LongTensor [B, S] (equal-length prompts, the reference's case) or a list of id lists (ragged batch).
         Tokens never leave the device inside a chunk of `chunk` steps, in both modes:
@@ -640,6 +680,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         # passed on only when they differ from the neutral values (the step methods default to them)
         warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
         pen = {} if rep_pen == 1.0 else {"repetition_penalty": rep_pen}
+        lpk = {"logprobs": True} if output_logprobs else {}    # the switch is on for this call only (turned off again in the finally below)
         reused = 0
         if kv_reuse_key is not None and B == 1 and rep_pen == 1.0:
             # (under a repetition penalty the slot's seen-set has to be exactly prompt + answer: the surplus steps a kept cache carries past a
@@ -649,75 +690,88 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             kv = self._reuse[1]
             if reused < len(self._reuse[3]):
                 _lib.check(self.ctx.lib.pgv_kv_truncate(kv, 0, reused, _lib.stream_ptr(self.device_)), "pgv_kv_truncate")
-            _kv, nxt, _ = self.prefill([seqs[0][reused:]], None, 0, append_to=kv)
+            _kv, nxt, _ = self.prefill([seqs[0][reused:]], None, 0, append_to=kv, **lpk)
         else:
-            kv, nxt, _ = self.prefill(seqs, video_spatio_temporal_features, max_seq)
-        raw: List[int] = []                                # B == 1: every token the device emitted, stop cuts ignored (= what the cache holds, shifted by one)
-        u = None
-        if do_sample and max_new_tokens >= 1:
-            u = torch.rand(max_new_tokens, B, device=self.device_, dtype=torch.float32, generator=generator)
-            nxt = self.sample_last(kv, u[0], temperature, top_k, **warp)
-        elif rep_pen != 1.0 and max_new_tokens >= 1:
-            # greedy under a penalty: the prefill's argmax knows no penalty -- re-pick over the penalised logits (top_k = 1, u = 0: first index on ties)
-            nxt = self.sample_last(kv, torch.zeros(B, device=self.device_), 1.0, 1, **pen)
-        states = [AnswerState(max_new_tokens, eos_i, stops[b] if stops is not None else None, tokenizer) for b in range(B)]
-        prompt_t = torch.tensor(seqs[0], dtype=torch.long)
+            kv, nxt, _ = self.prefill(seqs, video_spatio_temporal_features, max_seq, **lpk)
+        try:
+            raw: List[int] = []                                # B == 1: every token the device emitted, stop cuts ignored (= what the cache holds, shifted by one)
+            u = None
+            if do_sample and max_new_tokens >= 1:
+                u = torch.rand(max_new_tokens, B, device=self.device_, dtype=torch.float32, generator=generator)
+                nxt = self.sample_last(kv, u[0], temperature, top_k, **warp)
+            elif rep_pen != 1.0 and max_new_tokens >= 1:
+                # greedy under a penalty: the prefill's argmax knows no penalty -- re-pick over the penalised logits (first index on ties)
+                nxt = self.greedy_last(kv, B, **pen)
+            lp_parts = []                                      # output_logprobs: [2, B, steps] blocks in generation order (first token, then every chunk)
+            if output_logprobs and max_new_tokens >= 1:
+                lp_parts.append(self.logprobs_last(kv, B)[:, :, None])
+            states = [AnswerState(max_new_tokens, eos_i, stops[b] if stops is not None else None, tokenizer) for b in range(B)]
+            prompt_t = torch.tensor(seqs[0], dtype=torch.long)
 
-        def criterion_fires() -> bool:
-            """HF: a stopping criterion is asked after every appended token (B == 1)."""
-            cur = torch.cat([prompt_t, torch.tensor(states[0].new, dtype=torch.long)])[None]
-            return any(c(cur, None) for c in criteria)
+            def criterion_fires() -> bool:
+                """HF: a stopping criterion is asked after every appended token (B == 1)."""
+                cur = torch.cat([prompt_t, torch.tensor(states[0].new, dtype=torch.long)])[None]
+                return any(c(cur, None) for c in criteria)
 
-        n_gen = 0
-        _t1 = _t0
-        if max_new_tokens >= 1:
-            first = nxt.cpu().numpy()
-            raw.append(int(first[0]))
-            for b, st in enumerate(states):
-                st.take(first[b:b + 1])
-            stop = all(st.done for st in states) or (bool(criteria) and criterion_fires())
-            _t1 = _time.perf_counter()
-            n_gen = 1
-            while not stop and n_gen < max_new_tokens:
-                n = min(chunk, max_new_tokens - n_gen)
-                if do_sample:
-                    toks = self.decode_sample(kv, nxt, n, eos_i, temperature, top_k, u[n_gen:n_gen + n], **warp)
-                else:
-                    toks = self.decode_greedy(kv, nxt, n, eos_i, **pen)
-                h = toks.cpu().numpy()
-                raw.extend(h[0].tolist())
-                if criteria:
-                    for i in range(n):
-                        stop = states[0].take(h[0, i:i + 1]) or criterion_fires()
-                        n_gen += 1
-                        if stop:
-                            break
-                else:
-                    # per SEQUENCE, not per step (a chunk of 64 steps x 8 sequences cost ~0.6 ms of Python between two decode launches, with the
-                    # GPU idle): AnswerState.take absorbs a live sequence's whole run at once
-                    last = 0
-                    for b, st in enumerate(states):
-                        if not st.done:
-                            st.take(h[b])
-                            last = max(last, st.taken)
-                    stop = all(st.done for st in states)
-                    n_gen += last if stop else n
-                nxt = toks[:, n - 1].contiguous()
-        new = [st.new for st in states]
-        if timings is not None:
-            _t2 = _time.perf_counter()
-            timings.update(prefill_s=_t1 - _t0, decode_s=_t2 - _t1, steps=n_gen, batch=B, reused_tokens=reused)
-        if kv_reuse_key is not None and B == 1:
-            # the cache holds the prompt and every emitted token that was fed back (all but the last one)
-            self._reuse = (kv_reuse_key, kv, max_seq, list(seqs[0]) + raw[:-1])
-            assert self.ctx.lib.pgv_kv_len(kv, 0) == len(self._reuse[3]), (self.ctx.lib.pgv_kv_len(kv, 0), len(self._reuse[3]))
-        width = max(len(s) + len(n_) for s, n_ in zip(seqs, new))
-        pad = eos_i if eos_i >= 0 else 0
-        out = torch.full((B, width), pad, dtype=torch.long)
-        for b in range(B):
-            row = seqs[b] + new[b]
-            out[b, :len(row)] = torch.tensor(row, dtype=torch.long)
-        return out.to(self.device_)
+            n_gen = 0
+            _t1 = _t0
+            if max_new_tokens >= 1:
+                first = nxt.cpu().numpy()
+                raw.append(int(first[0]))
+                for b, st in enumerate(states):
+                    st.take(first[b:b + 1])
+                stop = all(st.done for st in states) or (bool(criteria) and criterion_fires())
+                _t1 = _time.perf_counter()
+                n_gen = 1
+                while not stop and n_gen < max_new_tokens:
+                    n = min(chunk, max_new_tokens - n_gen)
+                    if do_sample:
+                        toks = self.decode_sample(kv, nxt, n, eos_i, temperature, top_k, u[n_gen:n_gen + n], **warp)
+                    else:
+                        toks = self.decode_greedy(kv, nxt, n, eos_i, **pen)
+                    if output_logprobs:
+                        lp_parts.append(self.logprobs_steps(kv, B, n))
+                    h = toks.cpu().numpy()
+                    raw.extend(h[0].tolist())
+                    if criteria:
+                        for i in range(n):
+                            stop = states[0].take(h[0, i:i + 1]) or criterion_fires()
+                            n_gen += 1
+                            if stop:
+                                break
+                    else:
+                        # per SEQUENCE, not per step (a chunk of 64 steps x 8 sequences cost ~0.6 ms of Python between two decode launches, with the
+                        # GPU idle): AnswerState.take absorbs a live sequence's whole run at once
+                        last = 0
+                        for b, st in enumerate(states):
+                            if not st.done:
+                                st.take(h[b])
+                                last = max(last, st.taken)
+                        stop = all(st.done for st in states)
+                        n_gen += last if stop else n
+                    nxt = toks[:, n - 1].contiguous()
+            new = [st.new for st in states]
+            if timings is not None:
+                _t2 = _time.perf_counter()
+                timings.update(prefill_s=_t1 - _t0, decode_s=_t2 - _t1, steps=n_gen, batch=B, reused_tokens=reused)
+            if kv_reuse_key is not None and B == 1:
+                # the cache holds the prompt and every emitted token that was fed back (all but the last one)
+                self._reuse = (kv_reuse_key, kv, max_seq, list(seqs[0]) + raw[:-1])
+                assert self.ctx.lib.pgv_kv_len(kv, 0) == len(self._reuse[3]), (self.ctx.lib.pgv_kv_len(kv, 0), len(self._reuse[3]))
+            width = max(len(s) + len(n_) for s, n_ in zip(seqs, new))
+            pad = eos_i if eos_i >= 0 else 0
+            out = torch.full((B, width), pad, dtype=torch.long)
+            for b in range(B):
+                row = seqs[b] + new[b]
+                out[b, :len(row)] = torch.tensor(row, dtype=torch.long)
+            if output_logprobs:
+                # a sequence's kept ids are a prefix of what the device emitted for it: the same cut applies to the values
+                lp = torch.cat(lp_parts, dim=2).cpu().numpy() if lp_parts else np.zeros((2, B, 0), dtype=np.float32)
+                return GenerateLogprobsOutput.assemble(out.to(self.device_), [len(n_) for n_ in new], lp[0], lp[1])
+            return out.to(self.device_)
+        finally:
+            if output_logprobs:
+                self.set_logprobs(kv, False)                   # also when a criterion, the tokenizer or an interrupt ends the call early
 
 
 def _vision_config_from(mm_vision_tower) -> VisionConfig:
