@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 326
+#define PGV_VERSION 327
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -401,6 +401,49 @@ int pgv_encode_w12_blocked(pgv_ctx *ctx, int dtype, const void *d_w16_blocked, v
  * N = the encoded row count (or fewer, mode 3). */
 int pgv_gemv_w12(pgv_ctx *ctx, int dtype, int mode, const void *d_W12, const void *d_x, int ldx, void *d_out, int ldo, int N, int K, int B,
                  void *stream);
+/* The decode GEMV with every argument of the internal launcher, as a decode step fills it (test entry: same kernels, the launch shape is chosen
+ * exactly as in decode).  Unused pointers are NULL.
+ *  mode      0..3 as pgv_gemv, or 5 = the residual + RMSNorm PRODUCER (o_proj, down_proj): d_out [B][ldo] fp32 residual += y (read-modify-write),
+ *            d_xg = round16(residual * d_gamma[n]) (16-bit, row-major [B][ldo] or blocked, below), d_ssq_out [ct][n / 16][16] = the sum of the
+ *            new residual's squares over each block of 16 rows per sequence (tile stride ssq_ts >= N; the slots of sequences >= B receive 0).
+ *  weights   d_W = 16-bit blocked (pgv_pack_blocked), or the fp8 codes with d_wscale [ceil16(N)] (pgv_quantize_fp8_blocked); d_W12 = the 12-bit
+ *            copy (pgv_encode_w12_blocked; bf16), streamed instead of d_W where the launch has one column tile (d_W may then be NULL).
+ *  consumer  (modes 0, 2, 3 with d_ssq_in): out = (W x) * rsqrt(sum_parts ssq_in / hidden + eps), applied to the fp32 accumulators;
+ *            d_ssq_in [ct][nparts_in][16] with tile stride ssq_ts >= 16 nparts_in, nparts_in <= 384.
+ *  head      (mode 3 with d_amax_val / d_amax_idx [ct][ceil(N / 16)][16], tile stride amax_ts >= 16 ceil(N / 16)): per block of 16 rows and
+ *            sequence the largest logit over rows < N and the smallest row index attaining it (NaN never wins; none: (-inf, 0x7fffffff)).
+ *            Every tile of the launch is written, also those beyond B.
+ *  strides   ssq_ts / amax_ts may be 0 only where the array they stride is NULL (the launcher is then handed the dense strides 16 and
+ *            16 ceil(N / 16), which it requires at B > 16 but never uses); with the array given, the bounds above are checked.
+ *  mode 1    (d_out fp32 += y, no norm field) is accepted for completeness; a decode step no longer runs it (the producer replaced it).
+ *  tiles     ct = 1 / 2 / 4 column tiles of 16 sequences for B <= 16 / 32 / 64; sequence b is entry b % 16 of tile b / 16.
+ *  x_blocked with B > 8 the 16-bit operand between producer and consumer (a consumer's d_x, a producer's d_xg) is in the fragment-blocked
+ *            activation layout [K / 32][ct][4 k-groups][16 sequences][8 elements] (ct * 16 * K elements; ldx is ignored); B <= 8: row-major.
+ *  d_k8_part scratch of the 8-phase form of a producer, (N / 16) * 8 * ct * 1024 bytes, k8_part_bytes = its size; NULL = 16-row kernel only.
+ *  shape     (optional) receives the launch shape that ran: row blocks per workgroup, column tiles, merged x load, 8-phase form and its row
+ *            blocks per workgroup, weight format streamed (0 = 16-bit, 1 = fp8, 2 = 12-bit). */
+typedef struct { int tl, ct, x2, k8, nwb, wfmt; } pgv_gemv_shape;
+typedef struct {
+    int mode;
+    const void *d_W; const float *d_wscale; const void *d_W12;
+    const void *d_x; int ldx;
+    void *d_out; int ldo;
+    int N, K, B;
+    const float *d_ssq_in; int nparts_in; int hidden; float eps;          /* consumer */
+    const float *d_gamma; void *d_xg; float *d_ssq_out;                    /* producer */
+    float *d_amax_val; int *d_amax_idx;                                    /* head */
+    int ssq_ts, amax_ts;
+    void *d_k8_part; size_t k8_part_bytes;
+    int x_blocked;
+    pgv_gemv_shape *shape;
+} pgv_gemv_desc;
+int pgv_gemv_ex(pgv_ctx *ctx, int dtype, const pgv_gemv_desc *desc, void *stream);
+/* The two kernels that start a chain of folded GEMVs (test entry).  d_tok NULL: d_resid [B][H] fp32 is read (the final norm's prep); else
+ * d_resid[b] = d_embed[d_tok[b]] (16-bit table [rows][H]; the ids are not checked) is written.  Both write d_xg = round16(resid * d_gamma)
+ * (row-major [B][H], or blocked as above when x_blocked and B > 8) and d_ssq[(b / 16) * H + b % 16] = sum of resid[b]^2: one partial per
+ * sequence, tile stride H.  H % 32 == 0, 1 <= B <= 64. */
+int pgv_gemv_prep(pgv_ctx *ctx, int dtype, const int32_t *d_tok, const void *d_embed, float *d_resid, const float *d_gamma, void *d_xg,
+                  float *d_ssq, int B, int H, int x_blocked, void *stream);
 /* LLaMA decode attention of one token step on caller buffers: the kernels and launcher pgv_llm_decode runs (RoPE on q and k at h_pos[b], append of
  * the rotated k and of v at row h_pos[b], softmax over cache rows [0, h_pos[b]] with scale 128^-0.5).  `llm` supplies the dtype, head count and
  * RoPE table (no weights need to be loaded).  d_qkv [B, 3H] 16-bit (q | k | v), d_Kc / d_Vc [B, heads, max_seq, 128], d_out [B, H]; rows at

@@ -55,56 +55,19 @@ import numpy as np
 import pytest
 import torch
 
+from bounds import EPS, MANT, U32, UACC, ULP1, hulp, rnd, sigmoid_mul_bound, silu_ref, swiglu_bound
+
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
 NAN = math.nan
-U32 = 2.0 ** -24                                  # one fp32 rounding
-UACC = 2.0 ** -23                                 # per addition of the MFMA accumulation
-ULP1 = 2.0 ** -23                                 # "1 ulp" of v_exp_f32 / v_rcp_f32, relative
-MINN = 2.0 ** -126                                # ... which return 0 where the result would be an fp32 denormal
-MANT = {torch.float16: 10, torch.bfloat16: 7}
-EMIN = {torch.float16: -14, torch.bfloat16: -126}
 DTYPES = [torch.float16, torch.bfloat16]
 DTN = {torch.float16: "f16", torch.bfloat16: "bf16"}
 GUARD = 3                                         # guard rows below M
 NONE, BIAS, QGELU, GELU, RESID, BIAS_RESID, SWIGLU, F32, LN_BIAS, LN_QGELU, LNOUT = range(11)
 EPN = ["NONE", "BIAS", "BIAS_QGELU", "BIAS_GELU", "RESID", "BIAS_RESID", "SWIGLU", "F32", "LN_BIAS", "LN_BIAS_QGELU", "BIAS_RESID_LNOUT"]
 K_QGELU = float(np.float32(-1.702) * np.float32(1.4426950408889634))       # the kernel's -1.702f * 1.4426950408889634f
-K_SILU = float(np.float32(-1.4426950408889634))
 C_ERF = float(np.float32(0.70710678118654752))
-EPS = float(np.float32(1e-5))
-
 WORST = {}                                        # (instance, dtype) -> worst err / bound seen
-
-
-# --------------------------------------------------------------------------------------------------
-# bounds (device-agnostic float64 tensor arithmetic)
-# --------------------------------------------------------------------------------------------------
-def rnd(x, E):
-    """Error bound after one fp32 rounding of a value x known to E."""
-    return E + U32 * (x.abs() + E)
-
-
-def hulp(x, dt):
-    """Half an ulp of `dt` at magnitude x."""
-    _, e = torch.frexp(x.abs().clamp_min(2.0 ** EMIN[dt]))
-    return torch.ldexp(torch.ones_like(x), e - 2 - MANT[dt])
-
-
-def sigmoid_mul_bound(x, E, k):
-    """y = x * rcp(1 + exp2(x * k)) as the kernel evaluates it; returns (y exact with the real constant, bound)."""
-    z = x * k
-    Ez = rnd(z, abs(k) * E)
-    t = torch.exp2(z)
-    thi = t * torch.exp2(Ez)
-    Et = (thi - t) + ULP1 * thi + MINN
-    s = 1.0 + t
-    Es = rnd(s, Et)
-    r = 1.0 / s
-    Er = Es / (s * (s - Es))
-    Er = Er + ULP1 * (r + Er) + MINN
-    y = x * r
-    return y, rnd(y, x.abs() * Er + r * E + E * Er)
 
 
 def quick_gelu_ref(x):
@@ -114,17 +77,6 @@ def quick_gelu_ref(x):
 def quick_gelu_bound(x, E):
     y, Ey = sigmoid_mul_bound(x, E, K_QGELU)
     return Ey + (y - quick_gelu_ref(x)).abs()      # the fp32 constant against the real one: part of the kernel's error
-
-
-def silu_ref(x):
-    return x / (1.0 + torch.exp(-x))
-
-
-def swiglu_bound(g, Eg, u, Eu):
-    y, Ey = sigmoid_mul_bound(g, Eg, K_SILU)
-    Ey = Ey + (y - silu_ref(g)).abs()
-    out = silu_ref(g) * u
-    return rnd(out, u.abs() * Ey + silu_ref(g).abs() * Eu + Ey * Eu)
 
 
 def gelu_ref(x):

@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgv.so")
 
-ABI_VERSION = 326          # PGV_VERSION of include/pgv.h this table was written against
+ABI_VERSION = 327          # PGV_VERSION of include/pgv.h this table was written against
 PGV_OK, PGV_EINVAL, PGV_EHIP, PGV_ENOMEM, PGV_ESTATE, PGV_ENAME = 0, 1, 2, 3, 4, 5
 PGV_F16, PGV_BF16, PGV_F32 = 0, 1, 2
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_GELU, EPI_RESID, EPI_BIAS_RESID, EPI_SWIGLU, EPI_F32 = range(8)
@@ -42,6 +42,19 @@ class GemmDesc(C.Structure):
     _fields_ = [("d_A", _vp), ("lda", _i), ("d_W", _vp), ("ldw", _i), ("w_blocked", _i), ("d_bias", _vp), ("d_C", _vp), ("ldc", _i),
                 ("M", _i), ("N", _i), ("K", _i), ("epi", _i), ("d_rowstat", _vp), ("d_colsum", _vp), ("d_gnext", _vp), ("d_x16", _vp),
                 ("ldx16", _i), ("d_stats_part", _vp), ("d_rowmean", _vp), ("d_cshift", _vp)]
+
+
+class GemvShape(C.Structure):
+    """pgv_gemv_shape of include/pgv.h: the launch shape pgv_gemv_ex ran."""
+    _fields_ = [("tl", _i), ("ct", _i), ("x2", _i), ("k8", _i), ("nwb", _i), ("wfmt", _i)]
+
+
+class GemvDesc(C.Structure):
+    """pgv_gemv_desc of include/pgv.h (pgv_gemv_ex)."""
+    _fields_ = [("mode", _i), ("d_W", _vp), ("d_wscale", _vp), ("d_W12", _vp), ("d_x", _vp), ("ldx", _i), ("d_out", _vp), ("ldo", _i),
+                ("N", _i), ("K", _i), ("B", _i), ("d_ssq_in", _vp), ("nparts_in", _i), ("hidden", _i), ("eps", _f),
+                ("d_gamma", _vp), ("d_xg", _vp), ("d_ssq_out", _vp), ("d_amax_val", _vp), ("d_amax_idx", _vp), ("ssq_ts", _i), ("amax_ts", _i),
+                ("d_k8_part", _vp), ("k8_part_bytes", C.c_size_t), ("x_blocked", _i), ("shape", C.POINTER(GemvShape))]
 
 
 # name -> (restype, argtypes); every symbol declared in include/pgv.h
@@ -109,6 +122,8 @@ PROTOTYPES = {
     "pgv_w12_bytes": (C.c_size_t, [_i, _i]),
     "pgv_encode_w12_blocked": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "pgv_gemv_w12": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "pgv_gemv_ex": (_i, [_vp, _i, C.POINTER(GemvDesc), _vp]),
+    "pgv_gemv_prep": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pgv_llm_get_weight": (_i, [_vp, _vp, C.c_char_p, _vp, _vp]),
     "pgv_decode_attention": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "pgv_prefill_attention": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _i, _vp]),

@@ -995,7 +995,7 @@ static GemvChoice choose_gemv(int mode, bool w8, int B, int grid, int K, int num
 }
 
 int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void* x, int ldx, void* out, int ldo, int N, int K, int B, hipStream_t s,
-                    const float* wscale, const GemvNorm* norm, const W12Ref* w12) {
+                    const float* wscale, const GemvNorm* norm, const W12Ref* w12, pgv_gemv_shape* ran) {
     PGV_CHECK(B >= 1 && B <= 64, "gemv: batch %d outside [1,64]", B);
     PGV_CHECK(K % 32 == 0, "gemv: K=%d must be a multiple of 32", K);
     PGV_CHECK(mode == GV_STORE16 || mode == GV_RESID || mode == GV_SWIGLU || mode == GV_F32 || mode == GV_RESIDNORM, "gemv: bad mode %d", mode);
@@ -1039,6 +1039,7 @@ int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void
         a.w12base = (const unsigned char*)w12->buf + pgv_w12_units_bytes(w12->rows, K) + pgv_w12_exc_bytes(w12->rows);
     }
     const int wf = use12 ? WF_12 : (w8 ? WF_FP8 : WF_16);
+    if (ran) *ran = pgv_gemv_shape{c.tl, c.ct, !c.k8 && c.x2 && c.ct == 1, c.k8, c.k8 ? c.nwb : 0, wf};
     pgv_prof_begin(ctx, 3, s);
     if (c.k8) {
 #ifdef PGV_LAB
@@ -1064,6 +1065,43 @@ extern "C" int pgv_gemv(pgv_ctx* ctx, int dtype, int mode, const void* d_W, cons
     PGV_CHECK(ctx && d_W && d_x && d_out, "pgv_gemv: null argument");
     PGV_CHECK(mode >= 0 && mode <= 3, "pgv_gemv: mode %d outside [0,3]", mode);
     return pgv_launch_gemv(ctx, dtype, mode, d_W, d_x, ldx, d_out, ldo, N, K, B, (hipStream_t)stream, nullptr, nullptr);
+}
+
+// Test entries: the launcher with the arguments a decode step gives it (pgv.h).  They check what a wrong test argument could turn into a stray write.
+extern "C" int pgv_gemv_ex(pgv_ctx* ctx, int dtype, const pgv_gemv_desc* d, void* stream) {
+    PGV_CHECK(ctx != nullptr && d != nullptr, "pgv_gemv_ex: null argument");
+    PGV_CHECK((d->d_W || d->d_W12) && d->d_x && d->d_out, "pgv_gemv_ex: null W / x / out");
+    const int mode = d->mode, N = d->N, K = d->K, B = d->B;
+    PGV_CHECK((mode >= GV_STORE16 && mode <= GV_F32) || mode == GV_RESIDNORM, "pgv_gemv_ex: mode %d is none of 0..3, 5", mode);
+    PGV_CHECK(B >= 1 && B <= kMaxBatch && N >= 1 && K >= 32, "pgv_gemv_ex: bad shape N = %d, K = %d, B = %d", N, K, B);
+    const int ct = B <= 16 ? 1 : (B <= 32 ? 2 : 4), nrb = (N + 15) / 16;
+    const bool producer = mode == GV_RESIDNORM, consumer = mode == GV_STORE16 || mode == GV_SWIGLU || mode == GV_F32;
+    const bool blocked = d->x_blocked && pgv_gemv_xblk_tiles(B) > 0;
+    PGV_CHECK((blocked && !producer) || (d->ldx >= K && d->ldx % 8 == 0), "pgv_gemv_ex: ldx = %d for K = %d (row-major x: 16-byte rows)", d->ldx, K);
+    PGV_CHECK(d->ldo >= (mode == GV_SWIGLU ? N / 2 : N) && (mode == GV_F32 || d->ldo % 4 == 0), "pgv_gemv_ex: ldo = %d for N = %d, mode %d", d->ldo, N, mode);
+    PGV_CHECK(d->ssq_ts >= 0 && d->amax_ts >= 0 && d->nparts_in >= 0, "pgv_gemv_ex: negative stride or count");
+    PGV_CHECK(d->d_ssq_in == nullptr || (consumer && d->nparts_in >= 1 && d->hidden >= 1 && d->ssq_ts >= 16 * d->nparts_in),
+              "pgv_gemv_ex: ssq_in needs a consumer mode, nparts_in >= 1, hidden >= 1 and ssq_ts >= 16 nparts_in (mode %d, %d parts, ssq_ts %d)", mode, d->nparts_in, d->ssq_ts);
+    PGV_CHECK(producer == (d->d_gamma || d->d_xg || d->d_ssq_out), "pgv_gemv_ex: gamma / xg / ssq_out belong to mode 5, and mode 5 needs all three");
+    if (producer) PGV_CHECK(d->d_gamma && d->d_xg && d->d_ssq_out && d->ssq_ts >= N, "pgv_gemv_ex: a producer needs gamma, xg, ssq_out and ssq_ts >= N (%d < %d)", d->ssq_ts, N);
+    PGV_CHECK((d->d_amax_val != nullptr) == (d->d_amax_idx != nullptr) && (d->d_amax_val == nullptr || (mode == GV_F32 && d->amax_ts >= 16 * nrb)),
+              "pgv_gemv_ex: the candidates need mode 3, both arrays and amax_ts >= 16 ceil(N / 16) (%d < %d)", d->amax_ts, 16 * nrb);
+    PGV_CHECK(d->d_k8_part == nullptr || (producer && d->k8_part_bytes >= (size_t)nrb * 8 * ct * 1024),
+              "pgv_gemv_ex: k8_part belongs to mode 5 and holds (N / 16) * 8 * ct * 1024 = %zu bytes (%zu given)", (size_t)nrb * 8 * ct * 1024, d->k8_part_bytes);
+    GemvNorm nm;
+    nm.ssq_in = d->d_ssq_in; nm.nparts_in = d->d_ssq_in ? d->nparts_in : 0; nm.hidden = d->hidden >= 1 ? d->hidden : 1; nm.eps = d->eps;
+    nm.gamma = d->d_gamma; nm.xg = d->d_xg; nm.ssq_out = d->d_ssq_out; nm.amax_val = d->d_amax_val; nm.amax_idx = d->d_amax_idx;
+    nm.k8_part = d->d_k8_part; nm.ssq_ts = d->ssq_ts > 0 ? d->ssq_ts : 16; nm.amax_ts = d->amax_ts > 0 ? d->amax_ts : 16 * nrb; nm.x_blocked = d->x_blocked != 0;
+    W12Ref r12; r12.buf = d->d_W12; r12.rows = (long long)nrb * 16;
+    return pgv_launch_gemv(ctx, dtype, mode, d->d_W, d->d_x, d->ldx, d->d_out, d->ldo, N, K, B, (hipStream_t)stream, d->d_wscale, &nm, d->d_W12 ? &r12 : nullptr, d->shape);
+}
+
+extern "C" int pgv_gemv_prep(pgv_ctx* ctx, int dtype, const int32_t* d_tok, const void* d_embed, float* d_resid, const float* d_gamma, void* d_xg, float* d_ssq, int B,
+                             int H, int x_blocked, void* stream) {
+    PGV_CHECK(ctx && d_resid && d_gamma && d_xg && d_ssq && (d_tok == nullptr) == (d_embed == nullptr), "pgv_gemv_prep: null argument (tok and embed go together)");
+    PGV_CHECK(B >= 1 && B <= kMaxBatch && H >= 32 && H % 32 == 0, "pgv_gemv_prep: B = %d, H = %d", B, H);
+    if (d_tok) return pgv_launch_embed_tok_norm(dtype, d_tok, d_embed, d_resid, d_gamma, d_xg, d_ssq, B, H, (hipStream_t)stream, x_blocked != 0);
+    return pgv_launch_final_prep(dtype, d_resid, d_gamma, d_xg, d_ssq, B, H, (hipStream_t)stream, x_blocked != 0);
 }
 
 #include "weights.h"

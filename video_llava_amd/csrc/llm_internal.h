@@ -27,8 +27,9 @@ int pgv_launch_prefill_attn(pgv_ctx* ctx, int dtype, const void* qkv, void* out,
 // w12: the 12-bit copy of W (w12.h), streamed instead of W at batches of one column tile (B <= 16) -- bitwise the same result; W may be null
 // only when B <= 16.  rows = the row count it was encoded with (>= N).
 struct W12Ref { const void* buf = nullptr; long long rows = 0; };
+// ran (optional): receives the launch shape chosen for this call (pgv_gemv_ex)
 int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void* x, int ldx, void* out, int ldo, int N, int K, int B, hipStream_t s,
-                    const float* wscale = nullptr, const GemvNorm* norm = nullptr, const W12Ref* w12 = nullptr);
+                    const float* wscale = nullptr, const GemvNorm* norm = nullptr, const W12Ref* w12 = nullptr, pgv_gemv_shape* ran = nullptr);
 int pgv_gemv_configure(pgv_ctx* ctx);      // per-device function attributes of the 8-phase producers: called once per context, outside graph capture
 int pgv_launch_embed_tok_norm(int dtype, const int* tok, const void* embed, float* resid, const float* gamma, void* xg, float* ssq, int B, int H, hipStream_t s, bool x_blocked);
 int pgv_launch_final_prep(int dtype, const float* resid, const float* gamma, void* xg, float* ssq, int B, int H, hipStream_t s, bool x_blocked);
