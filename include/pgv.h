@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PGV_VERSION 327
+#define PGV_VERSION 328
 
 enum { PGV_OK = 0, PGV_EINVAL = 1, PGV_EHIP = 2, PGV_ENOMEM = 3, PGV_ESTATE = 4, PGV_ENAME = 5 };
 enum { PGV_F16 = 0, PGV_BF16 = 1, PGV_F32 = 2 };
@@ -233,6 +233,30 @@ int pgv_llm_score(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_ids, 
  * Used when a new chat turn shares only a prefix with what the cache holds (surplus decode steps past a stop string,
  * video_chatgpt/model/utils.py:6-26). */
 int pgv_kv_truncate(pgv_kv *kv, int b, int len, void *stream);
+
+/* Fork the live group: slot p of the P = active sequences becomes h_counts[p] >= 1 consecutive slots, in order (HF's
+ * _expand_inputs_for_generation: input_ids.repeat_interleave(n) -- what num_return_sequences does to a batch): new slot i is a copy of old
+ * slot src(i), src = [0]*c0 + [1]*c1 + ...  New width W = sum of counts <= the batch the cache was created with.  One prefill, then N sampled
+ * answers per prompt; the same primitive is the cache side of a beam search.
+ *  - Result: as if every read preceded every write (the copy runs in place: a slot may be a source and another source's destination).  New
+ *    slot i holds old slot src(i)'s cache rows [0, len) in every layer, K and V, its pgv_kv_len, device position, current token, done flag,
+ *    seen-set bitmap (repetition penalty), row of the logits of the last prefill / decode call (pgv_llm_sample draws the first token from it) and
+ *    both pgv_kv_logprobs_last values.  The per-call step counter is cleared, as every stepping call does.  The group's width becomes W.
+ *    Rows [len, max_seq) of a destination are neither read nor written.  Everything else a slot has (residual, norms, greedy candidates) is
+ *    rebuilt by the next decode step from the current token and position: a forked slot's later tokens and logits are bitwise those of the
+ *    same prompt prefilled W times.
+ *  - Valid on any live group between calls: right after pgv_llm_prefill / _append / _slots / pgv_llm_score, and after decode steps.
+ *  - Enqueued on the caller's stream, no host synchronisation (lengths are host bookkeeping).  One launch per source whose slot moves or
+ *    multiplies; with all counts 1 nothing is launched.  Not attributed to a pgv_prof family.
+ *  - No decode kernel or graph changes: the captured decode graphs are keyed on the group's width and rebuild themselves at the next step.
+ *  - Refused, cache and state unchanged: no live group (PGV_ESTATE); P != the group's width, a count < 1, W > the cache's batch (PGV_EINVAL);
+ *    the message names the offending value.
+ *  - The sampling state of pgv_kv_set_warpers / pgv_kv_set_logprobs belongs to the cache, not to a slot, and is untouched.
+ * Not provided: a general (non-monotone) slot gather; sharing the prompt's K / V between the copies inside decode attention. */
+int pgv_kv_fork(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_counts, int P, void *stream);
+/* Test / debug read-back: rows [row0, row0 + nrows) of every head of `slot` (< the cache's batch, live or not) of layer `layer`,
+ * which = 0 K / 1 V  ->  d_out [heads][nrows][128] 16-bit.  row0 + nrows <= max_seq. */
+int pgv_kv_peek(pgv_kv *kv, int layer, int which, int slot, int row0, int nrows, void *d_out, void *stream);
 
 /* One decode step for all B sequences (the `input_ids.shape[1] == 1` branch, :103): consumes
  * d_last [B] token ids, appends to the KV cache, writes d_logits [B, vocab] and/or d_next [B]. */

@@ -1,0 +1,69 @@
+// pgv_kv_fork, device side: one cache slot becomes a run of slots (sample N answers from one prefill; the cache primitive of a beam search).
+//   kv_fork_kernel : slot `src` -> slots [d0, d0 + nd) except itself -- the cache rows [0, len) of every layer, K / V plane and head, and the
+//                    short per-slot state a decode step does not rebuild (position, current token, done flag, seen-set bitmap, logits row, the
+//                    two latest log-probabilities).  HBM-bound: every 16-byte piece of the source is read once and stored nd times.
+// The host (llm.hip) launches it once per source, sources in DESCENDING order: see pgv_kv_fork for why that order is safe in place.
+#include "llm_internal.h"
+
+namespace {
+
+constexpr int kForkThreads = 256;
+constexpr int kForkPieces = 4;          // 16-byte pieces a lane has in flight: 4 loads, then 4 stores per destination
+
+// Grid (ceil(run_pieces / (kForkThreads * kForkPieces)), nrun + 1).  Row y < nrun of the grid copies run y = (plane, head): the len * 256 contiguous
+// bytes of the source slot's rows [0, len) in that plane and head.  The last row copies the per-slot state, 4 bytes per lane.
+// Nothing beyond piece run_pieces of a run is touched: rows [len, max_seq) of a destination keep what they held.  No lane reads a byte another
+// lane of the launch writes (the source slot is no destination), so the launch needs no ordering inside itself.
+__global__ __launch_bounds__(kForkThreads) void kv_fork_kernel(KvForkArgs a) {
+    const int run = blockIdx.y;
+    if (run < a.nrun) {
+        const int plane = run / a.heads, h = run - plane * a.heads;
+        char* base = a.cache + (size_t)plane * a.plane_stride + (size_t)h * a.head_stride;
+        const u32x4_t* s = (const u32x4_t*)(base + (size_t)a.src * a.slot_stride);
+        const unsigned i0 = blockIdx.x * (kForkThreads * kForkPieces) + threadIdx.x;
+        u32x4_t v[kForkPieces];
+#pragma unroll
+        for (int k = 0; k < kForkPieces; ++k) {
+            const unsigned i = i0 + k * kForkThreads;
+            v[k] = u32x4_t{0u, 0u, 0u, 0u};
+            if (i < a.run_pieces) v[k] = s[i];
+        }
+        for (int d = a.d0; d < a.d0 + a.nd; ++d) {
+            if (d == a.src) continue;
+            u32x4_t* t = (u32x4_t*)(base + (size_t)d * a.slot_stride);
+#pragma unroll
+            for (int k = 0; k < kForkPieces; ++k) {
+                const unsigned i = i0 + k * kForkThreads;
+                if (i < a.run_pieces) t[i] = v[k];
+            }
+        }
+        return;
+    }
+    // per-slot state as one list of 32-bit words: seen-set bitmap | logits row | position, current token, done flag, lp model, lp pick
+    const int n_words = a.seen_words + a.vocab + 5;
+    for (int i = blockIdx.x * kForkThreads + threadIdx.x; i < n_words; i += gridDim.x * kForkThreads) {
+        unsigned* p;                    // the word of slot 0
+        size_t stride;                  // words from one slot to the next
+        if (i < a.seen_words) { p = a.seen + i; stride = (size_t)a.seen_words; }
+        else if (i < a.seen_words + a.vocab) { p = (unsigned*)a.logits + (i - a.seen_words); stride = (size_t)a.vocab; }
+        else {
+            const int j = i - a.seen_words - a.vocab;
+            p = j == 0 ? (unsigned*)a.pos : j == 1 ? (unsigned*)a.cur : j == 2 ? (unsigned*)a.done : (unsigned*)a.lp_last + (size_t)(j - 3) * a.lp_stride;
+            stride = 1;
+        }
+        const unsigned v = p[(size_t)a.src * stride];
+        for (int d = a.d0; d < a.d0 + a.nd; ++d)
+            if (d != a.src) p[(size_t)d * stride] = v;
+    }
+}
+
+}  // namespace
+
+int pgv_launch_kv_fork(const KvForkArgs& a, hipStream_t s) {
+    PGV_CHECK(a.src >= 0 && a.d0 >= 0 && a.nd >= 1 && a.nrun >= 0 && a.nrun < 65535 && a.heads >= 1, "kv fork: bad launch arguments");
+    const unsigned per_block = kForkThreads * kForkPieces;
+    unsigned gx = (a.run_pieces + per_block - 1) / per_block;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(kv_fork_kernel, dim3(gx, a.nrun + 1), dim3(kForkThreads), 0, s, a);
+    return PGV_OK;
+}

@@ -50,6 +50,7 @@ struct pgv_kv {
     int B, max_seq;
     char* blob = nullptr;
     std::vector<void*> Kc, Vc;          // per layer [B][heads][max_seq][128]
+    size_t plane_bytes = 0;             // Kc[0], Vc[0], Kc[1], ... sit this far apart in the blob (pgv_kv_fork covers them in one launch)
     // fixed-address decode buffers (so a decode step can be captured into a hipGraph)
     float* resid; void* xn; void* qkv; void* ao; void* act; float* logits;
     float* amax_val; int* amax_idx;     // greedy candidates of the lm_head GEMV, tile-major: [ceil(B / 16)][vocab_cap / 16][16]
@@ -331,6 +332,7 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
     if (e != hipSuccess) { delete kv; pgv_set_error("pgv_kv_create: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
     char* b = kv->blob;
     for (size_t i = 0; i < L; ++i) { kv->Kc.push_back(b + o_cache + per * 2 * i); kv->Vc.push_back(b + o_cache + per * (2 * i + 1)); }
+    kv->plane_bytes = per;
     kv->resid = (float*)(b + o_resid); kv->xn = b + o_xn; kv->qkv = b + o_qkv; kv->ao = b + o_ao; kv->act = b + o_act; kv->logits = (float*)(b + o_logits); kv->ssq = (float*)(b + o_ssq); kv->amax_val = (float*)(b + o_av); kv->amax_idx = (int*)(b + o_ai);
     int* ints = (int*)(b + o_ints);
     kv->d_pos = ints; kv->d_cur = ints + B; kv->d_step = ints + 2 * B; kv->d_done = ints + 3 * B; kv->d_hist = ints + 4 * B;
@@ -682,6 +684,67 @@ extern "C" int pgv_kv_truncate(pgv_kv* kv, int b, int len, void* stream) {
     kv->h_len[b] = len;
     PGV_HIP(hipMemcpyAsync(kv->d_pos + b, &kv->h_len[b], 4, hipMemcpyHostToDevice, (hipStream_t)stream));
     PGV_HIP(hipStreamSynchronize((hipStream_t)stream));          // the source is host bookkeeping that the next call may change
+    return PGV_OK;
+}
+
+// Fork the live group: sequence p becomes h_counts[p] consecutive slots (new slot i = old slot src(i), src = [0]*c0 + [1]*c1 + ...).
+// What defines a slot, and is therefore copied: its cache rows [0, len), its length, and the state a decode step does not rebuild from the
+// current token and position -- position, current token, done flag, seen-set bitmap, logits row (the first token of a fresh prefill is drawn
+// from it) and the two lp_last values.  Residual, norms, candidates and qkv are rebuilt by every step; the token / log-probability histories
+// restart with every stepping call.
+// IN PLACE, one launch per source on the stream, sources in DESCENDING order.  The destinations of source p are slots [base_p, base_p + c_p)
+// with base_p = c_0 + ... + c_(p-1) >= p (every count is >= 1).  When source p runs, every source q > p has run already and is never read
+// again; every source q < p is still unread and every destination of p is >= base_p >= p > q: no slot is overwritten before it has been
+// read.  Inside a launch the source slot itself is skipped as a destination, so no launch reads what it writes.  The result is as if every
+// read preceded every write.  (counts [2,2,2]: slot 1 is source 1 and second destination of source 0 -- source 2 -> slots 4, 5; then source
+// 1 -> slots 2, 3; only then source 0 -> slot 1.)
+extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_counts, int P, void* stream) {
+    PGV_CHECK(ctx && m && kv && h_counts, "pgv_kv_fork: null argument");
+    PGV_CHECK(kv->llm == m, "pgv_kv_fork: kv cache belongs to another model");
+    if (kv->active < 1) { pgv_set_error("pgv_kv_fork: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
+    PGV_CHECK(P == kv->active, "pgv_kv_fork: %d counts for a live group of %d sequences", P, kv->active);
+    long long W = 0;
+    for (int p = 0; p < P; ++p) {
+        PGV_CHECK(h_counts[p] >= 1, "pgv_kv_fork: count %d of sequence %d is below 1", h_counts[p], p);
+        W += h_counts[p];
+    }
+    PGV_CHECK(W <= kv->B, "pgv_kv_fork: new width %lld exceeds the %d sequences the cache was created with", W, kv->B);
+    if (W == P) return PGV_OK;            // every count is 1: the group is its own fork
+    hipStream_t s = (hipStream_t)stream;
+    const int heads = m->cfg.heads, L = m->cfg.layers;
+    KvForkArgs a;
+    a.cache = L > 0 ? (char*)kv->Kc[0] : kv->blob;
+    a.head_stride = (size_t)kv->max_seq * kHD * 2; a.slot_stride = a.head_stride * heads; a.plane_stride = kv->plane_bytes;
+    a.heads = heads; a.nrun = 2 * L * heads;
+    a.pos = kv->d_pos; a.cur = kv->d_cur; a.done = kv->d_done; a.lp_last = kv->lp_last; a.lp_stride = kv->B;
+    a.seen = kv->d_seen; a.seen_words = kv->seen_words; a.logits = kv->logits; a.vocab = m->cfg.vocab;
+    PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
+    std::vector<int> len((size_t)W);
+    int base = (int)W;
+    for (int p = P - 1; p >= 0; --p) {
+        const int c = h_counts[p];
+        base -= c;
+        for (int i = 0; i < c; ++i) len[(size_t)base + i] = kv->h_len[p];
+        if (c == 1 && base == p) continue;                 // the slot stays where it is
+        a.src = p; a.d0 = base; a.nd = c; a.run_pieces = (unsigned)kv->h_len[p] * (kHD * 2 / 16);
+        PGV_TRY(pgv_launch_kv_fork(a, s));
+    }
+    for (int i = 0; i < (int)W; ++i) kv->h_len[i] = len[i];
+    kv->active = (int)W;
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+extern "C" int pgv_kv_peek(pgv_kv* kv, int layer, int which, int slot, int row0, int nrows, void* d_out, void* stream) {
+    PGV_CHECK(kv && d_out, "pgv_kv_peek: null argument");
+    PGV_CHECK(layer >= 0 && layer < (int)kv->Kc.size(), "pgv_kv_peek: layer %d outside [0,%d)", layer, (int)kv->Kc.size());
+    PGV_CHECK(which == 0 || which == 1, "pgv_kv_peek: which = %d is neither 0 (K) nor 1 (V)", which);
+    PGV_CHECK(slot >= 0 && slot < kv->B, "pgv_kv_peek: slot %d outside the %d of the cache", slot, kv->B);
+    PGV_CHECK(row0 >= 0 && nrows >= 1 && row0 <= kv->max_seq - nrows, "pgv_kv_peek: rows [%d,%d + %d) outside the cache's %d", row0, row0, nrows, kv->max_seq);
+    const int heads = kv->llm->cfg.heads;
+    const size_t row = (size_t)kHD * 2, head = (size_t)kv->max_seq * row;
+    const char* src = (const char*)(which ? kv->Vc[layer] : kv->Kc[layer]) + ((size_t)slot * heads) * head + (size_t)row0 * row;
+    PGV_HIP(hipMemcpy2DAsync(d_out, (size_t)nrows * row, src, head, (size_t)nrows * row, heads, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PGV_OK;
 }
 

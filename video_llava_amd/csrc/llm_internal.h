@@ -23,6 +23,18 @@ int pgv_launch_rope_kv_write(int dtype, void* qkv, const int* row_b, const int* 
 // slot [B]: cache slot of sequence b (null: b; pgv_llm_prefill_slots)
 int pgv_launch_prefill_attn(pgv_ctx* ctx, int dtype, const void* qkv, void* out, const void* Kc, const void* Vc, const int* cu, const int* koff, int B, int max_len,
                             int H, int heads, int max_seq, double flops, hipStream_t s, const int* slot = nullptr);
+// kv_fork.hip: slot `src` of a cache -> slots [d0, d0 + nd) except itself (pgv_kv_fork).  Cache rows: nrun = planes * heads runs of run_pieces
+// 16-byte pieces each (rows [0, len) of one head are contiguous); plane = one layer's K or V, [slots][heads][max_seq][128] 16-bit, the planes a
+// constant plane_stride bytes apart.  State: the slot's words of pos / cur / done, of lp_last [2][lp_stride], of seen [slots][seen_words] and
+// of logits [slots][vocab].  The caller has checked every slot index against the cache's batch.
+struct KvForkArgs {
+    char* cache; size_t plane_stride, slot_stride, head_stride;
+    int heads, nrun; unsigned run_pieces;
+    int src, d0, nd;
+    int *pos, *cur, *done; float* lp_last; int lp_stride;
+    unsigned* seen; int seen_words; float* logits; int vocab;
+};
+int pgv_launch_kv_fork(const KvForkArgs& a, hipStream_t s);
 // gemv.hip
 // w12: the 12-bit copy of W (w12.h), streamed instead of W at batches of one column tile (B <= 16) -- bitwise the same result; W may be null
 // only when B <= 16.  rows = the row count it was encoded with (>= N).

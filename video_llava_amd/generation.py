@@ -87,8 +87,9 @@ def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: s
         else:
             v, where = _config_get(generation_config, name), "generation_config field"
         if asks(v):
+            hint = "; several sampled answers per prompt: this package's own keyword `samples_per_prompt`" if name == "num_return_sequences" else ""
             raise ValueError(f"{who}: {where} `{name}`={v!r} is not implemented by this package (it would change the result of HF's generate()); "
-                             f"implemented: temperature, top_k, top_p, repetition_penalty")
+                             f"implemented: temperature, top_k, top_p, repetition_penalty{hint}")
     for name in ("output_scores", "output_attentions", "output_hidden_states", "return_dict_in_generate"):
         if kwargs.get(name):
             raise ValueError(f"{who}: argument `{name}`={kwargs[name]!r} is not implemented by this package (generate() returns the ids only; "
@@ -98,6 +99,40 @@ def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: s
         import torch
         if not bool(torch.as_tensor(mask).to(torch.bool).all()):
             raise ValueError(f"{who}: argument `attention_mask` with padding is not implemented; pass a list of prompts for a ragged batch")
+
+
+MAX_GROUP = 64          # sequences one decode group holds (pgv_kv_create's batch limit)
+
+
+def fork_sources(counts: Sequence[int]) -> list:
+    """The slot map of pgv_kv_fork / model.fork(kv, counts): new slot i is a copy of old slot fork_sources(counts)[i] -- prompt p repeated
+    counts[p] times, in order (HF's _expand_inputs_for_generation: repeat_interleave).  fork_sources([2, 1, 3]) == [0, 0, 1, 2, 2, 2]."""
+    src = []
+    for p, c in enumerate(counts):
+        if int(c) != c or c < 1:
+            raise ValueError(f"fork_sources: count {c!r} of sequence {p} is not an integer >= 1")
+        src += [p] * int(c)
+    return src
+
+
+def check_samples_per_prompt(n, batch: int, do_sample: bool, has_criteria: bool, has_reuse_key: bool, who: str = "generate()") -> int:
+    """Validate generate(samples_per_prompt=n) on the host, before any device work; returns n as an int."""
+    if isinstance(n, bool) or int(n) != n or n < 1:
+        raise ValueError(f"{who}: `samples_per_prompt`={n!r} has to be an integer >= 1")
+    n = int(n)
+    if n == 1:
+        return n
+    if not do_sample:
+        raise ValueError(f"{who}: `samples_per_prompt`={n} needs do_sample=True (HF: \"Greedy methods without beam search do not support "
+                         f"`num_return_sequences` different than 1\")")
+    if batch * n > MAX_GROUP:
+        raise ValueError(f"{who}: {batch} prompts x `samples_per_prompt`={n} = {batch * n} sequences exceed the {MAX_GROUP} of one decode group")
+    if has_criteria:
+        raise ValueError(f"{who}: `samples_per_prompt`={n} cannot be combined with `stopping_criteria` (they are evaluated on one sequence); "
+                         f"use `stop_strings`")
+    if has_reuse_key:
+        raise ValueError(f"{who}: `samples_per_prompt`={n} cannot be combined with `kv_reuse_key` (the kept cache would hold {n} different answers)")
+    return n
 
 
 def resolve_sampling(temperature=None, top_k=None, top_p=None, repetition_penalty=None, generation_config=None) -> Tuple[float, int, float, float]:
@@ -125,11 +160,12 @@ class GenerateLogprobsOutput:
     transition_scores: fp32 [B, n_new] on the host, entry i belongs to new token i of the sequence -- the `model` / `pick` values of pgv.h
     (pgv_kv_set_logprobs): HF's compute_transition_scores(sequences, logits / scores, normalize_logits=True).  Both are cut exactly where the ids
     are cut (EOS, stop strings, stopping criteria, budget) and are 0 beyond a sequence's end.  sequence_logprob: fp64 [B], the sums of
-    token_logprobs."""
+    token_logprobs.  new_lengths: int64 [B], the new tokens each sequence kept (`sequences` pads shorter rows to the longest)."""
     sequences: Any
     token_logprobs: Any
     transition_scores: Any
     sequence_logprob: Any
+    new_lengths: Any = None
 
     @classmethod
     def assemble(cls, sequences, n_kept: Sequence[int], model_rows: Sequence, pick_rows: Sequence) -> "GenerateLogprobsOutput":
@@ -145,4 +181,5 @@ class GenerateLogprobsOutput:
                 if row.size < n:
                     raise ValueError(f"sequence {b} kept {n} tokens but has {row.size} log-probabilities")
                 out[k, b, :n] = row[:n]
-        return cls(sequences, torch.from_numpy(out[0]), torch.from_numpy(out[1]), torch.from_numpy(out[0].astype(np.float64).sum(axis=1)))
+        return cls(sequences, torch.from_numpy(out[0]), torch.from_numpy(out[1]), torch.from_numpy(out[0].astype(np.float64).sum(axis=1)),
+                   torch.tensor([int(n) for n in n_kept], dtype=torch.long))

@@ -198,6 +198,43 @@ def video_chatgpt_infer_logprobs(video_frames, question, conv_mode, model, visio
             "logprob": float(out.sequence_logprob[0])}
 
 
+def video_chatgpt_infer_samples(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len, n,
+                                transcript=None, temperature=0.2, max_new_tokens=1024, features=None, **generate_kwargs):
+    """n sampled answers to one question about one clip for the price of ONE CLIP pass and ONE prefill (model.generate(samples_per_prompt=n):
+    the prompt's KV-cache slot is forked n ways on the device, pgv_kv_fork) -- the raw material of best-of-N ranking and self-consistency voting.
+    Always samples (do_sample=True; greedy decoding has one answer).  The stop string ends each answer on its own (generate's `stop_strings`, the
+    batched form of the reference's KeywordsStoppingCriteria).  Returns a list of n dicts shaped like video_chatgpt_infer_logprobs', in sample
+    order: "text", "ids", "token_logprobs", "transition_scores", "logprob".  `features`: pooled features computed earlier (skips the tower);
+    `generate_kwargs` (top_p, repetition_penalty, generator, ...) go to model.generate as they are."""
+    prompt, stop_str = build_prompt(question, conv_mode, video_token_len, model.get_model().vision_config.use_vid_start_end, transcript)
+    input_ids = torch.as_tensor(tokenizer([prompt]).input_ids)
+    feats = features if features is not None else video_features(video_frames, vision_tower, image_processor)
+    with torch.inference_mode():
+        out = model.generate(input_ids, video_spatio_temporal_features=feats.unsqueeze(0), do_sample=True, temperature=temperature,
+                             max_new_tokens=max_new_tokens, stop_strings=[stop_str], tokenizer=tokenizer, samples_per_prompt=n,
+                             **dict(generate_kwargs, output_logprobs=True))
+    n_in = input_ids.shape[1]
+    res = []
+    for j in range(int(n)):
+        k = int(out.new_lengths[j])                 # the rows of a batch are padded to the longest answer: cut each at its own length
+        new_ids = out.sequences[j, n_in:n_in + k].tolist()
+        text = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0].strip().rstrip(stop_str).strip()
+        res.append({"text": text, "ids": new_ids, "token_logprobs": out.token_logprobs[j, :k].tolist(),
+                    "transition_scores": out.transition_scores[j, :k].tolist(), "logprob": float(out.sequence_logprob[j])})
+    return res
+
+
+def best_sample(samples) -> int:
+    """Index of the sample with the largest "logprob" (video_chatgpt_infer_samples' dicts); ties go to the first."""
+    if not samples:
+        raise ValueError("best_sample: no samples")
+    best = 0
+    for i, s_ in enumerate(samples):
+        if s_["logprob"] > samples[best]["logprob"]:
+            best = i
+    return best
+
+
 def video_chatgpt_score(video_frames, question, answers, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                         transcript=None, features=None):
     """How likely is each of `answers` (a list of candidate strings) as the reply to `question` about one clip: the prompt of

@@ -21,7 +21,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..constants import CLIP_WIDTH
-from ..generation import GenerateLogprobsOutput, check_generate_kwargs, load_generation_config, resolve_sampling
+from ..generation import GenerateLogprobsOutput, check_generate_kwargs, check_samples_per_prompt, fork_sources, load_generation_config, resolve_sampling
 from ..scoring import ScoreOutput, id_rows, shift_labels
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
 from .utils import AnswerState
@@ -364,12 +364,14 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         return proj, proj.shape[1], self._video_positions(seqs, proj.shape[1])
 
     def prefill(self, seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor], max_seq: int,
-                want_logits: bool = False, want_all_logits: bool = False, append_to=None, logprobs: Optional[bool] = None):
+                want_logits: bool = False, want_all_logits: bool = False, append_to=None, logprobs: Optional[bool] = None,
+                capacity: Optional[int] = None):
         """Run the prompt(s); returns (kv handle, next-token ids [B] int32 on device, logits [B, vocab] or None) -- with want_all_logits a fourth
         entry: the logits of EVERY position, [sum of lengths, vocab] fp32 (what the reference's forward returns, model/video_chatgpt.py:225-226).
         `append_to` = a kv handle this model filled before: the rows continue its sequences (pgv_llm_prefill_append; `max_seq` is ignored).
         `logprobs` (True / False): set the cache's log-probability switch (set_logprobs) before the prompt runs, so that the greedy first token is
-        recorded too; None leaves the switch as it is."""
+        recorded too; None leaves the switch as it is.
+        `capacity`: the cache is created for max(B, capacity) sequences, so that fork() has slots to grow into (ignored with `append_to`)."""
         B = len(seqs)
         lens = [len(s) for s in seqs]
         feats = video_spatio_temporal_features
@@ -379,7 +381,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         if feats is not None and not (max(lens) == 1):     # the reference skips the splice when input_ids.shape[1]==1 (:103)
             proj, V, vid_pos = self._project_video(feats, seqs)
         if append_to is None:
-            kv = self._get_kv(max(B, 1), max_seq)
+            kv = self._get_kv(max(B, 1, int(capacity or 0)), max_seq)
             self._kv_epoch += 1
             self._reuse = None
         else:
@@ -505,6 +507,25 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         _lib.check(self.ctx.lib.pgv_llm_pick_greedy(self.ctx.handle, self.handle, kv, nxt.data_ptr(), _lib.stream_ptr(self.device_)), "pgv_llm_pick_greedy")
         return nxt
 
+    def fork(self, kv, counts: Sequence[int]) -> int:
+        """pgv_kv_fork: sequence p of the live group of `kv` becomes counts[p] consecutive slots (new slot i copies old slot
+        generation.fork_sources(counts)[i]: cache rows, length, current token, done flag, seen-set, logits row, latest log-probabilities).
+        The cache must have been created for at least sum(counts) sequences (prefill(..., capacity=)).  Returns the new width."""
+        src = fork_sources(counts)
+        P = len(counts)
+        _lib.check(self.ctx.lib.pgv_kv_fork(self.ctx.handle, self.handle, kv, (C.c_int32 * P)(*[int(c) for c in counts]), P,
+                                            _lib.stream_ptr(self.device_)), "pgv_kv_fork")
+        self._kv_epoch += 1                 # a PastKeyValues object handed out earlier describes another group width
+        return len(src)
+
+    def kv_peek(self, kv, layer: int, which: int, slot: int, row0: int, nrows: int) -> torch.Tensor:
+        """pgv_kv_peek (tests / debugging): cache rows [row0, row0 + nrows) of `slot` in `layer`, which = 0 keys / 1 values ->
+        [heads, nrows, 128] in the model's dtype."""
+        out = torch.empty(self.config.num_attention_heads, int(nrows), 128, dtype=self.dtype_, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_kv_peek(kv, int(layer), int(which), int(slot), int(row0), int(nrows), out.data_ptr(),
+                                            _lib.stream_ptr(self.device_)), "pgv_kv_peek")
+        return out
+
     def kv_len(self, kv, b: int) -> int:
         return int(self.ctx.lib.pgv_kv_len(kv, int(b)))
 
@@ -610,7 +631,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  chunk: int = 32, generator: Optional[torch.Generator] = None, top_k: Optional[int] = None,
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
-                 **_unused):
+                 samples_per_prompt: int = 1, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -645,7 +666,13 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         must lie inside the common prefix (it was spliced when the cache was filled); otherwise the call falls back to a full prefill.  The
         appended rows are bitwise what one prefill over the same cache contents computes; cache entries that DECODE steps wrote (the previous
         answer) carry the decode path's 16-bit rounding instead of the prefill path's -- as with any KV cache that is kept across calls.
-        `timings["reused_tokens"]` reports the prefix."""
+        `timings["reused_tokens"]` reports the prefix.
+        `samples_per_prompt=n` (a keyword of this package; HF's `num_return_sequences` stays refused): n sampled answers per prompt from ONE
+        prefill.  The B prompts run once in a cache created for B * n sequences, pgv_kv_fork copies every prompt's cache rows and slot state to n
+        consecutive slots, and the loop above runs at width B * n -- the result is what generate() returns for the prompts repeated n times each
+        (repeat_interleave: row b * n + j is sample j of prompt b) with the same generator, minus n - 1 prefills per prompt.  Uniforms are
+        torch.rand(max_new_tokens, B * n); `stop_strings` and `video_spatio_temporal_features` stay per PROMPT.  Needs do_sample=True and
+        B * n <= 64; not combinable with `stopping_criteria` or `kv_reuse_key`.  n = 1 is the path above, unchanged."""
         check_generate_kwargs(_unused, self.generation_config)
         temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
         if torch.is_tensor(input_ids):
@@ -653,6 +680,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         else:
             seqs = [list(s) for s in input_ids]
         B = len(seqs)
+        n_samples = check_samples_per_prompt(samples_per_prompt, B, bool(do_sample), bool(stopping_criteria), kv_reuse_key is not None)
         eos = self.config.eos_token_id if eos_token_id == "config" else eos_token_id
         eos_i = -1 if eos is None else int(eos)
         max_seq = max(len(s) for s in seqs) + max_new_tokens
@@ -691,6 +719,19 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             if reused < len(self._reuse[3]):
                 _lib.check(self.ctx.lib.pgv_kv_truncate(kv, 0, reused, _lib.stream_ptr(self.device_)), "pgv_kv_truncate")
             _kv, nxt, _ = self.prefill([seqs[0][reused:]], None, 0, append_to=kv, **lpk)
+        elif n_samples > 1:
+            # one prefill of the B prompts, then every prompt's slot becomes n consecutive slots: from here on the call IS the call on the
+            # prompts repeated n times each (the prefill's own greedy first token is replaced by the draw below, per slot)
+            kv, _nxt, _ = self.prefill(seqs, video_spatio_temporal_features, max_seq, capacity=B * n_samples, **lpk)
+            try:
+                B = self.fork(kv, [n_samples] * B)
+            except Exception:
+                if output_logprobs:
+                    self.set_logprobs(kv, False)
+                raise
+            seqs = [seqs[i] for i in fork_sources([n_samples] * len(seqs))]
+            if stops is not None:
+                stops = [stops[i // n_samples] for i in range(B)]
         else:
             kv, nxt, _ = self.prefill(seqs, video_spatio_temporal_features, max_seq, **lpk)
         try:
@@ -753,7 +794,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             new = [st.new for st in states]
             if timings is not None:
                 _t2 = _time.perf_counter()
-                timings.update(prefill_s=_t1 - _t0, decode_s=_t2 - _t1, steps=n_gen, batch=B, reused_tokens=reused)
+                timings.update(prefill_s=_t1 - _t0, decode_s=_t2 - _t1, steps=n_gen, batch=B, reused_tokens=reused, samples_per_prompt=n_samples)
             if kv_reuse_key is not None and B == 1:
                 # the cache holds the prompt and every emitted token that was fed back (all but the last one)
                 self._reuse = (kv_reuse_key, kv, max_seq, list(seqs[0]) + raw[:-1])
