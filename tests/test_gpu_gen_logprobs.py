@@ -498,6 +498,37 @@ def test_switch_off_on_off_rebuilds_the_graphs(ctx):
     m.set_logprobs(kv, False)
 
 
+# (temperature, top_k, top_p, repetition_penalty) of a sampled run, or ("greedy", repetition_penalty): neighbours differ in exactly one field
+PICK_SETS = [(0.7, 50, 0.9, 1.0), (1.3, 50, 0.9, 1.0), (1.3, 5, 0.9, 1.0), (1.3, 5, 0.5, 1.0), (1.3, 5, 0.5, 1.5), ("greedy", 1.5), ("greedy", 1.0)]
+
+
+def test_one_cache_rebuilds_the_graphs_for_every_pick_parameter(ctx):
+    """One cache, the same prompts (B = 2) and the same uniforms throughout; every call is a prefill and 10 steps (the cache's first call: one eager
+    step, the 8-step graph, one single-step graph; later ones: the 8-step graph and two single steps).  PICK_SETS forwards, then backwards: every
+    set returns bitwise the same ids both times, and no two sets return the same ids -- a captured graph that kept a neighbour's temperature,
+    top_k, top_p, penalty or greedy flag would repeat the neighbour's ids."""
+    cfg, m = _tiny()
+    prompts, feats_t = _prompts(cfg, np.random.default_rng(5), 20, (4, 9))
+    B, n = 2, 10
+    u = torch.rand(n, B, generator=torch.Generator().manual_seed(23)).to(DEV)
+    runs, handles = {}, set()
+    for ps in PICK_SETS + PICK_SETS[::-1]:
+        kv, nxt, _ = m.prefill(prompts, feats_t, 128, logprobs=False)
+        handles.add(kv.value)
+        if ps[0] == "greedy":
+            ids = m.decode_greedy(kv, nxt, n, repetition_penalty=ps[1]).cpu()
+        else:
+            ids = m.decode_sample(kv, nxt, n, -1, ps[0], ps[1], u, top_p=ps[2], repetition_penalty=ps[3]).cpu()
+        print(ps, ids.tolist())
+        runs.setdefault(ps, []).append(ids)
+    assert len(handles) == 1
+    for ps, (fwd, back) in runs.items():
+        assert torch.equal(fwd, back), (ps, fwd.tolist(), back.tolist())
+    for i, a in enumerate(PICK_SETS):
+        for b in PICK_SETS[i + 1:]:
+            assert not torch.equal(runs[a][0], runs[b][0]), (a, b, runs[a][0].tolist())
+
+
 # ---- 9. real vocabulary --------------------------------------------------------------------------------------------------------------------------
 _REAL = {}
 

@@ -763,6 +763,67 @@ int main(int argc, char** argv) {
     assert users == ["llm.hip"], users
 
 
+def test_pick_params_and_decode_graph_key(tmp_path):
+    """csrc/pick_params.h, compiled on its own with g++ (it must need no HIP header): (1) pick_greedy(p) is temperature 1, top_k 1, top_p 1,
+    penalty p, greedy; (2) two decode-graph keys that differ in exactly one of B, eos, flags, generation, the log-probability switch or one of the
+    five PickParams fields compare unequal -- a field left out of the comparison would replay a stale graph; (3) the keys of two runs without
+    AM_SAMPLE compare equal whatever sampled parameters an earlier run left in flight, and differ from the key of a sampled run.  Where g++ has the
+    sanitizer runtimes the same stand-alone program runs a second time under ASan + UBSan."""
+    import shutil
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    csrc = os.path.join(ROOT, "video_llava_amd", "csrc")
+    prog = r"""#include <cstdio>
+#include "pick_params.h"
+static int bad = 0;
+#define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); bad = 1; } } while (0)
+int main() {
+    const PickParams d;
+    EXPECT(d.temperature == 1.f && d.top_k == 0 && d.top_p == 1.f && d.penalty == 1.f && !d.greedy);
+    const PickParams g = pick_greedy(1.3f);
+    EXPECT(g.temperature == 1.f && g.top_k == 1 && g.top_p == 1.f && g.penalty == 1.3f && g.greedy);
+    EXPECT((g == PickParams{1.f, 1, 1.f, 1.3f, true}) && !(g == pick_greedy(1.2f)));
+    const PickParams p{0.7f, 50, 0.9f, 1.2f, false};
+    const int F = AM_INC_POS | AM_RECORD | AM_SAMPLE;
+    const DecodeGraphKey k = decode_graph_key(2, 7, F, 3, false, p);
+    EXPECT(k == decode_graph_key(2, 7, F, 3, false, p));
+    EXPECT(k.B == 2 && k.eos == 7 && k.flags == F && k.generation == 3 && !k.logprobs && k.pick == p);
+    EXPECT(!(DecodeGraphKey{} == k) && DecodeGraphKey{}.generation == -1);
+    int differ = 0;
+    differ += !(k == decode_graph_key(3, 7, F, 3, false, p));
+    differ += !(k == decode_graph_key(2, -1, F, 3, false, p));
+    differ += !(k == decode_graph_key(2, 7, F & ~AM_RECORD, 3, false, p));
+    differ += !(k == decode_graph_key(2, 7, F, 4, false, p));
+    differ += !(k == decode_graph_key(2, 7, F, 3, true, p));
+    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.8f, 50, 0.9f, 1.2f, false}));
+    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 49, 0.9f, 1.2f, false}));
+    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 50, 0.8f, 1.2f, false}));
+    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 50, 0.9f, 1.3f, false}));
+    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 50, 0.9f, 1.2f, true}));
+    EXPECT(differ == 10);
+    const int G = AM_INC_POS | AM_RECORD;
+    const DecodeGraphKey a = decode_graph_key(2, 7, G, 3, false, p), b = decode_graph_key(2, 7, G, 3, false, pick_greedy(2.f));
+    EXPECT(a == b && a.pick == PickParams{} && !(a == k));
+    if (!bad) printf("OK %d\n", differ);
+    return bad;
+}
+"""
+    cpp, exe, exe_san = tmp_path / "pick.cpp", tmp_path / "pick", tmp_path / "pick_san"
+    cpp.write_text(prog)
+    base = [gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", csrc, str(cpp)]
+    subprocess.run([*base, "-o", str(exe)], check=True)
+    exes = [exe]
+    san = subprocess.run([*base, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe_san)], capture_output=True, text=True)
+    if san.returncode == 0:
+        exes.append(exe_san)
+    else:
+        assert "asan" in san.stderr or "ubsan" in san.stderr, san.stderr        # only a missing sanitizer runtime excuses the second build
+        print("g++ has no sanitizer runtimes here: plain build only")
+    for x in exes:
+        r = subprocess.run([str(x)], capture_output=True, text=True)
+        assert r.returncode == 0 and not r.stderr and r.stdout == "OK 10\n", (x, r.returncode, r.stdout, r.stderr[-2000:])
+
+
 # --------------------------------------------------------------------------------------------------
 # offline feature extraction (scripts/save_spatio_temporal_clip_features.py) and the QA runner: host logic
 # --------------------------------------------------------------------------------------------------

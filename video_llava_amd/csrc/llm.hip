@@ -65,20 +65,17 @@ struct pgv_kv {
     // one decode step captured as a hipGraph (all kernel arguments are fixed device addresses; positions, current
     // tokens and step counters live in device memory and are advanced by the argmax kernel)
     hipGraphExec_t gexec[2] = {nullptr, nullptr};      // [0]: one token step, [1]: kGraphSteps consecutive steps
-    int g_B = 0, g_eos = 0, g_flags = 0, g_gen = -1, g_topk = 0;
-    float g_temp = 0.f, g_topp = 1.f, g_pen = 1.f;
+    DecodeGraphKey gkey;                // what they baked in
     float* d_u = nullptr;               // uniforms of a sampled decode run: [max_seq][B], indexed by the device-side step counter
-    float s_temp = 1.f; int s_topk = 0; // sampling parameters of the run in flight (AM_SAMPLE)
-    float s_topp = 1.f, s_pen = 1.f;
-    float w_topp = 1.f, w_pen = 1.f;    // pgv_kv_set_warpers: what every later pick on this cache runs with
+    PickParams warpers;                 // pgv_kv_set_warpers: the top_p and penalty every later pick on this cache runs with (the other fields stay neutral)
+    PickParams run;                     // the stepping run in flight (AM_SAMPLE)
     unsigned* d_seen = nullptr;         // seen-set of every slot (repetition penalty): [B][seen_words] bitmaps over the vocabulary
     int seen_words = 0;
     // pgv_kv_set_logprobs: the two log-probabilities of every pick.  lp_stat [B][2] row statistics (row_lse_kernel), lp_last [2][B] the values of each
     // slot's latest pick (model | pick), lp_hist [2][B][max_seq] those of the stepping calls, parallel to d_hist
-    bool lp_on = false; int g_lp = 0;
+    bool lp_on = false;
     float *lp_stat = nullptr, *lp_last = nullptr, *lp_hist = nullptr;
     int lp_steps = -1;                  // steps of the last pgv_llm_decode_greedy / _sample call that ran with the switch on (-1: it was off)
-    bool s_greedy = false; int g_greedy = 0;     // the run in flight picks the arg-max of the penalised logits (decode_greedy under a penalty)
     bool warmed = false;
 };
 
@@ -364,31 +361,17 @@ extern "C" void pgv_kv_destroy(pgv_kv* kv) {
 extern "C" int pgv_kv_set_warpers(pgv_kv* kv, float top_p, float repetition_penalty) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_warpers: null cache");
     PGV_TRY(pgv_check_warpers("pgv_kv_set_warpers", top_p, repetition_penalty));
-    kv->w_topp = top_p; kv->w_pen = repetition_penalty;
+    kv->warpers.top_p = top_p; kv->warpers.penalty = repetition_penalty;
     return PGV_OK;
 }
 
-// the cache's warpers for a pick on its own slots (rows = slots unless `slot_map` says otherwise); greedy = argmax of the penalised logits
-static SampleWarp kv_warp(pgv_kv* kv, bool greedy, const int* slot_map = nullptr) {
-    SampleWarp w;
-    w.top_p = greedy ? 1.f : kv->w_topp; w.penalty = kv->w_pen;
-    w.seen_bits = kv->d_seen; w.seen_words = kv->seen_words; w.seen_slot = slot_map;
-    return w;
-}
+// a sampled pick on this cache: the caller's temperature and top_k, the cache's warpers
+static PickParams kv_sampled(const pgv_kv* kv, float temperature, int top_k) { return {temperature, top_k, kv->warpers.top_p, kv->warpers.penalty, false}; }
 
 extern "C" int pgv_kv_set_logprobs(pgv_kv* kv, int on) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_logprobs: null cache");
     if (kv->lp_on != (on != 0)) { kv->lp_on = on != 0; kv->lp_steps = -1; }
     return PGV_OK;
-}
-
-// what a pick on the cache's own rows records (rows = slots unless `slot_map` says otherwise); switch off: nothing
-static PickLp kv_lp(pgv_kv* kv, int flags, bool greedy, const int* slot_map = nullptr) {
-    PickLp lp;
-    if (!kv->lp_on) return lp;
-    lp.stat = kv->lp_stat; lp.last_model = kv->lp_last; lp.last_pick = kv->lp_last + kv->B; lp.slot = slot_map; lp.greedy = greedy;
-    if (flags & AM_RECORD) { lp.hist_model = kv->lp_hist; lp.hist_pick = kv->lp_hist + (size_t)kv->B * kv->max_seq; lp.hist_stride = kv->max_seq; }
-    return lp;
 }
 
 extern "C" int pgv_kv_logprobs_last(pgv_kv* kv, float* d_model, float* d_pick, void* stream) {
@@ -442,20 +425,29 @@ static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hip
     return gemv_mat(ctx, m, GV_F32, m->mats[0], kv->xn, kv->logits, V, B, s, &nm);
 }
 
+// Every pick on rows [0, B) of kv->logits.  `sampled` null: the arg-max of the candidates lm_head left; else the sampled pick with those parameters
+// and the uniforms u [B], or u [steps][B] indexed by the device-side step counter (u_by_step).  `st`: the cache's own state (kv_state) or a refill's
+// scratch.  Row b reads the seen-set of slot slot_map[b] (null: b) and, with pgv_kv_set_logprobs on, records its log-probabilities there.
+static PickState kv_state(pgv_kv* kv, int eos, int advance) { return {kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, eos, advance}; }
+static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u, bool u_by_step, const PickState& st, const int* slot_map, hipStream_t s) {
+    const int V = kv->llm->cfg.vocab;
+    PickLp lp;
+    if (kv->lp_on) {
+        lp.stat = kv->lp_stat; lp.last_model = kv->lp_last; lp.last_pick = kv->lp_last + kv->B; lp.slot = slot_map;
+        if (st.advance & AM_RECORD) { lp.hist_model = kv->lp_hist; lp.hist_pick = kv->lp_hist + (size_t)kv->B * kv->max_seq; lp.hist_stride = kv->max_seq; }
+        PGV_TRY(pgv_launch_row_lse(kv->logits, V, V, B, kv->lp_stat, s));
+    }
+    if (!sampled) return pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (V + 15) / 16, kv->amax_ts, V, B, st, s, kv->logits, &lp);
+    SampleWarp w;
+    w.seen_bits = kv->d_seen; w.seen_words = kv->seen_words; w.seen_slot = slot_map;
+    return pgv_launch_sample(kv->logits, V, B, *sampled, u, B, u_by_step, st, s, &w, &lp);
+}
+
 static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos, int flags, hipStream_t s, int nparts) {
-    const int V = m->cfg.vocab;
-    PGV_TRY(lm_head(ctx, m, kv, B, !(flags & AM_SAMPLE), s, nparts));
+    const bool sampled = flags & AM_SAMPLE;
+    PGV_TRY(lm_head(ctx, m, kv, B, !sampled, s, nparts));
     pgv_prof_begin(ctx, 6, s);
-    const PickLp lp = kv_lp(kv, flags, (flags & AM_SAMPLE) && kv->s_greedy);
-    if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, V, V, B, kv->lp_stat, s));
-    if (flags & AM_SAMPLE) {
-        SampleWarp w = kv_warp(kv, false);
-        w.top_p = kv->s_topp; w.penalty = kv->s_pen;
-        PGV_TRY(pgv_launch_sample(kv->logits, V, B, kv->s_temp, kv->s_topk, kv->d_u, B, 1, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
-                                  eos, flags & (AM_INC_POS | AM_RECORD), s, &w, &lp));
-    } else
-        PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (V + 15) / 16, kv->amax_ts, V, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, eos,
-                                        flags, s, kv->logits, &lp));
+    PGV_TRY(kv_pick(kv, B, sampled ? &kv->run : nullptr, kv->d_u, true, kv_state(kv, eos, flags & (AM_INC_POS | AM_RECORD)), nullptr, s));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     return PGV_OK;
 }
@@ -469,14 +461,14 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
 // row of one full prefill over prefix + new tokens.
 // `h_slots` (pgv_llm_prefill_slots): sequence b of the call is a NEW prompt for cache slot h_slots[b] of the live group; the other slots keep their
 // cache rows, lengths, current tokens and flags.  The new rows run through the same kernels (the slot only redirects the cache rows they write and
-// read), the pick lands in rows [0, B) of the scratch and is scattered to the slots: d_u null = greedy, else sampled with d_u[b].
+// read), the pick (`pick`, d_u: as kv_pick takes them; pick->greedy: zeroed uniforms) lands in rows [0, B) of the scratch and is scattered to the slots.
 // `score` (pgv_llm_score): a plain prefill with a scoring tail.  The rows with a target go, PGV_SCORE_CHUNK_ROWS at a time, through the final norm
 // and the lm_head GEMM of the d_all_logits branch into a workspace buffer (so their logits are bit for bit that branch's: the GEMM has one tile
 // shape and no split-K, a row does not depend on M), and logprob_rows (score.hip) reduces every row to (log-probability, logsumexp, argmax).
 struct ScoreReq { const int32_t* h_targets; float* d_logprob; float* d_lse; int32_t* d_argmax; };
 static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video,
                         int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream, bool append,
-                        const int32_t* h_slots = nullptr, float temperature = 0.f, int top_k = 0, const float* d_u = nullptr, const ScoreReq* score = nullptr) {
+                        const int32_t* h_slots = nullptr, const PickParams* pick = nullptr, const float* d_u = nullptr, const ScoreReq* score = nullptr) {
     const bool slots = h_slots != nullptr;
     const char* who = score ? "pgv_llm_score" : append ? "pgv_llm_prefill_append" : slots ? "pgv_llm_prefill_slots" : "pgv_llm_prefill";
     PGV_CHECK(ctx && m && kv && h_ids && h_seq_lens, "%s: null argument", who);
@@ -491,7 +483,7 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
             PGV_CHECK(h_slots[b] >= 0 && h_slots[b] < kv->active, "pgv_llm_prefill_slots: slot %d outside the %d of the live group", h_slots[b], kv->active);
             for (int c = 0; c < b; ++c) PGV_CHECK(h_slots[c] != h_slots[b], "pgv_llm_prefill_slots: slot %d listed twice", h_slots[b]);
         }
-        PGV_CHECK(d_u == nullptr || temperature > 0.f, "pgv_llm_prefill_slots: temperature must be positive (got %g)", (double)temperature);
+        PGV_CHECK(!pick || pick->temperature > 0.f, "pgv_llm_prefill_slots: temperature must be positive (got %g)", (double)pick->temperature);
         PGV_CHECK(d_all_logits == nullptr, "pgv_llm_prefill_slots: no all-position logits");
     }
     hipStream_t s = (hipStream_t)stream;
@@ -625,15 +617,8 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     } else {
         PGV_TRY(lm_head(ctx, m, kv, B, true, s, nparts));           // the greedy candidates too: the same launch as a plain prefill, same logits
         pgv_prof_begin(ctx, 6, s);
-        const SampleWarp w = kv_warp(kv, d_u == nullptr, d_slots);
-        const PickLp lp = kv_lp(kv, 0, d_u == nullptr, d_slots);      // the pick runs in scratch rows [0, B): its values land at the slots
-        if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, vocab, vocab, B, kv->lp_stat, s));
-        if (d_u) PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, temperature, top_k, d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w, &lp));
-        else if (kv->w_pen != 1.f) {        // greedy under a penalty: the pick over the penalised logits with top_k = 1, u = 0 (first index on ties, as the argmax)
-            PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)B * 4, s));
-            PGV_TRY(pgv_launch_sample(kv->logits, vocab, B, 1.f, 1, kv->d_u, B, 0, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w, &lp));
-        } else PGV_TRY(pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (vocab + 15) / 16, kv->amax_ts, vocab, B, d_pick, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s,
-                                               kv->logits, &lp));
+        if (pick && pick->greedy) { d_u = kv->d_u; PGV_TRY(pgv_zero_uniforms(kv->d_u, B, s)); }
+        PGV_TRY(kv_pick(kv, B, pick, d_u, false, PickState{d_pick}, d_slots, s));      // in scratch rows [0, B): what it records lands at the slots
         PGV_TRY(pgv_launch_slot_scatter(d_slots, d_pick, d_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
         pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
@@ -664,14 +649,16 @@ extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
                                      const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k, const float* d_u, float* d_logits,
                                      int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots, "pgv_llm_prefill_slots: null slot list");
-    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, n, d_video, Vt, h_vid_pos, d_logits, d_next, nullptr, 0, stream, false, h_slots, temperature, top_k, d_u);
+    // uniforms: sampled; none: greedy, from the lm_head candidates unless a penalty applies (prefill_impl refuses a null cache)
+    const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);
+    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, n, d_video, Vt, h_vid_pos, d_logits, d_next, nullptr, 0, stream, false, h_slots, !d_u && p.penalty == 1.f ? nullptr : &p, d_u);
 }
 
 extern "C" int pgv_llm_score(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video, int Vt,
                              const int32_t* h_vid_pos, const int32_t* h_targets, float* d_logprob, float* d_lse, int32_t* d_argmax, void* stream) {
     PGV_CHECK(h_targets, "pgv_llm_score: null target list");
     const ScoreReq sc{h_targets, d_logprob, d_lse, d_argmax};
-    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, B, d_video, Vt, h_vid_pos, nullptr, nullptr, nullptr, 0, stream, false, nullptr, 0.f, 0, nullptr, &sc);
+    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, B, d_video, Vt, h_vid_pos, nullptr, nullptr, nullptr, 0, stream, false, nullptr, nullptr, nullptr, &sc);
 }
 
 // Drop the tail of sequence b: the next pgv_llm_prefill_append / decode call continues at position `len` (the entries beyond it are simply
@@ -815,12 +802,10 @@ static bool graphs_enabled() {
 constexpr int kGraphSteps = 8;
 
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s) {
-    const int B = kv->active;
-    if (kv->g_B != B || kv->g_eos != eos || kv->g_flags != flags || kv->g_lp != (int)kv->lp_on || kv->g_gen != m->generation ||
-        ((flags & AM_SAMPLE) && (kv->g_temp != kv->s_temp || kv->g_topk != kv->s_topk || kv->g_topp != kv->s_topp || kv->g_pen != kv->s_pen || kv->g_greedy != (int)kv->s_greedy))) {
+    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run);
+    if (!(kv->gkey == key)) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-        kv->g_B = B; kv->g_eos = eos; kv->g_flags = flags; kv->g_gen = m->generation; kv->g_temp = kv->s_temp; kv->g_topk = kv->s_topk;
-        kv->g_topp = kv->s_topp; kv->g_pen = kv->s_pen; kv->g_lp = kv->lp_on; kv->g_greedy = kv->s_greedy;
+        kv->gkey = key;
     }
     if (!kv->gexec[which]) {
         // capture on a library-owned stream (the caller's may be the legacy default stream, which cannot be
@@ -860,8 +845,6 @@ static int decode_steps(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags
     return PGV_OK;
 }
 
-static int decode_step(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s) { return decode_steps(ctx, m, kv, eos, flags, 1, s); }
-
 static int check_decode(pgv_llm* m, pgv_kv* kv, int steps, const char* who) {
     PGV_CHECK(m && kv && kv->llm == m, "%s: bad model / cache", who);
     if (kv->active < 1) { pgv_set_error("%s: no prefilled sequences in this cache", who); return PGV_ESTATE; }
@@ -876,9 +859,22 @@ extern "C" int pgv_llm_decode(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_
     hipStream_t s = (hipStream_t)stream;
     const int B = kv->active;
     if (d_last != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_last, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    PGV_TRY(decode_step(ctx, m, kv, -1, AM_INC_POS, s));
+    PGV_TRY(decode_steps(ctx, m, kv, -1, AM_INC_POS, 1, s));
     if (d_logits) PGV_HIP(hipMemcpyAsync(d_logits, kv->logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
     if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+// n recorded steps from d_first, picking with *run (null: the arg-max of the lm_head candidates); a run's uniforms are in kv->d_u already
+static int decode_run(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int n, int eos_id, const PickParams* run, int32_t* d_tokens, hipStream_t s) {
+    const int B = kv->active;
+    if (d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
+    if (run) kv->run = *run;
+    PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | (run ? AM_SAMPLE : 0), n, s));
+    kv->lp_steps = kv->lp_on ? n : -1;
+    PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
@@ -887,55 +883,31 @@ extern "C" int pgv_llm_decode_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_CHECK(ctx && d_first && d_tokens, "pgv_llm_decode_greedy: null argument");
     PGV_CHECK(n >= 1, "pgv_llm_decode_greedy: n must be positive");
     PGV_TRY(check_decode(m, kv, n, "pgv_llm_decode_greedy"));
-    hipStream_t s = (hipStream_t)stream;
-    const int B = kv->active;
-    if (d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
-    if (kv->w_pen != 1.f) {
-        // greedy under a repetition penalty (pgv_kv_set_warpers): the argmax candidates of lm_head know no penalty, so the steps run the sampled
-        // pick over the penalised logits with top_k = 1 and u = 0 -- the largest value, the first index on ties
-        PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)n * B * 4, s));
-        kv->s_temp = 1.f; kv->s_topk = 1; kv->s_topp = 1.f; kv->s_pen = kv->w_pen; kv->s_greedy = true;
-        PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | AM_SAMPLE, n, s));
-    } else
-    PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD, n, s));
-    kv->lp_steps = kv->lp_on ? n : -1;
-    PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
+    if (kv->warpers.penalty == 1.f) return decode_run(ctx, m, kv, d_first, n, eos_id, nullptr, d_tokens, (hipStream_t)stream);
+    const PickParams p = pick_greedy(kv->warpers.penalty);
+    PGV_TRY(pgv_zero_uniforms(kv->d_u, (size_t)n * kv->active, (hipStream_t)stream));
+    return decode_run(ctx, m, kv, d_first, n, eos_id, &p, d_tokens, (hipStream_t)stream);
+}
+
+// one pick on the logits the last prefill / decode call left: the cache's state takes the token, nothing advances
+static int pick_last(pgv_kv* kv, const PickParams& p, const float* d_u, int32_t* d_next, hipStream_t s) {
+    PGV_TRY(kv_pick(kv, kv->active, &p, d_u, false, kv_state(kv, -1, 0), nullptr, s));
+    if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
 extern "C" int pgv_llm_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, float temperature, int top_k, const float* d_u, int32_t* d_next, void* stream) {
     PGV_CHECK(ctx && d_u, "pgv_llm_sample: null argument");
-    PGV_CHECK(m && kv && kv->llm == m, "pgv_llm_sample: bad model / cache");
-    if (kv->active < 1) { pgv_set_error("pgv_llm_sample: no prefilled sequences in this cache"); return PGV_ESTATE; }
-    hipStream_t s = (hipStream_t)stream;
-    const int B = kv->active;
-    const SampleWarp w = kv_warp(kv, false);
-    const PickLp lp = kv_lp(kv, 0, false);
-    if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, m->cfg.vocab, m->cfg.vocab, B, kv->lp_stat, s));
-    PGV_TRY(pgv_launch_sample(kv->logits, m->cfg.vocab, B, temperature, top_k, d_u, B, 0, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done,
-                              -1, 0, s, &w, &lp));
-    if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    PGV_HIP(hipGetLastError());
-    return PGV_OK;
+    PGV_TRY(check_decode(m, kv, 0, "pgv_llm_sample"));
+    return pick_last(kv, kv_sampled(kv, temperature, top_k), d_u, d_next, (hipStream_t)stream);
 }
 
 extern "C" int pgv_llm_pick_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int32_t* d_next, void* stream) {
     PGV_CHECK(ctx != nullptr, "pgv_llm_pick_greedy: null argument");
-    PGV_CHECK(m && kv && kv->llm == m, "pgv_llm_pick_greedy: bad model / cache");
-    if (kv->active < 1) { pgv_set_error("pgv_llm_pick_greedy: no prefilled sequences in this cache"); return PGV_ESTATE; }
-    hipStream_t s = (hipStream_t)stream;
-    const int B = kv->active;
-    // the pick over the penalised logits with top_k = 1 and u = 0: the largest value, the first index on ties (as pgv_llm_decode_greedy steps)
-    PGV_HIP(hipMemsetAsync(kv->d_u, 0, (size_t)B * 4, s));
-    const SampleWarp w = kv_warp(kv, true);
-    const PickLp lp = kv_lp(kv, 0, true);
-    if (lp.stat) PGV_TRY(pgv_launch_row_lse(kv->logits, m->cfg.vocab, m->cfg.vocab, B, kv->lp_stat, s));
-    PGV_TRY(pgv_launch_sample(kv->logits, m->cfg.vocab, B, 1.f, 1, kv->d_u, B, 0, kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, -1, 0, s, &w, &lp));
-    if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    PGV_HIP(hipGetLastError());
-    return PGV_OK;
+    PGV_TRY(check_decode(m, kv, 0, "pgv_llm_pick_greedy"));
+    PGV_TRY(pgv_zero_uniforms(kv->d_u, kv->active, (hipStream_t)stream));
+    return pick_last(kv, pick_greedy(kv->warpers.penalty), kv->d_u, d_next, (hipStream_t)stream);      // as pgv_llm_decode_greedy steps under a penalty
 }
 
 extern "C" int pgv_llm_decode_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int n, int eos_id, float temperature, int top_k,
@@ -944,17 +916,9 @@ extern "C" int pgv_llm_decode_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_CHECK(n >= 1, "pgv_llm_decode_sample: n must be positive");
     PGV_CHECK(temperature > 0.f, "pgv_llm_decode_sample: temperature must be positive (got %g)", (double)temperature);
     PGV_TRY(check_decode(m, kv, n, "pgv_llm_decode_sample"));
-    hipStream_t s = (hipStream_t)stream;
-    const int B = kv->active;
-    if (d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
-    PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)n * B * 4, hipMemcpyDeviceToDevice, s));     // n <= max_seq (check_decode)
-    kv->s_temp = temperature; kv->s_topk = top_k; kv->s_topp = kv->w_topp; kv->s_pen = kv->w_pen; kv->s_greedy = false;
-    PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | AM_SAMPLE, n, s));
-    kv->lp_steps = kv->lp_on ? n : -1;
-    PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
-    PGV_HIP(hipGetLastError());
-    return PGV_OK;
+    PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)n * kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));     // n <= max_seq (check_decode)
+    const PickParams p = kv_sampled(kv, temperature, top_k);
+    return decode_run(ctx, m, kv, d_first, n, eos_id, &p, d_tokens, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -2,11 +2,11 @@
 // kernels + launchers): launcher prototypes, mode enums and the few device helpers more than one of them uses.
 #pragma once
 #include "pgv_common.h"
+#include "pick_params.h"
 
 constexpr int kHD = 128;             // LLaMA head_dim
 constexpr int kMaxBatch = 64;        // decode GEMVs: up to 4 MFMA column tiles of 16 sequences per weight fragment
 enum { GV_STORE16 = 0, GV_RESID = 1, GV_SWIGLU = 2, GV_F32 = 3, GV_RESIDNORM = 5 };     // gemv.hip epilogues
-enum { AM_INC_POS = 1, AM_RECORD = 2, AM_SAMPLE = 4 };                                  // sampling.hip bookkeeping flags
 constexpr int kDattnSplitMax = 8, kDattnPart = kHD + 2;                                 // w12.hip
 int pgv_launch_encode_w12(const void* w16_blocked, void* w12, int* counts, long long N, long long K, hipStream_t s);
 // decode_attn.hip: context splits, floats per partial state
@@ -54,9 +54,14 @@ int pgv_launch_unpack_blocked(int dtype, const void* src, float* dst, long long 
 int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const void* rope, void* Kc, void* Vc, void* out, int B, int H,
                            int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket, int split_force);
 // sampling.hip
-// The processors beyond temperature / top-k (null or neutral values: the pick runs without them).  Seen-set of row b: the bitmap of slot
-// seen_slot[b] (null: b) in seen_bits [slots][seen_words] -- the pick then sets the bit of the token it returns -- and / or the id list
-// seen_ids[b * seen_stride .. + seen_lens[b]).  kept [B] (optional): vocabulary entries left with non-zero probability.
+// Where a pick puts the token of row b and what it advances (the defaults: the caller's `next` only).  advance: AM_INC_POS does pos[b]++;
+// AM_RECORD does hist[b * hist_stride + step[b]++] = token and keeps EOS sticky through done[b] (eos < 0: no EOS).
+struct PickState {
+    int* next = nullptr; int* pos = nullptr; int* step = nullptr; int* hist = nullptr; int hist_stride = 0; int* done = nullptr; int eos = -1, advance = 0;
+};
+// The seen-set a sampled pick's repetition penalty reads (top_p / penalty: pgv_launch_sample copies them in from its PickParams, a caller leaves
+// them alone).  Row b: the bitmap of slot seen_slot[b] (null: b) in seen_bits [slots][seen_words] -- the pick then sets the bit of the token it returns --
+// and / or the id list seen_ids[b * seen_stride .. + seen_lens[b]).  kept [B] (optional): vocabulary entries left with non-zero probability.
 struct SampleWarp {
     float top_p = 1.f, penalty = 1.f;
     unsigned* seen_bits = nullptr; int seen_words = 0; const int* seen_slot = nullptr;
@@ -67,8 +72,8 @@ struct SampleWarp {
 // of every raw logit row, written by pgv_launch_row_lse in front of the pick.  Row b's two values -- `model`: x[t] - logsumexp(x); `pick`: the log of
 // the probability the pick used -- go to index slot[b] (null: b) of last_model / last_pick (each may be null) and, when the pick records
 // (AM_RECORD), to hist_model / hist_pick [b * hist_stride + step[b]], next to the token history.  A sticky EOS step (the done flag was set before
-// the pick) stores 0 for both.  greedy: the pick is the arg-max of the penalised logits (top_k = 1, u = 0, temperature 1) and its value their
-// log-softmax over the WHOLE vocabulary, as HF's greedy loop has it -- without a penalty that is `model`, the same float.
+// the pick) stores 0 for both.  greedy: PickParams::greedy, copied in by pgv_launch_sample (a caller leaves it alone) -- without a penalty the
+// `pick` value of such a pick is `model`, the same float.
 struct PickLp {
     const float* stat = nullptr;
     float *last_model = nullptr, *last_pick = nullptr;
@@ -77,14 +82,15 @@ struct PickLp {
     int greedy = 0;
 };
 int pgv_check_warpers(const char* who, float top_p, float penalty);
-int pgv_launch_sample(const float* logits, int V, int B, float temperature, int top_k, const float* u, int u_stride, int u_by_step, int* next, int* pos,
-                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp = nullptr,
-                      const PickLp* lp = nullptr);
+// n zeros: the uniforms of a pick_greedy pick
+inline int pgv_zero_uniforms(float* u, size_t n, hipStream_t s) { PGV_HIP(hipMemsetAsync(u, 0, n * 4, s)); return PGV_OK; }
+int pgv_launch_sample(const float* logits, int V, int B, const PickParams& p, const float* u, int u_stride, int u_by_step, const PickState& st, hipStream_t s,
+                      const SampleWarp* warp = nullptr, const PickLp* lp = nullptr);
 // prefill: ids [M] of B sequences (row ranges cu [B + 1]) -> bitmap of slot slots[b] (null: b); clear = start from an empty set
 int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s);
 // logits [B, V] (row stride V) + lp: also store the log-probability of the pick (both values are `model`: a plain arg-max has no processor)
-int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, int* next, int* pos, int* step, int* hist, int hist_stride, int* done,
-                            int eos, int advance, hipStream_t s, const float* logits = nullptr, const PickLp* lp = nullptr);
+int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, const PickState& st, hipStream_t s, const float* logits = nullptr,
+                            const PickLp* lp = nullptr);
 // pgv_llm_prefill_slots: sequence i of the call becomes slot slots[i] -- cur = pick[i], pos = lens[i], step = done = 0
 int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, int n, int* cur, int* pos, int* step, int* done, hipStream_t s);
 

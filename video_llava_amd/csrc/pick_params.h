@@ -1,0 +1,25 @@
+// The parameters of a token pick and the key of the captured decode graphs that bake them in.  Host-only, plain C++ without HIP headers:
+// llm_internal.h includes it, and tests/test_host_cpu.py compiles it on its own.
+#pragma once
+
+enum { AM_INC_POS = 1, AM_RECORD = 2, AM_SAMPLE = 4 };      // bookkeeping flags of a pick (sampling.hip); AM_SAMPLE: a stepping run picks with PickParams
+
+// HF's processors in HF's order: repetition penalty, temperature, top-k, top-p (the defaults: none of them).  greedy: the pick is the arg-max of
+// the penalised logits and its log-probability their log-softmax over the WHOLE vocabulary, as HF's greedy loop has it.
+struct PickParams {
+    float temperature = 1.f; int top_k = 0; float top_p = 1.f, penalty = 1.f; bool greedy = false;
+    bool operator==(const PickParams& o) const { return temperature == o.temperature && top_k == o.top_k && top_p == o.top_p && penalty == o.penalty && greedy == o.greedy; }
+};
+// Greedy under a repetition penalty: the arg-max candidates of the lm_head GEMV know no penalty, so the pick is the sampled one over the penalised
+// logits with temperature 1, top_k = 1, no nucleus and a uniform of 0 (pgv_zero_uniforms) -- the largest value, the first index on ties.
+inline PickParams pick_greedy(float penalty) { return {1.f, 1, 1.f, penalty, true}; }
+
+// What a captured decode step bakes in besides fixed device addresses (generation: pgv_llm::generation; logprobs: pgv_kv_set_logprobs).  A run
+// without AM_SAMPLE picks from the lm_head candidates and reads no PickParams: its key holds the defaults, whatever an earlier run left in flight.
+struct DecodeGraphKey {
+    int B = 0, eos = 0, flags = 0, generation = -1; bool logprobs = false; PickParams pick;
+    bool operator==(const DecodeGraphKey& o) const { return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick; }
+};
+inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight) {
+    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}};
+}

@@ -475,14 +475,14 @@ static int check_lp(const char* who, const PickLp& lp, int advance) {
     return PGV_OK;
 }
 
-int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, int* next, int* pos, int* step, int* hist, int hist_stride, int* done,
-                            int eos, int advance, hipStream_t s, const float* logits, const PickLp* lp) {
+int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, const PickState& st, hipStream_t s, const float* logits, const PickLp* lp) {
     if (lp && lp->stat) {
         PGV_CHECK(logits != nullptr, "argmax: the log-probabilities need the logits");
-        PGV_TRY(check_lp("argmax", *lp, advance));
-        hipLaunchKernelGGL(argmax_parts_lp_kernel, dim3(B), dim3(256), 0, s, val, idx, nblk, amax_ts, V, next, pos, step, hist, hist_stride, done, eos, advance, logits, *lp);
+        PGV_TRY(check_lp("argmax", *lp, st.advance));
+        hipLaunchKernelGGL(argmax_parts_lp_kernel, dim3(B), dim3(256), 0, s, val, idx, nblk, amax_ts, V, st.next, st.pos, st.step, st.hist, st.hist_stride, st.done, st.eos,
+                           st.advance, logits, *lp);
     } else
-        hipLaunchKernelGGL(argmax_parts_kernel, dim3(B), dim3(256), 0, s, val, idx, nblk, amax_ts, V, next, pos, step, hist, hist_stride, done, eos, advance);
+        hipLaunchKernelGGL(argmax_parts_kernel, dim3(B), dim3(256), 0, s, val, idx, nblk, amax_ts, V, st.next, st.pos, st.step, st.hist, st.hist_stride, st.done, st.eos, st.advance);
     return PGV_OK;
 }
 
@@ -499,21 +499,23 @@ int pgv_check_warpers(const char* who, float top_p, float penalty) {
     return PGV_OK;
 }
 
-int pgv_launch_sample(const float* logits, int V, int B, float temperature, int top_k, const float* u, int u_stride, int u_by_step, int* next, int* pos,
-                      int* step, int* hist, int hist_stride, int* done, int eos, int advance, hipStream_t s, const SampleWarp* warp, const PickLp* lp) {
+int pgv_launch_sample(const float* logits, int V, int B, const PickParams& p, const float* u, int u_stride, int u_by_step, const PickState& st, hipStream_t s,
+                      const SampleWarp* warp, const PickLp* lp) {
     PGV_CHECK(V >= 1 && V <= 16 * 64 * SAMPLE_MAXR, "sample: vocabulary %d outside [1, %d]", V, 16 * 64 * SAMPLE_MAXR);
-    PGV_CHECK(temperature > 0.f, "sample: temperature must be positive (got %g); use the greedy path for temperature 0", (double)temperature);
+    PGV_CHECK(p.temperature > 0.f, "sample: temperature must be positive (got %g); use the greedy path for temperature 0", (double)p.temperature);
     SampleArgsLp a;
     const SampleArgs& plain = a;      // what the two kernels without log-probabilities take
-    a.logits = logits; a.V = V; a.c = 1.4426950408889634f / temperature; a.top_k = top_k; a.u = u; a.u_stride = u_stride; a.u_by_step = u_by_step;
-    a.next = next; a.pos = pos; a.step = step; a.hist = hist; a.hist_stride = hist_stride; a.done = done; a.eos = eos; a.advance = advance;
+    a.logits = logits; a.V = V; a.c = 1.4426950408889634f / p.temperature; a.top_k = p.top_k; a.u = u; a.u_stride = u_stride; a.u_by_step = u_by_step;
+    a.next = st.next; a.pos = st.pos; a.step = st.step; a.hist = st.hist; a.hist_stride = st.hist_stride; a.done = st.done; a.eos = st.eos; a.advance = st.advance;
     a.w = warp ? *warp : SampleWarp{};
+    a.w.top_p = p.top_p; a.w.penalty = p.penalty;
     a.lp = (lp && lp->stat) ? *lp : PickLp{};
-    if (a.lp.stat) PGV_TRY(check_lp("sample", a.lp, advance));
+    a.lp.greedy = p.greedy;
+    if (a.lp.stat) PGV_TRY(check_lp("sample", a.lp, st.advance));
     // the neutral values run the kernel without the two extra processors: bit for bit the tokens of the temperature / top-k chain alone
-    if (warp && (warp->top_p < 1.f || warp->penalty != 1.f || warp->kept)) {
-        PGV_TRY(pgv_check_warpers("sample", warp->top_p, warp->penalty));
-        PGV_CHECK(warp->seen_bits == nullptr || warp->seen_words * 32 >= V, "sample: seen-set bitmap of %d words for a vocabulary of %d", warp->seen_words, V);
+    if (p.top_p < 1.f || p.penalty != 1.f || a.w.kept) {
+        PGV_TRY(pgv_check_warpers("sample", p.top_p, p.penalty));
+        PGV_CHECK(a.w.seen_bits == nullptr || a.w.seen_words * 32 >= V, "sample: seen-set bitmap of %d words for a vocabulary of %d", a.w.seen_words, V);
         if (a.lp.stat) hipLaunchKernelGGL((sample_kernel<true, true>), dim3(B), dim3(1024), 0, s, a);
         else hipLaunchKernelGGL(sample_kernel<true>, dim3(B), dim3(1024), 0, s, plain);
     } else if (a.lp.stat) {        // neutral processors: the same weights, total and token as sample_kernel<false>
@@ -524,17 +526,23 @@ int pgv_launch_sample(const float* logits, int V, int B, float temperature, int 
     return PGV_OK;
 }
 
+// the pick of the three building blocks: the seen-set as id lists (none: no penalty applies), the token to d_next and nothing advanced
+static int sample_ids(const float* d_logits, int V, int B, const PickParams& p, const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u,
+                      int32_t* d_next, int32_t* d_kept, const PickLp* lp, hipStream_t s) {
+    SampleWarp w;
+    w.seen_ids = d_seen_ids; w.seen_stride = seen_stride; w.seen_lens = d_seen_lens; w.kept = d_kept;
+    PGV_TRY(pgv_launch_sample(d_logits, V, B, p, d_u, B, 0, PickState{d_next}, s, &w, lp));
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
 extern "C" int pgv_sample_logits_ex(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
                                     const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u, int32_t* d_next, int32_t* d_kept,
                                     void* stream) {
     PGV_CHECK(ctx && d_logits && d_u && d_next && B >= 1, "pgv_sample_logits_ex: bad arguments");
     PGV_CHECK((d_seen_ids == nullptr) == (d_seen_lens == nullptr) && seen_stride >= 0, "pgv_sample_logits_ex: d_seen_ids and d_seen_lens go together");
     PGV_TRY(pgv_check_warpers("pgv_sample_logits_ex", top_p, repetition_penalty));
-    SampleWarp w;
-    w.top_p = top_p; w.penalty = repetition_penalty; w.seen_ids = d_seen_ids; w.seen_stride = seen_stride; w.seen_lens = d_seen_lens; w.kept = d_kept;
-    PGV_TRY(pgv_launch_sample(d_logits, V, B, temperature, top_k, d_u, B, 0, d_next, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, (hipStream_t)stream, &w));
-    PGV_HIP(hipGetLastError());
-    return PGV_OK;
+    return sample_ids(d_logits, V, B, {temperature, top_k, top_p, repetition_penalty}, d_seen_ids, seen_stride, d_seen_lens, d_u, d_next, d_kept, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pgv_sample_logits_lp(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
@@ -542,22 +550,19 @@ extern "C" int pgv_sample_logits_lp(pgv_ctx* ctx, const float* d_logits, int V, 
                                     int greedy, float* d_lp_model, float* d_lp_pick, void* stream) {
     PGV_CHECK(ctx && d_logits && (d_u || greedy) && d_next && B >= 1, "pgv_sample_logits_lp: bad arguments");
     PGV_CHECK((d_seen_ids == nullptr) == (d_seen_lens == nullptr) && seen_stride >= 0, "pgv_sample_logits_lp: d_seen_ids and d_seen_lens go together");
-    if (greedy) { temperature = 1.f; top_k = 1; top_p = 1.f; }
-    PGV_TRY(pgv_check_warpers("pgv_sample_logits_lp", top_p, repetition_penalty));
+    const PickParams p = greedy ? pick_greedy(repetition_penalty) : PickParams{temperature, top_k, top_p, repetition_penalty};
+    PGV_TRY(pgv_check_warpers("pgv_sample_logits_lp", p.top_p, p.penalty));
     hipStream_t s = (hipStream_t)stream;
-    // row statistics [B][2] and, for the greedy form, B uniforms of 0 (top_k = 1, u = 0: the first index of the largest penalised logit)
+    // row statistics [B][2] and, for the greedy form, its B uniforms
     PGV_TRY(pgv_ws_reserve(ctx, 2 * pgv_align((size_t)B * 8), s));
     float* stat = (float*)pgv_ws_alloc(ctx, (size_t)B * 8);
     float* zero = (float*)pgv_ws_alloc(ctx, (size_t)B * 4);
     PGV_CHECK(stat && zero, "pgv_sample_logits_lp: workspace exhausted");
-    if (greedy) PGV_HIP(hipMemsetAsync(zero, 0, (size_t)B * 4, s));
+    if (greedy) PGV_TRY(pgv_zero_uniforms(zero, B, s));
     PGV_TRY(pgv_launch_row_lse(d_logits, V, V, B, stat, s));
-    SampleWarp w;
-    w.top_p = top_p; w.penalty = repetition_penalty; w.seen_ids = d_seen_ids; w.seen_stride = seen_stride; w.seen_lens = d_seen_lens; w.kept = d_kept;
     PickLp lp;
-    lp.stat = stat; lp.last_model = d_lp_model; lp.last_pick = d_lp_pick; lp.greedy = greedy != 0;
-    PGV_TRY(pgv_launch_sample(d_logits, V, B, temperature, top_k, greedy ? zero : d_u, B, 0, d_next, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, s, &w, &lp));
-    PGV_HIP(hipGetLastError());
+    lp.stat = stat; lp.last_model = d_lp_model; lp.last_pick = d_lp_pick;
+    PGV_TRY(sample_ids(d_logits, V, B, p, d_seen_ids, seen_stride, d_seen_lens, greedy ? zero : d_u, d_next, d_kept, &lp, s));
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
 }
@@ -565,7 +570,5 @@ extern "C" int pgv_sample_logits_lp(pgv_ctx* ctx, const float* d_logits, int V, 
 extern "C" int pgv_sample_logits(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, const float* d_u, int32_t* d_next,
                                  void* stream) {
     PGV_CHECK(ctx && d_logits && d_u && d_next && B >= 1, "pgv_sample_logits: bad arguments");
-    PGV_TRY(pgv_launch_sample(d_logits, V, B, temperature, top_k, d_u, B, 0, d_next, nullptr, nullptr, nullptr, 0, nullptr, -1, 0, (hipStream_t)stream));
-    PGV_HIP(hipGetLastError());
-    return PGV_OK;
+    return sample_ids(d_logits, V, B, {temperature, top_k}, nullptr, 0, nullptr, d_u, d_next, nullptr, nullptr, (hipStream_t)stream);
 }
