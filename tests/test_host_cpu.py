@@ -824,6 +824,182 @@ int main() {
         assert r.returncode == 0 and not r.stderr and r.stdout == "OK 10\n", (x, r.returncode, r.stdout, r.stderr[-2000:])
 
 
+def test_prefill_plan_row_maps_and_refusals(tmp_path):
+    """csrc/prefill_plan.h, compiled on its own with g++ (it must need no HIP header), owns the int block of row maps a prefill uploads: (1) the
+    section offsets and the total for (M, B, nscore), the same accessor over a mutable and a const base; (2) every section of the built block,
+    element by element against arrays written out below by hand, for a plain call, one with a video run (a placeholder id beyond the vocabulary is
+    accepted on a video row and kept in raw_ids), an appended one (positions, lengths and the attention FLOP count behind a cached prefix), a
+    refill into slots, a scored one (-1 / -100 targets skipped; srows / stgts follow raw_ids) and the id-less form of pgv_prefill_attention;
+    (3) every refusal of the loops prefill_impl had, with its message and class, the accepted neighbour of each bound next to it.  Where g++ has
+    the sanitizer runtimes the same stand-alone program runs a second time under ASan + UBSan."""
+    import shutil
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    csrc = os.path.join(ROOT, "video_llava_amd", "csrc")
+    prog = r"""#include <cstdio>
+#include <cstring>
+#include <initializer_list>
+#include "prefill_plan.h"
+static int bad = 0;
+#define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); bad = 1; } } while (0)
+typedef std::initializer_list<int> L;
+// section `off` of the block holds exactly `want` up to the next section `end`
+static bool sec(const std::vector<int>& meta, size_t off, size_t end, L want) {
+    if (end - off != want.size() || end > meta.size()) return false;
+    size_t i = off;
+    for (int v : want) if (meta[i++] != v) return false;
+    return true;
+}
+static const int lens35[2] = {3, 5}, ids8[8] = {5, 6, 7, 8, 9, 10, 11, 12};
+static PrefillRows rows35(const int* ids) {
+    PrefillRows r;
+    r.who = "who"; r.ids = ids; r.seq_lens = lens35; r.B = 2; r.vocab = 20; r.max_seq = 16; r.hidden = 4;
+    return r;
+}
+static std::vector<int> meta;
+static PrefillPlan plan;
+static char err[256];
+static bool ok(const PrefillRows& r) { err[0] = 0; return prefill_plan_build(r, meta, plan, err, sizeof(err)) == PLAN_OK && !err[0]; }
+static bool refused(const PrefillRows& r, const char* msg) {
+    err[0] = 0;
+    const bool hit = prefill_plan_build(r, meta, plan, err, sizeof(err)) == PLAN_EINVAL && !strncmp(err, "who: ", 5) && strstr(err, msg);
+    if (!hit) printf("got \"%s\", want \"%s\"\n", err, msg);
+    return hit;
+}
+int main() {
+    {   // layout: row_src | row_b | row_pos | cu | last | lens | offs | slots | raw_ids | srows | stgts
+        const PrefillLayout lo(8, 2, 5);
+        EXPECT(lo.row_src == 0 && lo.row_b == 8 && lo.row_pos == 16 && lo.cu == 24 && lo.last == 27 && lo.lens == 29 && lo.offs == 31 && lo.slots == 33);
+        EXPECT(lo.raw_ids == 35 && lo.srows == 43 && lo.stgts == 48 && lo.total == 53);
+        int base[53];
+        const PrefillMaps<int> a = lo.maps(base);
+        const PrefillMaps<const int> c = lo.maps((const int*)base);
+        EXPECT(a.row_src == base && a.row_b == base + 8 && a.row_pos == base + 16 && a.cu == base + 24 && a.last == base + 27 && a.lens == base + 29);
+        EXPECT(a.offs == base + 31 && a.slots == base + 33 && a.raw_ids == base + 35 && a.srows == base + 43 && a.stgts == base + 48);
+        EXPECT(c.row_src == a.row_src && c.row_b == a.row_b && c.row_pos == a.row_pos && c.cu == a.cu && c.last == a.last && c.lens == a.lens);
+        EXPECT(c.offs == a.offs && c.slots == a.slots && c.raw_ids == a.raw_ids && c.srows == a.srows && c.stgts == a.stgts);
+        EXPECT(PrefillLayout(0, 0, 0).total == 1 && PrefillLayout(1, 1, 0).total == 10);
+    }
+    {   // plain
+        EXPECT(ok(rows35(ids8)));
+        const PrefillLayout& lo = plan.lo;
+        EXPECT(plan.M == 8 && plan.max_len == 5 && plan.nscore == 0 && lo.total == 4 * 8 + 5 * 2 + 1 && meta.size() == 43);
+        EXPECT(sec(meta, lo.row_src, lo.row_b, {5, 6, 7, 8, 9, 10, 11, 12}));
+        EXPECT(sec(meta, lo.row_b, lo.row_pos, {0, 0, 0, 1, 1, 1, 1, 1}));
+        EXPECT(sec(meta, lo.row_pos, lo.cu, {0, 1, 2, 0, 1, 2, 3, 4}));
+        EXPECT(sec(meta, lo.cu, lo.last, {0, 3, 8}) && sec(meta, lo.last, lo.lens, {2, 7}) && sec(meta, lo.lens, lo.offs, {3, 5}));
+        EXPECT(sec(meta, lo.offs, lo.slots, {0, 0}) && sec(meta, lo.slots, lo.raw_ids, {0, 1}));
+        EXPECT(sec(meta, lo.raw_ids, lo.srows, {5, 6, 7, 8, 9, 10, 11, 12}) && sec(meta, lo.srows, lo.stgts, {}) && sec(meta, lo.stgts, lo.total, {}));
+        EXPECT(plan.attn_flops == 2.0 * 3 * 3 * 4 + 2.0 * 5 * 5 * 4);
+    }
+    {   // video: sequence 0 has none, sequence 1 its 2 rows behind row 1; the placeholder id 25 is beyond the vocabulary of 20
+        const int ids[8] = {5, 6, 7, 8, 9, 25, 19, 12}, vp[2] = {-1, 1};
+        PrefillRows r = rows35(ids);
+        r.vid_pos = vp; r.Vt = 2;
+        EXPECT(ok(r));
+        const PrefillLayout& lo = plan.lo;
+        EXPECT(lo.total == 43 && sec(meta, lo.row_src, lo.row_b, {5, 6, 7, 8, 9, -3, -4, 12}));
+        EXPECT(sec(meta, lo.raw_ids, lo.srows, {5, 6, 7, 8, 9, 25, 19, 12}));
+        EXPECT(sec(meta, lo.row_b, lo.row_pos, {0, 0, 0, 1, 1, 1, 1, 1}) && sec(meta, lo.row_pos, lo.cu, {0, 1, 2, 0, 1, 2, 3, 4}));
+        const int late[2] = {-1, 2};            // 2 + 2 + 1 rows do not fit in front of the last of 5
+        r.vid_pos = late;
+        EXPECT(refused(r, "video run of sequence 1 (start 2, 2 rows) overruns its 5 tokens"));
+        const int vp0[2] = {0, -1};             // the same id on a row outside the run
+        r.vid_pos = vp0; r.Vt = 1;
+        EXPECT(refused(r, "token id 25 at row 5 outside the vocabulary (20)"));
+    }
+    {   // append behind prefixes of 4 and 0 positions
+        const int start[2] = {4, 0};
+        PrefillRows r = rows35(ids8);
+        r.start = start;
+        EXPECT(ok(r));
+        const PrefillLayout& lo = plan.lo;
+        EXPECT(sec(meta, lo.row_pos, lo.cu, {4, 5, 6, 0, 1, 2, 3, 4}) && sec(meta, lo.lens, lo.offs, {7, 5}) && sec(meta, lo.offs, lo.slots, {4, 0}));
+        EXPECT(sec(meta, lo.cu, lo.last, {0, 3, 8}) && sec(meta, lo.last, lo.lens, {2, 7}) && sec(meta, lo.row_b, lo.row_pos, {0, 0, 0, 1, 1, 1, 1, 1}));
+        EXPECT(plan.attn_flops == 2.0 * 3 * (3 + 2 * 4) * 4 + 2.0 * 5 * 5 * 4 && plan.attn_flops == 464.0);
+        const int full[2] = {13, 11}, over[2] = {14, 0};
+        r.start = full;
+        EXPECT(ok(r) && sec(meta, plan.lo.lens, plan.lo.offs, {16, 16}));
+        r.start = over;
+        EXPECT(refused(r, "sequence 0 has 14 + 3 tokens (cache holds 16)"));
+        const int neg[2] = {0, -1};
+        r.start = neg;
+        EXPECT(refused(r, "sequence 1 has -1 + 5 tokens (cache holds 16)"));
+    }
+    {   // slots of a live group of 3
+        const int slots[2] = {2, 0}, out[2] = {3, 0}, below[2] = {0, -1}, twice[2] = {1, 1};
+        PrefillRows r = rows35(ids8);
+        r.slots = slots; r.active = 3;
+        EXPECT(ok(r));
+        const PrefillLayout& lo = plan.lo;
+        EXPECT(sec(meta, lo.row_b, lo.row_pos, {2, 2, 2, 0, 0, 0, 0, 0}) && sec(meta, lo.slots, lo.raw_ids, {2, 0}) && sec(meta, lo.cu, lo.last, {0, 3, 8}));
+        r.slots = out;
+        EXPECT(refused(r, "slot 3 outside the 3 of the live group"));
+        r.slots = below;
+        EXPECT(refused(r, "slot -1 outside the 3 of the live group"));
+        r.slots = twice;
+        EXPECT(refused(r, "slot 1 listed twice"));
+    }
+    {   // score: five rows have a target
+        const int tg[8] = {-1, 6, 7, -1, -100, 10, 19, 0};
+        PrefillRows r = rows35(ids8);
+        r.targets = tg;
+        EXPECT(ok(r));
+        const PrefillLayout& lo = plan.lo;
+        EXPECT(plan.nscore == 5 && lo.total == 4 * 8 + 5 * 2 + 1 + 2 * 5 && lo.srows == lo.raw_ids + 8 && lo.stgts == lo.srows + 5 && lo.total == lo.stgts + 5);
+        EXPECT(sec(meta, lo.srows, lo.stgts, {1, 2, 5, 6, 7}) && sec(meta, lo.stgts, lo.total, {6, 7, 10, 19, 0}));
+        EXPECT(sec(meta, lo.raw_ids, lo.srows, {5, 6, 7, 8, 9, 10, 11, 12}) && sec(meta, lo.row_src, lo.row_b, {5, 6, 7, 8, 9, 10, 11, 12}));
+        const int tg_out[8] = {-1, 6, 20, -1, -100, 10, 19, 0};
+        r.targets = tg_out;
+        EXPECT(refused(r, "target 20 of row 2 outside the vocabulary (20)"));
+    }
+    {   // lengths and token ids
+        const int zero[2] = {3, 0};
+        PrefillRows r = rows35(ids8);
+        r.seq_lens = zero;
+        EXPECT(refused(r, "sequence 1 has 0 + 0 tokens (cache holds 16)"));
+        const int minus[8] = {-1, 6, 7, 8, 9, 10, 11, 12}, at_vocab[8] = {5, 6, 7, 8, 9, 10, 11, 20}, top[8] = {0, 6, 7, 8, 9, 10, 11, 19};
+        EXPECT(refused(rows35(minus), "token id -1 at row 0 outside the vocabulary (20)"));
+        EXPECT(refused(rows35(at_vocab), "token id 20 at row 7 outside the vocabulary (20)"));
+        EXPECT(ok(rows35(top)));
+        char tiny[8];                           // a short message buffer is not overrun
+        EXPECT(prefill_plan_build(rows35(minus), meta, plan, tiny, sizeof(tiny)) == PLAN_EINVAL && !strcmp(tiny, "who: to"));
+    }
+    {   // the id-less form of pgv_prefill_attention
+        const int lens[2] = {2, 1}, start[2] = {3, 0};
+        PrefillRows r;
+        r.who = "who"; r.seq_lens = lens; r.B = 2; r.start = start; r.max_seq = 8; r.hidden = 4;
+        EXPECT(ok(r));
+        const PrefillLayout& lo = plan.lo;
+        EXPECT(plan.M == 3 && plan.max_len == 2 && plan.nscore == 0 && lo.total == 4 * 3 + 5 * 2 + 1);
+        EXPECT(sec(meta, lo.row_b, lo.row_pos, {0, 0, 1}) && sec(meta, lo.row_pos, lo.cu, {3, 4, 0}) && sec(meta, lo.cu, lo.last, {0, 2, 3}));
+        EXPECT(sec(meta, lo.offs, lo.slots, {3, 0}) && sec(meta, lo.lens, lo.offs, {5, 1}) && sec(meta, lo.last, lo.lens, {1, 2}));
+        EXPECT(sec(meta, lo.row_src, lo.row_b, {0, 0, 0}) && sec(meta, lo.raw_ids, lo.srows, {0, 0, 0}));
+        EXPECT(plan.attn_flops == 2.0 * 2 * (2 + 2 * 3) * 4 + 2.0 * 1 * 1 * 4);
+    }
+    if (!bad) printf("OK\n");
+    return bad;
+}
+"""
+    cpp, exe, exe_san = tmp_path / "plan.cpp", tmp_path / "plan", tmp_path / "plan_san"
+    cpp.write_text(prog)
+    base = [gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", csrc, str(cpp)]
+    subprocess.run([*base, "-o", str(exe)], check=True)
+    exes = [exe]
+    san = subprocess.run([*base, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe_san)], capture_output=True, text=True)
+    if san.returncode == 0:
+        exes.append(exe_san)
+    else:
+        assert "asan" in san.stderr or "ubsan" in san.stderr, san.stderr        # only a missing sanitizer runtime excuses the second build
+        print("g++ has no sanitizer runtimes here: plain build only")
+    for x in exes:
+        r = subprocess.run([str(x)], capture_output=True, text=True)
+        assert r.returncode == 0 and not r.stderr and r.stdout == "OK\n", (x, r.returncode, r.stdout, r.stderr[-2000:])
+    # nothing but llm.hip builds row maps
+    users = [f for f in sorted(os.listdir(csrc)) if '#include "prefill_plan.h"' in open(os.path.join(csrc, f)).read()]
+    assert users == ["llm.hip"], users
+
+
 # --------------------------------------------------------------------------------------------------
 # offline feature extraction (scripts/save_spatio_temporal_clip_features.py) and the QA runner: host logic
 # --------------------------------------------------------------------------------------------------

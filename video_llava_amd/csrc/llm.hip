@@ -7,6 +7,7 @@
 
 #include "llm_internal.h"
 #include "llm_weights.h"
+#include "prefill_plan.h"
 #include "w12.h"
 #include "weights.h"
 
@@ -465,150 +466,165 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
 // `score` (pgv_llm_score): a plain prefill with a scoring tail.  The rows with a target go, PGV_SCORE_CHUNK_ROWS at a time, through the final norm
 // and the lm_head GEMM of the d_all_logits branch into a workspace buffer (so their logits are bit for bit that branch's: the GEMM has one tile
 // shape and no split-K, a row does not depend on M), and logprob_rows (score.hip) reduces every row to (log-probability, logsumexp, argmax).
+// The row maps every stage reads (which row is which token or video row, of which sequence, at which position, in which slot) are one int block:
+// prefill_plan.h owns its layout and the loops that fill and check it; the host staging copy and the device copy are read through the same accessor.
 struct ScoreReq { const int32_t* h_targets; float* d_logprob; float* d_lse; int32_t* d_argmax; };
-static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video,
-                        int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream, bool append,
-                        const int32_t* h_slots = nullptr, const PickParams* pick = nullptr, const float* d_u = nullptr, const ScoreReq* score = nullptr) {
-    const bool slots = h_slots != nullptr;
-    const char* who = score ? "pgv_llm_score" : append ? "pgv_llm_prefill_append" : slots ? "pgv_llm_prefill_slots" : "pgv_llm_prefill";
-    PGV_CHECK(ctx && m && kv && h_ids && h_seq_lens, "%s: null argument", who);
+enum PrefillMode { PREFILL_PLAIN, PREFILL_APPEND, PREFILL_SLOTS, PREFILL_SCORE };
+// One prefill call as its entry point states it; what a mode does not use stays null.
+struct PrefillReq {
+    const char* who = nullptr; PrefillMode mode = PREFILL_PLAIN;
+    const int32_t *h_ids = nullptr, *h_seq_lens = nullptr; int B = 0;                                  // the token rows
+    const void* d_video = nullptr; int Vt = 0; const int32_t* h_vid_pos = nullptr;                     // the optional video
+    float* d_logits = nullptr; int32_t* d_next = nullptr; float* d_all_logits = nullptr; int ld_all = 0;
+    const int32_t* h_slots = nullptr; const PickParams* pick = nullptr; const float* d_u = nullptr;    // PREFILL_SLOTS
+    ScoreReq score{};                                                                                  // PREFILL_SCORE
+};
+// What the stages hand on: the plan, the two views of its block (kv->h_meta, the device copy) and the workspace buffers.
+struct PrefillWork {
+    PrefillPlan plan;
+    PrefillMaps<const int> h, d;
+    const int *d_offs, *d_slots;         // d.offs / d.slots for the calls whose kernels read them (append / slots), else null
+    float* resid; char *xn, *qkv, *ao, *act;
+    int* d_pick;                         // the refilled sequences' first tokens, before they go to their slots
+    int schunk; float* sres; char* sxn; float* slog;     // scoring tail: gathered residual rows, their normalised 16-bit form and the fp32 logits of one chunk
+};
+// prefill_plan_build with its refusal forwarded as this library reports errors
+static int plan_build(const PrefillRows& rows, std::vector<int>& meta, PrefillPlan& plan) {
+    char err[512];
+    if (prefill_plan_build(rows, meta, plan, err, sizeof(err)) != PLAN_OK) { pgv_set_error("%s", err); return PGV_EINVAL; }
+    return PGV_OK;
+}
+static int vocab16(const pgv_llm* m) { return (m->cfg.vocab + 15) & ~15; }      // the lm_head rows a GEMM computes: whole 16-row fragments
+
+// One prefill GEMM over a matrix's 16-bit blocked copy, the twin of gemv_mat: C [rows][ldc] = epi(A [rows][K] * W[0, N)^T)
+static int gemm_mat(pgv_ctx* ctx, const pgv_llm* m, const LlmMat& w, int N, const void* A, void* C, int ldc, int rows, int epi, hipStream_t s) {
+    GemmArgs g{};
+    g.A = A; g.lda = (int)w.K; g.W = w.w16; g.ldw = (int)w.K; g.bias = nullptr; g.C = C; g.ldc = ldc; g.M = rows; g.N = N; g.K = (int)w.K; g.epi = epi; g.w_blocked = true;
+    return pgv_launch_gemm(ctx, m->dtype, g, s);
+}
+// Final RMSNorm of `rows` residual rows into the 16-bit buffer x16, then lm_head to fp32 logits [rows][ld >= vocab16]: one tile shape, no
+// split-K, so a row's logits do not depend on which rows go with it
+static int head_logits(pgv_ctx* ctx, const pgv_llm* m, const float* resid, void* x16, int rows, float* logits, int ld, hipStream_t s) {
+    PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, m->norm_g, m->cfg.eps, x16, rows, m->cfg.hidden, s));
+    return gemm_mat(ctx, m, m->mats[0], vocab16(m), x16, logits, ld, rows, PGV_EPI_F32, s);
+}
+
+static int prefill_check(const pgv_ctx* ctx, const pgv_llm* m, const pgv_kv* kv, const PrefillReq& q) {
+    const char* who = q.who;
+    PGV_CHECK(ctx && m && kv && q.h_ids && q.h_seq_lens, "%s: null argument", who);
     PGV_CHECK(kv->llm == m, "%s: kv cache belongs to another model", who);
-    PGV_CHECK(B >= 1 && B <= kv->B, "%s: batch %d outside [1,%d]", who, B, kv->B);
+    PGV_CHECK(q.B >= 1 && q.B <= kv->B, "%s: batch %d outside [1,%d]", who, q.B, kv->B);
     if (pgv_llm_missing(m) != 0) { pgv_set_error("%s: %d weight tensors not loaded", who, pgv_llm_missing(m)); return PGV_ESTATE; }
-    if (append && kv->active != B) { pgv_set_error("pgv_llm_prefill_append: %d sequences for a cache that holds %d prefilled ones", B, kv->active); return PGV_ESTATE; }
-    if (slots) {
+    if (q.mode == PREFILL_APPEND && kv->active != q.B) { pgv_set_error("pgv_llm_prefill_append: %d sequences for a cache that holds %d prefilled ones", q.B, kv->active); return PGV_ESTATE; }
+    if (q.mode == PREFILL_SLOTS) {
         if (kv->active < 1) { pgv_set_error("pgv_llm_prefill_slots: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
-        PGV_CHECK(B <= kv->active, "pgv_llm_prefill_slots: %d sequences for a group of %d", B, kv->active);
-        for (int b = 0; b < B; ++b) {
-            PGV_CHECK(h_slots[b] >= 0 && h_slots[b] < kv->active, "pgv_llm_prefill_slots: slot %d outside the %d of the live group", h_slots[b], kv->active);
-            for (int c = 0; c < b; ++c) PGV_CHECK(h_slots[c] != h_slots[b], "pgv_llm_prefill_slots: slot %d listed twice", h_slots[b]);
-        }
-        PGV_CHECK(!pick || pick->temperature > 0.f, "pgv_llm_prefill_slots: temperature must be positive (got %g)", (double)pick->temperature);
-        PGV_CHECK(d_all_logits == nullptr, "pgv_llm_prefill_slots: no all-position logits");
+        PGV_CHECK(q.B <= kv->active, "pgv_llm_prefill_slots: %d sequences for a group of %d", q.B, kv->active);
+        PGV_CHECK(!q.pick || q.pick->temperature > 0.f, "pgv_llm_prefill_slots: temperature must be positive (got %g)", (double)q.pick->temperature);
+        PGV_CHECK(q.d_all_logits == nullptr, "pgv_llm_prefill_slots: no all-position logits");
     }
-    hipStream_t s = (hipStream_t)stream;
-    const int H = m->cfg.hidden, I = m->cfg.inter, heads = m->cfg.heads, vocab = m->cfg.vocab;
-    int M = 0, max_len = 0;
-    for (int b = 0; b < B; ++b) {
-        const int off = append ? kv->h_len[b] : 0;
-        PGV_CHECK(h_seq_lens[b] >= 1 && off + h_seq_lens[b] <= kv->max_seq, "%s: sequence %d has %d + %d tokens (cache holds %d)", who, b, off, h_seq_lens[b], kv->max_seq);
-        M += h_seq_lens[b];
-        if (h_seq_lens[b] > max_len) max_len = h_seq_lens[b];
-    }
-    int nscore = 0;                                             // rows with a target (pgv_llm_score)
-    if (score) PGV_CHECK(((vocab + 15) & ~15) <= m->vocab_cap, "%s: vocabulary %d beyond the %d allocated lm_head rows", who, vocab, m->vocab_cap);
-    if (score)
-        for (int r = 0; r < M; ++r) {
-            PGV_CHECK(score->h_targets[r] < vocab, "%s: target %d of row %d outside the vocabulary (%d)", who, score->h_targets[r], r, vocab);
-            nscore += score->h_targets[r] >= 0;
-        }
-    // ---- host-built row maps: [row_src | row_b | row_pos | cu (B+1) | last_rows (B) | lens (B) = positions after this call | offs (B) | slots (B)] ----
-    std::vector<int>& meta = kv->h_meta;
-    meta.assign((size_t)4 * M + 5 * B + 1 + 2 * nscore, 0);     // + the ids as given [M], for the seen-set (pgv_launch_seen_mark); + scored rows, their targets
-    int* row_src = meta.data(); int* row_b = row_src + M; int* row_pos = row_b + M; int* cu = row_pos + M; int* last = cu + B + 1; int* lens = last + B; int* offs = lens + B;
-    int* slot = offs + B;
-    int* raw_ids = slot + B;
-    int* srows = raw_ids + M; int* stgts = srows + nscore;
-    for (int i = 0, k = 0; score && i < M; ++i)
-        if (score->h_targets[i] >= 0) { srows[k] = i; stgts[k++] = score->h_targets[i]; }
-    int r = 0;
-    for (int b = 0; b < B; ++b) {
-        cu[b] = r;
-        const int off = append ? kv->h_len[b] : 0;
-        const int vp = (d_video && h_vid_pos) ? h_vid_pos[b] : -1;
-        if (vp >= 0) PGV_CHECK(vp + Vt + 1 < h_seq_lens[b], "%s: video run of sequence %d (start %d, %d rows) overruns its %d tokens", who, b, vp, Vt, h_seq_lens[b]);
-        for (int p = 0; p < h_seq_lens[b]; ++p, ++r) {
-            const int id = h_ids[r];
-            const bool vid = vp >= 0 && p > vp && p <= vp + Vt;
-            if (!vid) PGV_CHECK(id >= 0 && id < vocab, "%s: token id %d at row %d outside the vocabulary (%d)", who, id, r, vocab);
-            row_src[r] = vid ? -(b * Vt + (p - vp - 1) + 1) : id;
-            raw_ids[r] = id;
-            row_b[r] = slots ? h_slots[b] : b; row_pos[r] = off + p;
-        }
-        last[b] = r - 1; lens[b] = off + h_seq_lens[b]; offs[b] = off; slot[b] = slots ? h_slots[b] : b;
-    }
-    cu[B] = r;
+    if (q.mode == PREFILL_SCORE) PGV_CHECK(vocab16(m) <= m->vocab_cap, "%s: vocabulary %d beyond the %d allocated lm_head rows", who, m->cfg.vocab, m->vocab_cap);
+    return PGV_OK;
+}
+
+// Builds the plan into kv->h_meta (it outlives the async copy), reserves the workspace and uploads the block; resets what a new prompt resets.
+static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& q, PrefillWork& w, hipStream_t s) {
+    const bool append = q.mode == PREFILL_APPEND, slots = q.mode == PREFILL_SLOTS;
+    const int B = q.B, H = m->cfg.hidden, I = m->cfg.inter, vocab = m->cfg.vocab;
+    const char* who = q.who;
+    PrefillRows rows;
+    rows.who = who; rows.ids = q.h_ids; rows.seq_lens = q.h_seq_lens; rows.B = B;
+    rows.start = append ? kv->h_len.data() : nullptr;
+    rows.slots = q.h_slots; rows.active = kv->active;
+    rows.vid_pos = q.d_video ? q.h_vid_pos : nullptr; rows.Vt = q.Vt;
+    rows.targets = q.score.h_targets;
+    rows.vocab = vocab; rows.max_seq = kv->max_seq; rows.hidden = H;
+    PGV_TRY(plan_build(rows, kv->h_meta, w.plan));
+    const std::vector<int>& meta = kv->h_meta;
+    const int M = w.plan.M, nscore = w.plan.nscore;
     // arrival tickets of the context-split decode attention: a launch re-arms its own, but an ABORTED decode launch (device fault, process kill
     // between launches) would leave one non-zero for the next user of this cache -- every prefill starts from zeros
-    PGV_HIP(hipMemsetAsync(kv->dattn_ticket, 0, (size_t)kv->B * heads * sizeof(unsigned), s));
+    PGV_HIP(hipMemsetAsync(kv->dattn_ticket, 0, (size_t)kv->B * m->cfg.heads * sizeof(unsigned), s));
 
     const size_t b_meta = pgv_align(meta.size() * 4), b_resid = pgv_align((size_t)M * H * 4), b_xn = pgv_align((size_t)M * H * 2),
                  b_qkv = pgv_align((size_t)M * 3 * H * 2), b_ao = pgv_align((size_t)M * H * 2), b_act = pgv_align((size_t)M * I * 2);
     const size_t b_pick = slots ? pgv_align((size_t)B * 4) : 0;
-    // scoring tail: gathered residual rows, their normalised 16-bit form and the fp32 logits of one chunk
-    const int n16 = (vocab + 15) & ~15;
-    const int schunk = nscore < PGV_SCORE_CHUNK_ROWS ? nscore : PGV_SCORE_CHUNK_ROWS;
-    const size_t b_sres = pgv_align((size_t)schunk * H * 4), b_sxn = pgv_align((size_t)schunk * H * 2), b_slog = pgv_align((size_t)schunk * n16 * 4);
+    const int schunk = w.schunk = nscore < PGV_SCORE_CHUNK_ROWS ? nscore : PGV_SCORE_CHUNK_ROWS;
+    const size_t b_sres = pgv_align((size_t)schunk * H * 4), b_sxn = pgv_align((size_t)schunk * H * 2), b_slog = pgv_align((size_t)schunk * vocab16(m) * 4);
     PGV_TRY(pgv_ws_reserve(ctx, b_meta + b_resid + b_xn + b_qkv + b_ao + b_act + b_pick + b_sres + b_sxn + b_slog, s));
     int* d_meta = (int*)pgv_ws_alloc(ctx, b_meta);
-    float* resid = (float*)pgv_ws_alloc(ctx, b_resid);
-    char* xn = (char*)pgv_ws_alloc(ctx, b_xn);
-    char* qkv = (char*)pgv_ws_alloc(ctx, b_qkv);
-    char* ao = (char*)pgv_ws_alloc(ctx, b_ao);
-    char* act = (char*)pgv_ws_alloc(ctx, b_act);
-    int* d_pick = slots ? (int*)pgv_ws_alloc(ctx, b_pick) : nullptr;       // the refilled sequences' first tokens, before they go to their slots
-    float* sres = schunk ? (float*)pgv_ws_alloc(ctx, b_sres) : nullptr;
-    char* sxn = schunk ? (char*)pgv_ws_alloc(ctx, b_sxn) : nullptr;
-    float* slog = schunk ? (float*)pgv_ws_alloc(ctx, b_slog) : nullptr;
-    PGV_CHECK(d_meta && resid && xn && qkv && ao && act && (!slots || d_pick) && (!schunk || (sres && sxn && slog)), "%s: workspace exhausted", who);
+    w.resid = (float*)pgv_ws_alloc(ctx, b_resid);
+    w.xn = (char*)pgv_ws_alloc(ctx, b_xn);
+    w.qkv = (char*)pgv_ws_alloc(ctx, b_qkv);
+    w.ao = (char*)pgv_ws_alloc(ctx, b_ao);
+    w.act = (char*)pgv_ws_alloc(ctx, b_act);
+    w.d_pick = slots ? (int*)pgv_ws_alloc(ctx, b_pick) : nullptr;
+    w.sres = schunk ? (float*)pgv_ws_alloc(ctx, b_sres) : nullptr;
+    w.sxn = schunk ? (char*)pgv_ws_alloc(ctx, b_sxn) : nullptr;
+    w.slog = schunk ? (float*)pgv_ws_alloc(ctx, b_slog) : nullptr;
+    PGV_CHECK(d_meta && w.resid && w.xn && w.qkv && w.ao && w.act && (!slots || w.d_pick) && (!schunk || (w.sres && w.sxn && w.slog)), "%s: workspace exhausted", who);
     PGV_HIP(hipMemcpyAsync(d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
-    const int* d_row_src = d_meta; const int* d_row_b = d_meta + M; const int* d_row_pos = d_row_b + M; const int* d_cu = d_row_pos + M;
-    const int* d_last = d_cu + B + 1; const int* d_lens = d_last + B; const int* d_offs = append ? d_lens + B : nullptr;
-    const int* d_slots = slots ? d_lens + 2 * B : nullptr;
+    w.h = w.plan.lo.maps(meta.data());
+    w.d = w.plan.lo.maps((const int*)d_meta);
+    w.d_offs = append ? w.d.offs : nullptr;
+    w.d_slots = slots ? w.d.slots : nullptr;
     // HF's repetition penalty sees the prompt ids as given, placeholder ids included: a new prompt starts its slot's set, an appended turn adds to it
-    PGV_TRY(pgv_launch_seen_mark(d_lens + 3 * B, d_cu, d_slots, B, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s));
+    PGV_TRY(pgv_launch_seen_mark(w.d.raw_ids, w.d.cu, w.d_slots, B, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s));
     if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
-        PGV_HIP(hipMemcpyAsync(kv->d_pos, d_lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+        PGV_HIP(hipMemcpyAsync(kv->d_pos, w.d.lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
         PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
     }
+    return PGV_OK;
+}
 
-    PGV_TRY(pgv_launch_embed_splice(m->dtype, d_row_src, m->embed, d_video, resid, M, H, s));
-    double attn_flops = 0;
-    for (int b = 0; b < B; ++b) attn_flops += 2.0 * (double)h_seq_lens[b] * (h_seq_lens[b] + 2.0 * offs[b]) * H;   // causal: 4 * S * (S / 2 + prefix) * H
+// Embedding + video splice, then every decoder layer over the M rows: w.resid holds the final residual stream.
+static int prefill_trunk(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& q, const PrefillWork& w, hipStream_t s) {
+    const int M = w.plan.M, H = m->cfg.hidden, I = m->cfg.inter, heads = m->cfg.heads;
+    PGV_TRY(pgv_launch_embed_splice(m->dtype, w.d.row_src, m->embed, q.d_video, w.resid, M, H, s));
     for (int li = 0; li < m->cfg.layers; ++li) {
         const LlmLayer& l = m->layers[li];
         const LlmMat &wqkv = layer_mat(m, li, MAT_QKV), &wo = layer_mat(m, li, MAT_O), &wgu = layer_mat(m, li, MAT_GU), &wdown = layer_mat(m, li, MAT_DOWN);
-        PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, l.in_g, m->cfg.eps, xn, M, H, s));
-        GemmArgs g{};
-        g.A = xn; g.lda = H; g.W = wqkv.w16; g.ldw = H; g.bias = nullptr; g.C = qkv; g.ldc = 3 * H; g.M = M; g.N = (int)wqkv.N; g.K = (int)wqkv.K; g.epi = PGV_EPI_NONE; g.w_blocked = true;
-        PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
-        PGV_TRY(pgv_launch_rope_kv_write(m->dtype, qkv, d_row_b, d_row_pos, m->rope, kv->Kc[li], kv->Vc[li], M, H, heads, kv->max_seq, s));
-        PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, qkv, ao, kv->Kc[li], kv->Vc[li], d_cu, d_offs, B, max_len, H, heads, kv->max_seq, attn_flops, s, d_slots));
-        g = GemmArgs{}; g.A = ao; g.lda = H; g.W = wo.w16; g.ldw = H; g.C = resid; g.ldc = H; g.M = M; g.N = (int)wo.N; g.K = (int)wo.K; g.epi = PGV_EPI_RESID; g.w_blocked = true;
-        PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
-        PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, l.post_g, m->cfg.eps, xn, M, H, s));
-        g = GemmArgs{}; g.A = xn; g.lda = H; g.W = wgu.w16; g.ldw = H; g.C = act; g.ldc = I; g.M = M; g.N = (int)wgu.N; g.K = (int)wgu.K; g.epi = PGV_EPI_SWIGLU; g.w_blocked = true;
-        PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
-        g = GemmArgs{}; g.A = act; g.lda = I; g.W = wdown.w16; g.ldw = I; g.C = resid; g.ldc = H; g.M = M; g.N = (int)wdown.N; g.K = (int)wdown.K; g.epi = PGV_EPI_RESID; g.w_blocked = true;
-        PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
+        PGV_TRY(pgv_launch_rmsnorm(m->dtype, w.resid, l.in_g, m->cfg.eps, w.xn, M, H, s));
+        PGV_TRY(gemm_mat(ctx, m, wqkv, (int)wqkv.N, w.xn, w.qkv, 3 * H, M, PGV_EPI_NONE, s));
+        PGV_TRY(pgv_launch_rope_kv_write(m->dtype, w.qkv, w.d.row_b, w.d.row_pos, m->rope, kv->Kc[li], kv->Vc[li], M, H, heads, kv->max_seq, s));
+        PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, w.qkv, w.ao, kv->Kc[li], kv->Vc[li], w.d.cu, w.d_offs, q.B, w.plan.max_len, H, heads, kv->max_seq,
+                                        w.plan.attn_flops, s, w.d_slots));
+        PGV_TRY(gemm_mat(ctx, m, wo, (int)wo.N, w.ao, w.resid, H, M, PGV_EPI_RESID, s));
+        PGV_TRY(pgv_launch_rmsnorm(m->dtype, w.resid, l.post_g, m->cfg.eps, w.xn, M, H, s));
+        PGV_TRY(gemm_mat(ctx, m, wgu, (int)wgu.N, w.xn, w.act, I, M, PGV_EPI_SWIGLU, s));
+        PGV_TRY(gemm_mat(ctx, m, wdown, (int)wdown.N, w.act, w.resid, H, M, PGV_EPI_RESID, s));
     }
-    if (d_all_logits) {
-        // the reference's forward output: final norm + lm_head over ALL positions (video_chatgpt.py:225-226) -- on request only
-        PGV_CHECK(ld_all >= n16 && ld_all % 4 == 0 && n16 <= m->vocab_cap, "%s: ld_all %d must be a multiple of 4 and at least %d", who, ld_all, n16);
-        PGV_TRY(pgv_launch_rmsnorm(m->dtype, resid, m->norm_g, m->cfg.eps, xn, M, H, s));
-        GemmArgs g{};
-        g.A = xn; g.lda = H; g.W = m->mats[0].w16; g.ldw = H; g.C = d_all_logits; g.ldc = ld_all; g.M = M; g.N = n16; g.K = H; g.epi = PGV_EPI_F32; g.w_blocked = true;
-        PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
+    return PGV_OK;
+}
+
+// The reference's forward output: final norm + lm_head over ALL positions (video_chatgpt.py:225-226) -- on request only
+static int prefill_all_logits(pgv_ctx* ctx, pgv_llm* m, const PrefillReq& q, const PrefillWork& w, hipStream_t s) {
+    const int n16 = vocab16(m);
+    PGV_CHECK(q.ld_all >= n16 && q.ld_all % 4 == 0 && n16 <= m->vocab_cap, "%s: ld_all %d must be a multiple of 4 and at least %d", q.who, q.ld_all, n16);
+    return head_logits(ctx, m, w.resid, w.xn, w.plan.M, q.d_all_logits, q.ld_all, s);
+}
+
+// What the reference's loss reads (video_chatgpt.py:228-239), for the rows that have a target only; unscored rows: 0 / 0 / -1
+static int prefill_score(pgv_ctx* ctx, pgv_llm* m, const ScoreReq& sc, const PrefillWork& w, hipStream_t s) {
+    const int M = w.plan.M, nscore = w.plan.nscore, n16 = vocab16(m);
+    if (sc.d_logprob) PGV_HIP(hipMemsetAsync(sc.d_logprob, 0, (size_t)M * 4, s));
+    if (sc.d_lse) PGV_HIP(hipMemsetAsync(sc.d_lse, 0, (size_t)M * 4, s));
+    if (sc.d_argmax) PGV_HIP(hipMemsetAsync(sc.d_argmax, 0xff, (size_t)M * 4, s));
+    for (int c0 = 0; c0 < nscore; c0 += w.schunk) {
+        const int n = nscore - c0 < w.schunk ? nscore - c0 : w.schunk;
+        PGV_TRY(pgv_launch_gather_rows(w.resid, w.d.srows + c0, w.sres, n, m->cfg.hidden, s));
+        PGV_TRY(head_logits(ctx, m, w.sres, w.sxn, n, w.slog, n16, s));
+        PGV_TRY(pgv_launch_logprob_rows(ctx, w.slog, n16, m->cfg.vocab, n, w.d.stgts + c0, w.d.srows + c0, sc.d_logprob, sc.d_lse, sc.d_argmax, s));
     }
-    if (score) {
-        // what the reference's loss reads (video_chatgpt.py:228-239), for the rows that have a target only; unscored rows: 0 / 0 / -1
-        if (score->d_logprob) PGV_HIP(hipMemsetAsync(score->d_logprob, 0, (size_t)M * 4, s));
-        if (score->d_lse) PGV_HIP(hipMemsetAsync(score->d_lse, 0, (size_t)M * 4, s));
-        if (score->d_argmax) PGV_HIP(hipMemsetAsync(score->d_argmax, 0xff, (size_t)M * 4, s));
-        const int* d_srows = d_lens + 3 * B + M; const int* d_stgts = d_srows + nscore;
-        for (int c0 = 0; c0 < nscore; c0 += schunk) {
-            const int n = nscore - c0 < schunk ? nscore - c0 : schunk;
-            PGV_TRY(pgv_launch_gather_rows(resid, d_srows + c0, sres, n, H, s));
-            PGV_TRY(pgv_launch_rmsnorm(m->dtype, sres, m->norm_g, m->cfg.eps, sxn, n, H, s));
-            GemmArgs g{};
-            g.A = sxn; g.lda = H; g.W = m->mats[0].w16; g.ldw = H; g.C = slog; g.ldc = n16; g.M = n; g.N = n16; g.K = H; g.epi = PGV_EPI_F32; g.w_blocked = true;
-            PGV_TRY(pgv_launch_gemm(ctx, m->dtype, g, s));
-            PGV_TRY(pgv_launch_logprob_rows(ctx, slog, n16, vocab, n, d_stgts + c0, d_srows + c0, score->d_logprob, score->d_lse, score->d_argmax, s));
-        }
-    }
-    // lm_head only on the last position of every sequence (the reference computes all S positions, video_chatgpt.py:226)
-    // (a refill runs this tail in rows [0, B) of the decode scratch: every decode step rebuilds resid / xn / ssq / logits / amax_* from d_cur)
-    PGV_TRY(pgv_launch_gather_rows(resid, d_last, kv->resid, B, H, s));
+    return PGV_OK;
+}
+
+// lm_head only on the last position of every sequence (the reference computes all S positions, video_chatgpt.py:226), the pick, the outputs and
+// the host-side lengths.  (A refill runs this tail in rows [0, B) of the decode scratch: every decode step rebuilds resid / xn / ssq / logits /
+// amax_* from d_cur.)
+static int prefill_last_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& q, const PrefillWork& w, hipStream_t s) {
+    const bool slots = q.mode == PREFILL_SLOTS;
+    const int B = q.B, H = m->cfg.hidden;
+    PGV_TRY(pgv_launch_gather_rows(w.resid, w.d.last, kv->resid, B, H, s));
     const int nparts = norm_fold_enabled() ? 1 : 0;
     if (nparts) PGV_TRY(pgv_launch_final_prep(m->dtype, kv->resid, m->norm_g, kv->xn, kv->ssq, B, H, s, true));
     else PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
@@ -617,19 +633,32 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
     } else {
         PGV_TRY(lm_head(ctx, m, kv, B, true, s, nparts));           // the greedy candidates too: the same launch as a plain prefill, same logits
         pgv_prof_begin(ctx, 6, s);
-        if (pick && pick->greedy) { d_u = kv->d_u; PGV_TRY(pgv_zero_uniforms(kv->d_u, B, s)); }
-        PGV_TRY(kv_pick(kv, B, pick, d_u, false, PickState{d_pick}, d_slots, s));      // in scratch rows [0, B): what it records lands at the slots
-        PGV_TRY(pgv_launch_slot_scatter(d_slots, d_pick, d_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
+        const float* d_u = q.d_u;
+        if (q.pick && q.pick->greedy) { d_u = kv->d_u; PGV_TRY(pgv_zero_uniforms(kv->d_u, B, s)); }
+        PGV_TRY(kv_pick(kv, B, q.pick, d_u, false, PickState{w.d_pick}, w.d_slots, s));      // in scratch rows [0, B): what it records lands at the slots
+        PGV_TRY(pgv_launch_slot_scatter(w.d_slots, w.d_pick, w.d.lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
         pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
-    if (d_logits) PGV_HIP(hipMemcpyAsync(d_logits, kv->logits, (size_t)B * vocab * 4, hipMemcpyDeviceToDevice, s));
-    if (d_next) PGV_HIP(hipMemcpyAsync(d_next, slots ? d_pick : kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    if (q.d_logits) PGV_HIP(hipMemcpyAsync(q.d_logits, kv->logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
+    if (q.d_next) PGV_HIP(hipMemcpyAsync(q.d_next, slots ? w.d_pick : kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     if (slots) {
-        for (int b = 0; b < B; ++b) kv->h_len[h_slots[b]] = lens[b];
+        for (int b = 0; b < B; ++b) kv->h_len[q.h_slots[b]] = w.h.lens[b];
     } else {
-        for (int b = 0; b < kv->B; ++b) kv->h_len[b] = b < B ? lens[b] : 0;
+        for (int b = 0; b < kv->B; ++b) kv->h_len[b] = b < B ? w.h.lens[b] : 0;
         kv->active = B;
     }
+    return PGV_OK;
+}
+
+static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& q, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    PrefillWork w;
+    PGV_TRY(prefill_check(ctx, m, kv, q));
+    PGV_TRY(prefill_plan_upload(ctx, m, kv, q, w, s));
+    PGV_TRY(prefill_trunk(ctx, m, kv, q, w, s));
+    if (q.d_all_logits) PGV_TRY(prefill_all_logits(ctx, m, q, w, s));
+    if (q.mode == PREFILL_SCORE) PGV_TRY(prefill_score(ctx, m, q.score, w, s));
+    PGV_TRY(prefill_last_rows(ctx, m, kv, q, w, s));
     PGV_HIP(hipGetLastError());
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
@@ -637,28 +666,48 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_i
 
 extern "C" int pgv_llm_prefill(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video,
                                int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream) {
-    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, B, d_video, Vt, h_vid_pos, d_logits, d_next, d_all_logits, ld_all, stream, false);
+    PrefillReq q;
+    q.who = "pgv_llm_prefill"; q.mode = PREFILL_PLAIN;
+    q.h_ids = h_ids; q.h_seq_lens = h_seq_lens; q.B = B;
+    q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
+    q.d_logits = d_logits; q.d_next = d_next; q.d_all_logits = d_all_logits; q.ld_all = ld_all;
+    return prefill_impl(ctx, m, kv, q, stream);
 }
 
 extern "C" int pgv_llm_prefill_append(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video,
                                       int Vt, const int32_t* h_vid_pos, float* d_logits, int32_t* d_next, float* d_all_logits, int ld_all, void* stream) {
-    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, B, d_video, Vt, h_vid_pos, d_logits, d_next, d_all_logits, ld_all, stream, true);
+    PrefillReq q;
+    q.who = "pgv_llm_prefill_append"; q.mode = PREFILL_APPEND;
+    q.h_ids = h_ids; q.h_seq_lens = h_seq_lens; q.B = B;
+    q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
+    q.d_logits = d_logits; q.d_next = d_next; q.d_all_logits = d_all_logits; q.ld_all = ld_all;
+    return prefill_impl(ctx, m, kv, q, stream);
 }
 
 extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_slots, int n, const int32_t* h_ids, const int32_t* h_seq_lens,
                                      const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k, const float* d_u, float* d_logits,
                                      int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots, "pgv_llm_prefill_slots: null slot list");
-    // uniforms: sampled; none: greedy, from the lm_head candidates unless a penalty applies (prefill_impl refuses a null cache)
+    // uniforms: sampled; none: greedy, from the lm_head candidates unless a penalty applies (prefill_check refuses a null cache)
     const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);
-    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, n, d_video, Vt, h_vid_pos, d_logits, d_next, nullptr, 0, stream, false, h_slots, !d_u && p.penalty == 1.f ? nullptr : &p, d_u);
+    PrefillReq q;
+    q.who = "pgv_llm_prefill_slots"; q.mode = PREFILL_SLOTS;
+    q.h_ids = h_ids; q.h_seq_lens = h_seq_lens; q.B = n;
+    q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
+    q.d_logits = d_logits; q.d_next = d_next;
+    q.h_slots = h_slots; q.pick = !d_u && p.penalty == 1.f ? nullptr : &p; q.d_u = d_u;
+    return prefill_impl(ctx, m, kv, q, stream);
 }
 
 extern "C" int pgv_llm_score(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_ids, const int32_t* h_seq_lens, int B, const void* d_video, int Vt,
                              const int32_t* h_vid_pos, const int32_t* h_targets, float* d_logprob, float* d_lse, int32_t* d_argmax, void* stream) {
     PGV_CHECK(h_targets, "pgv_llm_score: null target list");
-    const ScoreReq sc{h_targets, d_logprob, d_lse, d_argmax};
-    return prefill_impl(ctx, m, kv, h_ids, h_seq_lens, B, d_video, Vt, h_vid_pos, nullptr, nullptr, nullptr, 0, stream, false, nullptr, nullptr, nullptr, &sc);
+    PrefillReq q;
+    q.who = "pgv_llm_score"; q.mode = PREFILL_SCORE;
+    q.h_ids = h_ids; q.h_seq_lens = h_seq_lens; q.B = B;
+    q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
+    q.score = ScoreReq{h_targets, d_logprob, d_lse, d_argmax};
+    return prefill_impl(ctx, m, kv, q, stream);
 }
 
 // Drop the tail of sequence b: the next pgv_llm_prefill_append / decode call continues at position `len` (the entries beyond it are simply
@@ -964,32 +1013,18 @@ extern "C" int pgv_prefill_attention(pgv_ctx* ctx, pgv_llm* m, void* d_qkv, cons
     PGV_CHECK(B >= 1 && B <= kMaxBatch, "pgv_prefill_attention: batch %d outside [1,%d]", B, kMaxBatch);
     PGV_CHECK(max_seq >= 1 && max_seq <= kMaxPos, "pgv_prefill_attention: max_seq %d outside [1,%d]", max_seq, kMaxPos);
     const int H = m->cfg.hidden, heads = m->cfg.heads;
-    int M = 0, max_len = 0;
-    for (int b = 0; b < B; ++b) {
-        const int off = h_koff ? h_koff[b] : 0;
-        PGV_CHECK(h_seq_lens[b] >= 1 && off >= 0 && off <= max_seq - h_seq_lens[b], "pgv_prefill_attention: sequence %d has %d + %d tokens (cache holds %d)", b,
-                  off, h_seq_lens[b], max_seq);
-        M += h_seq_lens[b];
-        max_len = h_seq_lens[b] > max_len ? h_seq_lens[b] : max_len;
-    }
-    // row maps as prefill_impl builds them: [row_b | row_pos | cu (B+1) | offs (B)]
-    std::vector<int> meta((size_t)2 * M + 2 * B + 1, 0);
-    int* row_b = meta.data(); int* row_pos = row_b + M; int* cu = row_pos + M; int* offs = cu + B + 1;
-    int r = 0;
-    for (int b = 0; b < B; ++b) {
-        cu[b] = r;
-        offs[b] = h_koff ? h_koff[b] : 0;
-        for (int p = 0; p < h_seq_lens[b]; ++p, ++r) { row_b[r] = b; row_pos[r] = offs[b] + p; }
-    }
-    cu[B] = r;
+    // the row maps of a prefill without ids, video or targets (prefill_plan.h)
+    PrefillRows rows;
+    rows.who = "pgv_prefill_attention"; rows.seq_lens = h_seq_lens; rows.B = B; rows.start = h_koff; rows.max_seq = max_seq; rows.hidden = H;
+    std::vector<int> meta;
+    PrefillPlan plan;
+    PGV_TRY(plan_build(rows, meta, plan));
     hipStream_t s = (hipStream_t)stream;
     int* d_meta = nullptr;
     PGV_TRY(upload_ints(ctx, meta, &d_meta, s));
-    const int* d_cu = d_meta + 2 * M;
-    double flops = 0;
-    for (int b = 0; b < B; ++b) flops += 2.0 * (double)h_seq_lens[b] * (h_seq_lens[b] + 2.0 * offs[b]) * H;
-    PGV_TRY(pgv_launch_rope_kv_write(m->dtype, d_qkv, d_meta, d_meta + M, m->rope, d_Kc, d_Vc, M, H, heads, max_seq, s));
-    PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, d_qkv, d_out, d_Kc, d_Vc, d_cu, h_koff ? d_cu + B + 1 : nullptr, B, max_len, H, heads, max_seq, flops, s));
+    const PrefillMaps<const int> d = plan.lo.maps((const int*)d_meta);
+    PGV_TRY(pgv_launch_rope_kv_write(m->dtype, d_qkv, d.row_b, d.row_pos, m->rope, d_Kc, d_Vc, plan.M, H, heads, max_seq, s));
+    PGV_TRY(pgv_launch_prefill_attn(ctx, m->dtype, d_qkv, d_out, d_Kc, d_Vc, d.cu, h_koff ? d.offs : nullptr, B, plan.max_len, H, heads, max_seq, plan.attn_flops, s));
     PGV_HIP(hipGetLastError());
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
