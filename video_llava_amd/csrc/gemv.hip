@@ -102,8 +102,19 @@ __device__ __forceinline__ typename T::v8 fp8x8_to_v8(unsigned lo, unsigned hi) 
 // register-buffer depth (64-column groups per buffer): one row block per workgroup buffers 2 groups, 2 - 3 row blocks 1; an fp8 group is one 16-byte
 // load per lane and row block where a 16-bit group is two, so the fp8 variants buffer twice as many groups for the same bytes in flight; batches
 // beyond one MFMA tile keep one group per buffer (the x fragments of CT tiles fill the registers)
-// (12-bit weights: the 16-bit depths -- a group is 1.5 KiB instead of 2, a quarter fewer bytes in flight per buffer)
-constexpr int gemv_pu(int tl, bool w8, int ct) { return (ct > 1 || tl >= 6) ? 1 : (tl == 1 ? 2 : 1) * (w8 ? 2 : 1); }
+// (12-bit weights: the 16-bit depths -- a group is 1.5 KiB instead of 2, a quarter fewer bytes in flight per buffer -- except in the residual
+// producers, whose depth was measured on its own (scripts/lab/w12_producer_chain.hip, LAB.md "12-bit producers: pipeline depth").  One workgroup
+// per CU and one row block: the two buffers ARE the bytes in flight of a CU, 24 KiB x depth.  More in flight is SLOWER, not faster -- o_proj /
+// down_proj at 8 sequences, us per launch in an HBM-cold chain: depth 1 6.5 / 14.7, 2 6.7 / 15.7, 3 7.3 / 16.3, 4 7.0 / 16.3 (bare read-only
+// chain of the same bytes 5.9 / 12.7) -- so the 12-bit producers buffer ONE group: three loads per wave and batch, and the decode of a group
+// starts as soon as it has landed.  -DPGV_W12_PRODUCER_PU=n rebuilds another depth (build.build_variant) to take the figures again.)
+#ifndef PGV_W12_PRODUCER_PU
+#define PGV_W12_PRODUCER_PU 1
+#endif
+constexpr int kW12ProducerPU = PGV_W12_PRODUCER_PU;
+constexpr int gemv_pu(int tl, bool w8, int ct, bool w12 = false, bool producer = false) {
+    return (w12 && producer && tl == 1 && ct == 1) ? kW12ProducerPU : (ct > 1 || tl >= 6) ? 1 : (tl == 1 ? 2 : 1) * (w8 ? 2 : 1);
+}
 constexpr int kGemvWaves = 8;          // waves per workgroup = K phases of a row block (the arithmetic of every launch shape is defined on these 8 chains)
 
 // W12 (one column tile): the 12-bit copy (w12.h) -- per unit and row block one 16-byte load of low bytes and one 8-byte load of codes per lane,
@@ -111,7 +122,7 @@ constexpr int kGemvWaves = 8;          // waves per workgroup = K phases of a ro
 // assembled with v_perm_b32: the MFMAs see the 16-bit operands, so the result is bitwise the 16-bit kernel's.
 template <typename T, int MODE, bool W8, int TL, bool X2, int CT = 1, bool W12 = false>
 __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) {
-    constexpr int NW = kGemvWaves, PU = gemv_pu(TL, W8, CT);
+    constexpr int NW = kGemvWaves, PU = gemv_pu(TL, W8, CT, W12, MODE == GV_RESIDNORM);
     constexpr int TILES = TL;
     static_assert(!X2 || CT == 1, "the merged x load uses the lanes of columns 8..15");
     // HS (six row blocks and more): the weight stream is pipelined in HALF groups (one 32-column k-block per register buffer) -- a whole group of
