@@ -209,6 +209,22 @@ int pgv_llm_prefill_append(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t
 int pgv_llm_prefill_slots(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_slots, int n, const int32_t *h_ids, const int32_t *h_seq_lens,
                           const void *d_video, int V, const int32_t *h_vid_pos, float temperature, int top_k, const float *d_u, float *d_logits,
                           int32_t *d_next, void *stream);
+/* pgv_llm_prefill_slots with h_counts[i] >= 1 sampled answers of prompt i (best-of-N / self-consistency voting inside a live group): h_slots lists
+ * S = sum of h_counts distinct slots of the live group, prompt 0's first, then prompt 1's, ..., in any order inside the group.  h_ids / h_seq_lens /
+ * d_video [n, V, hidden] / h_vid_pos describe the n PROMPTS; d_u (NULL: greedy first tokens, also under a repetition penalty), d_next and d_logits
+ * have S entries / rows, in slot-list order.
+ *  - Result: bit for bit what pgv_llm_prefill_slots leaves when prompt i is repeated h_counts[i] times in that slot order with the same d_u -- cache
+ *    rows [0, len) of every layer, K and V, of every listed slot, pgv_kv_len, device position, current token, done flag, step counter, seen-set
+ *    bitmap, both pgv_kv_logprobs_last values, d_next and d_logits.  Unlisted slots and rows [len, max_seq) of the listed ones are untouched;
+ *    the width and the captured decode graphs stay valid.
+ *  - Cost: the decoder trunk runs over the n prompts' rows once.  The cache rows of the first slot of a run are copied to the run's other slots
+ *    (one launch per prompt with more than one sample); last-row gather, final norm, lm_head, pick and the seen-set (built per slot from the
+ *    prompt's ids alone -- a pick adds its token to its own slot's set only) run per sample.
+ *  - Refused, cache and state unchanged, the message names the offending value: no live group (PGV_ESTATE); a count < 1, S beyond the live width,
+ *    a duplicate slot, a slot outside the group, and whatever pgv_llm_prefill_slots refuses (PGV_EINVAL). */
+int pgv_llm_prefill_slots_n(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_slots, const int32_t *h_counts, int n, const int32_t *h_ids,
+                            const int32_t *h_seq_lens, const void *d_video, int V, const int32_t *h_vid_pos, float temperature, int top_k,
+                            const float *d_u, float *d_logits, int32_t *d_next, void *stream);
 /* Teacher-forced scoring: the log-probability of GIVEN tokens -- the per-token terms of the loss the reference's forward(labels=...) computes
  * (video_chatgpt/model/video_chatgpt.py:228-239: shift logits and labels by one, flatten, CrossEntropyLoss) -- without materialising the
  * logits of every position.
@@ -252,7 +268,7 @@ int pgv_kv_truncate(pgv_kv *kv, int b, int len, void *stream);
  *  - Refused, cache and state unchanged: no live group (PGV_ESTATE); P != the group's width, a count < 1, W > the cache's batch (PGV_EINVAL);
  *    the message names the offending value.
  *  - The sampling state of pgv_kv_set_warpers / pgv_kv_set_logprobs belongs to the cache, not to a slot, and is untouched.
- * Not provided: a general (non-monotone) slot gather; sharing the prompt's K / V between the copies inside decode attention. */
+ * Not provided: a general (non-monotone) slot gather (pgv_llm_prefill_slots_n copies a fresh prompt to listed slots, not live state); sharing the prompt's K / V between the copies inside decode attention. */
 int pgv_kv_fork(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_counts, int P, void *stream);
 /* Test / debug read-back: rows [row0, row0 + nrows) of every head of `slot` (< the cache's batch, live or not) of layer `layer`,
  * which = 0 K / 1 V  ->  d_out [heads][nrows][128] 16-bit.  row0 + nrows <= max_seq. */

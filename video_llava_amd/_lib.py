@@ -90,6 +90,8 @@ PROTOTYPES = {
     "pgv_llm_prefill_append": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _i, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _vp]),
     "pgv_llm_prefill_slots": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, _vp, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32), _f, _i, _vp, _vp,
                                    _vp, _vp]),
+    "pgv_llm_prefill_slots_n": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _vp, C.POINTER(C.c_int32), _vp, _i, C.POINTER(C.c_int32),
+                                     _f, _i, _vp, _vp, _vp, _vp]),
     "pgv_logprob_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "pgv_llm_score": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32), _i, _vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp]),
     "pgv_kv_truncate": (_i, [_vp, _i, _i, _vp]),

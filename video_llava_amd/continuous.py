@@ -19,18 +19,26 @@ import torch
 from .model.utils import AnswerState
 
 DEFAULT_CHUNK = 16          # decode steps between two host checks (EOS / stop strings / budgets) and refills
+SAMPLE_SEED_STRIDE = 2 ** 20        # seeds of one task's samples lie this far apart: runs that seed their tasks base, base + 1, ... do not collide below 2^20 tasks
+
+
+def sample_seed(base: int, j: int) -> int:
+    """Seed of sample j of a task whose seed is `base`; sample 0 draws from the task's own stream."""
+    return int(base) + int(j) * SAMPLE_SEED_STRIDE
 
 
 @dataclass
 class Task:
     """One prompt to answer.  feats: pooled video features [V, C] (None: text only).  stop: stop string (needs the tokenizer).
-    max_new_tokens: this task's token budget (None: the call's).  seed: seed of the task's uniform stream (do_sample)."""
+    max_new_tokens: this task's token budget (None: the call's).  seed: seed of the task's uniform stream (do_sample).
+    samples: sampled answers wanted from ONE prefill of the prompt (do_sample; sample j draws from the stream seeded sample_seed(seed, j))."""
     task_id: Any
     ids: List[int]
     feats: Optional[torch.Tensor] = None
     stop: Optional[str] = None
     max_new_tokens: Optional[int] = None
     seed: Optional[int] = None
+    samples: int = 1
 
 
 def task_uniforms(n: int, seed: int, device) -> torch.Tensor:
@@ -42,10 +50,11 @@ def task_uniforms(n: int, seed: int, device) -> torch.Tensor:
 
 class _Slot:
     """A decode slot's task: its answer state and what the scheduler keeps about it (uniform stream, timing counters)."""
-    __slots__ = ("task", "answer", "u", "prefill_s", "decode_s", "steps", "group_size", "lp")
+    __slots__ = ("task", "answer", "u", "prefill_s", "decode_s", "steps", "group_size", "lp", "arrival", "j")
 
-    def __init__(self, task: Task, answer: AnswerState, u: Optional[torch.Tensor], prefill_s: float, group_size: int):
+    def __init__(self, task: Task, answer: AnswerState, u: Optional[torch.Tensor], prefill_s: float, group_size: int, arrival: int = 0, j: int = 0):
         self.task, self.answer, self.u, self.group_size = task, answer, u, group_size
+        self.arrival, self.j = arrival, j       # the task's arrival index and which of its samples this is
         self.prefill_s, self.decode_s, self.steps = prefill_s, 0.0, 0
         self.lp: List[np.ndarray] = []      # logprobs: [2, steps] blocks (model | pick) of every token the device emitted for the task, in order
 
@@ -94,6 +103,13 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     `generate`; a task's seen-set is its own prompt and answer -- a refilled slot starts clean (pgv_llm_prefill_slots).
     max_seq: cache positions per slot (default: longest prompt of the first group + `prompt_slack` + max_new_tokens + chunk, rounded to 64);
     a later task that does not fit fails alone.
+    Task.samples = n > 1 (needs do_sample; n <= width): the prompt is prefilled ONCE and answered n times -- the opening group forks the prompt's
+    slot (model.fork), a refill hands the task n free slots in one prefill_slots(counts=) call -- sample j drawing from
+    task_uniforms(budget, sample_seed(base, j)), base = the task's seed as above.  Each sample decodes, ends and frees its slot on its own; the task
+    yields once, with its last sample: (task_id, [new_ids_0, ..., new_ids_(n-1)]), and timings / logprobs hold lists of n dicts for it.  Admission is
+    strictly first in, first out: the head task waits until n slots are free (all are once nothing is live), nothing overtakes it.  The opening
+    group takes tasks while their samples fit `width`; when a task is left waiting the group still opens `width` slots wide (the last prompt's fork
+    run is padded with slots that start idle), so that the waiting task fits later.
     timings (a dict): timings[task_id] = {prefill_s, decode_s, steps, group_size} of each finished task (host clock; the prefill call that
     started it and the decode chunks it was live in).
     logprobs (a dict): logprobs[task_id] = {"token_logprobs": [...], "transition_scores": [...]} of each finished task, one entry per new id --
@@ -103,7 +119,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         raise ValueError(f"width {width} outside [1, 64]")
     if do_sample and not float(temperature) > 0.0:
         raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float; use do_sample=False for greedy decoding")
-    from .generation import resolve_sampling
+    from .generation import check_samples_per_prompt, fork_sources, resolve_sampling
     _, _, top_p, rep_pen = resolve_sampling(temperature if do_sample else 1.0, top_k, top_p, repetition_penalty)      # validates, HF's wording
     # passed on only when they differ from the neutral values: the model calls below then keep the argument lists they have always had
     warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
@@ -132,8 +148,15 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     def budget_of(t: Task) -> int:
         return int(t.max_new_tokens) if t.max_new_tokens is not None else int(max_new_tokens)
 
-    def check(t: Task, limit: int):
+    def samples_of(t: Task) -> int:
+        n = getattr(t, "samples", 1)            # anything but an integer >= 1 counts as one slot until check() refuses the task
+        return n if isinstance(n, int) and not isinstance(n, bool) and n >= 1 else 1
+
+    def check(t: Task, limit: int, slots_limit: int):
         """Host-side checks of one task (the ones the library would refuse a whole call for): a bad task fails alone."""
+        n = check_samples_per_prompt(getattr(t, "samples", 1), 1, do_sample, False, False, who=f"task {t.task_id!r}")
+        if n > slots_limit:
+            raise ValueError(f"task {t.task_id!r}: `samples`={n} exceeds the {slots_limit} slots of the decode group")
         if len(t.ids) < 1:
             raise ValueError("empty prompt")
         if budget_of(t) < 1:
@@ -160,10 +183,17 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         ref = next(t.feats for t in group if t.feats is not None)
         return torch.stack([(t.feats if t.feats is not None else torch.zeros_like(ref)).to(dev) for t in group])
 
-    def uniforms(arrival: int, t: Task) -> Optional[torch.Tensor]:
+    def uniforms(arrival: int, t: Task, j: int = 0) -> Optional[torch.Tensor]:
         if not do_sample:
             return None
-        return task_uniforms(budget_of(t), t.seed if t.seed is not None else seed + arrival, dev)
+        return task_uniforms(budget_of(t), sample_seed(t.seed if t.seed is not None else seed + arrival, j), dev)
+
+    boxes: dict = {}            # arrival index of a live task with samples > 1 -> what its finished samples left, until the last one ends
+
+    def admit(arrival: int, t: Task):
+        n = samples_of(t)
+        if n > 1:
+            boxes[arrival] = {"left": n, "ids": [None] * n, "tm": [None] * n, "lp": [None] * n}
 
     # ---- open the group ------------------------------------------------------------------------------------------
     pull(width)
@@ -174,81 +204,143 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         longest = max(len(t.ids) for _, t in pending)
         max_seq = longest + prompt_slack + int(max_new_tokens) + chunk
         max_seq = min((max_seq + 63) // 64 * 64, int(getattr(model.config, "max_position_embeddings", 4096)), 4096)
-    while pending and len(first) < width:
-        a, t = pending.pop(0)
+    taken = 0                                   # slots the first group's samples take
+    while pending and taken < width:
+        a, t = pending[0]
         try:
-            check(t, max_seq)
-            first.append((a, t))
+            check(t, max_seq, width)
         except Exception as e:                                     # noqa: BLE001 -- one bad task fails alone
+            pending.pop(0)
             on_error(t.task_id, e)
             yield t.task_id, None
+            pull(width)
+            continue
+        if taken + samples_of(t) > width:
+            break                                                  # first in, first out: the head waits for its slots, nothing overtakes it
+        pending.pop(0)
+        first.append((a, t))
+        taken += samples_of(t)
         pull(width)
     if not first:
         return
-    W = len(first)
+    # the group is as wide as its samples; a head task left waiting needs up to `width` slots later, so then the group opens at full width and the
+    # last prompt's run is padded with slots that start idle
+    W = width if pending else taken
+    counts = [samples_of(t) for _, t in first]
+    counts[-1] += W - taken
+    forked = W != len(first)
     t0 = time.perf_counter()
     want_lp = logprobs is not None
-    kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq, **({"logprobs": True} if want_lp else {}))
+    kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq, **({"logprobs": True} if want_lp else {}),
+                               **({"capacity": W} if forked else {}))
     try:
         slots: List[Optional[_Slot]] = [None] * W
-        us = [uniforms(a, t) for a, t in first]
+        # slot s holds sample j of first[i]; j beyond the task's samples: an idle padding slot
+        owner = [(i, s - sum(counts[:i])) for s, i in enumerate(fork_sources(counts))]
+        us = [uniforms(*first[i], j) if j < samples_of(first[i][1]) else None for i, j in owner]
+        if forked:
+            model.fork(kv, counts)
+            nxt = nxt[torch.as_tensor(fork_sources(counts), device=nxt.device)]
         if do_sample:
-            nxt = model.sample_last(kv, torch.stack([u[0] for u in us]), temperature, top_k, **warp)
+            idle = torch.full((), 0.5, dtype=torch.float32, device=dev)
+            nxt = model.sample_last(kv, torch.stack([u[0] if u is not None else idle for u in us]), temperature, top_k, **warp)
         elif rep_pen != 1.0:
             nxt = model.greedy_last(kv, W, **pen)                  # greedy over the penalised logits (as generate does)
         cur = nxt.clone()
         first_lp = model.logprobs_last(kv, W).cpu().numpy() if want_lp else None
         first_tok = nxt.cpu().numpy()
         dt = time.perf_counter() - t0
-        for s, (a, t) in enumerate(first):
-            slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), us[s], dt, W)
+        for a, t in first:
+            admit(a, t)
+        for s, (i, j) in enumerate(owner):
+            a, t = first[i]
+            if j >= samples_of(t):
+                continue
+            slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), us[s], dt, W, a, j)
             if want_lp:
                 slots[s].lp.append(first_lp[:, s:s + 1])
 
         def finish(s: int):
+            """Slot s ended its answer: frees the slot; returns what the task yields, or None while other samples of the task are still live."""
             sl = slots[s]
             slots[s] = None
-            if timings is not None:
-                timings[sl.task.task_id] = {"prefill_s": sl.prefill_s, "decode_s": sl.decode_s, "steps": sl.steps, "group_size": sl.group_size}
+            tm = {"prefill_s": sl.prefill_s, "decode_s": sl.decode_s, "steps": sl.steps, "group_size": sl.group_size}
+            lpd = None
             if want_lp:
                 # the kept ids are a prefix of what the device emitted for the task: the same cut applies to the values
                 lp = np.concatenate(sl.lp, axis=1)[:, :len(sl.answer.new)]
-                logprobs[sl.task.task_id] = {"token_logprobs": lp[0].tolist(), "transition_scores": lp[1].tolist()}
-            return sl.task.task_id, sl.answer.new
+                lpd = {"token_logprobs": lp[0].tolist(), "transition_scores": lp[1].tolist()}
+            box = boxes.get(sl.arrival)
+            out = sl.answer.new
+            if box is not None:
+                box["ids"][sl.j], box["tm"][sl.j], box["lp"][sl.j] = sl.answer.new, tm, lpd
+                box["left"] -= 1
+                if box["left"]:
+                    return None
+                del boxes[sl.arrival]
+                out, tm, lpd = box["ids"], box["tm"], box["lp"]
+            if timings is not None:
+                timings[sl.task.task_id] = tm
+            if want_lp:
+                logprobs[sl.task.task_id] = lpd
+            return sl.task.task_id, out
 
         for s in range(W):
-            if slots[s].answer.take(first_tok[s:s + 1]):
-                yield finish(s)
+            if slots[s] is not None and slots[s].answer.take(first_tok[s:s + 1]):
+                done = finish(s)
+                if done is not None:
+                    yield done
 
         # ---- decode / refill loop --------------------------------------------------------------------------------------
+        head_ok = [-1]                      # arrival index of the queue's head once it has passed check()
         while True:
             free = [s for s in range(W) if slots[s] is None]
             live = W - len(free)
             pull(len(free) + width)
-            if free and pending and (len(free) >= k_min or live == 0 or (exhausted[0] and len(pending) <= len(free))):
-                group: List[Tuple[int, int, Task]] = []
-                for s in free:
-                    while pending:
-                        a, t = pending.pop(0)
+            while pending and pending[0][0] != head_ok[0]:          # the head of the queue is a task that can run: a bad one fails alone, now
+                a, t = pending[0]
+                try:
+                    check(t, max_seq, W)
+                    head_ok[0] = a
+                except Exception as e:                             # noqa: BLE001
+                    pending.pop(0)
+                    on_error(t.task_id, e)
+                    yield t.task_id, None
+                    pull(1)
+            queued = sum(samples_of(t) for _, t in pending)
+            if free and pending and (len(free) >= k_min or live == 0 or (exhausted[0] and queued <= len(free))) and len(free) >= samples_of(pending[0][1]):
+                group: List[Tuple[List[int], int, Task]] = []       # (the task's slots, arrival index, task), first in first out
+                avail = list(free)
+                while pending and avail:
+                    a, t = pending[0]
+                    if a != head_ok[0]:
                         try:
-                            check(t, max_seq)
-                            group.append((s, a, t))
-                            break
-                        except Exception as e:                         # noqa: BLE001
+                            check(t, max_seq, W)
+                        except Exception as e:                     # noqa: BLE001
+                            pending.pop(0)
                             on_error(t.task_id, e)
                             yield t.task_id, None
+                            pull(1)
+                            continue
+                    n = samples_of(t)
+                    if n > len(avail):
+                        head_ok[0] = a
+                        break                                      # it waits for its slots; nothing overtakes it
+                    pending.pop(0)
+                    group.append((avail[:n], a, t))
+                    del avail[:n]
                     if not pending:
                         pull(1)
-                        if not pending:
-                            break
 
                 def prefill_part(part):
                     t0 = time.perf_counter()
-                    u_part = [uniforms(a, t) for _, a, t in part]
-                    u0 = torch.stack([u[0] for u in u_part]) if do_sample else None
-                    nx, _ = model.prefill_slots(kv, [s for s, _, _ in part], [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
-                                                u=u0, temperature=temperature, top_k=top_k, **(warp if do_sample else pen))
-                    cur[[s for s, _, _ in part]] = nx
+                    u_part = [[uniforms(a, t, j) for j in range(len(ss))] for ss, a, t in part]
+                    u0 = torch.stack([u[0] for us_ in u_part for u in us_]) if do_sample else None
+                    flat = [s for ss, _, _ in part for s in ss]
+                    many = {"counts": [len(ss) for ss, _, _ in part]} if len(flat) != len(part) else {}
+                    nx, _ = model.prefill_slots(kv, flat, [t.ids for _, _, t in part], feats_for([t for _, _, t in part]),
+                                                u=u0, temperature=temperature, top_k=top_k, **(warp if do_sample else pen), **many)
+                    cur[flat] = nx
                     lp_part = model.logprobs_last(kv, W).cpu().numpy() if want_lp else None
                     return u_part, nx.cpu().numpy(), lp_part, time.perf_counter() - t0
 
@@ -259,14 +351,21 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                         yield part[0][2].task_id, None
                         continue
                     u_part, firsts, lp_part, dt = res
-                    for i, (s, _, t) in enumerate(part):
-                        slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), u_part[i], dt, len(part))
-                        if want_lp:
-                            slots[s].lp.append(lp_part[:, s:s + 1])
-                        ok.append((s, firsts[i:i + 1]))
+                    size = sum(len(ss) for ss, _, _ in part)
+                    i = 0
+                    for k, (ss, a, t) in enumerate(part):
+                        admit(a, t)
+                        for j, s in enumerate(ss):
+                            slots[s] = _Slot(t, AnswerState(budget_of(t), eos_i, t.stop, tokenizer), u_part[k][j], dt, size, a, j)
+                            if want_lp:
+                                slots[s].lp.append(lp_part[:, s:s + 1])
+                            ok.append((s, firsts[i:i + 1]))
+                            i += 1
                 for s, f in ok:
                     if slots[s].answer.take(f):
-                        yield finish(s)
+                        done = finish(s)
+                        if done is not None:
+                            yield done
                 continue                                                # re-evaluate: refilled slots may have finished at their first token
             if live == 0:
                 if not pending and exhausted[0]:
@@ -301,7 +400,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                 if want_lp:
                     sl.lp.append(lp_chunk[:, s])
                 if sl.answer.take(host[s]):
-                    yield finish(s)
+                    done = finish(s)
+                    if done is not None:
+                        yield done
     finally:
         if want_lp:
             model.set_logprobs(kv, False)                           # the switch was on for this call only: also when the generator is closed early

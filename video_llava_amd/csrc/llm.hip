@@ -463,6 +463,10 @@ static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos
 // `h_slots` (pgv_llm_prefill_slots): sequence b of the call is a NEW prompt for cache slot h_slots[b] of the live group; the other slots keep their
 // cache rows, lengths, current tokens and flags.  The new rows run through the same kernels (the slot only redirects the cache rows they write and
 // read), the pick (`pick`, d_u: as kv_pick takes them; pick->greedy: zeroed uniforms) lands in rows [0, B) of the scratch and is scattered to the slots.
+// `h_counts` (pgv_llm_prefill_slots_n): sequence b of the call is answered h_counts[b] times and h_slots lists one slot per SAMPLE, those of sequence 0
+// first.  The trunk runs over the sequences' rows once and writes the first slot of every run; kv_fork_list copies those cache rows to the run's other
+// slots; the tail (last-row gather, final norm, lm_head, pick, scatter) and seen_mark run per sample, sample j on the last row / the ids of its
+// sequence -- bit for bit what PREFILL_SLOTS leaves for the sequences repeated.
 // `score` (pgv_llm_score): a plain prefill with a scoring tail.  The rows with a target go, PGV_SCORE_CHUNK_ROWS at a time, through the final norm
 // and the lm_head GEMM of the d_all_logits branch into a workspace buffer (so their logits are bit for bit that branch's: the GEMM has one tile
 // shape and no split-K, a row does not depend on M), and logprob_rows (score.hip) reduces every row to (log-probability, logsumexp, argmax).
@@ -477,6 +481,7 @@ struct PrefillReq {
     const void* d_video = nullptr; int Vt = 0; const int32_t* h_vid_pos = nullptr;                     // the optional video
     float* d_logits = nullptr; int32_t* d_next = nullptr; float* d_all_logits = nullptr; int ld_all = 0;
     const int32_t* h_slots = nullptr; const PickParams* pick = nullptr; const float* d_u = nullptr;    // PREFILL_SLOTS
+    const int32_t* h_counts = nullptr;                                                                 // PREFILL_SLOTS, pgv_llm_prefill_slots_n only
     ScoreReq score{};                                                                                  // PREFILL_SCORE
 };
 // What the stages hand on: the plan, the two views of its block (kv->h_meta, the device copy) and the workspace buffers.
@@ -485,7 +490,8 @@ struct PrefillWork {
     PrefillMaps<const int> h, d;
     const int *d_offs, *d_slots;         // d.offs / d.slots for the calls whose kernels read them (append / slots), else null
     float* resid; char *xn, *qkv, *ao, *act;
-    int* d_pick;                         // the refilled sequences' first tokens, before they go to their slots
+    int T; const int *t_last, *t_lens, *t_slots, *ht_lens;      // the tail's rows: one per sample (the plan's samp_* maps), without counts one per sequence (last / lens / d_slots)
+    int* d_pick;                         // the refilled samples' first tokens, before they go to their slots
     int schunk; float* sres; char* sxn; float* slog;     // scoring tail: gathered residual rows, their normalised 16-bit form and the fp32 logits of one chunk
 };
 // prefill_plan_build with its refusal forwarded as this library reports errors
@@ -517,10 +523,10 @@ static int prefill_check(const pgv_ctx* ctx, const pgv_llm* m, const pgv_kv* kv,
     if (pgv_llm_missing(m) != 0) { pgv_set_error("%s: %d weight tensors not loaded", who, pgv_llm_missing(m)); return PGV_ESTATE; }
     if (q.mode == PREFILL_APPEND && kv->active != q.B) { pgv_set_error("pgv_llm_prefill_append: %d sequences for a cache that holds %d prefilled ones", q.B, kv->active); return PGV_ESTATE; }
     if (q.mode == PREFILL_SLOTS) {
-        if (kv->active < 1) { pgv_set_error("pgv_llm_prefill_slots: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
-        PGV_CHECK(q.B <= kv->active, "pgv_llm_prefill_slots: %d sequences for a group of %d", q.B, kv->active);
-        PGV_CHECK(!q.pick || q.pick->temperature > 0.f, "pgv_llm_prefill_slots: temperature must be positive (got %g)", (double)q.pick->temperature);
-        PGV_CHECK(q.d_all_logits == nullptr, "pgv_llm_prefill_slots: no all-position logits");
+        if (kv->active < 1) { pgv_set_error("%s: no live group in this cache (run pgv_llm_prefill first)", who); return PGV_ESTATE; }
+        PGV_CHECK(q.B <= kv->active, "%s: %d sequences for a group of %d", who, q.B, kv->active);
+        PGV_CHECK(!q.pick || q.pick->temperature > 0.f, "%s: temperature must be positive (got %g)", who, (double)q.pick->temperature);
+        PGV_CHECK(q.d_all_logits == nullptr, "%s: no all-position logits", who);
     }
     if (q.mode == PREFILL_SCORE) PGV_CHECK(vocab16(m) <= m->vocab_cap, "%s: vocabulary %d beyond the %d allocated lm_head rows", who, m->cfg.vocab, m->vocab_cap);
     return PGV_OK;
@@ -534,20 +540,20 @@ static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefi
     PrefillRows rows;
     rows.who = who; rows.ids = q.h_ids; rows.seq_lens = q.h_seq_lens; rows.B = B;
     rows.start = append ? kv->h_len.data() : nullptr;
-    rows.slots = q.h_slots; rows.active = kv->active;
+    rows.slots = q.h_slots; rows.active = kv->active; rows.counts = q.h_counts;
     rows.vid_pos = q.d_video ? q.h_vid_pos : nullptr; rows.Vt = q.Vt;
     rows.targets = q.score.h_targets;
     rows.vocab = vocab; rows.max_seq = kv->max_seq; rows.hidden = H;
     PGV_TRY(plan_build(rows, kv->h_meta, w.plan));
     const std::vector<int>& meta = kv->h_meta;
-    const int M = w.plan.M, nscore = w.plan.nscore;
+    const int M = w.plan.M, nscore = w.plan.nscore, T = w.T = q.h_counts ? w.plan.S : B;
     // arrival tickets of the context-split decode attention: a launch re-arms its own, but an ABORTED decode launch (device fault, process kill
     // between launches) would leave one non-zero for the next user of this cache -- every prefill starts from zeros
     PGV_HIP(hipMemsetAsync(kv->dattn_ticket, 0, (size_t)kv->B * m->cfg.heads * sizeof(unsigned), s));
 
     const size_t b_meta = pgv_align(meta.size() * 4), b_resid = pgv_align((size_t)M * H * 4), b_xn = pgv_align((size_t)M * H * 2),
                  b_qkv = pgv_align((size_t)M * 3 * H * 2), b_ao = pgv_align((size_t)M * H * 2), b_act = pgv_align((size_t)M * I * 2);
-    const size_t b_pick = slots ? pgv_align((size_t)B * 4) : 0;
+    const size_t b_pick = slots ? pgv_align((size_t)T * 4) : 0;
     const int schunk = w.schunk = nscore < PGV_SCORE_CHUNK_ROWS ? nscore : PGV_SCORE_CHUNK_ROWS;
     const size_t b_sres = pgv_align((size_t)schunk * H * 4), b_sxn = pgv_align((size_t)schunk * H * 2), b_slog = pgv_align((size_t)schunk * vocab16(m) * 4);
     PGV_TRY(pgv_ws_reserve(ctx, b_meta + b_resid + b_xn + b_qkv + b_ao + b_act + b_pick + b_sres + b_sxn + b_slog, s));
@@ -567,8 +573,11 @@ static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefi
     w.d = w.plan.lo.maps((const int*)d_meta);
     w.d_offs = append ? w.d.offs : nullptr;
     w.d_slots = slots ? w.d.slots : nullptr;
+    if (q.h_counts) { w.t_last = w.d.samp_last; w.t_lens = w.d.samp_lens; w.t_slots = w.d.samp_slots; w.ht_lens = w.h.samp_lens; }
+    else { w.t_last = w.d.last; w.t_lens = w.d.lens; w.t_slots = w.d_slots; w.ht_lens = w.h.lens; }
     // HF's repetition penalty sees the prompt ids as given, placeholder ids included: a new prompt starts its slot's set, an appended turn adds to it
-    PGV_TRY(pgv_launch_seen_mark(w.d.raw_ids, w.d.cu, w.d_slots, B, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s));
+    // (and every sample of a prompt starts from the prompt's ids alone: the pick adds its own token to the set of its own slot)
+    PGV_TRY(pgv_launch_seen_mark(w.d.raw_ids, w.d.cu, w.t_slots, T, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s, q.h_counts ? w.d.samp_seq : nullptr));
     if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
         PGV_HIP(hipMemcpyAsync(kv->d_pos, w.d.lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
         PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
@@ -592,6 +601,23 @@ static int prefill_trunk(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq&
         PGV_TRY(pgv_launch_rmsnorm(m->dtype, w.resid, l.post_g, m->cfg.eps, w.xn, M, H, s));
         PGV_TRY(gemm_mat(ctx, m, wgu, (int)wgu.N, w.xn, w.act, I, M, PGV_EPI_SWIGLU, s));
         PGV_TRY(gemm_mat(ctx, m, wdown, (int)wdown.N, w.act, w.resid, H, M, PGV_EPI_RESID, s));
+    }
+    return PGV_OK;
+}
+
+// pgv_llm_prefill_slots_n: the cache rows [0, len) the trunk wrote into the first slot of every run go to the run's other slots, one launch per
+// sequence that has more than one sample.  The destinations are the entries behind the run's first in the device copy of the sample slot map.
+static int prefill_fork_runs(pgv_llm* m, pgv_kv* kv, const PrefillReq& q, const PrefillWork& w, hipStream_t s) {
+    const int heads = m->cfg.heads, L = m->cfg.layers;
+    if (L < 1) return PGV_OK;
+    KvForkArgs a{};
+    a.cache = (char*)kv->Kc[0];
+    a.head_stride = (size_t)kv->max_seq * kHD * 2; a.slot_stride = a.head_stride * heads; a.plane_stride = kv->plane_bytes;
+    a.heads = heads; a.nrun = 2 * L * heads;
+    for (int b = 0, j = 0; b < q.B; j += q.h_counts[b], ++b) {
+        if (q.h_counts[b] < 2) continue;
+        a.src = w.h.slots[b]; a.dst = w.d.samp_slots + j + 1; a.nd = q.h_counts[b] - 1; a.run_pieces = (unsigned)w.h.lens[b] * (kHD * 2 / 16);
+        PGV_TRY(pgv_launch_kv_fork_list(a, s));
     }
     return PGV_OK;
 }
@@ -623,8 +649,8 @@ static int prefill_score(pgv_ctx* ctx, pgv_llm* m, const ScoreReq& sc, const Pre
 // amax_* from d_cur.)
 static int prefill_last_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& q, const PrefillWork& w, hipStream_t s) {
     const bool slots = q.mode == PREFILL_SLOTS;
-    const int B = q.B, H = m->cfg.hidden;
-    PGV_TRY(pgv_launch_gather_rows(w.resid, w.d.last, kv->resid, B, H, s));
+    const int B = w.T, H = m->cfg.hidden;          // rows of the tail: the samples
+    PGV_TRY(pgv_launch_gather_rows(w.resid, w.t_last, kv->resid, B, H, s));
     const int nparts = norm_fold_enabled() ? 1 : 0;
     if (nparts) PGV_TRY(pgv_launch_final_prep(m->dtype, kv->resid, m->norm_g, kv->xn, kv->ssq, B, H, s, true));
     else PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
@@ -635,14 +661,14 @@ static int prefill_last_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefill
         pgv_prof_begin(ctx, 6, s);
         const float* d_u = q.d_u;
         if (q.pick && q.pick->greedy) { d_u = kv->d_u; PGV_TRY(pgv_zero_uniforms(kv->d_u, B, s)); }
-        PGV_TRY(kv_pick(kv, B, q.pick, d_u, false, PickState{w.d_pick}, w.d_slots, s));      // in scratch rows [0, B): what it records lands at the slots
-        PGV_TRY(pgv_launch_slot_scatter(w.d_slots, w.d_pick, w.d.lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
+        PGV_TRY(kv_pick(kv, B, q.pick, d_u, false, PickState{w.d_pick}, w.t_slots, s));      // in scratch rows [0, B): what it records lands at the slots
+        PGV_TRY(pgv_launch_slot_scatter(w.t_slots, w.d_pick, w.t_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
         pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
     if (q.d_logits) PGV_HIP(hipMemcpyAsync(q.d_logits, kv->logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
     if (q.d_next) PGV_HIP(hipMemcpyAsync(q.d_next, slots ? w.d_pick : kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     if (slots) {
-        for (int b = 0; b < B; ++b) kv->h_len[q.h_slots[b]] = w.h.lens[b];
+        for (int b = 0; b < B; ++b) kv->h_len[q.h_slots[b]] = w.ht_lens[b];
     } else {
         for (int b = 0; b < kv->B; ++b) kv->h_len[b] = b < B ? w.h.lens[b] : 0;
         kv->active = B;
@@ -656,6 +682,7 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& 
     PGV_TRY(prefill_check(ctx, m, kv, q));
     PGV_TRY(prefill_plan_upload(ctx, m, kv, q, w, s));
     PGV_TRY(prefill_trunk(ctx, m, kv, q, w, s));
+    if (q.h_counts) PGV_TRY(prefill_fork_runs(m, kv, q, w, s));
     if (q.d_all_logits) PGV_TRY(prefill_all_logits(ctx, m, q, w, s));
     if (q.mode == PREFILL_SCORE) PGV_TRY(prefill_score(ctx, m, q.score, w, s));
     PGV_TRY(prefill_last_rows(ctx, m, kv, q, w, s));
@@ -696,6 +723,20 @@ extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
     q.d_logits = d_logits; q.d_next = d_next;
     q.h_slots = h_slots; q.pick = !d_u && p.penalty == 1.f ? nullptr : &p; q.d_u = d_u;
+    return prefill_impl(ctx, m, kv, q, stream);
+}
+
+extern "C" int pgv_llm_prefill_slots_n(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_slots, const int32_t* h_counts, int n, const int32_t* h_ids,
+                                       const int32_t* h_seq_lens, const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k,
+                                       const float* d_u, float* d_logits, int32_t* d_next, void* stream) {
+    PGV_CHECK(h_slots && h_counts, "pgv_llm_prefill_slots_n: null slot or count list");
+    const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);       // as pgv_llm_prefill_slots
+    PrefillReq q;
+    q.who = "pgv_llm_prefill_slots_n"; q.mode = PREFILL_SLOTS;
+    q.h_ids = h_ids; q.h_seq_lens = h_seq_lens; q.B = n;
+    q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
+    q.d_logits = d_logits; q.d_next = d_next;
+    q.h_slots = h_slots; q.h_counts = h_counts; q.pick = !d_u && p.penalty == 1.f ? nullptr : &p; q.d_u = d_u;
     return prefill_impl(ctx, m, kv, q, stream);
 }
 

@@ -31,10 +31,13 @@ struct KvForkArgs {
     char* cache; size_t plane_stride, slot_stride, head_stride;
     int heads, nrun; unsigned run_pieces;
     int src, d0, nd;
+    const int* dst = nullptr;   // pgv_launch_kv_fork_list: device list of the nd destination slots (d0 and the state pointers below are not read)
     int *pos, *cur, *done; float* lp_last; int lp_stride;
     unsigned* seen; int seen_words; float* logits; int vocab;
 };
 int pgv_launch_kv_fork(const KvForkArgs& a, hipStream_t s);
+// the cache rows only, slot `src` -> slots dst[0 .. nd): distinct, none of them src (pgv_llm_prefill_slots_n)
+int pgv_launch_kv_fork_list(const KvForkArgs& a, hipStream_t s);
 // gemv.hip
 // w12: the 12-bit copy of W (w12.h), streamed instead of W at batches of one column tile (B <= 16) -- bitwise the same result; W may be null
 // only when B <= 16.  rows = the row count it was encoded with (>= N).
@@ -86,8 +89,10 @@ int pgv_check_warpers(const char* who, float top_p, float penalty);
 inline int pgv_zero_uniforms(float* u, size_t n, hipStream_t s) { PGV_HIP(hipMemsetAsync(u, 0, n * 4, s)); return PGV_OK; }
 int pgv_launch_sample(const float* logits, int V, int B, const PickParams& p, const float* u, int u_stride, int u_by_step, const PickState& st, hipStream_t s,
                       const SampleWarp* warp = nullptr, const PickLp* lp = nullptr);
-// prefill: ids [M] of B sequences (row ranges cu [B + 1]) -> bitmap of slot slots[b] (null: b); clear = start from an empty set
-int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s);
+// prefill: ids [M] of sequences with row ranges cu -> block b marks the ids of sequence seq[b] (null: b) in the bitmap of slot slots[b] (null: b);
+// clear = start from an empty set
+int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s,
+                         const int* seq = nullptr);
 // logits [B, V] (row stride V) + lp: also store the log-probability of the pick (both values are `model`: a plain arg-max has no processor)
 int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax_ts, int V, int B, const PickState& st, hipStream_t s, const float* logits = nullptr,
                             const PickLp* lp = nullptr);

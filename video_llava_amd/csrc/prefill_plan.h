@@ -12,19 +12,23 @@
 //   lens    [B]   positions of the sequence after this call;  offs [B]  positions before it (the cached prefix);  slots [B]  its cache slot
 //   raw_ids [M]   the ids as given, placeholder ids included (seen_mark)
 //   srows [nscore] the rows that have a target;  stgts [nscore]  their targets (pgv_llm_score)
-template <class T> struct PrefillMaps { T *row_src, *row_b, *row_pos, *cu, *last, *lens, *offs, *slots, *raw_ids, *srows, *stgts; };
+//   samp_seq [S]  the sequence sample j is an answer to;  samp_last [S]  that sequence's last row;  samp_lens [S]  its positions;  samp_slots [S]  the
+//                 cache slot of sample j (pgv_llm_prefill_slots_n: S = sum of the counts; no counts: S = 0, one sample per sequence, read last / lens / slots)
+template <class T> struct PrefillMaps { T *row_src, *row_b, *row_pos, *cu, *last, *lens, *offs, *slots, *raw_ids, *srows, *stgts, *samp_seq, *samp_last, *samp_lens, *samp_slots; };
 
 struct PrefillLayout {
-    size_t row_src, row_b, row_pos, cu, last, lens, offs, slots, raw_ids, srows, stgts, total;       // offsets and size, in ints
-    PrefillLayout(int M = 0, int B = 0, int nscore = 0) {
+    size_t row_src, row_b, row_pos, cu, last, lens, offs, slots, raw_ids, srows, stgts, samp_seq, samp_last, samp_lens, samp_slots, total;       // offsets and size, in ints
+    PrefillLayout(int M = 0, int B = 0, int nscore = 0, int S = 0) {
         size_t at = 0;
         auto take = [&at](size_t n) { const size_t o = at; at += n; return o; };
         row_src = take(M); row_b = take(M); row_pos = take(M); cu = take((size_t)B + 1); last = take(B); lens = take(B); offs = take(B); slots = take(B);
         raw_ids = take(M); srows = take(nscore); stgts = take(nscore);
+        samp_seq = take(S); samp_last = take(S); samp_lens = take(S); samp_slots = take(S);
         total = at;
     }
     template <class T> PrefillMaps<T> maps(T* p) const {
-        return {p + row_src, p + row_b, p + row_pos, p + cu, p + last, p + lens, p + offs, p + slots, p + raw_ids, p + srows, p + stgts};
+        return {p + row_src, p + row_b, p + row_pos, p + cu, p + last, p + lens, p + offs, p + slots, p + raw_ids, p + srows, p + stgts,
+                p + samp_seq, p + samp_last, p + samp_lens, p + samp_slots};
     }
 };
 
@@ -35,6 +39,8 @@ struct PrefillRows {
     const int* seq_lens = nullptr; int B = 0;        // rows of every sequence
     const int* start = nullptr;                      // [B] positions already in the cache (null: 0)
     const int* slots = nullptr; int active = 0;      // [B] cache slot of sequence b, each a distinct one of the `active` live slots (null: b)
+    const int* counts = nullptr;                     // [B] samples of sequence b, each >= 1 (null: one): `slots` then lists S = sum of the counts slots, those of
+                                                     // sequence 0 first; the rows of sequence b go to the FIRST slot of its run, the caller copies them to the others
     const int* vid_pos = nullptr; int Vt = 0;        // [B] row behind which the Vt video rows of sequence b sit, < 0: none (null: no video)
     const int* targets = nullptr;                    // [M] target of every row, < 0: not scored (null: no scoring)
     int vocab = 0, max_seq = 0, hidden = 0;
@@ -43,6 +49,7 @@ struct PrefillRows {
 struct PrefillPlan {
     PrefillLayout lo;
     int M = 0, max_len = 0, nscore = 0;
+    int S = 0;                   // samples (0: no counts were given)
     double attn_flops = 0;       // causal attention over the new rows and their prefix: 4 * S * (S / 2 + prefix) * H per sequence
 };
 
@@ -52,7 +59,16 @@ enum PrefillPlanStatus { PLAN_OK = 0, PLAN_EINVAL = 1 };
 static inline PrefillPlanStatus prefill_plan_build(const PrefillRows& in, std::vector<int>& meta, PrefillPlan& plan, char* err, size_t err_len) {
 #define PLAN_CHECK(cond, ...) do { if (!(cond)) { snprintf(err, err_len, __VA_ARGS__); return PLAN_EINVAL; } } while (0)
     const int B = in.B;
-    for (int b = 0; in.slots && b < B; ++b) {
+    int S = 0;
+    if (in.counts) {
+        PLAN_CHECK(in.slots != nullptr, "%s: sample counts without a slot list", in.who);
+        for (int b = 0; b < B; ++b) {
+            PLAN_CHECK(in.counts[b] >= 1, "%s: count %d of sequence %d is below 1", in.who, in.counts[b], b);
+            PLAN_CHECK(in.counts[b] <= in.active - S, "%s: %lld samples up to sequence %d for a live group of %d", in.who, (long long)S + in.counts[b], b, in.active);
+            S += in.counts[b];
+        }
+    }
+    for (int b = 0; in.slots && b < (in.counts ? S : B); ++b) {
         PLAN_CHECK(in.slots[b] >= 0 && in.slots[b] < in.active, "%s: slot %d outside the %d of the live group", in.who, in.slots[b], in.active);
         for (int c = 0; c < b; ++c) PLAN_CHECK(in.slots[c] != in.slots[b], "%s: slot %d listed twice", in.who, in.slots[b]);
     }
@@ -67,14 +83,15 @@ static inline PrefillPlanStatus prefill_plan_build(const PrefillRows& in, std::v
         PLAN_CHECK(in.targets[r] < in.vocab, "%s: target %d of row %d outside the vocabulary (%d)", in.who, in.targets[r], r, in.vocab);
         nscore += in.targets[r] >= 0;
     }
-    plan = PrefillPlan{PrefillLayout(M, B, nscore), M, max_len, nscore, 0.0};
+    plan = PrefillPlan{PrefillLayout(M, B, nscore, S), M, max_len, nscore, S, 0.0};
     meta.assign(plan.lo.total, 0);
     const PrefillMaps<int> h = plan.lo.maps(meta.data());
     for (int i = 0, k = 0; in.targets && i < M; ++i)
         if (in.targets[i] >= 0) { h.srows[k] = i; h.stgts[k++] = in.targets[i]; }
     int r = 0;
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0, j = 0; b < B; ++b) {
         h.cu[b] = r;
+        const int slot = !in.slots ? b : in.slots[in.counts ? j : b];       // of the sequence's rows: its (first) slot
         const int off = in.start ? in.start[b] : 0, len = in.seq_lens[b];
         const int vp = in.vid_pos ? in.vid_pos[b] : -1;
         if (vp >= 0) PLAN_CHECK(vp + in.Vt + 1 < len, "%s: video run of sequence %d (start %d, %d rows) overruns its %d tokens", in.who, b, vp, in.Vt, len);
@@ -86,9 +103,10 @@ static inline PrefillPlanStatus prefill_plan_build(const PrefillRows& in, std::v
                 h.row_src[r] = vid ? -(b * in.Vt + (p - vp - 1) + 1) : id;
                 h.raw_ids[r] = id;
             }
-            h.row_b[r] = in.slots ? in.slots[b] : b; h.row_pos[r] = off + p;
+            h.row_b[r] = slot; h.row_pos[r] = off + p;
         }
-        h.last[b] = r - 1; h.lens[b] = off + len; h.offs[b] = off; h.slots[b] = in.slots ? in.slots[b] : b;
+        h.last[b] = r - 1; h.lens[b] = off + len; h.offs[b] = off; h.slots[b] = slot;
+        for (int c = 0; in.counts && c < in.counts[b]; ++c, ++j) { h.samp_seq[j] = b; h.samp_last[j] = r - 1; h.samp_lens[j] = off + len; h.samp_slots[j] = in.slots[j]; }
         plan.attn_flops += 2.0 * (double)len * (len + 2.0 * off) * in.hidden;
     }
     h.cu[B] = r;

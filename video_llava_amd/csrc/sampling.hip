@@ -432,12 +432,14 @@ __global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, Sam
 
 // ---------------------------------------------------------------------------------------------
 // Seen-set of a prefill: sequence b's ids (placeholder ids included, ids outside the vocabulary ignored) are set in the bitmap of its slot;
-// `clear` first empties it (a new prompt; an appended turn keeps what the slot has seen).  One workgroup per sequence.
+// `clear` first empties it (a new prompt; an appended turn keeps what the slot has seen).  One workgroup per sequence -- or, with `seq`, per sample:
+// workgroup b marks the ids of sequence seq[b] in slot slots[b] (pgv_llm_prefill_slots_n: every sample's set is built from the prompt's ids alone).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void seen_mark_kernel(const int* __restrict__ ids, const int* __restrict__ cu, const int* __restrict__ slots, int V,
-                                                        unsigned* __restrict__ bits, int words, int clear) {
-    const int b = blockIdx.x, tid = threadIdx.x;
-    unsigned* row = bits + (size_t)(slots ? slots[b] : b) * words;
+                                                        unsigned* __restrict__ bits, int words, int clear, const int* __restrict__ seq) {
+    const int tid = threadIdx.x;
+    unsigned* row = bits + (size_t)(slots ? slots[blockIdx.x] : blockIdx.x) * words;
+    const int b = seq ? seq[blockIdx.x] : blockIdx.x;
     if (clear) {
         for (int i = tid; i < words; i += 256) row[i] = 0u;
         __syncthreads();
@@ -486,8 +488,8 @@ int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax
     return PGV_OK;
 }
 
-int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s) {
-    hipLaunchKernelGGL(seen_mark_kernel, dim3(B), dim3(256), 0, s, ids, cu, slots, V, bits, words, clear);
+int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s, const int* seq) {
+    hipLaunchKernelGGL(seen_mark_kernel, dim3(B), dim3(256), 0, s, ids, cu, slots, V, bits, words, clear, seq);
     return PGV_OK;
 }
 

@@ -41,12 +41,35 @@ def add_runtime_arguments(parser):
     parser.add_argument("--seed", type=int, default=0,
                         help="--schedule refill --do_sample: task i samples from torch.Generator seeded with seed * 1000003 + i, so its answer does "
                              "not depend on --batch or on the slot it lands in")
+    parser.add_argument("--samples_per_prompt", type=int, default=1, metavar="N",
+                        help="--schedule refill --do_sample: N sampled answers per task from ONE prefill of its prompt (sample j seeded "
+                             "continuous.sample_seed(task seed, j)); --sample_pick chooses the one that is recorded")
+    parser.add_argument("--sample_pick", choices=("best", "majority"), default="best",
+                        help="best (default): the sample with the largest summed log-probability (inference.best_sample); majority: the most frequent "
+                             "answer string, ties to the larger summed log-probability, then to the first (inference.majority_sample)")
+    parser.add_argument("--samples_out", default=None, metavar="FILE.jsonl",
+                        help="--samples_per_prompt: append one JSON line per task with all its samples (text, ids, logprob) and the index picked "
+                             "(rank-local file `FILE.jsonl.rank<r>` when world > 1)")
     parser.add_argument("--timings", default=None, metavar="OUT.jsonl",
                         help="append one JSON line per answered task (rank-local file `OUT.jsonl.rank<r>` when world > 1): frame load, upload + ingest, "
                              "tower + pool, prefill, decode seconds, generated tokens, group size, feature-cache hit (SURVEY 5: per-clip stage timings)")
     parser.add_argument("--feature-cache", type=int, default=FEATURE_CACHE_CLIPS, metavar="N",
                         help="pooled video features of the last N distinct clips stay on the device and are reused by later questions about the same "
                              "video (ActivityNet-QA asks several per clip; the reference recomputes them, chat.py:137-144); 0 disables")
+    # flags that only mean something together are checked once all of them are parsed
+    inner = parser.parse_known_args
+
+    def parse_known_args(args=None, namespace=None):
+        ns, rest = inner(args, namespace)
+        if ns.samples_per_prompt < 1 or ns.samples_per_prompt > MAX_BATCH:
+            parser.error(f"--samples_per_prompt {ns.samples_per_prompt} outside [1, {MAX_BATCH}]")
+        if ns.samples_per_prompt > 1 and not (ns.schedule == "refill" and ns.do_sample):
+            parser.error(f"--samples_per_prompt {ns.samples_per_prompt} needs --schedule refill --do_sample")
+        if ns.batch != "auto" and ns.samples_per_prompt > ns.batch:
+            parser.error(f"--samples_per_prompt {ns.samples_per_prompt} exceeds the --batch {ns.batch} decode slots")
+        return ns, rest
+
+    parser.parse_known_args = parse_known_args
     return parser
 
 
@@ -149,9 +172,9 @@ class _Runner:
     Length encoding: lens[j] = 0 = the task failed (no prediction), k + 1 = an answer of k tokens (k = 0 is a legitimate empty answer: the
     reference writes pred = '' when the first token is EOS)."""
 
-    def __init__(self, args, tasks, components, load_frames, rank, tfile):
+    def __init__(self, args, tasks, components, load_frames, rank, tfile, sfile=None):
         from ..feature_extraction import PinnedRing
-        self.args, self.tasks, self.load_frames, self.rank, self.tfile = args, tasks, load_frames, rank, tfile
+        self.args, self.tasks, self.load_frames, self.rank, self.tfile, self.sfile = args, tasks, load_frames, rank, tfile, sfile
         self.model, self.vision_tower, self.tokenizer, self.image_processor, self.video_token_len = components
         self.use_se = self.model.get_model().vision_config.use_vid_start_end
         self.cache = FeatureCache(getattr(args, "feature_cache", FEATURE_CACHE_CLIPS))
@@ -325,6 +348,8 @@ class _Runner:
         toks, lens = torch.zeros(len(indices), args.max_new_tokens, dtype=torch.int32), [0] * len(indices)
         row = {idx: j for j, idx in enumerate(indices)}
         info = {}                                                      # task -> (its group, the group's host half)
+        n_samples = int(getattr(args, "samples_per_prompt", 1))
+        many = {"samples": n_samples} if n_samples > 1 else {}
 
         def stream():
             pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="pgv-prefetch")
@@ -341,7 +366,7 @@ class _Runner:
                         info[idx] = (gi, host)
                         inp = self.inputs(idx, clips_g, feat_of)
                         if inp is not None:
-                            yield Task(idx, inp[0], inp[1], stop=inp[2], seed=int(getattr(args, "seed", 0)) * 1000003 + idx)
+                            yield Task(idx, inp[0], inp[1], stop=inp[2], seed=int(getattr(args, "seed", 0)) * 1000003 + idx, **many)
             finally:
                 pool.shutdown(wait=True, cancel_futures=True)
 
@@ -350,16 +375,39 @@ class _Runner:
         from ..generation import resolve_sampling
         _, _, top_p, rep_pen = resolve_sampling(0.2, 50, generation_config=getattr(self.model, "generation_config", None), **self.warpers())
         warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
+        lps = {} if many else None                                    # the samples are ranked by their log-probabilities
         for idx, new in generate_continuous(self.model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
-                                            tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp):
+                                            tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp, **({"logprobs": lps} if many else {})):
+            if new is not None and many:
+                new = self.pick_sample(idx, new, lps.pop(idx))
             if new is not None:
                 self.record(toks, lens, row[idx], new)
         if self.tfile:
             for j, idx in enumerate(indices):
                 g = tm.get(idx, {})
+                if isinstance(g, list):                                # one entry per sample: the task's prefill, its samples' decode chunks together
+                    g = {"prefill_s": g[0]["prefill_s"], "decode_s": max(x["decode_s"] for x in g), "steps": max(x["steps"] for x in g),
+                         "group_size": g[0]["group_size"]}
                 self.write_timing(idx, lens[j], info[idx][0], info[idx][1], g, g.get("group_size"))
             self.tfile.flush()
         return toks, lens
+
+    def pick_sample(self, idx, news, lps):
+        """--samples_per_prompt: the ids of the sample of task idx that --sample_pick chooses; every sample goes to --samples_out."""
+        import json
+        from ..inference import best_sample, majority_sample
+        stop = self.stop_strs.get(idx)
+        eos = self.model.config.eos_token_id
+        samples = []
+        for new, lp in zip(news, lps):
+            ids = new[:new.index(eos)] if eos is not None and eos in new else new
+            text = self.tokenizer.batch_decode([ids[:self.args.max_new_tokens]], skip_special_tokens=True)[0].strip()       # as answer_tasks cleans the recorded one
+            samples.append({"text": text.rstrip(stop).strip() if stop else text, "ids": new, "logprob": float(sum(lp["token_logprobs"]))})
+        k = majority_sample(samples) if getattr(self.args, "sample_pick", "best") == "majority" else best_sample(samples)
+        if self.sfile:
+            self.sfile.write(json.dumps({"task": idx, "video": self.tasks[idx]["name"], "rank": self.rank, "picked": k, "samples": samples}) + "\n")
+            self.sfile.flush()
+        return news[k]
 
     def infer_sampled(self, indices, clips=None):
         """--do_sample (--schedule group): the reference's temperature-0.2 sampling with its stopping criterion, one task at a time
@@ -398,7 +446,11 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
     if timings_path and world > 1:
         timings_path = f"{timings_path}.rank{rank}"
     tfile = open(timings_path, "a") if timings_path else None
-    run = _Runner(args, tasks, components, load_frames, rank, tfile)
+    samples_path = getattr(args, "samples_out", None)
+    if samples_path and world > 1:
+        samples_path = f"{samples_path}.rank{rank}"
+    sfile = open(samples_path, "a") if samples_path else None
+    run = _Runner(args, tasks, components, load_frames, rank, tfile, sfile)
     device = vision_tower.device if hasattr(vision_tower, "device") else torch.device("cpu")
     if getattr(args, "batch", "auto") == "auto":
         free_b = torch.cuda.mem_get_info(device)[0] if device.type == "cuda" else 0
@@ -431,6 +483,8 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
     finally:
         if tfile:
             tfile.close()
+        if sfile:
+            sfile.close()
     from ..model.utils import first_stop_length
     preds = []
     for idx, ids in enumerate(answers):

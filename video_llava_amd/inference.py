@@ -235,6 +235,23 @@ def best_sample(samples) -> int:
     return best
 
 
+def majority_sample(samples) -> int:
+    """Self-consistency vote over video_chatgpt_infer_samples' dicts: index of the first sample carrying the most frequent "text"; among equally
+    frequent texts the one whose samples' "logprob" values sum highest wins, then the one seen first."""
+    if not samples:
+        raise ValueError("majority_sample: no samples")
+    votes = {}                  # text -> [count, summed logprob, first index]; dicts keep insertion order
+    for i, s_ in enumerate(samples):
+        v = votes.setdefault(s_["text"], [0, 0.0, i])
+        v[0] += 1
+        v[1] += float(s_["logprob"])
+    best = None
+    for v in votes.values():
+        if best is None or (v[0], v[1]) > (best[0], best[1]):
+            best = v
+    return best[2]
+
+
 def video_chatgpt_score(video_frames, question, answers, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                         transcript=None, features=None):
     """How likely is each of `answers` (a list of candidate strings) as the reply to `question` about one clip: the prompt of

@@ -449,33 +449,42 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
 
     def prefill_slots(self, kv, slots: Sequence[int], seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor],
                       want_logits: bool = False, u: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 50,
-                      top_p: float = 1.0, repetition_penalty: float = 1.0):
+                      top_p: float = 1.0, repetition_penalty: float = 1.0, counts: Optional[Sequence[int]] = None):
         """Prefill NEW prompts `seqs` into cache slots `slots` of the live group `kv` (a handle prefill() returned) while the other slots keep
         their state (pgv_llm_prefill_slots: continuous batching).  `video_spatio_temporal_features` [n, V, C] (None: text only; a text-only
         prompt next to video ones takes any [V, C] block, it is not read).  u [n] (optional): draw each first token as sample_last does,
         else greedy.  top_p / repetition_penalty: the cache's warpers from this call on (set_warpers); the refilled slots start from a seen-set
-        of their own prompt only.  Returns (first tokens [n] int32 on device, logits [n, vocab] or None)."""
+        of their own prompt only.  Returns (first tokens [n] int32 on device, logits [n, vocab] or None).
+        `counts` (pgv_llm_prefill_slots_n): prompt i gets counts[i] >= 1 sampled answers from ONE prefill -- `slots` and `u` then have
+        S = sum(counts) entries, prompt 0's first, and S first tokens / logits rows come back; bit for bit the call with prompt i repeated
+        counts[i] times."""
         n = len(seqs)
         self.set_warpers(kv, top_p, repetition_penalty)
-        if len(slots) != n:
-            raise ValueError(f"{len(slots)} slots for {n} prompts")
+        if counts is not None and len(counts) != n:
+            raise ValueError(f"{len(counts)} counts for {n} prompts")
+        S = n if counts is None else sum(int(c) for c in counts)
+        if len(slots) != S:
+            raise ValueError(f"{len(slots)} slots for {n} prompts" + ("" if counts is None else f" with {S} samples"))
         lens = [len(s) for s in seqs]
         feats = video_spatio_temporal_features
         proj, V, vid_pos = None, 0, [-1] * n
         if feats is not None:
             proj, V, vid_pos = self._project_video(feats, seqs)
         flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
-        nxt = torch.empty(n, dtype=torch.int32, device=self.device_)
-        logits = torch.empty(n, self.vocab_size, dtype=torch.float32, device=self.device_) if want_logits else None
+        nxt = torch.empty(S, dtype=torch.int32, device=self.device_)
+        logits = torch.empty(S, self.vocab_size, dtype=torch.float32, device=self.device_) if want_logits else None
         if u is not None:
             u = u.to(device=self.device_, dtype=torch.float32).contiguous()
-            assert u.numel() == n
-        _lib.check(self.ctx.lib.pgv_llm_prefill_slots(self.ctx.handle, self.handle, kv, (C.c_int32 * n)(*[int(s) for s in slots]), n,
-                                                      flat.ctypes.data_as(C.c_void_p), (C.c_int32 * n)(*lens),
-                                                      proj.data_ptr() if proj is not None else None, V, (C.c_int32 * n)(*vid_pos),
-                                                      float(temperature), int(top_k), u.data_ptr() if u is not None else None,
-                                                      logits.data_ptr() if logits is not None else None, nxt.data_ptr(),
-                                                      _lib.stream_ptr(self.device_)), "pgv_llm_prefill_slots")
+            assert u.numel() == S
+        h_slots = (C.c_int32 * S)(*[int(s) for s in slots])
+        tail = (flat.ctypes.data_as(C.c_void_p), (C.c_int32 * n)(*lens), proj.data_ptr() if proj is not None else None, V, (C.c_int32 * n)(*vid_pos),
+                float(temperature), int(top_k), u.data_ptr() if u is not None else None, logits.data_ptr() if logits is not None else None,
+                nxt.data_ptr(), _lib.stream_ptr(self.device_))
+        if counts is None:
+            _lib.check(self.ctx.lib.pgv_llm_prefill_slots(self.ctx.handle, self.handle, kv, h_slots, n, *tail), "pgv_llm_prefill_slots")
+        else:
+            _lib.check(self.ctx.lib.pgv_llm_prefill_slots_n(self.ctx.handle, self.handle, kv, h_slots, (C.c_int32 * n)(*[int(c) for c in counts]), n, *tail),
+                       "pgv_llm_prefill_slots_n")
         return nxt, logits
 
     def set_warpers(self, kv, top_p: float = 1.0, repetition_penalty: float = 1.0):
