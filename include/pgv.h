@@ -498,6 +498,8 @@ int pgv_decode_attention(pgv_ctx *ctx, pgv_llm *llm, const void *d_qkv, const in
  * 1 <= B <= 64, 1 <= max_seq <= 4096, koff >= 0, koff + len <= max_seq.  Synchronises the stream once. */
 int pgv_prefill_attention(pgv_ctx *ctx, pgv_llm *llm, void *d_qkv, const int32_t *h_seq_lens, const int32_t *h_koff, void *d_Kc, void *d_Vc,
                           void *d_out, int B, int max_seq, void *stream);
+/* Row norms of an fp32 [rows, cols] matrix -> 16-bit d_y.  cols must be one of the instantiated widths 256, 512, 768, 1024, 2048, 4096, 5120; any
+ * other width returns PGV_EINVAL before anything is launched. */
 int pgv_layernorm(pgv_ctx *ctx, int dtype, const float *d_x, const float *d_gamma, const float *d_beta, float eps,
                   void *d_y, int rows, int cols, void *stream);
 int pgv_rmsnorm(pgv_ctx *ctx, int dtype, const float *d_x, const float *d_gamma, float eps, void *d_y, int rows, int cols,

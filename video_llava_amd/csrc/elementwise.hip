@@ -52,7 +52,8 @@ int launch_norm(const float* x, const float* g, const float* b, float eps, void*
     const int grid = (rows + 3) / 4;
 #define PGV_NORM_CASE(NV_) \
     case NV_: hipLaunchKernelGGL((norm_kernel<T, NV_, RMS>), dim3(grid), dim3(256), 0, s, x, g, b, eps, (char*)y, rows); break;
-    switch (cols / 256) {
+    // a width that is no multiple of 256 has no case: the quotient alone would run it at the stride of the next lower instantiated width
+    switch (cols > 0 && cols % 256 == 0 ? cols / 256 : 0) {
         PGV_NORM_CASE(1) PGV_NORM_CASE(2) PGV_NORM_CASE(3) PGV_NORM_CASE(4) PGV_NORM_CASE(8)
         PGV_NORM_CASE(16) PGV_NORM_CASE(20)
         default:
