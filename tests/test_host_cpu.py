@@ -1000,6 +1000,264 @@ int main() {
     assert users == ["llm.hip"], users
 
 
+def test_gemv_plan_shapes_totality_sizes_and_refusals(tmp_path):
+    """csrc/gemv_plan.h, compiled on its own with g++ (it must need no HIP header), owns the launch plan of a decode GEMV: (1) the launch shape
+    (tl, ct, x2, k8, nwb) and the streamed weight format of the five matrices of the 7B and 13B decoders on 256 CUs at B = 1, 8, 9, 16, 17, 32,
+    33, 64, 16-bit and fp8, against literals written out below (what choose_gemv returned before it moved here), and no 8-phase choice anywhere
+    without its scratch; (2) totality: over every mode, both formats, B 1..64, 1..2600 row blocks, six K, four CU counts, scratch on and off,
+    every choice has an instantiation by the predicates the kernel list is expanded with, a GV_STORE16 tl divides the row-block count, an 8-phase
+    choice implies mode 5, scratch and whole row groups (and fp8 at one column tile, which pgv_llm_weight_stream_bytes leans on), x2 implies
+    B <= 8, one tile and tl < 6, and ct is gemv_col_tiles(B); (3) the 8-phase scratch and LDS sizes; (4) every refusal of the two check
+    functions with its message, the accepted neighbour of each bound next to it.  Where g++ has the sanitizer runtimes the same stand-alone
+    program runs a second time under ASan + UBSan."""
+    import shutil
+    gxx = shutil.which("g++")
+    assert gxx, "g++ is part of the image"
+    csrc = os.path.join(ROOT, "video_llava_amd", "csrc")
+    prog = r"""#include <cstdio>
+#include <cstring>
+#include "gemv_plan.h"
+static int bad = 0;
+#define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); bad = 1; } } while (0)
+static GemvPlan plan;
+static char err[512];
+static bool ok(const GemvCall& c) { err[0] = 0; const bool r = gemv_plan_build(c, plan, err, sizeof(err)) == GEMV_PLAN_OK && !err[0]; if (!r) printf("refused: \"%s\"\n", err); return r; }
+static bool refused(const GemvCall& c, const char* msg) {
+    err[0] = 0;
+    const bool hit = gemv_plan_build(c, plan, err, sizeof(err)) == GEMV_PLAN_EINVAL && !strcmp(err, msg);
+    if (!hit) printf("got \"%s\", want \"%s\"\n", err, msg);
+    return hit;
+}
+static bool dok(const GemvDescShape& d) { err[0] = 0; const bool r = gemv_check_desc(d, err, sizeof(err)) == GEMV_PLAN_OK && !err[0]; if (!r) printf("refused: \"%s\"\n", err); return r; }
+static bool drefused(const GemvDescShape& d, const char* msg) {
+    err[0] = 0;
+    const bool hit = gemv_check_desc(d, err, sizeof(err)) == GEMV_PLAN_EINVAL && !strcmp(err, msg);
+    if (!hit) printf("got \"%s\", want \"%s\"\n", err, msg);
+    return hit;
+}
+// a decode step's call of one matrix on 256 CUs
+static GemvCall call(int mode, int N, int K, int B, bool w8, bool scratch, bool w12) {
+    GemvCall c;
+    c.mode = mode; c.N = N; c.K = K; c.B = B; c.w8 = w8; c.bf16 = true; c.W = true; c.w12 = w12; c.rows12 = (N + 15) / 16 * 16;
+    c.norm = true; c.ssq_ts = 8192; c.amax_ts = 32064; c.nparts_in = mode == GV_RESIDNORM ? 0 : 256;
+    c.gamma = c.xg = c.ssq_out = mode == GV_RESIDNORM; c.k8_part = scratch && mode == GV_RESIDNORM; c.x_blocked = true;
+    return c;
+}
+static bool shape_is(int tl, int ct, int x2, int k8, int nwb, int wf) {
+    const bool r = plan.tl == tl && plan.ct == ct && plan.x2 == x2 && plan.k8 == k8 && plan.nwb == nwb && plan.wf == wf;
+    if (!r) printf("shape (%d %d %d %d %d %d), want (%d %d %d %d %d %d)\n", plan.tl, plan.ct, plan.x2, plan.k8, plan.nwb, plan.wf, tl, ct, x2, k8, nwb, wf);
+    return r;
+}
+int main() {
+    {   // (1) the launch shapes of the 7B and 13B decoders
+        const int Bs[8] = {1, 8, 9, 16, 17, 32, 33, 64};
+        for (int big = 0; big < 2; ++big) for (int w8 = 0; w8 < 2; ++w8) for (int w12 = 0; w12 < 2 - w8; ++w12) for (int bi = 0; bi < 8; ++bi) for (int scratch = 0; scratch < 2; ++scratch) {
+            const int H = big ? 5120 : 4096, I = big ? 13824 : 11008, B = Bs[bi];
+            const int ct = B <= 16 ? 1 : (B <= 32 ? 2 : 4), x2 = B <= 8;
+            const int wf = w8 ? WF_FP8 : WF_16, wf1 = (w12 && ct == 1) ? WF_12 : wf;        // wf1: the format of a launch that is not 8-phase
+            EXPECT(ok(call(GV_STORE16, 3 * H, H, B, w8, scratch, w12)) && shape_is(big ? 4 : 3, ct, x2, 0, 0, wf1) && plan.units == 3 * H / 16 && plan.grid * plan.tl == plan.units);
+            EXPECT(ok(call(GV_SWIGLU, 2 * I, H, B, w8, scratch, w12)) && shape_is(B <= 16 ? 2 : (big ? 8 : 6), ct, x2, 0, 0, wf1) && plan.units == I / 16);
+            EXPECT(plan.grid == (B <= 16 ? I / 16 : (big ? 216 : 230)));
+            EXPECT(ok(call(GV_F32, 2001 * 16 - 5, H, B, w8, scratch, w12)) && shape_is(B <= 8 ? 1 : 8, ct, x2, 0, 0, wf1) && plan.units == 2001 && plan.grid == (B <= 8 ? 2001 : 251));
+            EXPECT(plan.xblk == (B > 8) && !plan.xgblk);
+            const bool o8 = scratch && (B >= 33 || (big && w8 && B <= 16)), d8 = scratch && (B >= 17 || (big && w8));
+            const int nwb = big ? 10 : 8;
+            EXPECT(ok(call(GV_RESIDNORM, H, H, B, w8, scratch, w12)) && shape_is(1, ct, x2 && !o8, o8, o8 ? nwb : 0, o8 ? wf : wf1) && plan.units == H / 16 && plan.grid == H / 16);
+            EXPECT(ok(call(GV_RESIDNORM, H, I, B, w8, scratch, w12)) && shape_is(1, ct, x2 && !d8, d8, d8 ? nwb : 0, d8 ? wf : wf1));
+            EXPECT(plan.xgblk == (B > 8) && !plan.xblk);
+            // the one predicate, also where a 12-bit copy next to fp8 weights is refused as an argument
+            GemvChoice c; c.ct = ct;
+            EXPECT(gemv_weight_format(w8, true, c) == (w8 ? WF_FP8 : (ct == 1 ? WF_12 : WF_16)) && gemv_weight_format(w8, false, c) == wf);
+            c.k8 = true;
+            EXPECT(gemv_weight_format(w8, true, c) == wf);
+        }
+    }
+    {   // (2) totality
+        const int modes[5] = {GV_STORE16, GV_RESID, GV_SWIGLU, GV_F32, GV_RESIDNORM}, Ks[6] = {32, 64, 4096, 5120, 11008, 13824}, cus[4] = {1, 64, 256, 304};
+        long long points = 0, holes = 0;
+        for (int mi = 0; mi < 5; ++mi) for (int w8 = 0; w8 < 2; ++w8) for (int B = 1; B <= 64; ++B) for (int ki = 0; ki < 6; ++ki) for (int ci = 0; ci < 4; ++ci)
+            for (int scratch = 0; scratch < 2; ++scratch) for (int units = 1; units <= 2600; ++units, ++points) {
+                const int mode = modes[mi];
+                const GemvChoice c = choose_gemv(mode, w8, B, units, Ks[ki], cus[ci], scratch);
+                bool good = c.ct == gemv_col_tiles(B);
+                if (c.k8) good = good && mode == GV_RESIDNORM && scratch && units % c.nwb == 0 && gemv_has_k8_kernel(c.ct, c.nwb) && (c.ct > 1 || w8);
+                else {
+                    const bool x2 = c.x2 && c.ct == 1;
+                    good = good && gemv_has_kernel(mode, c.tl, c.ct, w8 ? WF_FP8 : WF_16, x2) && (w8 || c.ct > 1 || gemv_has_kernel(mode, c.tl, c.ct, WF_12, x2));
+                }
+                if (mode == GV_STORE16) good = good && units % c.tl == 0;
+                if (c.x2) good = good && B <= 8 && c.ct == 1 && c.tl < 6;
+                if (!good && holes++ < 10) printf("mode %d w8 %d B %d units %d K %d CUs %d scratch %d -> tl %d ct %d x2 %d k8 %d nwb %d\n", mode, w8, B, units, Ks[ki], cus[ci], scratch, c.tl, c.ct, c.x2, c.k8, c.nwb);
+            }
+        EXPECT(holes == 0 && points == 5LL * 2 * 64 * 6 * 4 * 2 * 2600);
+        // the predicates themselves: what the list holds and what it forbids
+        EXPECT(gemv_has_kernel(GV_F32, 8, 1, WF_12, false) && !gemv_has_kernel(GV_F32, 8, 1, WF_12, true) && !gemv_has_kernel(GV_F32, 8, 1, WF_16, true));
+        EXPECT(gemv_has_kernel(GV_STORE16, 4, 1, WF_12, true) && !gemv_has_kernel(GV_STORE16, 4, 2, WF_12, false) && !gemv_has_kernel(GV_STORE16, 4, 2, WF_FP8, true));
+        EXPECT(gemv_has_kernel(GV_SWIGLU, 6, 4, WF_FP8, false) && !gemv_has_kernel(GV_SWIGLU, 6, 1, WF_16, false) && !gemv_has_kernel(GV_STORE16, 2, 1, WF_16, false));
+        EXPECT(!gemv_has_kernel(4, 1, 1, WF_16, false) && gemv_has_k8_kernel(4, 10) && !gemv_has_k8_kernel(3, 8) && !gemv_has_k8_kernel(1, 9));
+        int rows = 0, k8s = 0;
+#define COUNT_ROW(M, TL, CT) ++rows;
+#define COUNT_K8(CT, NWB) ++k8s;
+        GEMV_KERNELS(COUNT_ROW, COUNT_K8)
+        EXPECT(rows == 30 && k8s == 6);
+        EXPECT(gemv_col_tiles(1) == 1 && gemv_col_tiles(16) == 1 && gemv_col_tiles(17) == 2 && gemv_col_tiles(32) == 2 && gemv_col_tiles(33) == 4 && gemv_col_tiles(64) == 4);
+        EXPECT(gemv_xblk_tiles(1) == 0 && gemv_xblk_tiles(8) == 0 && gemv_xblk_tiles(9) == 1 && gemv_xblk_tiles(16) == 1 && gemv_xblk_tiles(17) == 2 && gemv_xblk_tiles(33) == 4);
+        EXPECT(gemv_grid(GV_SWIGLU, 25, 8) == 7 && gemv_grid(GV_SWIGLU, 24, 8) == 6 && gemv_grid(GV_F32, 2001, 8) == 251 && gemv_grid(GV_STORE16, 768, 3) == 256);
+        EXPECT(kGemvSsqChunks == 1536);
+    }
+    {   // (3) sizes
+        for (int H = 4096; H <= 5120; H += 1024) for (int ct = 1; ct <= 4; ct *= 2) {
+            const size_t nrb = (size_t)H / 16;
+            EXPECT(gemv_k8_part_bytes(H / 16, ct) == nrb * 8 * ct * 64 * 16 && gemv_k8_part_bytes(H / 16, ct) == nrb * 8 * ct * 1024);
+        }
+        for (int K = 32; K <= 13824; K += 32) for (int ct = 1; ct <= 4; ct *= 2) {
+            const unsigned lds = gemv_k8_lds_bytes(K, ct), group = ct * 16 * 128;
+            EXPECT(lds >= group && lds <= 98304 && lds % group == 0);
+        }
+        EXPECT(gemv_k8_lds_bytes(4096, 1) == 8 * 2048 && gemv_k8_lds_bytes(13824, 4) == 98304 && gemv_k8_lds_bytes(13824, 2) == 98304 && gemv_k8_lds_bytes(5120, 4) == 10 * 8192 && gemv_k8_lds_bytes(11008, 4) == 12 * 8192);
+    }
+    {   // (4a) the refusals of a launch
+        GemvCall c = call(GV_STORE16, 64, 64, 1, false, false, false);
+        EXPECT(ok(c));
+        c.B = 0;  EXPECT(refused(c, "gemv: batch 0 outside [1,64]"));
+        c.B = 65; EXPECT(refused(c, "gemv: batch 65 outside [1,64]"));
+        c.B = 64; EXPECT(ok(c));
+        c.K = 48; EXPECT(refused(c, "gemv: K=48 must be a multiple of 32"));
+        c.K = 96; EXPECT(ok(c));
+        c.w8 = true; EXPECT(refused(c, "gemv fp8: K=96 must be a multiple of 64"));
+        c.K = 128; EXPECT(ok(c) && plan.wf == WF_FP8);
+        c = call(4, 64, 64, 1, false, false, false); EXPECT(refused(c, "gemv: bad mode 4"));
+        c.mode = 6; EXPECT(refused(c, "gemv: bad mode 6"));
+        c.mode = -1; EXPECT(refused(c, "gemv: bad mode -1"));
+        // the tile strides of the side arrays
+        c = call(GV_F32, 64, 64, 17, false, false, false);
+        c.amax_val = true; EXPECT(ok(c));
+        c.amax_ts = 0; EXPECT(refused(c, "gemv: batches beyond 16 need the tile strides of the side arrays"));
+        c.amax_val = false; EXPECT(ok(c));
+        c.ssq_ts = 0; EXPECT(refused(c, "gemv: batches beyond 16 need the tile strides of the side arrays"));
+        c.B = 16; EXPECT(ok(c));
+        c.B = 17; c.norm = false; EXPECT(ok(c) && !plan.xblk);
+        // sum-of-squares partials
+        c = call(GV_STORE16, 64, 64, 1, false, false, false);
+        c.nparts_in = 384; EXPECT(ok(c));
+        c.nparts_in = 385; EXPECT(refused(c, "gemv: 385 sum-of-squares partials exceed what a consumer workgroup loads (hidden <= 6144)"));
+        // row counts
+        c = call(GV_STORE16, 40, 64, 1, false, false, false); EXPECT(refused(c, "gemv: N=40 must be a multiple of 16"));
+        c.mode = GV_RESID; EXPECT(refused(c, "gemv: N=40 must be a multiple of 16"));
+        c.mode = GV_F32; EXPECT(ok(c) && plan.units == 3);
+        c = call(GV_SWIGLU, 96, 64, 1, false, false, false); EXPECT(refused(c, "gemv swiglu: N=96 must be a multiple of 64"));
+        c.N = 128; EXPECT(ok(c) && plan.units == 4 && plan.grid == 4 && plan.tl == 2);
+        // the producer
+        c = call(GV_RESIDNORM, 48, 64, 9, false, false, false); EXPECT(refused(c, "gemv: a blocked xg needs N in multiples of 32"));
+        c.B = 8; EXPECT(ok(c) && !plan.xgblk);
+        c.B = 9; c.x_blocked = false; EXPECT(ok(c) && !plan.xgblk);
+        c.x_blocked = true; c.N = 64; EXPECT(ok(c) && plan.xgblk);
+        c.gamma = false; EXPECT(refused(c, "gemv: the residual+norm producer needs gamma / xg / ssq_out"));
+        c.gamma = true; c.xg = false; EXPECT(refused(c, "gemv: the residual+norm producer needs gamma / xg / ssq_out"));
+        c.xg = true; c.ssq_out = false; EXPECT(refused(c, "gemv: the residual+norm producer needs gamma / xg / ssq_out"));
+        c.ssq_out = true; c.norm = false; EXPECT(refused(c, "gemv: the residual+norm producer needs gamma / xg / ssq_out"));
+        // the 12-bit copy
+        c = call(GV_STORE16, 64, 64, 16, false, false, true); EXPECT(ok(c) && plan.wf == WF_12);
+        c.w8 = true; EXPECT(refused(c, "gemv: bad 12-bit weight copy (64 rows for N = 64, K = 64)"));
+        c.w8 = false; c.bf16 = false; EXPECT(refused(c, "gemv: bad 12-bit weight copy (64 rows for N = 64, K = 64)"));
+        c.bf16 = true; c.K = 96; EXPECT(refused(c, "gemv: bad 12-bit weight copy (64 rows for N = 64, K = 96)"));
+        c.K = 64; c.rows12 = 72; EXPECT(refused(c, "gemv: bad 12-bit weight copy (72 rows for N = 64, K = 64)"));
+        c.rows12 = 48; EXPECT(refused(c, "gemv: bad 12-bit weight copy (48 rows for N = 64, K = 64)"));
+        c.rows12 = 80; EXPECT(ok(c));
+        c.mode = GV_F32; c.N = 70; EXPECT(ok(c));
+        c.N = 81; EXPECT(refused(c, "gemv: bad 12-bit weight copy (80 rows for N = 81, K = 64)"));
+        c = call(GV_STORE16, 64, 64, 16, false, false, true); c.W = false; EXPECT(ok(c) && plan.wf == WF_12);
+        c.B = 17; EXPECT(refused(c, "gemv: 17 sequences need the 16-bit matrix (the 12-bit copy serves one column tile)"));
+        c.W = true; EXPECT(ok(c) && plan.wf == WF_16);
+        char tiny[8];                           // a short message buffer is not overrun
+        c.B = 0; EXPECT(gemv_plan_build(c, plan, tiny, sizeof(tiny)) == GEMV_PLAN_EINVAL && !strcmp(tiny, "gemv: b"));
+    }
+    {   // (4b) the refusals of the test entry
+        GemvDescShape g;
+        g.mode = GV_STORE16; g.N = 64; g.K = 64; g.B = 33; g.ldx = 64; g.ldo = 64; g.W = g.x = g.out = true;
+        GemvDescShape d = g;
+        EXPECT(dok(d));
+        d.W = false; EXPECT(drefused(d, "pgv_gemv_ex: null W / x / out"));
+        d.W12 = true; EXPECT(dok(d));
+        d = g; d.x = false; EXPECT(drefused(d, "pgv_gemv_ex: null W / x / out"));
+        d = g; d.out = false; EXPECT(drefused(d, "pgv_gemv_ex: null W / x / out"));
+        d = g; d.mode = 4; EXPECT(drefused(d, "pgv_gemv_ex: mode 4 is none of 0..3, 5"));
+        d.mode = -1; EXPECT(drefused(d, "pgv_gemv_ex: mode -1 is none of 0..3, 5"));
+        d.mode = 6; EXPECT(drefused(d, "pgv_gemv_ex: mode 6 is none of 0..3, 5"));
+        d = g; d.B = 65; EXPECT(drefused(d, "pgv_gemv_ex: bad shape N = 64, K = 64, B = 65"));
+        d.B = 0; EXPECT(drefused(d, "pgv_gemv_ex: bad shape N = 64, K = 64, B = 0"));
+        d.B = 64; EXPECT(dok(d));
+        d.B = 1; EXPECT(dok(d));
+        d.N = 0; EXPECT(drefused(d, "pgv_gemv_ex: bad shape N = 0, K = 64, B = 1"));
+        d = g; d.K = 31; d.ldx = 32; EXPECT(drefused(d, "pgv_gemv_ex: bad shape N = 64, K = 31, B = 33"));
+        d.K = 32; EXPECT(dok(d));
+        d = g; d.ldx = 56; EXPECT(drefused(d, "pgv_gemv_ex: ldx = 56 for K = 64 (row-major x: 16-byte rows)"));
+        d.ldx = 68; EXPECT(drefused(d, "pgv_gemv_ex: ldx = 68 for K = 64 (row-major x: 16-byte rows)"));
+        d.ldx = 72; EXPECT(dok(d));
+        d.ldx = 0; d.x_blocked = true; EXPECT(dok(d));                 // a blocked consumer operand has no row stride
+        d.B = 8; EXPECT(drefused(d, "pgv_gemv_ex: ldx = 0 for K = 64 (row-major x: 16-byte rows)"));      // up to 8 sequences x stays row-major
+        d = g; d.ldo = 60; EXPECT(drefused(d, "pgv_gemv_ex: ldo = 60 for N = 64, mode 0"));
+        d.ldo = 66; EXPECT(drefused(d, "pgv_gemv_ex: ldo = 66 for N = 64, mode 0"));
+        d.mode = GV_F32; EXPECT(dok(d));
+        d.mode = GV_SWIGLU; d.ldo = 32; EXPECT(dok(d));
+        d.ldo = 28; EXPECT(drefused(d, "pgv_gemv_ex: ldo = 28 for N = 64, mode 2"));
+        d = g; d.ssq_ts = -1; EXPECT(drefused(d, "pgv_gemv_ex: negative stride or count"));
+        d = g; d.amax_ts = -1; EXPECT(drefused(d, "pgv_gemv_ex: negative stride or count"));
+        d = g; d.nparts_in = -1; EXPECT(drefused(d, "pgv_gemv_ex: negative stride or count"));
+        // the consumer side
+        d = g; d.ssq_in = true; d.nparts_in = 4; d.hidden = 64; d.ssq_ts = 64; EXPECT(dok(d));
+        d.ssq_ts = 63; EXPECT(drefused(d, "pgv_gemv_ex: ssq_in needs a consumer mode, nparts_in >= 1, hidden >= 1 and ssq_ts >= 16 nparts_in (mode 0, 4 parts, ssq_ts 63)"));
+        d.ssq_ts = 64; d.hidden = 0; EXPECT(drefused(d, "pgv_gemv_ex: ssq_in needs a consumer mode, nparts_in >= 1, hidden >= 1 and ssq_ts >= 16 nparts_in (mode 0, 4 parts, ssq_ts 64)"));
+        d.hidden = 1; d.nparts_in = 0; EXPECT(drefused(d, "pgv_gemv_ex: ssq_in needs a consumer mode, nparts_in >= 1, hidden >= 1 and ssq_ts >= 16 nparts_in (mode 0, 0 parts, ssq_ts 64)"));
+        d.nparts_in = 1; EXPECT(dok(d));
+        d.mode = GV_RESID; EXPECT(drefused(d, "pgv_gemv_ex: ssq_in needs a consumer mode, nparts_in >= 1, hidden >= 1 and ssq_ts >= 16 nparts_in (mode 1, 1 parts, ssq_ts 64)"));
+        // the producer side
+        GemvDescShape p = g;
+        p.mode = GV_RESIDNORM; p.gamma = p.xg = p.ssq_out = true; p.ssq_ts = 64;
+        d = p; EXPECT(dok(d));
+        d.ssq_ts = 63; EXPECT(drefused(d, "pgv_gemv_ex: a producer needs gamma, xg, ssq_out and ssq_ts >= N (63 < 64)"));
+        d = p; d.gamma = false; EXPECT(drefused(d, "pgv_gemv_ex: a producer needs gamma, xg, ssq_out and ssq_ts >= N (64 < 64)"));
+        d = p; d.xg = false; EXPECT(drefused(d, "pgv_gemv_ex: a producer needs gamma, xg, ssq_out and ssq_ts >= N (64 < 64)"));
+        d = p; d.ssq_out = false; EXPECT(drefused(d, "pgv_gemv_ex: a producer needs gamma, xg, ssq_out and ssq_ts >= N (64 < 64)"));
+        d = p; d.gamma = d.xg = d.ssq_out = false; EXPECT(drefused(d, "pgv_gemv_ex: gamma / xg / ssq_out belong to mode 5, and mode 5 needs all three"));
+        d = g; d.gamma = true; EXPECT(drefused(d, "pgv_gemv_ex: gamma / xg / ssq_out belong to mode 5, and mode 5 needs all three"));
+        d = p; d.x_blocked = true; d.ldx = 0; EXPECT(drefused(d, "pgv_gemv_ex: ldx = 0 for K = 64 (row-major x: 16-byte rows)"));       // a producer reads x row-major
+        d = p; d.k8_part = true; d.k8_part_bytes = 4 * 8 * 4 * 1024; EXPECT(dok(d));
+        d.k8_part_bytes -= 1; EXPECT(drefused(d, "pgv_gemv_ex: k8_part belongs to mode 5 and holds (N / 16) * 8 * ct * 1024 = 131072 bytes (131071 given)"));
+        d.B = 32; EXPECT(dok(d));                                       // two column tiles: half the scratch
+        d = g; d.k8_part = true; d.k8_part_bytes = 1 << 20; EXPECT(drefused(d, "pgv_gemv_ex: k8_part belongs to mode 5 and holds (N / 16) * 8 * ct * 1024 = 131072 bytes (1048576 given)"));
+        // the arg-max candidates
+        GemvDescShape h = g;
+        h.mode = GV_F32; h.N = 70; h.ldo = 70; h.amax_val = h.amax_idx = true; h.amax_ts = 80;
+        d = h; EXPECT(dok(d));
+        d.amax_ts = 79; EXPECT(drefused(d, "pgv_gemv_ex: the candidates need mode 3, both arrays and amax_ts >= 16 ceil(N / 16) (79 < 80)"));
+        d = h; d.amax_idx = false; EXPECT(drefused(d, "pgv_gemv_ex: the candidates need mode 3, both arrays and amax_ts >= 16 ceil(N / 16) (80 < 80)"));
+        d = h; d.amax_val = false; EXPECT(drefused(d, "pgv_gemv_ex: the candidates need mode 3, both arrays and amax_ts >= 16 ceil(N / 16) (80 < 80)"));
+        d = g; d.amax_val = d.amax_idx = true; d.amax_ts = 64; EXPECT(drefused(d, "pgv_gemv_ex: the candidates need mode 3, both arrays and amax_ts >= 16 ceil(N / 16) (64 < 64)"));
+    }
+    if (!bad) printf("OK\n");
+    return bad;
+}
+"""
+    cpp, exe, exe_san = tmp_path / "gemv_plan.cpp", tmp_path / "gemv_plan", tmp_path / "gemv_plan_san"
+    cpp.write_text(prog)
+    base = [gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", csrc, str(cpp)]
+    subprocess.run([*base, "-o", str(exe)], check=True)
+    exes = [exe]
+    san = subprocess.run([*base, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe_san)], capture_output=True, text=True)
+    if san.returncode == 0:
+        exes.append(exe_san)
+    else:
+        assert "asan" in san.stderr or "ubsan" in san.stderr, san.stderr        # only a missing sanitizer runtime excuses the second build
+        print("g++ has no sanitizer runtimes here: plain build only")
+    for x in exes:
+        r = subprocess.run([str(x)], capture_output=True, text=True)
+        assert r.returncode == 0 and not r.stderr and r.stdout == "OK\n", (x, r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    # the column-tile rule is written once
+    tiles = [f for f in sorted(os.listdir(csrc)) if "<= 32 ? 2 : 4" in open(os.path.join(csrc, f)).read()]
+    assert tiles == ["gemv_plan.h"], tiles
+
+
 # --------------------------------------------------------------------------------------------------
 # offline feature extraction (scripts/save_spatio_temporal_clip_features.py) and the QA runner: host logic
 # --------------------------------------------------------------------------------------------------

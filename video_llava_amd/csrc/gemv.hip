@@ -24,30 +24,30 @@ namespace {
 // W (r rstd gamma) = rstd W (r gamma) exactly in real arithmetic; in floating point the 16-bit rounding now happens before the scale by rstd
 // instead of after it -- the same relative error, no weight is modified, so the fp8 path keeps its bit-equality with the 16-bit path.
 struct GemvArgs {
-    const char* W; const char* x; char* out;
-    int N, K, B, ldx, ldo;
-    const float* wscale;   // W8 = true: per-row power-of-two scales of the fp8 matrix (fp8.hip)
+    const char* W = nullptr; const char* x = nullptr; char* out = nullptr;
+    int N = 0, K = 0, B = 0, ldx = 0, ldo = 0;
+    const float* wscale = nullptr;   // W8 = true: per-row power-of-two scales of the fp8 matrix (fp8.hip)
     // consumer side of the folded RMSNorm (null ssq_in: plain GEMV)
-    const float* ssq_in; int nparts_in; float inv_h, eps;      // ssq_in [nparts_in][16]
+    const float* ssq_in = nullptr; int nparts_in = 0; float inv_h = 0.f, eps = 0.f;      // ssq_in [nparts_in][16]
     // producer side (GV_RESIDNORM): out = fp32 residual [B][ldo] (read-modify-write)
-    const float* gamma; char* xg; float* ssq_out;              // xg [B][ldo] 16-bit, ssq_out [gridDim.x][16]
+    const float* gamma = nullptr; char* xg = nullptr; float* ssq_out = nullptr;              // xg [B][ldo] 16-bit, ssq_out [gridDim.x][16]
     // GV_F32 (lm_head): per-workgroup greedy candidates -- the largest logit of the workgroup's 16 rows and its (smallest) index per batch
     // column -- so the token pick scans N / 16 candidates instead of N logits (null: not wanted)
-    float* amax_val; int* amax_idx;                            // [gridDim.x][16]
+    float* amax_val = nullptr; int* amax_idx = nullptr;                            // [gridDim.x][16]
     // batches beyond one MFMA tile (CT column tiles of 16 sequences, B <= 16 CT): every per-batch-column side array above is tile-major,
     // [CT][...][16], with these tile strides in elements
-    int ssq_ts, amax_ts;
-    unsigned lds_bytes;                                        // gemv_k8_kernel: bytes of LDS for the x slice of one pass
+    int ssq_ts = 0, amax_ts = 0;
+    unsigned lds_bytes = 0;                                    // gemv_k8_kernel: bytes of LDS for the x slice of one pass
     // Batches beyond 16 (round 6): the activation operand of the CONSUMERS (qkv, gate/up, lm_head) is in the fragment-blocked activation layout
     // [K / 32][CT][4 k-groups][16 sequences][8 elements] (gv_xblk_offset): an MFMA B fragment is one contiguous 1 KiB wave-load, like a weight
     // fragment, instead of 16 rows x 64 B.  The activation operand is re-read by every workgroup and at 64 sequences it is MORE bytes on a CU's
     // load path than its weights (512 KB against 393 KB for qkv); with row-major rows the loads alone took 26 us of the 38 us qkv launch
     // (x-only ablation, LAB.md), blocked 19.  xblk: x is blocked; xgblk: the producer writes xg blocked.
-    int xblk, xgblk;
+    int xblk = 0, xgblk = 0;
     // W12 = true: W is the unit plane of the 12-bit copy (w12.h), with its row blocks' exception lists and row bases
-    const unsigned* w12exc; const unsigned char* w12base;
+    const unsigned* w12exc = nullptr; const unsigned char* w12base = nullptr;
 #ifdef PGV_LAB
-    int abl;           // lab builds only (PGV_GEMV_ABLATE; results are garbage): 1 = no x loads in the K loop, 2 = no MFMA, 4 = no weight loads
+    int abl = 0;       // lab builds only (PGV_GEMV_ABLATE; results are garbage): 1 = no x loads in the K loop, 2 = no MFMA, 4 = no weight loads
 #endif
 };
 #ifdef PGV_LAB
@@ -77,7 +77,7 @@ __device__ __forceinline__ typename T::v8 fp8x8_to_v8(unsigned lo, unsigned hi) 
     return r;
 }
 
-// NW = kGemvWaves = waves per workgroup (the K split inside a workgroup): 8.  The residual producers cannot split K across workgroups (the workgroup that
+// NW = kGemvWaves (gemv_plan.h) = waves per workgroup (the K split inside a workgroup): 8.  The residual producers cannot split K across workgroups (the workgroup that
 // owns 16 output rows must see their complete sums to emit xg and the sum of squares), so o_proj / down_proj run 256 workgroups = one per CU
 // with 8 waves; the pipelined weight stream below keeps enough loads in flight for that (down_proj 16.4 us; a 16-wave variant, needed
 // before the stream was pipelined, takes 19.3 us: twice the LDS partials and 12 % dead tail loads at 10.75 groups per wave).
@@ -115,7 +115,6 @@ constexpr int kW12ProducerPU = PGV_W12_PRODUCER_PU;
 constexpr int gemv_pu(int tl, bool w8, int ct, bool w12 = false, bool producer = false) {
     return (w12 && producer && tl == 1 && ct == 1) ? kW12ProducerPU : (ct > 1 || tl >= 6) ? 1 : (tl == 1 ? 2 : 1) * (w8 ? 2 : 1);
 }
-constexpr int kGemvWaves = 8;          // waves per workgroup = K phases of a row block (the arithmetic of every launch shape is defined on these 8 chains)
 
 // W12 (one column tile): the 12-bit copy (w12.h) -- per unit and row block one 16-byte load of low bytes and one 8-byte load of codes per lane,
 // the high bytes rebuilt with packed byte arithmetic, the rare exceptions patched in (wave-uniform branch), and the two 16-bit A fragments
@@ -166,6 +165,7 @@ __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) 
     // (three independent loads whose first USE is after the weight loop: summing them here would park the wave on an L2 round trip
     // before its first weight load -- measured +1.4 us on the 18 us qkv GEMV)
     constexpr int SSQ_LD = 3;                                   // 3 x NW x 64 float4 >= 4 x hidden / 16 up to hidden 6144
+    static_assert(SSQ_LD * NW * 64 == kGemvSsqChunks, "gemv_plan.h refuses more partials than these loads cover");
     // ... except in the widest shapes (4 row blocks x 4 column tiles): there the 48 registers the partials would occupy across the weight loop
     // are what decides between 256 VGPRs and a spill, and a 60 us launch does not notice the round trip: requested after the loop.
     constexpr bool SSQ_LATE = (CT * TILES >= 16);
@@ -607,6 +607,8 @@ __global__ __launch_bounds__(kGemvWaves * 64) void gemv_mfma_kernel(GemvArgs p) 
 // NWB row blocks (= waves) per workgroup: 8.
 // ---------------------------------------------------------------------------------------------
 // Sum of the eight phase tiles of row block rb in phase order + the epilogue of gemv_mfma_kernel<GV_RESIDNORM>, statement for statement (one wave).
+// (A second copy on purpose: one shared __forceinline__ function was tried and hipcc then schedules the 2- and 4-tile 16-row producers differently,
+// LAB.md "GEMV plan header"; the bitwise equality of the two forms rests on the two copies staying identical.)
 template <typename T, bool W8, int CT>
 __device__ __forceinline__ void k8_finish_row_block(const GemvArgs& p, const f32x4_t* __restrict__ part, int rb, int lane, const f32x4_t (&r_old)[CT], f32x4_t g_nx) {
     const int l15 = lane & 15, kg = lane >> 4;
@@ -764,13 +766,21 @@ __global__ __launch_bounds__(64) void gemv_k8_finish_kernel(GemvArgs p, const f3
     k8_finish_row_block<T, W8, CT>(p, part, rb, lane, r_old, g_nx);
 }
 
+// Tail of the two prep kernels (256 threads, one sequence): the sum of squares over the four waves -> ssq, tile-major [B / 16][...][16]
+__device__ __forceinline__ void prep_ssq_store(float ss, float* __restrict__ ssq, int b, int ssq_ts) {
+    __shared__ float red[4];
+    ss = wave_sum(ss);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) ssq[(size_t)(b >> 4) * ssq_ts + (b & 15)] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // decode: resid[b] = embed[tok[b]] plus the producer side of the folded RMSNorm (see GemvArgs): xg = round16(resid * gamma of layer 0's
 // input norm), ssq[0][b] = sum resid^2 (one partial per sequence).
 // xct > 0: xg is written in the fragment-blocked activation layout with xct column tiles (gv_xblk_offset); 0: row-major [B][H].
 template <typename T>
 __global__ __launch_bounds__(256) void embed_tok_norm_kernel(const int* __restrict__ tok, const typename T::elem* __restrict__ embed, float* __restrict__ resid,
                                                              const float* __restrict__ gamma, typename T::elem* __restrict__ xg, float* __restrict__ ssq, int H, int ssq_ts, int xct) {
-    __shared__ float red[4];
     const int b = blockIdx.x;
     const typename T::elem* p = embed + (size_t)tok[b] * H;
     float ss = 0.f;
@@ -788,10 +798,7 @@ __global__ __launch_bounds__(256) void embed_tok_norm_kernel(const int* __restri
 #pragma unroll
         for (int e = 0; e < 4; ++e) ss += a[e] * a[e] + bb[e] * bb[e];
     }
-    ss = wave_sum(ss);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) ssq[(size_t)(b >> 4) * ssq_ts + (b & 15)] = (red[0] + red[1]) + (red[2] + red[3]);     // tile-major [B / 16][...][16]
+    prep_ssq_store(ss, ssq, b, ssq_ts);
 }
 
 // Producer side of the folded RMSNorm for rows that already sit in the fp32 residual (the last prompt position of every sequence
@@ -799,7 +806,6 @@ __global__ __launch_bounds__(256) void embed_tok_norm_kernel(const int* __restri
 template <typename T>
 __global__ __launch_bounds__(256) void resid_norm_prep_kernel(const float* __restrict__ resid, const float* __restrict__ gamma, typename T::elem* __restrict__ xg,
                                                               float* __restrict__ ssq, int H, int ssq_ts, int xct) {
-    __shared__ float red[4];
     const int b = blockIdx.x;
     float ss = 0.f;
     for (int c = threadIdx.x * 4; c < H; c += 256 * 4) {
@@ -807,17 +813,12 @@ __global__ __launch_bounds__(256) void resid_norm_prep_kernel(const float* __res
         *(u32x2_t*)((char*)xg + (xct ? gv_xblk_offset(b, c, xct) : ((size_t)b * H + c) * 2)) = pack4<T>(r[0] * g[0], r[1] * g[1], r[2] * g[2], r[3] * g[3]);
         ss += (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]);
     }
-    ss = wave_sum(ss);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) ssq[(size_t)(b >> 4) * ssq_ts + (b & 15)] = (red[0] + red[1]) + (red[2] + red[3]);
+    prep_ssq_store(ss, ssq, b, ssq_ts);
 }
 
 }  // namespace
 
-// Column tiles of the blocked activation layout for a batch of B sequences (0: row-major -- up to 8 sequences the merged row loads of the
-// narrow kernels, one full line per sequence and group, are cheaper).  The ONE place that decides it: producers and consumers must agree.
-int pgv_gemv_xblk_tiles(int B) { return B <= 8 ? 0 : (B <= 16 ? 1 : (B <= 32 ? 2 : 4)); }
+int pgv_gemv_xblk_tiles(int B) { return gemv_xblk_tiles(B); }
 
 int pgv_launch_final_prep(int dtype, const float* resid, const float* gamma, void* xg, float* ssq, int B, int H, hipStream_t s, bool x_blocked) {
     PGV_CHECK(H % 32 == 0, "final_prep: hidden %d unsupported", H);
@@ -835,239 +836,129 @@ int pgv_launch_embed_tok_norm(int dtype, const int* tok, const void* embed, floa
 }
 
 // ---------------------------------------------------------------------------------------------
-// launch-shape selection: ONE table of instantiations keyed on (epilogue, row blocks per workgroup, column tiles) x (fp8 weights, merged x load),
-// and one function that picks the key from (mode, w8, B, N, K, CUs).  Nothing here depends on anything but the model shape and the batch's
-// column-tile count, and every shape computes bit-identical results per batch column (tests/test_gpu_llm.py), so the choice is performance only.
+// launch: gemv_plan.h checks the arguments and picks the shape from (mode, w8, B, N, K, CUs); its list of instantiations (GEMV_KERNELS) becomes
+// the launch lookup, the 8-phase launch and the per-device configure loop here.
 // ---------------------------------------------------------------------------------------------
-// Launch-shape A/B switches exist in the lab library only (-DPGV_LAB, never loaded by the product): PGV_GEMV_TL3, PGV_GEMV_X2, PGV_GEMV_K8,
-// PGV_GEMV_K8_NARROW_MINK.  The release library uses the defaults.
-static int lab_switch(const char* name, int dflt) {
+// Launch-shape A/B switches exist in the lab library only (-DPGV_LAB, never loaded by the product); the release library runs GemvLab's defaults.
 #ifdef PGV_LAB
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-#else
-    (void)name;
-    return dflt;
+static int lab_switch(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 #endif
+static GemvLab gemv_lab() {
+    GemvLab l;
+#ifdef PGV_LAB
+    l.x2 = lab_switch("PGV_GEMV_X2", l.x2); l.k8 = lab_switch("PGV_GEMV_K8", l.k8); l.k8_nwb10 = lab_switch("PGV_GEMV_K8_NWB10", l.k8_nwb10);
+    l.k8_narrow_mink = lab_switch("PGV_GEMV_K8_NARROW_MINK", l.k8_narrow_mink); l.tl3 = lab_switch("PGV_GEMV_TL3", l.tl3); l.tl4 = lab_switch("PGV_GEMV_TL4", l.tl4);
+    l.wide_qkv4 = lab_switch("PGV_GEMV_WIDE_QKV4", l.wide_qkv4); l.wide_tl4 = lab_switch("PGV_GEMV_WIDE_TL4", l.wide_tl4); l.wide_tl6 = lab_switch("PGV_GEMV_WIDE_TL6", l.wide_tl6);
+    l.wide_tl8 = lab_switch("PGV_GEMV_WIDE_TL8", l.wide_tl8); l.wide_fp8 = lab_switch("PGV_GEMV_WIDE_FP8", l.wide_fp8); l.wide_head8 = lab_switch("PGV_GEMV_WIDE_HEAD8", l.wide_head8);
+#endif
+    return l;
 }
 
 using gemv_launch_fn = int (*)(int dtype, int grid, const GemvArgs& a, hipStream_t s);
 
-template <int MODE, bool W8, int TL, bool X2, int CT, bool W12 = false>
-static int launch_variant(int dtype, int grid, const GemvArgs& a, hipStream_t s) {
-    if constexpr (W12) {
+// One 16-row instantiation per (ROW entry, weight format, merged x load) that gemv_variant_ok allows -- 16-bit and fp8 in both activation
+// dtypes, 12-bit in bf16 -- and null for the rest.
+template <int MODE, int TL, int CT, int WF, bool X2>
+static int launch_row(int dtype, int grid, const GemvArgs& a, hipStream_t s) {
+    if constexpr (WF == WF_12) {
         PGV_CHECK(dtype == PGV_BF16, "gemv: the 12-bit weight stream is bf16 only");
         hipLaunchKernelGGL((gemv_mfma_kernel<TBF16, MODE, false, TL, X2, CT, true>), dim3(grid), dim3(kGemvWaves * 64), 0, s, a);
     } else {
-        PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gemv_mfma_kernel<T, MODE, W8, TL, X2, CT>), dim3(grid), dim3(kGemvWaves * 64), 0, s, a));
+        PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gemv_mfma_kernel<T, MODE, WF == WF_FP8, TL, X2, CT>), dim3(grid), dim3(kGemvWaves * 64), 0, s, a));
     }
     return PGV_OK;
 }
-
-template <int MODE, bool W8, int TL, int CT, bool W12 = false>
-constexpr gemv_launch_fn x2_variant() {          // the merged x load (B <= 8) uses the lanes of batch columns 8..15: one column tile only, not the half-group pipeline
-    if constexpr (CT == 1 && TL < 6) return &launch_variant<MODE, W8, TL, true, 1, W12>;
+template <int MODE, int TL, int CT, int WF, bool X2>
+constexpr gemv_launch_fn row_variant() {
+    if constexpr (gemv_variant_ok(TL, CT, WF, X2)) return &launch_row<MODE, TL, CT, WF, X2>;
     else return nullptr;
 }
-
-template <int MODE, int TL, int CT>
-constexpr gemv_launch_fn w12_variant() {
-    if constexpr (CT == 1) return &launch_variant<MODE, false, TL, false, 1, true>;
-    else return nullptr;
+static gemv_launch_fn find_row_kernel(int mode, const GemvPlan& pl) {
+#define GEMV_ROW(M, TL, CT)                                                                                                                          \
+    if (mode == M && pl.tl == TL && pl.ct == CT) {                                                                                                   \
+        constexpr gemv_launch_fn fn[3][2] = {{row_variant<M, TL, CT, WF_16, false>(), row_variant<M, TL, CT, WF_16, true>()},                        \
+                                             {row_variant<M, TL, CT, WF_FP8, false>(), row_variant<M, TL, CT, WF_FP8, true>()},                      \
+                                             {row_variant<M, TL, CT, WF_12, false>(), row_variant<M, TL, CT, WF_12, true>()}};                       \
+        return fn[pl.wf][pl.x2];                                                                                                                     \
+    }
+    GEMV_KERNELS(GEMV_ROW, GEMV_NONE)
+#undef GEMV_ROW
+    return nullptr;
 }
-
-enum { WF_16 = 0, WF_FP8 = 1, WF_12 = 2 };      // weight formats of the decode GEMVs
-struct GemvShape {
-    int mode, tl, ct;
-    gemv_launch_fn fn[3][2];                     // [weight format][merged x load]
-};
-template <int MODE, int TL, int CT>
-constexpr GemvShape gemv_shape() {
-    // 12-bit weights: one column tile (the main loop of the 16-row kernel, also at six and more row blocks)
-    constexpr gemv_launch_fn w12 = w12_variant<MODE, TL, CT>();
-    if constexpr (TL >= 6)                       // six row blocks and more: no merged x load (half-group pipelining for 16-bit weights; an fp8 group is ONE load per lane: whole groups)
-        return {MODE, TL, CT, {{&launch_variant<MODE, false, TL, false, CT>, nullptr}, {&launch_variant<MODE, true, TL, false, CT>, nullptr}, {w12, nullptr}}};
-    else
-        return {MODE, TL, CT, {{&launch_variant<MODE, false, TL, false, CT>, x2_variant<MODE, false, TL, CT>()},
-                               {&launch_variant<MODE, true, TL, false, CT>, x2_variant<MODE, true, TL, CT>()},
-                               {w12, x2_variant<MODE, false, TL, CT, true>()}}};
-}
-static const GemvShape kGemvShapes[] = {
-    // one MFMA tile of sequences (B <= 16)
-    gemv_shape<GV_STORE16, 1, 1>(), gemv_shape<GV_STORE16, 3, 1>(), gemv_shape<GV_STORE16, 4, 1>(), gemv_shape<GV_RESID, 1, 1>(), gemv_shape<GV_SWIGLU, 2, 1>(),
-    gemv_shape<GV_F32, 1, 1>(), gemv_shape<GV_F32, 8, 1>(), gemv_shape<GV_RESIDNORM, 1, 1>(),
-    // 2 / 4 column tiles (B <= 32 / 64)
-    gemv_shape<GV_STORE16, 1, 2>(), gemv_shape<GV_STORE16, 3, 2>(), gemv_shape<GV_STORE16, 4, 2>(), gemv_shape<GV_RESID, 1, 2>(), gemv_shape<GV_SWIGLU, 2, 2>(),
-    gemv_shape<GV_SWIGLU, 4, 2>(), gemv_shape<GV_SWIGLU, 6, 2>(), gemv_shape<GV_SWIGLU, 8, 2>(), gemv_shape<GV_F32, 1, 2>(), gemv_shape<GV_F32, 8, 2>(),
-    gemv_shape<GV_RESIDNORM, 1, 2>(),
-    gemv_shape<GV_STORE16, 1, 4>(), gemv_shape<GV_STORE16, 3, 4>(), gemv_shape<GV_STORE16, 4, 4>(), gemv_shape<GV_RESID, 1, 4>(), gemv_shape<GV_SWIGLU, 2, 4>(),
-    gemv_shape<GV_SWIGLU, 4, 4>(), gemv_shape<GV_SWIGLU, 6, 4>(), gemv_shape<GV_SWIGLU, 8, 4>(), gemv_shape<GV_F32, 1, 4>(), gemv_shape<GV_F32, 8, 4>(),
-    gemv_shape<GV_RESIDNORM, 1, 4>(),
-};
 
 // The 8-phase form of a residual producer with CT column tiles and NWB row blocks (= waves) per workgroup; `a` is complete except lds_bytes.
 // nrb = row blocks of the matrix (N / 16, a multiple of NWB): (nrb / NWB) row groups x 8 phases workgroups, then the finish launch.
 template <bool W8, int CT, int NWB>
 static int launch_k8(int dtype, GemvArgs a, int nrb, void* k8_part, hipStream_t s) {
-    const int gpw_max = ((a.K / 32 + 1) / 2 + 7) / 8;
-    const unsigned budget = 96u * 1024u, per_group = (unsigned)CT * 16u * 128u;
-    unsigned lds = (unsigned)gpw_max * per_group;
-    if (lds > budget) lds = budget / per_group * per_group;
-    a.lds_bytes = lds;
+    a.lds_bytes = gemv_k8_lds_bytes(a.K, CT);
     f32x4_t* part = (f32x4_t*)k8_part;
-    PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gemv_k8_kernel<T, W8, CT, NWB>), dim3(nrb / NWB * 8), dim3(NWB * 64), lds, s, a, part));
+    PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gemv_k8_kernel<T, W8, CT, NWB>), dim3(nrb / NWB * 8), dim3(NWB * 64), a.lds_bytes, s, a, part));
     if (GV_ABL(a, 16)) return PGV_OK;
     PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gemv_k8_finish_kernel<T, W8, CT>), dim3(nrb), dim3(64), 0, s, a, (const f32x4_t*)part));
     return PGV_OK;
 }
-using k8_launch_fn = int (*)(int dtype, GemvArgs a, int nrb, void* k8_part, hipStream_t s);
-static const k8_launch_fn kK8[2][3][2] = {      // [fp8 weights][column tiles 1 / 2 / 4][row blocks per workgroup 8 / 10]
-    {{&launch_k8<false, 1, 8>, &launch_k8<false, 1, 10>}, {&launch_k8<false, 2, 8>, &launch_k8<false, 2, 10>}, {&launch_k8<false, 4, 8>, &launch_k8<false, 4, 10>}},
-    {{&launch_k8<true, 1, 8>, &launch_k8<true, 1, 10>}, {&launch_k8<true, 2, 8>, &launch_k8<true, 2, 10>}, {&launch_k8<true, 4, 8>, &launch_k8<true, 4, 10>}}};
+static int launch_k8_shape(bool w8, const GemvPlan& pl, int dtype, const GemvArgs& a, void* k8_part, hipStream_t s) {
+#define GEMV_K8(CT, NWB) \
+    if (pl.ct == CT && pl.nwb == NWB) return w8 ? launch_k8<true, CT, NWB>(dtype, a, pl.units, k8_part, s) : launch_k8<false, CT, NWB>(dtype, a, pl.units, k8_part, s);
+    GEMV_KERNELS(GEMV_NONE, GEMV_K8)
+#undef GEMV_K8
+    PGV_CHECK(false, "gemv: no 8-phase kernel with %d column tiles x %d row blocks per workgroup", pl.ct, pl.nwb);
+    return PGV_EINVAL;
+}
 
 // The 8-phase kernels stage up to 96 KB of x in dynamic LDS: the opt-in attribute is per function AND per device, so it is set for every
 // instantiation when a context is created on a device (pgv_ctx_create), never lazily inside a launch (which may sit in a graph capture).
-template <bool W8, int CT, int NWB>
-static int configure_k8() {
-    PGV_HIP(hipFuncSetAttribute((const void*)gemv_k8_kernel<TF16, W8, CT, NWB>, hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-    PGV_HIP(hipFuncSetAttribute((const void*)gemv_k8_kernel<TBF16, W8, CT, NWB>, hipFuncAttributeMaxDynamicSharedMemorySize, 98304));
-    return PGV_OK;
-}
-template <bool W8, int CT>
-static int configure_k8_row() { PGV_TRY((configure_k8<W8, CT, 8>())); PGV_TRY((configure_k8<W8, CT, 10>())); return PGV_OK; }
+template <typename T, bool W8, int CT, int NWB>
+static int k8_opt_in() { PGV_HIP(hipFuncSetAttribute((const void*)gemv_k8_kernel<T, W8, CT, NWB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemvK8LdsMax)); return PGV_OK; }
 int pgv_gemv_configure(pgv_ctx*) {
-    PGV_TRY((configure_k8_row<false, 1>())); PGV_TRY((configure_k8_row<false, 2>())); PGV_TRY((configure_k8_row<false, 4>()));
-    PGV_TRY((configure_k8_row<true, 1>())); PGV_TRY((configure_k8_row<true, 2>())); PGV_TRY((configure_k8_row<true, 4>()));
+#define GEMV_K8(CT, NWB) \
+    PGV_TRY((k8_opt_in<TF16, false, CT, NWB>())); PGV_TRY((k8_opt_in<TBF16, false, CT, NWB>())); PGV_TRY((k8_opt_in<TF16, true, CT, NWB>())); PGV_TRY((k8_opt_in<TBF16, true, CT, NWB>()));
+    GEMV_KERNELS(GEMV_NONE, GEMV_K8)
+#undef GEMV_K8
     return PGV_OK;
 }
 
-struct GemvChoice { int tl, ct; bool x2, k8; int nwb; };
-
-// TL = row blocks per workgroup (they share the x fragments), CT = column tiles, x2 = merged x load, k8 = the 8-phase residual producer.
-static GemvChoice choose_gemv(int mode, bool w8, int B, int grid, int K, int num_cu, bool have_k8_scratch) {
-    GemvChoice c{1, B <= 16 ? 1 : (B <= 32 ? 2 : 4), B <= 8 && lab_switch("PGV_GEMV_X2", 1) != 0, false, 8};
-    // row blocks (= waves) per 8-phase workgroup: 8, or 10 where that makes (row groups x 8 phases) exactly one workgroup per CU (13B: 320 row
-    // blocks -> 32 groups x 8 = 256 workgroups of 10 waves instead of 320 of 8 = 1 1/4 rounds).  The (row block, phase) partition and the phase
-    // order of the sums do not depend on it: bitwise the same result.
-    // (13B fp8, 8 sequences, same box: 6.53 -> 6.64 videos/s with down_proj alone in that shape, 6.71 with o_proj as well.)
-    if (lab_switch("PGV_GEMV_K8_NWB10", 1) != 0 && grid % 10 == 0 && grid / 10 * 8 == num_cu) c.nwb = 10;
-    const bool k8_ok = have_k8_scratch && lab_switch("PGV_GEMV_K8", 1) != 0 && grid % c.nwb == 0;
-    if (B > 16) {
-        // Wide batches re-read 2 - 4 x the activation lines per workgroup, so the row blocks that share them matter more: qkv 3, gate/up two
-        // (gate, up) pairs when the block counts divide.
-        if (mode == GV_STORE16 && grid % 3 == 0) c.tl = 3;
-        // ... four where three leave a ragged second round and four fill one (13B qkv: 960 row blocks -> 320 workgroups = 1 1/4 rounds with three,
-        // 240 with four -- the choice the narrow batches make below, for the same reason)
-        if (mode == GV_STORE16 && lab_switch("PGV_GEMV_WIDE_QKV4", 1) != 0 && grid % 4 == 0 && grid / 4 <= num_cu && (grid % 3 != 0 || grid / 3 > num_cu)) c.tl = 4;
-        // (four column tiles: 228 VGPRs once the sum-of-squares partials are requested after the weight loop, SSQ_LATE)
-        if (mode == GV_SWIGLU) c.tl = (grid % 2 == 0 && (B <= 32 || lab_switch("PGV_GEMV_WIDE_TL4", 1) != 0)) ? 4 : 2;
-        // A wide workgroup holds a CU to itself (its registers and the LDS of its partial tiles), so the launch runs in ROUNDS of num_cu workgroups
-        // and every workgroup moves the whole activation operand through its CU: 7B gate/up = 688 (gate, up) pairs -> 344 workgroups of two pairs =
-        // two rounds (88 CUs run a second workgroup, the others wait: 50.9 us at 64 sequences), 230 workgroups of THREE pairs = one round and a third
-        // fewer reads of x (LAB.md round 6).  Taken when three pairs per workgroup fit one round and two do not.
-        if (mode == GV_SWIGLU && (!w8 || lab_switch("PGV_GEMV_WIDE_FP8", 1) != 0) && lab_switch("PGV_GEMV_WIDE_TL6", 1) != 0 && (grid + 2) / 3 <= num_cu && (grid + 1) / 2 > num_cu) c.tl = 6;
-        // ... four pairs where three still need a second round (13B gate/up: 864 pairs -> 288 workgroups of three, 216 of four)
-        else if (mode == GV_SWIGLU && (!w8 || lab_switch("PGV_GEMV_WIDE_FP8", 1) != 0) && lab_switch("PGV_GEMV_WIDE_TL8", 1) != 0 && (grid + 3) / 4 <= num_cu && (grid + 1) / 2 > num_cu) c.tl = 8;
-        // lm_head: 2001 row blocks; one per workgroup means 2001 passes over the activation operand (512 KB each against 128 KB of weights: 102 us at
-        // 64 sequences).  Eight per workgroup: 251 workgroups, one round.
-        if (mode == GV_F32 && (!w8 || lab_switch("PGV_GEMV_WIDE_FP8", 1) != 0) && lab_switch("PGV_GEMV_WIDE_HEAD8", 1) != 0 && (grid + 7) / 8 <= num_cu) c.tl = 8;
-        // narrow matrices (o_proj, down_proj): 8 row blocks x K phase per workgroup + a finish launch where it pays (kernel trace at 32 clips:
-        // down_proj 32.0 -> 22.4 + 4.9 us (finish), o_proj 13.3 -> 9.6 + 4.9: the short-K matrix only gains once the batch spans four tiles)
-        if (mode == GV_RESIDNORM) c.k8 = k8_ok && (K / 64) >= 16 && (B > 32 || K >= 8192);
-        return c;
-    }
-    switch (mode) {
-        case GV_STORE16:
-            // three row blocks per workgroup when that puts at most ~one workgroup on every CU and nothing is left over (7B qkv: 768 -> 256;
-            // 13B: 960 -> 320 workgroups, two resident per CU -- with fp8 weights a 16-row workgroup requests as many activation lines as weight
-            // lines: qkv 20.7 -> 18.7 us; with 16-bit weights the same launch shape LOSES 4 us per layer, so the relaxed bound is for fp8 only)
-            if (lab_switch("PGV_GEMV_TL3", 1) != 0 && grid % 3 == 0 && grid / 3 <= (w8 ? 2 : 1) * num_cu && grid / 3 >= num_cu / 2) c.tl = 3;
-            // ... unless three blocks leave a ragged second round and FOUR give one round that nearly fills the chip (13B qkv: 960 row blocks ->
-            // 320 workgroups = 1 1/4 rounds with three, 240 workgroups on 256 CUs with four: same box, fp8 weights 6.68 -> 6.92 videos/s and the
-            // GEMV family 0.539 -> 0.570 of 8 TB/s; 16-bit weights 4.79 -> 4.84)
-            if (lab_switch("PGV_GEMV_TL4", 1) != 0 && grid % 4 == 0 && grid / 4 <= num_cu && grid / 4 >= num_cu - num_cu / 8 &&
-                !(grid % 3 == 0 && grid / 3 == num_cu)) c.tl = 4;
-            break;
-        case GV_SWIGLU: c.tl = 2; break;
-        case GV_F32:
-            // lm_head at 9 .. 16 sequences: 2001 workgroups of one row block each read the whole activation operand (128 KB against 128 KB of
-            // weights); eight row blocks per workgroup as at the wide batches (251 workgroups, one round)
-            if ((!w8 || lab_switch("PGV_GEMV_WIDE_FP8", 1) != 0) && B > 8 && lab_switch("PGV_GEMV_WIDE_HEAD8", 1) != 0 && (grid + 7) / 8 <= num_cu) c.tl = 8;
-            break;
-        case GV_RESIDNORM:
-            // fp8 down_proj of the 13B shapes (K = 13 824, 320 row blocks): a 16-row workgroup requests as many activation lines as weight lines
-            // (LAB.md "what the activation operand costs"); the 8-phase form reads 1/8 of x per workgroup and is bitwise the same result
-            // With 10 row blocks per workgroup (13B) the short-K producer (o_proj, K = 5120) gains too: one workgroup per CU, 1/8 of x each.
-            c.k8 = w8 && k8_ok && K >= lab_switch("PGV_GEMV_K8_NARROW_MINK", c.nwb == 10 ? 4096 : 12288);
-            break;
-        default: break;
-    }
-    return c;
-}
+// a refusal of gemv_plan.h forwarded as this library reports errors (`call` formats it into err)
+#define GEMV_PLAN_TRY(call) do { char err[512]; if ((call) != GEMV_PLAN_OK) { pgv_set_error("%s", err); return PGV_EINVAL; } } while (0)
 
 int pgv_launch_gemv(pgv_ctx* ctx, int dtype, int mode, const void* W, const void* x, int ldx, void* out, int ldo, int N, int K, int B, hipStream_t s,
                     const float* wscale, const GemvNorm* norm, const W12Ref* w12, pgv_gemv_shape* ran) {
-    PGV_CHECK(B >= 1 && B <= 64, "gemv: batch %d outside [1,64]", B);
-    PGV_CHECK(K % 32 == 0, "gemv: K=%d must be a multiple of 32", K);
-    PGV_CHECK(mode == GV_STORE16 || mode == GV_RESID || mode == GV_SWIGLU || mode == GV_F32 || mode == GV_RESIDNORM, "gemv: bad mode %d", mode);
     const bool w8 = wscale != nullptr;                  // W is the fp8 blocked copy (fp8.hip) with per-row scales
+    GemvCall in;
+    in.mode = mode; in.N = N; in.K = K; in.B = B; in.num_cu = ctx->num_cu; in.w8 = w8; in.bf16 = dtype == PGV_BF16; in.W = W != nullptr;
+    in.w12 = w12 && w12->buf; in.rows12 = w12 ? w12->rows : 0;
     GemvArgs a;
     a.W = (const char*)W; a.x = (const char*)x; a.out = (char*)out; a.N = N; a.K = K; a.B = B; a.ldx = ldx; a.ldo = ldo; a.wscale = wscale;
-    a.ssq_in = nullptr; a.nparts_in = 0; a.inv_h = 0.f; a.eps = 0.f; a.gamma = nullptr; a.xg = nullptr; a.ssq_out = nullptr; a.amax_val = nullptr; a.amax_idx = nullptr;
-    a.ssq_ts = 0; a.amax_ts = 0; a.lds_bytes = 0; a.xblk = 0; a.xgblk = 0; a.w12exc = nullptr; a.w12base = nullptr;
-#ifdef PGV_LAB
-    a.abl = lab_switch("PGV_GEMV_ABLATE", 0);
-    if (B > 16 && lab_switch("PGV_GEMV_XBLK", 0) != 0) a.xblk = 1;      // lab: the caller hands over x in the blocked layout (scripts/microbench.py gemvwide)
-#endif
-    PGV_CHECK(B <= 16 || norm == nullptr || (norm->ssq_ts > 0 && (norm->amax_val == nullptr || norm->amax_ts > 0)), "gemv: batches beyond 16 need the tile strides of the side arrays");
     if (norm) {
+        in.norm = true; in.nparts_in = norm->nparts_in; in.ssq_ts = norm->ssq_ts; in.amax_ts = norm->amax_ts; in.amax_val = norm->amax_val != nullptr;
+        in.gamma = norm->gamma != nullptr; in.xg = norm->xg != nullptr; in.ssq_out = norm->ssq_out != nullptr; in.k8_part = norm->k8_part != nullptr; in.x_blocked = norm->x_blocked;
         a.ssq_ts = norm->ssq_ts; a.amax_ts = norm->amax_ts;
         a.ssq_in = norm->ssq_in; a.nparts_in = norm->nparts_in; a.inv_h = 1.0f / (float)norm->hidden; a.eps = norm->eps;
         a.gamma = norm->gamma; a.xg = (char*)norm->xg; a.ssq_out = norm->ssq_out; a.amax_val = norm->amax_val; a.amax_idx = norm->amax_idx;
-        if (norm->x_blocked && pgv_gemv_xblk_tiles(B) > 0) {          // consumers read x blocked, producers write xg blocked
-            if (mode == GV_RESIDNORM) { PGV_CHECK(N % 32 == 0, "gemv: a blocked xg needs N in multiples of 32"); a.xgblk = 1; }
-            else a.xblk = 1;                                       // (K % 32 == 0 is checked above)
-        }
-        PGV_CHECK(norm->nparts_in * 4 <= 3 * 8 * 64, "gemv: %d sum-of-squares partials exceed what a consumer workgroup loads (hidden <= 6144)", norm->nparts_in);
     }
-    PGV_CHECK(mode != GV_RESIDNORM || (a.gamma && a.xg && a.ssq_out), "gemv: the residual+norm producer needs gamma / xg / ssq_out");
-    if (w8) PGV_CHECK(K % 64 == 0, "gemv fp8: K=%d must be a multiple of 64", K);
-    int grid;
-    // W must be in the fragment-blocked layout with its row count padded to a multiple of 16 (zero rows)
-    if (mode == GV_SWIGLU) { PGV_CHECK(N % 64 == 0, "gemv swiglu: N=%d must be a multiple of 64", N); grid = N / 32; }
-    else { if (mode != GV_F32) PGV_CHECK(N % 16 == 0, "gemv: N=%d must be a multiple of 16", N); grid = (N + 15) / 16; }
-    const GemvChoice c = choose_gemv(mode, w8, B, grid, K, ctx->num_cu, norm && norm->k8_part);
-    // the 12-bit copy replaces W at one column tile (w12.h); beyond, the 16-bit matrix is streamed (the same products in the same order)
-    const bool use12 = w12 && w12->buf && !w8 && c.ct == 1 && !c.k8;
-    if (w12 && w12->buf) {
-        PGV_CHECK(!w8 && dtype == PGV_BF16 && K % 64 == 0 && w12->rows % 16 == 0 && w12->rows >= ((N + 15) & ~15), "gemv: bad 12-bit weight copy (%lld rows for N = %d, K = %d)",
-                  w12->rows, N, K);
-        PGV_CHECK(use12 || W != nullptr, "gemv: %d sequences need the 16-bit matrix (the 12-bit copy serves one column tile)", B);
-    }
-    if (use12) {
+    GemvPlan pl;
+    GEMV_PLAN_TRY(gemv_plan_build(in, pl, err, sizeof(err), gemv_lab()));
+    a.xblk = pl.xblk; a.xgblk = pl.xgblk;
+#ifdef PGV_LAB
+    // garbage results.  16-row kernel: GemvArgs::abl; 8-phase: 1 = no x staging, 2 = no MFMA / fragment reads, 4 = no weight loads, 8 = no partial-tile stores, 16 = no finish launch
+    a.abl = lab_switch(pl.k8 ? "PGV_K8_ABLATE" : "PGV_GEMV_ABLATE", 0);
+    if (B > 16 && lab_switch("PGV_GEMV_XBLK", 0) != 0) a.xblk = 1;          // lab: the caller hands over x in the blocked layout (scripts/microbench.py gemvwide)
+#endif
+    if (pl.wf == WF_12) {
         a.W = (const char*)w12->buf;
         a.w12exc = (const unsigned*)((const char*)w12->buf + pgv_w12_units_bytes(w12->rows, K));
         a.w12base = (const unsigned char*)w12->buf + pgv_w12_units_bytes(w12->rows, K) + pgv_w12_exc_bytes(w12->rows);
     }
-    const int wf = use12 ? WF_12 : (w8 ? WF_FP8 : WF_16);
-    if (ran) *ran = pgv_gemv_shape{c.tl, c.ct, !c.k8 && c.x2 && c.ct == 1, c.k8, c.k8 ? c.nwb : 0, wf};
+    if (ran) *ran = pgv_gemv_shape{pl.tl, pl.ct, pl.x2, pl.k8, pl.nwb, pl.wf};
     pgv_prof_begin(ctx, 3, s);
-    if (c.k8) {
-#ifdef PGV_LAB
-        a.abl = lab_switch("PGV_K8_ABLATE", 0);     // lab: 1 = no x staging, 2 = no MFMA / fragment reads, 4 = no weight loads, 8 = no partial-tile stores, 16 = no finish launch (garbage results)
-#endif
-        PGV_TRY(kK8[w8][c.ct == 1 ? 0 : (c.ct == 2 ? 1 : 2)][c.nwb == 10](dtype, a, grid, norm->k8_part, s));
+    if (pl.k8) {
+        PGV_TRY(launch_k8_shape(w8, pl, dtype, a, norm->k8_part, s));
     } else {
-        const GemvShape* shape = nullptr;
-        for (const GemvShape& g : kGemvShapes)
-            if (g.mode == mode && g.tl == c.tl && g.ct == c.ct) { shape = &g; break; }
-        PGV_CHECK(shape != nullptr, "gemv: no kernel for mode %d with %d row blocks x %d column tiles", mode, c.tl, c.ct);
-        const int tiles_per_wg = mode == GV_SWIGLU ? c.tl / 2 : c.tl;       // SwiGLU: the grid counts (gate, up) pairs
-        gemv_launch_fn fn = shape->fn[wf][c.x2 && c.ct == 1];
-        PGV_CHECK(fn != nullptr, "gemv: mode %d with %d row blocks x %d column tiles has no %s kernel", mode, c.tl, c.ct, wf == WF_12 ? "12-bit" : (w8 ? "fp8" : "16-bit"));
-        PGV_TRY(fn(dtype, (grid + tiles_per_wg - 1) / tiles_per_wg, a, s));     // (only the three-pair SwiGLU shape can leave a ragged last workgroup)
+        const gemv_launch_fn fn = find_row_kernel(mode, pl);    // never null: tests/test_host_cpu.py sweeps choose_gemv against the predicates of the list
+        PGV_CHECK(fn != nullptr, "gemv: no kernel for mode %d with %d row blocks x %d column tiles (weight format %d, merged x load %d)", mode, pl.tl, pl.ct, pl.wf, pl.x2);
+        PGV_TRY(fn(dtype, pl.grid, a, s));     // (a ragged last workgroup -- lm_head with 8 row blocks, SwiGLU with three or four pairs -- clamps and stores nothing past the matrix)
     }
-    pgv_prof_end(ctx, 3, s, 2.0 * B * (double)N * K, (w8 ? 1.0 : (use12 ? 1.5 : 2.0)) * (double)N * K);
+    pgv_prof_end(ctx, 3, s, 2.0 * B * (double)N * K, (w8 ? 1.0 : (pl.wf == WF_12 ? 1.5 : 2.0)) * (double)N * K);
     return PGV_OK;
 }
 
@@ -1081,30 +972,19 @@ extern "C" int pgv_gemv(pgv_ctx* ctx, int dtype, int mode, const void* d_W, cons
 // Test entries: the launcher with the arguments a decode step gives it (pgv.h).  They check what a wrong test argument could turn into a stray write.
 extern "C" int pgv_gemv_ex(pgv_ctx* ctx, int dtype, const pgv_gemv_desc* d, void* stream) {
     PGV_CHECK(ctx != nullptr && d != nullptr, "pgv_gemv_ex: null argument");
-    PGV_CHECK((d->d_W || d->d_W12) && d->d_x && d->d_out, "pgv_gemv_ex: null W / x / out");
-    const int mode = d->mode, N = d->N, K = d->K, B = d->B;
-    PGV_CHECK((mode >= GV_STORE16 && mode <= GV_F32) || mode == GV_RESIDNORM, "pgv_gemv_ex: mode %d is none of 0..3, 5", mode);
-    PGV_CHECK(B >= 1 && B <= kMaxBatch && N >= 1 && K >= 32, "pgv_gemv_ex: bad shape N = %d, K = %d, B = %d", N, K, B);
-    const int ct = B <= 16 ? 1 : (B <= 32 ? 2 : 4), nrb = (N + 15) / 16;
-    const bool producer = mode == GV_RESIDNORM, consumer = mode == GV_STORE16 || mode == GV_SWIGLU || mode == GV_F32;
-    const bool blocked = d->x_blocked && pgv_gemv_xblk_tiles(B) > 0;
-    PGV_CHECK((blocked && !producer) || (d->ldx >= K && d->ldx % 8 == 0), "pgv_gemv_ex: ldx = %d for K = %d (row-major x: 16-byte rows)", d->ldx, K);
-    PGV_CHECK(d->ldo >= (mode == GV_SWIGLU ? N / 2 : N) && (mode == GV_F32 || d->ldo % 4 == 0), "pgv_gemv_ex: ldo = %d for N = %d, mode %d", d->ldo, N, mode);
-    PGV_CHECK(d->ssq_ts >= 0 && d->amax_ts >= 0 && d->nparts_in >= 0, "pgv_gemv_ex: negative stride or count");
-    PGV_CHECK(d->d_ssq_in == nullptr || (consumer && d->nparts_in >= 1 && d->hidden >= 1 && d->ssq_ts >= 16 * d->nparts_in),
-              "pgv_gemv_ex: ssq_in needs a consumer mode, nparts_in >= 1, hidden >= 1 and ssq_ts >= 16 nparts_in (mode %d, %d parts, ssq_ts %d)", mode, d->nparts_in, d->ssq_ts);
-    PGV_CHECK(producer == (d->d_gamma || d->d_xg || d->d_ssq_out), "pgv_gemv_ex: gamma / xg / ssq_out belong to mode 5, and mode 5 needs all three");
-    if (producer) PGV_CHECK(d->d_gamma && d->d_xg && d->d_ssq_out && d->ssq_ts >= N, "pgv_gemv_ex: a producer needs gamma, xg, ssq_out and ssq_ts >= N (%d < %d)", d->ssq_ts, N);
-    PGV_CHECK((d->d_amax_val != nullptr) == (d->d_amax_idx != nullptr) && (d->d_amax_val == nullptr || (mode == GV_F32 && d->amax_ts >= 16 * nrb)),
-              "pgv_gemv_ex: the candidates need mode 3, both arrays and amax_ts >= 16 ceil(N / 16) (%d < %d)", d->amax_ts, 16 * nrb);
-    PGV_CHECK(d->d_k8_part == nullptr || (producer && d->k8_part_bytes >= (size_t)nrb * 8 * ct * 1024),
-              "pgv_gemv_ex: k8_part belongs to mode 5 and holds (N / 16) * 8 * ct * 1024 = %zu bytes (%zu given)", (size_t)nrb * 8 * ct * 1024, d->k8_part_bytes);
+    GemvDescShape ds;
+    ds.mode = d->mode; ds.N = d->N; ds.K = d->K; ds.B = d->B; ds.ldx = d->ldx; ds.ldo = d->ldo; ds.ssq_ts = d->ssq_ts; ds.amax_ts = d->amax_ts; ds.nparts_in = d->nparts_in;
+    ds.hidden = d->hidden; ds.k8_part_bytes = d->k8_part_bytes; ds.W = d->d_W != nullptr; ds.W12 = d->d_W12 != nullptr; ds.x = d->d_x != nullptr; ds.out = d->d_out != nullptr;
+    ds.ssq_in = d->d_ssq_in != nullptr; ds.gamma = d->d_gamma != nullptr; ds.xg = d->d_xg != nullptr; ds.ssq_out = d->d_ssq_out != nullptr; ds.amax_val = d->d_amax_val != nullptr;
+    ds.amax_idx = d->d_amax_idx != nullptr; ds.k8_part = d->d_k8_part != nullptr; ds.x_blocked = d->x_blocked != 0;
+    GEMV_PLAN_TRY(gemv_check_desc(ds, err, sizeof(err)));
+    const int nrb = (d->N + 15) / 16;
     GemvNorm nm;
     nm.ssq_in = d->d_ssq_in; nm.nparts_in = d->d_ssq_in ? d->nparts_in : 0; nm.hidden = d->hidden >= 1 ? d->hidden : 1; nm.eps = d->eps;
     nm.gamma = d->d_gamma; nm.xg = d->d_xg; nm.ssq_out = d->d_ssq_out; nm.amax_val = d->d_amax_val; nm.amax_idx = d->d_amax_idx;
     nm.k8_part = d->d_k8_part; nm.ssq_ts = d->ssq_ts > 0 ? d->ssq_ts : 16; nm.amax_ts = d->amax_ts > 0 ? d->amax_ts : 16 * nrb; nm.x_blocked = d->x_blocked != 0;
     W12Ref r12; r12.buf = d->d_W12; r12.rows = (long long)nrb * 16;
-    return pgv_launch_gemv(ctx, dtype, mode, d->d_W, d->d_x, d->ldx, d->d_out, d->ldo, N, K, B, (hipStream_t)stream, d->d_wscale, &nm, d->d_W12 ? &r12 : nullptr, d->shape);
+    return pgv_launch_gemv(ctx, dtype, d->mode, d->d_W, d->d_x, d->ldx, d->d_out, d->ldo, d->N, d->K, d->B, (hipStream_t)stream, d->d_wscale, &nm, d->d_W12 ? &r12 : nullptr, d->shape);
 }
 
 extern "C" int pgv_gemv_prep(pgv_ctx* ctx, int dtype, const int32_t* d_tok, const void* d_embed, float* d_resid, const float* d_gamma, void* d_xg, float* d_ssq, int B,

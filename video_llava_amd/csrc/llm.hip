@@ -186,10 +186,12 @@ extern "C" int pgv_llm_set_weight_stream(pgv_llm* m, int use12) {
 extern "C" int64_t pgv_llm_weight_stream_bytes(const pgv_llm* m, int batch) {
     if (!m || batch < 1) return -1;
     double b = 0;
+    GemvChoice c; c.ct = gemv_col_tiles(batch);       // (the 8-phase form at one column tile is fp8-only, choose_gemv: the format does not depend on it)
     for (const LlmMat& x : m->mats) {
         const long long N = (x.N + 15) / 16 * 16, K = x.K;        // the GEMVs stream whole 16-row blocks (only the lm_head's N is no multiple of 16)
-        if (m->fp8) b += (double)N * K + 4.0 * N;                                       // e4m3 + per-row fp32 scales
-        else if (batch <= 16 && z12(m, x.z)) b += (double)pgv_w12_total_bytes(N, K);
+        const int wf = gemv_weight_format(m->fp8, z12(m, x.z) != nullptr, c);
+        if (wf == WF_FP8) b += (double)N * K + 4.0 * N;                                 // e4m3 + per-row fp32 scales
+        else if (wf == WF_12) b += (double)pgv_w12_total_bytes(N, K);
         else b += 2.0 * N * K;
     }
     return (int64_t)b;
@@ -313,7 +315,7 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
     kv->llm = llm; kv->B = batch; kv->max_seq = max_seq;
     const size_t H = llm->cfg.hidden, I = llm->cfg.inter, V = llm->vocab_cap, L = llm->cfg.layers, B = batch;
     const size_t per = pgv_align(B * llm->cfg.heads * (size_t)max_seq * kHD * 2);
-    const size_t CTn = B <= 16 ? 1 : (B <= 32 ? 2 : 4);      // column tiles the decode GEMVs run with (1 / 2 / 4): every tile's slice of the side arrays is written, also the empty ones
+    const size_t CTn = gemv_col_tiles(batch);                // column tiles the decode GEMVs run with (1 / 2 / 4): every tile's slice of the side arrays is written, also the empty ones
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
     const size_t o_cache = take(per * 2 * L);
@@ -321,7 +323,7 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
                  o_qkv = take(B * 3 * H * 2), o_ao = take(B * H * 2), o_act = take(B * I * 2),
                  o_logits = take(B * V * 4), o_ssq = take(CTn * H * 4), o_av = take(CTn * V * 4), o_ai = take(CTn * V * 4), o_ints = take((4 * B + B * (size_t)max_seq) * 4),
                  o_u = take(B * (size_t)max_seq * 4), o_dpart = take(B * llm->cfg.heads * (size_t)kDattnSplitMax * kDattnPart * 4), o_dtick = take(B * llm->cfg.heads * 4),
-                 o_k8 = take((H / 16) * 8 * CTn * 64 * 16);
+                 o_k8 = take(gemv_k8_part_bytes((int)(H / 16), (int)CTn));
     kv->seen_words = (int)(V / 32);                          // vocab_cap is a multiple of 16: round up
     if ((size_t)kv->seen_words * 32 < V) kv->seen_words += 1;
     const size_t o_seen = take(B * (size_t)kv->seen_words * 4);

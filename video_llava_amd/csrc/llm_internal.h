@@ -2,11 +2,10 @@
 // kernels + launchers): launcher prototypes, mode enums and the few device helpers more than one of them uses.
 #pragma once
 #include "pgv_common.h"
+#include "gemv_plan.h"     // GV_* epilogues, kMaxBatch, the decode GEMVs' launch plan
 #include "pick_params.h"
 
 constexpr int kHD = 128;             // LLaMA head_dim
-constexpr int kMaxBatch = 64;        // decode GEMVs: up to 4 MFMA column tiles of 16 sequences per weight fragment
-enum { GV_STORE16 = 0, GV_RESID = 1, GV_SWIGLU = 2, GV_F32 = 3, GV_RESIDNORM = 5 };     // gemv.hip epilogues
 constexpr int kDattnSplitMax = 8, kDattnPart = kHD + 2;                                 // w12.hip
 int pgv_launch_encode_w12(const void* w16_blocked, void* w12, int* counts, long long N, long long K, hipStream_t s);
 // decode_attn.hip: context splits, floats per partial state
