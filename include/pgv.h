@@ -49,7 +49,8 @@ size_t pgv_ctx_workspace_bytes(const pgv_ctx *ctx);
 
 /* Per-kernel-family device timers (hipEvent pairs around every launch of the family on the
  * caller's stream).  family: 0 = MFMA GEMM, 1 = ViT attention, 2 = LLM prefill attention,
- * 3 = decode GEMV, 4 = decode attention, 5 = pooling, 6 = the short decode kernels (residual+RMSNorm, embedding, argmax) and logprob_rows.
+ * 3 = decode GEMV, 4 = decode attention, 5 = pooling and the cache gather of a beam step, 6 = the short decode kernels (residual+RMSNorm, embedding,
+ * argmax, the beam pick with its row statistics) and logprob_rows.
  * Off by default. */
 #define PGV_NFAMILY 7
 int pgv_prof_enable(pgv_ctx *ctx, int on);
@@ -268,8 +269,20 @@ int pgv_kv_truncate(pgv_kv *kv, int b, int len, void *stream);
  *  - Refused, cache and state unchanged: no live group (PGV_ESTATE); P != the group's width, a count < 1, W > the cache's batch (PGV_EINVAL);
  *    the message names the offending value.
  *  - The sampling state of pgv_kv_set_warpers / pgv_kv_set_logprobs belongs to the cache, not to a slot, and is untouched.
- * Not provided: a general (non-monotone) slot gather (pgv_llm_prefill_slots_n copies a fresh prompt to listed slots, not live state); sharing the prompt's K / V between the copies inside decode attention. */
+ * Not provided: sharing the prompt's K / V between the copies inside decode attention.  (The non-monotone slot gather a beam search needs on top of
+ * the fork is pgv_kv_gather, below; pgv_llm_prefill_slots_n copies a fresh prompt to listed slots, not live state.) */
 int pgv_kv_fork(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_counts, int P, void *stream);
+/* In-place slot gather inside groups of K consecutive slots of the live group (the cache reorder of a beam step): with W = the group's width (a
+ * multiple of K) and P = W / K groups, slot g * K + i receives the cache rows [h_row0[g], len) of slot g * K + h_src[g * K + i] in every layer, K and V,
+ * and its current token.  Rows [0, h_row0[g]) are NOT moved: the caller states that the K slots of group g agree on them -- they do, bit for bit,
+ * when h_row0[g] is the length the group had when pgv_kv_fork made it, which is why a beam step moves only the rows generated since the fork.
+ *  - Result: as if every read preceded every write (any map: broadcasts, swaps, cycles).  A destination whose source is itself is not written; a
+ *    group whose map is the identity costs the read of its map.  Rows [len, max_seq) are neither read nor written.  Lengths, done flags, seen-sets,
+ *    logits rows and log-probabilities stay with their slots (a beam run uses none of them); the lengths inside a group must be equal.
+ *  - One launch whose grid does not depend on the lengths; enqueued on the caller's stream after one synchronising upload of the two lists.
+ *  - Refused, cache unchanged: no live group (PGV_ESTATE); K outside [1, 8], W no multiple of K, an entry of h_src outside [0, K), unequal lengths
+ *    inside a group, h_row0[g] outside [1, len] (PGV_EINVAL). */
+int pgv_kv_gather(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, int K, const int32_t *h_src, const int32_t *h_row0, void *stream);
 /* Test / debug read-back: rows [row0, row0 + nrows) of every head of `slot` (< the cache's batch, live or not) of layer `layer`,
  * which = 0 K / 1 V  ->  d_out [heads][nrows][128] 16-bit.  row0 + nrows <= max_seq. */
 int pgv_kv_peek(pgv_kv *kv, int layer, int which, int slot, int row0, int nrows, void *d_out, void *stream);
@@ -366,6 +379,53 @@ int pgv_llm_pick_greedy(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, int32_t *d_next,
 int pgv_sample_logits_lp(pgv_ctx *ctx, const float *d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
                          const int32_t *d_seen_ids, int seen_stride, const int32_t *d_seen_lens, const float *d_u, int32_t *d_next, int32_t *d_kept,
                          int greedy, float *d_lp_model, float *d_lp_pick, void *stream);
+
+/* Beam search (HF: generate(num_beams = K); GenerationMixin._beam_search of transformers 5, steps b-g), K beams per prompt from ONE prefill, every
+ * step on the device.  Per prompt, with t = tokens generated so far, N = max_new_tokens, all arithmetic fp32, NEG = -1e9f:
+ *   start  running scores [0, NEG, ...]; finished scores all NEG, finished flags all 0; unsat = 1; open = 1.
+ *   b.     logp[k][v] = (x[k][v] - max_k) - ln sum_v exp(x[k][v] - max_k) (the row statistics of pgv_logprob_rows); acc[k * V + v] = logp[k][v] + run[k].
+ *   c.     the top 2K of acc.  TIE RULE (torch.topk leaves it open): higher score first, then the lower flat index; a NaN ranks as -inf.
+ *          parent = index / V, token = index % V.
+ *   d.     hit[j] = token[j] == eos_id || t + 1 >= N   (eos_id < 0: only the budget ends a beam).
+ *   e.     r[j] = top[j] + (hit[j] ? NEG : 0); the next running beams are the top K of r (ties: lower j) with those r as scores.
+ *   f.     s[j] = top[j] / (t + 1)^length_penalty, + NEG if all K finished flags are set and early_stopping is True, + NEG if !unsat, + NEG unless
+ *          (hit[j] && j < K); the K old finished entries followed by the 2K new ones, the top K by score kept (ties: earlier in that list).
+ *   g.     best = run'[0] / len^length_penalty with len = N if early_stopping is "never" and length_penalty > 0, else t + 1;
+ *          unsat &= any_i (best > (flag'[i] ? min(finished scores') : NEG));  open &= unsat && !(all flags' && early_stopping True) && !all_j hit[j].
+ *   A prompt that is no longer open keeps stepping with its group; its finished set, unsat and open stand.
+ * (t + 1)^length_penalty is (float)pow((double)(t + 1), (double)length_penalty), computed on the host.
+ * State words of one prompt (32-bit, PGV_BEAM_STATE_WORDS(K) of them): run [K] f32 | finished score [K] f32, best first | finished length [K] (tokens;
+ * 0: none) | finished parent [K] (the beam the last token continued) | finished last token [K] | finished flag [K] | unsat | open.
+ *
+ * pgv_beam_begin: on a live group of P prompts (right after pgv_llm_prefill / _append / pgv_llm_score), P * beams <= the batch the cache was created
+ *   with.  Forks every prompt to `beams` consecutive slots (pgv_kv_fork), allocates the run's device state on first use (a cache that never runs
+ *   beams allocates nothing), and runs the first pick on the prefill's logits.  Refused: no live group (PGV_ESTATE); beams outside [1, 8],
+ *   max_new_tokens < 1 or beyond what the cache holds, early_stopping outside 0 (False) / 1 (True) / 2 ("never"), eos_id >= the vocabulary (PGV_EINVAL).
+ * pgv_llm_decode_beam: n further steps, each the decode trunk + lm_head of pgv_llm_decode on the current tokens, the row statistics, the beam pick
+ *   (token -> current token, parent -> the gather map, both appended to a per-step history, position + 1) and pgv_kv_gather's kernel over the rows
+ *   generated since the fork, with map, lengths and every run parameter other than K read from device memory: steps replay from captured graphs
+ *   like those of pgv_llm_decode_greedy.  Host-checked before anything is enqueued: a beam run is live (PGV_ESTATE: any other call that moves the
+ *   slots -- prefill, fork, gather, truncate, the other decode / pick calls -- ends it), the cache has room, picks done + n <= max_new_tokens.
+ * pgv_beam_open: h_open [P] = the open flags (a caller stops stepping when none is set).  Synchronises the stream.
+ * pgv_beam_result: finished entry `rank` (0 = best) of prompt p: *n tokens (0: the entry is empty) written to h_tokens [cap >= *n], traced back
+ *   through the parent history; *score = HF's sequences_scores; *finished = its flag.  Each output may be NULL.  Synchronises the stream.
+ * pgv_beam_pick_logits (building block, same kernels): step t (0 <= t < max_new_tokens) of the rules on caller logits [P * beams, V] fp32 (row
+ *   stride V; rows p * beams + k) and caller state d_state [P][PGV_BEAM_STATE_WORDS(beams)], updated in place; d_tokens / d_parents [P * beams]
+ *   receive the new running beams.  Every reduction has a fixed order: same logits, same state -> same result on any launch and group width. */
+#define PGV_BEAM_STATE_WORDS(K) (6 * (K) + 2)
+typedef struct {
+    int beams;             /* K, 1..8 */
+    int max_new_tokens;    /* N */
+    int eos_id;            /* < 0: none */
+    float length_penalty;
+    int early_stopping;    /* 0 False, 1 True, 2 "never" */
+} pgv_beam_config;
+int pgv_beam_begin(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const pgv_beam_config *cfg, void *stream);
+int pgv_llm_decode_beam(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, int n, void *stream);
+int pgv_beam_open(pgv_kv *kv, int32_t *h_open, void *stream);
+int pgv_beam_result(pgv_kv *kv, int p, int rank, int32_t *h_tokens, int cap, int32_t *n, float *score, int32_t *finished, void *stream);
+int pgv_beam_pick_logits(pgv_ctx *ctx, const float *d_logits, int V, int P, const pgv_beam_config *cfg, int t, uint32_t *d_state, int32_t *d_tokens,
+                         int32_t *d_parents, void *stream);
 
 /* current length (tokens in cache) of sequence b, host-side bookkeeping */
 int pgv_kv_len(const pgv_kv *kv, int b);

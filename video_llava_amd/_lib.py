@@ -37,6 +37,16 @@ class LlmConfig(C.Structure):
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 
+class BeamConfig(C.Structure):
+    """pgv_beam_config of include/pgv.h.  early_stopping: 0 False, 1 True, 2 "never"."""
+    _fields_ = [("beams", _i), ("max_new_tokens", _i), ("eos_id", _i), ("length_penalty", _f), ("early_stopping", _i)]
+
+
+def beam_state_words(K: int) -> int:
+    """PGV_BEAM_STATE_WORDS(K): 32-bit words of one prompt's beam state."""
+    return 6 * int(K) + 2
+
+
 class GemmDesc(C.Structure):
     """pgv_gemm_desc of include/pgv.h (pgv_gemm_ex)."""
     _fields_ = [("d_A", _vp), ("lda", _i), ("d_W", _vp), ("ldw", _i), ("w_blocked", _i), ("d_bias", _vp), ("d_C", _vp), ("ldc", _i),
@@ -97,6 +107,12 @@ PROTOTYPES = {
     "pgv_kv_truncate": (_i, [_vp, _i, _i, _vp]),
     "pgv_kv_fork": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, _vp]),
     "pgv_kv_peek": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pgv_kv_gather": (_i, [_vp, _vp, _vp, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp]),
+    "pgv_beam_begin": (_i, [_vp, _vp, _vp, C.POINTER(BeamConfig), _vp]),
+    "pgv_llm_decode_beam": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "pgv_beam_open": (_i, [_vp, C.POINTER(C.c_int32), _vp]),
+    "pgv_beam_result": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(_f), C.POINTER(C.c_int32), _vp]),
+    "pgv_beam_pick_logits": (_i, [_vp, _vp, _i, _i, C.POINTER(BeamConfig), _i, _vp, _vp, _vp, _vp]),
     "pgv_llm_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pgv_llm_decode_greedy": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "pgv_llm_sample": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
@@ -362,6 +378,22 @@ class Context:
                                             out.data_ptr(), kept.data_ptr(), 1 if greedy else 0, lp[0].data_ptr(), lp[1].data_ptr(),
                                             stream_ptr(logits.device)), "pgv_sample_logits_lp")
         return out, kept, lp[0], lp[1]
+
+    def beam_pick_logits(self, logits: torch.Tensor, state: torch.Tensor, beams: int, t: int, max_new_tokens: int, eos_id: int = -1,
+                         length_penalty: float = 1.0, early_stopping: int = 0):
+        """pgv_beam_pick_logits: step t of the beam-search rules (include/pgv.h) on logits [P * beams, V] fp32 and the state words
+        int32 [P, beam_state_words(beams)], updated in place.  early_stopping: 0 False, 1 True, 2 "never".  Returns (tokens, parents), int32 [P * beams]."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+        K = int(beams)
+        assert state.is_cuda and state.dtype == torch.int32 and state.is_contiguous() and state.dim() == 2 and state.shape[1] == beam_state_words(K)
+        P = state.shape[0]
+        assert logits.shape[0] == P * K
+        cfg = BeamConfig(K, int(max_new_tokens), int(eos_id), float(length_penalty), int(early_stopping))
+        tok = torch.empty(P * K, dtype=torch.int32, device=logits.device)
+        par = torch.empty(P * K, dtype=torch.int32, device=logits.device)
+        check(self.lib.pgv_beam_pick_logits(self.handle, logits.data_ptr(), logits.shape[1], P, C.byref(cfg), int(t), state.data_ptr(), tok.data_ptr(),
+                                            par.data_ptr(), stream_ptr(logits.device)), "pgv_beam_pick_logits")
+        return tok, par
 
     def logprob_rows(self, logits: torch.Tensor, targets: torch.Tensor, V: "int | None" = None):
         """pgv_logprob_rows on fp32 logits [R, ld] (unit column stride, ld % 4 == 0) over columns [0, V) (default: all): -> (logprob [R] fp32,

@@ -1,4 +1,5 @@
-// pgv_kv_fork, device side: one cache slot becomes a run of slots (sample N answers from one prefill; the cache primitive of a beam search).
+// pgv_kv_fork, device side: one cache slot becomes a run of slots (sample N answers from one prefill; the first half of a beam search's cache
+// handling -- the per-step reorder inside a run of slots is kv_gather_kernel, beam.hip).
 //   kv_fork_kernel : slot `src` -> slots [d0, d0 + nd) except itself -- the cache rows [0, len) of every layer, K / V plane and head, and the
 //                    short per-slot state a decode step does not rebuild (position, current token, done flag, seen-set bitmap, logits row, the
 //                    two latest log-probabilities).  HBM-bound: every 16-byte piece of the source is read once and stored nd times.

@@ -78,7 +78,16 @@ struct pgv_kv {
     float *lp_stat = nullptr, *lp_last = nullptr, *lp_hist = nullptr;
     int lp_steps = -1;                  // steps of the last pgv_llm_decode_greedy / _sample call that ran with the switch on (-1: it was off)
     bool warmed = false;
+    // beam search (pgv_beam_begin): one allocation on first use, sized for the cache's batch -- state words [B][PGV_BEAM_STATE_WORDS(8)], gather map [B],
+    // prompt lengths row0 [B], step counters t [B], the run parameters, the length-penalty table denom [max_seq] and the per-step history of tokens
+    // and parents, hist [2][max_seq][B]
+    char* bm_blob = nullptr;
+    unsigned* bm_state = nullptr; int *bm_map = nullptr, *bm_row0 = nullptr, *bm_t = nullptr, *bm_hist = nullptr; BeamParams* bm_prm = nullptr; float* bm_denom = nullptr;
+    std::vector<unsigned> bm_stage;     // host staging of the initial state (kept alive across the async copy)
+    int bm_K = 0, bm_P = 0, bm_N = 0, bm_steps = 0;      // the run in flight (bm_K 0: none): width K, prompts, token budget, picks done
 };
+// every call that changes what the slots of the live group hold ends a beam run
+static void beam_drop(pgv_kv* kv) { kv->bm_K = 0; }
 
 extern "C" int pgv_llm_create(pgv_ctx* ctx, const pgv_llm_config* cfg, int dtype, pgv_llm** out) {
     PGV_CHECK(ctx && cfg && out, "pgv_llm_create: null argument");
@@ -358,6 +367,7 @@ extern "C" void pgv_kv_destroy(pgv_kv* kv) {
     if (!kv) return;
     for (auto g : kv->gexec) if (g) (void)hipGraphExecDestroy(g);
     if (kv->blob) (void)hipFree(kv->blob);
+    if (kv->bm_blob) (void)hipFree(kv->bm_blob);
     delete kv;
 }
 
@@ -446,7 +456,43 @@ static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u,
     return pgv_launch_sample(kv->logits, V, B, *sampled, u, B, u_by_step, st, s, &w, &lp);
 }
 
+// The pick of a beam step on the logits of rows [0, P * K): row statistics, the beam pick (token -> d_cur, parent -> the gather map, both into the
+// history; `advance`: d_pos += 1), then the in-group gather of the cache rows generated since the fork.  K == 1 has nothing to gather.
+static KvGatherArgs kv_gather_args(pgv_kv* kv, int K, int groups, const int* map, const int* row0, int* cur) {
+    const pgv_llm* m = kv->llm;
+    const int heads = m->cfg.heads, L = m->cfg.layers;
+    KvGatherArgs g{};
+    g.cache = L > 0 ? (char*)kv->Kc[0] : kv->blob;
+    g.head_stride = (size_t)kv->max_seq * kHD * 2; g.slot_stride = g.head_stride * heads; g.plane_stride = kv->plane_bytes;
+    g.heads = heads; g.nrun = 2 * L * heads; g.K = K; g.groups = groups; g.max_seq = kv->max_seq;
+    g.map = map; g.row0 = row0; g.len = kv->d_pos; g.cur = cur;
+    return g;
+}
+static int beam_pick_and_gather(pgv_ctx* ctx, pgv_kv* kv, bool advance, hipStream_t s) {
+    const int V = kv->llm->cfg.vocab, K = kv->bm_K, P = kv->bm_P;
+    pgv_prof_begin(ctx, 6, s);
+    PGV_TRY(pgv_launch_row_lse(kv->logits, V, V, P * K, kv->lp_stat, s));
+    BeamPickArgs a{};
+    a.logits = kv->logits; a.ld = V; a.V = V; a.K = K; a.stat = kv->lp_stat;
+    a.state = kv->bm_state; a.state_stride = PGV_BEAM_STATE_WORDS(K);
+    a.t_dev = kv->bm_t; a.prm_dev = kv->bm_prm; a.denom = kv->bm_denom;
+    a.cur = kv->d_cur; a.map = kv->bm_map; a.pos = kv->d_pos; a.advance = advance ? 1 : 0;
+    a.hist_tok = kv->bm_hist; a.hist_par = kv->bm_hist + (size_t)kv->max_seq * kv->B; a.hist_stride = kv->B; a.hist_steps = kv->max_seq;
+    PGV_TRY(pgv_launch_beam_pick(a, P, s));
+    pgv_prof_end(ctx, 6, s, 0.0, 0.0);
+    if (K > 1 && advance) {
+        pgv_prof_begin(ctx, 5, s);
+        PGV_TRY(pgv_launch_kv_gather(kv_gather_args(kv, K, P, kv->bm_map, kv->bm_row0, nullptr), s));
+        pgv_prof_end(ctx, 5, s, 0.0, 0.0);
+    }
+    return PGV_OK;
+}
+
 static int lm_head_and_pick(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, int eos, int flags, hipStream_t s, int nparts) {
+    if (flags & AM_BEAM) {
+        PGV_TRY(lm_head(ctx, m, kv, B, false, s, nparts));
+        return beam_pick_and_gather(ctx, kv, true, s);
+    }
     const bool sampled = flags & AM_SAMPLE;
     PGV_TRY(lm_head(ctx, m, kv, B, !sampled, s, nparts));
     pgv_prof_begin(ctx, 6, s);
@@ -682,6 +728,7 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& 
     hipStream_t s = (hipStream_t)stream;
     PrefillWork w;
     PGV_TRY(prefill_check(ctx, m, kv, q));
+    beam_drop(kv);
     PGV_TRY(prefill_plan_upload(ctx, m, kv, q, w, s));
     PGV_TRY(prefill_trunk(ctx, m, kv, q, w, s));
     if (q.h_counts) PGV_TRY(prefill_fork_runs(m, kv, q, w, s));
@@ -761,6 +808,7 @@ extern "C" int pgv_kv_truncate(pgv_kv* kv, int b, int len, void* stream) {
     PGV_CHECK(b >= 0 && b < kv->active, "pgv_kv_truncate: sequence %d outside the %d prefilled ones", b, kv->active);
     PGV_CHECK(len >= 1 && len <= kv->h_len[b], "pgv_kv_truncate: length %d outside [1,%d]", len, kv->h_len[b]);
     kv->h_len[b] = len;
+    beam_drop(kv);
     PGV_HIP(hipMemcpyAsync(kv->d_pos + b, &kv->h_len[b], 4, hipMemcpyHostToDevice, (hipStream_t)stream));
     PGV_HIP(hipStreamSynchronize((hipStream_t)stream));          // the source is host bookkeeping that the next call may change
     return PGV_OK;
@@ -789,6 +837,7 @@ extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* 
     }
     PGV_CHECK(W <= kv->B, "pgv_kv_fork: new width %lld exceeds the %d sequences the cache was created with", W, kv->B);
     if (W == P) return PGV_OK;            // every count is 1: the group is its own fork
+    beam_drop(kv);
     hipStream_t s = (hipStream_t)stream;
     const int heads = m->cfg.heads, L = m->cfg.layers;
     KvForkArgs a;
@@ -894,7 +943,7 @@ static bool graphs_enabled() {
 constexpr int kGraphSteps = 8;
 
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s) {
-    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run);
+    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K);
     if (!(kv->gkey == key)) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->gkey = key;
@@ -950,6 +999,7 @@ extern "C" int pgv_llm_decode(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_
     PGV_TRY(check_decode(m, kv, 1, "pgv_llm_decode"));
     hipStream_t s = (hipStream_t)stream;
     const int B = kv->active;
+    beam_drop(kv);
     if (d_last != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_last, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_TRY(decode_steps(ctx, m, kv, -1, AM_INC_POS, 1, s));
     if (d_logits) PGV_HIP(hipMemcpyAsync(d_logits, kv->logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
@@ -961,6 +1011,7 @@ extern "C" int pgv_llm_decode(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_
 // n recorded steps from d_first, picking with *run (null: the arg-max of the lm_head candidates); a run's uniforms are in kv->d_u already
 static int decode_run(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int n, int eos_id, const PickParams* run, int32_t* d_tokens, hipStream_t s) {
     const int B = kv->active;
+    beam_drop(kv);
     if (d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
     if (run) kv->run = *run;
@@ -983,6 +1034,7 @@ extern "C" int pgv_llm_decode_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
 
 // one pick on the logits the last prefill / decode call left: the cache's state takes the token, nothing advances
 static int pick_last(pgv_kv* kv, const PickParams& p, const float* d_u, int32_t* d_next, hipStream_t s) {
+    beam_drop(kv);
     PGV_TRY(kv_pick(kv, kv->active, &p, d_u, false, kv_state(kv, -1, 0), nullptr, s));
     if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
@@ -1011,6 +1063,192 @@ extern "C" int pgv_llm_decode_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)n * kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));     // n <= max_seq (check_decode)
     const PickParams p = kv_sampled(kv, temperature, top_k);
     return decode_run(ctx, m, kv, d_first, n, eos_id, &p, d_tokens, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// beam search (pgv.h; kernels: beam.hip)
+// ---------------------------------------------------------------------------------------------
+static int upload_ints(pgv_ctx* ctx, const std::vector<int>& h, int** d, hipStream_t s);      // below: host values through the workspace arena
+static int beam_check_config(const char* who, const pgv_beam_config* c, int V) {
+    PGV_CHECK(c != nullptr, "%s: null configuration", who);
+    PGV_CHECK(c->beams >= 1 && c->beams <= 8, "%s: beams %d outside [1,8]", who, c->beams);
+    PGV_CHECK(c->max_new_tokens >= 1, "%s: max_new_tokens %d is below 1", who, c->max_new_tokens);
+    PGV_CHECK(c->early_stopping >= 0 && c->early_stopping <= 2, "%s: early_stopping %d is not 0 (False), 1 (True) or 2 (\"never\")", who, c->early_stopping);
+    PGV_CHECK(isfinite(c->length_penalty), "%s: length_penalty is not finite", who);
+    PGV_CHECK(c->eos_id < V, "%s: eos_id %d outside the vocabulary (%d)", who, c->eos_id, V);
+    PGV_CHECK(V >= 2 * c->beams, "%s: a vocabulary of %d has no %d candidates", who, V, 2 * c->beams);
+    return PGV_OK;
+}
+// HF divides by (length ** length_penalty), a Python float, rounded to fp32 by the division
+static float beam_denom(int len, float length_penalty) { return (float)pow((double)len, (double)length_penalty); }
+
+extern "C" int pgv_kv_gather(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int K, const int32_t* h_src, const int32_t* h_row0, void* stream) {
+    PGV_CHECK(ctx && m && kv && h_src && h_row0, "pgv_kv_gather: null argument");
+    PGV_CHECK(kv->llm == m, "pgv_kv_gather: kv cache belongs to another model");
+    if (kv->active < 1) { pgv_set_error("pgv_kv_gather: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
+    const int W = kv->active;
+    PGV_CHECK(K >= 1 && K <= 8, "pgv_kv_gather: group width %d outside [1,8]", K);
+    PGV_CHECK(W % K == 0, "pgv_kv_gather: the live group of %d sequences is no multiple of the group width %d", W, K);
+    const int P = W / K;
+    std::vector<int> up((size_t)W + P);
+    for (int i = 0; i < W; ++i) {
+        PGV_CHECK(h_src[i] >= 0 && h_src[i] < K, "pgv_kv_gather: source %d of slot %d outside [0,%d)", h_src[i], i, K);
+        PGV_CHECK(kv->h_len[i] == kv->h_len[i / K * K], "pgv_kv_gather: slots %d and %d of one group hold %d and %d tokens", i / K * K, i, kv->h_len[i / K * K], kv->h_len[i]);
+        up[i] = h_src[i];
+    }
+    for (int p = 0; p < P; ++p) {
+        PGV_CHECK(h_row0[p] >= 1 && h_row0[p] <= kv->h_len[p * K], "pgv_kv_gather: row0 %d of group %d outside [1,%d]", h_row0[p], p, kv->h_len[p * K]);
+        up[(size_t)W + p] = h_row0[p];
+    }
+    beam_drop(kv);
+    hipStream_t s = (hipStream_t)stream;
+    int* d_up = nullptr;
+    PGV_TRY(upload_ints(ctx, up, &d_up, s));
+    PGV_TRY(pgv_launch_kv_gather(kv_gather_args(kv, K, P, d_up, d_up + W, kv->d_cur), s));
+    PGV_HIP(hipGetLastError());
+    PGV_TRY(pgv_ws_release(ctx, s));
+    return PGV_OK;
+}
+
+extern "C" int pgv_beam_begin(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const pgv_beam_config* cfg, void* stream) {
+    PGV_CHECK(ctx && m && kv, "pgv_beam_begin: null argument");
+    PGV_CHECK(kv->llm == m, "pgv_beam_begin: kv cache belongs to another model");
+    PGV_TRY(beam_check_config("pgv_beam_begin", cfg, m->cfg.vocab));
+    if (kv->active < 1) { pgv_set_error("pgv_beam_begin: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
+    const int P = kv->active, K = cfg->beams, N = cfg->max_new_tokens, B = kv->B;
+    PGV_CHECK((long long)P * K <= B, "pgv_beam_begin: %d prompts x %d beams exceed the %d sequences the cache was created with", P, K, B);
+    PGV_CHECK(N <= kv->max_seq, "pgv_beam_begin: max_new_tokens %d exceeds the cache's %d positions", N, kv->max_seq);
+    for (int p = 0; p < P; ++p)
+        PGV_CHECK(kv->h_len[p] + N - 1 <= kv->max_seq, "pgv_beam_begin: sequence %d would grow to %d tokens (cache holds %d)", p, kv->h_len[p] + N - 1, kv->max_seq);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t SW = PGV_BEAM_STATE_WORDS(8);
+    if (!kv->bm_blob) {
+        size_t off = 0;
+        auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
+        const size_t o_state = take((size_t)B * SW * 4), o_map = take((size_t)B * 4), o_row0 = take((size_t)B * 4), o_t = take((size_t)B * 4), o_prm = take(sizeof(BeamParams)),
+                     o_den = take((size_t)kv->max_seq * 4), o_hist = take((size_t)2 * kv->max_seq * B * 4);
+        hipError_t e = hipMalloc((void**)&kv->bm_blob, off);
+        if (e != hipSuccess) { kv->bm_blob = nullptr; pgv_set_error("pgv_beam_begin: hipMalloc(%zu KiB): %s", off >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
+        char* b = kv->bm_blob;
+        kv->bm_state = (unsigned*)(b + o_state); kv->bm_map = (int*)(b + o_map); kv->bm_row0 = (int*)(b + o_row0); kv->bm_t = (int*)(b + o_t);
+        kv->bm_prm = (BeamParams*)(b + o_prm); kv->bm_denom = (float*)(b + o_den); kv->bm_hist = (int*)(b + o_hist);
+    }
+    // host staging: state words of the P prompts | row0 [P] | parameters | denom [N]
+    const int S = PGV_BEAM_STATE_WORDS(K);
+    std::vector<unsigned>& st = kv->bm_stage;
+    st.assign((size_t)P * S + P + 4 + N, 0u);
+    auto fbits = [](float f) { unsigned u; memcpy(&u, &f, 4); return u; };
+    for (int p = 0; p < P; ++p) {
+        unsigned* w = st.data() + (size_t)p * S;
+        for (int i = 0; i < K; ++i) { w[i] = fbits(i == 0 ? 0.f : -1.0e9f); w[K + i] = fbits(-1.0e9f); }
+        w[6 * K] = 1u; w[6 * K + 1] = 1u;
+        st[(size_t)P * S + p] = (unsigned)kv->h_len[p];
+    }
+    unsigned* hp = st.data() + (size_t)P * S + P;
+    hp[0] = (unsigned)N; hp[1] = (unsigned)cfg->eos_id; hp[2] = (unsigned)cfg->early_stopping; hp[3] = fbits(cfg->length_penalty);
+    for (int i = 0; i < N; ++i) hp[4 + i] = fbits(beam_denom(i + 1, cfg->length_penalty));
+    if (K > 1) {
+        std::vector<int32_t> counts((size_t)P, K);
+        PGV_TRY(pgv_kv_fork(ctx, m, kv, counts.data(), P, stream));
+    }
+    PGV_HIP(hipMemcpyAsync(kv->bm_state, st.data(), (size_t)P * S * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->bm_row0, st.data() + (size_t)P * S, (size_t)P * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->bm_prm, hp, sizeof(BeamParams), hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->bm_denom, hp + 4, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemsetAsync(kv->bm_t, 0, (size_t)B * 4, s));
+    kv->bm_K = K; kv->bm_P = P; kv->bm_N = N; kv->bm_steps = 0;
+    // the first pick, on the logits of the prefill (pgv_kv_fork copied the row of every prompt to its K slots); nothing to gather yet
+    int rc = beam_pick_and_gather(ctx, kv, false, s);
+    if (rc == PGV_OK) { hipError_t e = hipGetLastError(); if (e != hipSuccess) { pgv_set_error("pgv_beam_begin: %s", hipGetErrorString(e)); rc = PGV_EHIP; } }
+    if (rc != PGV_OK) { beam_drop(kv); return rc; }
+    kv->bm_steps = 1;
+    return PGV_OK;
+}
+
+static int beam_live(const pgv_kv* kv, const char* who) {
+    PGV_CHECK(kv != nullptr, "%s: null cache", who);
+    if (kv->bm_K < 1 || kv->active != kv->bm_P * kv->bm_K) { pgv_set_error("%s: no beam run on this cache (pgv_beam_begin starts one; any other call that moves its slots ends it)", who); return PGV_ESTATE; }
+    return PGV_OK;
+}
+
+extern "C" int pgv_llm_decode_beam(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int n, void* stream) {
+    PGV_CHECK(ctx != nullptr, "pgv_llm_decode_beam: null argument");
+    PGV_CHECK(n >= 1, "pgv_llm_decode_beam: n must be positive");
+    PGV_TRY(check_decode(m, kv, n, "pgv_llm_decode_beam"));
+    PGV_TRY(beam_live(kv, "pgv_llm_decode_beam"));
+    PGV_CHECK(kv->bm_steps + n <= kv->bm_N, "pgv_llm_decode_beam: %d picks done + %d steps exceed max_new_tokens %d", kv->bm_steps, n, kv->bm_N);
+    PGV_TRY(decode_steps(ctx, m, kv, -1, AM_INC_POS | AM_BEAM, n, (hipStream_t)stream));
+    kv->bm_steps += n;
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+extern "C" int pgv_beam_open(pgv_kv* kv, int32_t* h_open, void* stream) {
+    PGV_TRY(beam_live(kv, "pgv_beam_open"));
+    PGV_CHECK(h_open != nullptr, "pgv_beam_open: null argument");
+    const int K = kv->bm_K, S = PGV_BEAM_STATE_WORDS(K);
+    PGV_HIP(hipMemcpy2DAsync(h_open, 4, kv->bm_state + 6 * K + 1, (size_t)S * 4, 4, kv->bm_P, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    PGV_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return PGV_OK;
+}
+
+extern "C" int pgv_beam_result(pgv_kv* kv, int p, int rank, int32_t* h_tokens, int cap, int32_t* n_out, float* score_out, int32_t* finished_out, void* stream) {
+    PGV_TRY(beam_live(kv, "pgv_beam_result"));
+    const int K = kv->bm_K, S = PGV_BEAM_STATE_WORDS(K);
+    PGV_CHECK(p >= 0 && p < kv->bm_P && rank >= 0 && rank < K, "pgv_beam_result: prompt %d / rank %d outside the run's %d prompts x %d beams", p, rank, kv->bm_P, K);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<unsigned> st((size_t)S);
+    PGV_HIP(hipMemcpyAsync(st.data(), kv->bm_state + (size_t)p * S, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+    PGV_HIP(hipStreamSynchronize(s));
+    float score; memcpy(&score, &st[K + rank], 4);
+    const int n = (int)st[2 * K + rank], flag = (int)st[5 * K + rank];
+    int par = (int)st[3 * K + rank];
+    PGV_CHECK(n >= 0 && n <= kv->bm_steps, "pgv_beam_result: the state holds a hypothesis of %d tokens after %d picks", n, kv->bm_steps);
+    if (n_out) *n_out = n;
+    if (score_out) *score_out = score;
+    if (finished_out) *finished_out = flag;
+    if (!h_tokens || n == 0) return PGV_OK;
+    PGV_CHECK(cap >= n, "pgv_beam_result: room for %d tokens, the hypothesis has %d", cap, n);
+    h_tokens[n - 1] = (int32_t)st[4 * K + rank];
+    if (n == 1) return PGV_OK;
+    // the tokens before the last: back through the parents of picks n - 2 .. 0 (the group's K columns of the history)
+    std::vector<int> hist((size_t)2 * (n - 1) * K);
+    const size_t pitch = (size_t)kv->B * 4;
+    PGV_HIP(hipMemcpy2DAsync(hist.data(), (size_t)K * 4, kv->bm_hist + p * K, pitch, (size_t)K * 4, n - 1, hipMemcpyDeviceToHost, s));
+    PGV_HIP(hipMemcpy2DAsync(hist.data() + (size_t)(n - 1) * K, (size_t)K * 4, kv->bm_hist + (size_t)kv->max_seq * kv->B + p * K, pitch, (size_t)K * 4, n - 1, hipMemcpyDeviceToHost, s));
+    PGV_HIP(hipStreamSynchronize(s));
+    for (int u = n - 2; u >= 0; --u) {
+        PGV_CHECK(par >= 0 && par < K, "pgv_beam_result: parent %d outside the group at pick %d", par, u + 1);
+        h_tokens[u] = hist[(size_t)u * K + par];
+        par = hist[(size_t)(n - 1 + u) * K + par];
+    }
+    return PGV_OK;
+}
+
+extern "C" int pgv_beam_pick_logits(pgv_ctx* ctx, const float* d_logits, int V, int P, const pgv_beam_config* cfg, int t, uint32_t* d_state, int32_t* d_tokens,
+                                    int32_t* d_parents, void* stream) {
+    PGV_CHECK(ctx && d_logits && d_state && d_tokens && d_parents, "pgv_beam_pick_logits: null argument");
+    PGV_CHECK(V >= 1, "pgv_beam_pick_logits: vocabulary %d is below 1", V);
+    PGV_TRY(beam_check_config("pgv_beam_pick_logits", cfg, V));
+    const int K = cfg->beams;
+    PGV_CHECK(P >= 1 && P * K <= kMaxBatch, "pgv_beam_pick_logits: %d prompts x %d beams outside [1,%d] rows", P, K, kMaxBatch);
+    PGV_CHECK(t >= 0 && t < cfg->max_new_tokens, "pgv_beam_pick_logits: step %d outside [0,%d)", t, cfg->max_new_tokens);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = pgv_align((size_t)P * K * 2 * 4);
+    PGV_TRY(pgv_ws_reserve(ctx, bytes, s));
+    float* stat = (float*)pgv_ws_alloc(ctx, bytes);
+    PGV_CHECK(stat != nullptr, "pgv_beam_pick_logits: workspace exhausted");
+    PGV_TRY(pgv_launch_row_lse(d_logits, V, V, P * K, stat, s));
+    BeamPickArgs a{};
+    a.logits = d_logits; a.ld = V; a.V = V; a.K = K; a.stat = stat;
+    a.state = d_state; a.state_stride = PGV_BEAM_STATE_WORDS(K);
+    a.t_val = t; a.prm_val = BeamParams{cfg->max_new_tokens, cfg->eos_id, cfg->early_stopping, cfg->length_penalty};
+    a.den_t = beam_denom(t + 1, cfg->length_penalty); a.den_n = beam_denom(cfg->max_new_tokens, cfg->length_penalty);
+    a.cur = d_tokens; a.map = d_parents;
+    PGV_TRY(pgv_launch_beam_pick(a, P, s));
+    PGV_HIP(hipGetLastError());
+    PGV_TRY(pgv_ws_release(ctx, s));
+    return PGV_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

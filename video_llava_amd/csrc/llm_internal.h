@@ -37,6 +37,35 @@ struct KvForkArgs {
 int pgv_launch_kv_fork(const KvForkArgs& a, hipStream_t s);
 // the cache rows only, slot `src` -> slots dst[0 .. nd): distinct, none of them src (pgv_llm_prefill_slots_n)
 int pgv_launch_kv_fork_list(const KvForkArgs& a, hipStream_t s);
+// beam.hip: the two kernels of a beam-search step (pgv.h: pgv_beam_begin).
+// kv_gather: inside every group of K consecutive slots, slot g0 + i receives rows [row0[g], len[g0]) of slot g0 + map[g0 + i], in every plane and
+// head (the layout of KvForkArgs).  map / row0 / len are DEVICE arrays, read by the kernel: a captured launch stays valid at any position.  cur
+// (optional): the slots' current tokens move with them.  The grid does not depend on len.
+struct KvGatherArgs {
+    char* cache; size_t plane_stride, slot_stride, head_stride;
+    int heads, nrun, K, groups, max_seq;
+    const int *map, *row0, *len;
+    int* cur;
+};
+int pgv_launch_kv_gather(const KvGatherArgs& a, hipStream_t s);
+// The run parameters of a beam search (HF's names); early: 0 False, 1 True, 2 "never"
+struct BeamParams { int max_new, eos, early; float length_penalty; };
+// beam_pick: one workgroup per prompt over the K logits rows of its group (rows p * K + k, stride ld, columns [0, V)), their statistics stat
+// [P * K][2] (pgv_launch_row_lse) and the prompt's state words (pgv.h: PGV_BEAM_STATE_WORDS).  Writes, per new slot p * K + i, the token to cur and
+// the parent to map, both also to hist_tok / hist_par [t][hist_stride] (null: no history; t < hist_steps), and with `advance` pos[slot] += 1.
+// t and the parameters come from device memory (t_dev [P], advanced by the kernel; prm_dev; denom [n] = (float)pow(n + 1, length_penalty)) or, where
+// those are null, by value (t_val, prm_val, den_t = the value for t, den_n = the value for max_new - 1).
+struct BeamPickArgs {
+    const float* logits; int ld, V, K;
+    const float* stat;
+    unsigned* state; int state_stride;
+    int* t_dev; int t_val;
+    const BeamParams* prm_dev; BeamParams prm_val;
+    const float* denom; float den_t, den_n;
+    int *cur, *map, *pos; int advance;
+    int *hist_tok, *hist_par; int hist_stride, hist_steps;
+};
+int pgv_launch_beam_pick(const BeamPickArgs& a, int P, hipStream_t s);
 // gemv.hip
 // w12: the 12-bit copy of W (w12.h), streamed instead of W at batches of one column tile (B <= 16) -- bitwise the same result; W may be null
 // only when B <= 16.  rows = the row count it was encoded with (>= N).

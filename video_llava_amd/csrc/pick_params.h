@@ -2,7 +2,8 @@
 // llm_internal.h includes it, and tests/test_host_cpu.py compiles it on its own.
 #pragma once
 
-enum { AM_INC_POS = 1, AM_RECORD = 2, AM_SAMPLE = 4 };      // bookkeeping flags of a pick (sampling.hip); AM_SAMPLE: a stepping run picks with PickParams
+enum { AM_INC_POS = 1, AM_RECORD = 2, AM_SAMPLE = 4, AM_BEAM = 8 };      // bookkeeping flags of a pick (sampling.hip); AM_SAMPLE: a stepping run picks with PickParams;
+                                                                         // AM_BEAM: the step ends in the beam pick and the in-group cache gather (beam.hip)
 
 // HF's processors in HF's order: repetition penalty, temperature, top-k, top-p (the defaults: none of them).  greedy: the pick is the arg-max of
 // the penalised logits and its log-probability their log-softmax over the WHOLE vocabulary, as HF's greedy loop has it.
@@ -18,8 +19,11 @@ inline PickParams pick_greedy(float penalty) { return {1.f, 1, 1.f, penalty, tru
 // without AM_SAMPLE picks from the lm_head candidates and reads no PickParams: its key holds the defaults, whatever an earlier run left in flight.
 struct DecodeGraphKey {
     int B = 0, eos = 0, flags = 0, generation = -1; bool logprobs = false; PickParams pick;
-    bool operator==(const DecodeGraphKey& o) const { return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick; }
+    int beams = 0;          // AM_BEAM: the group width K of the run (the grid of the gather and the slots a pick writes); every other beam parameter lives in device memory
+    bool operator==(const DecodeGraphKey& o) const {
+        return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick && beams == o.beams;
+    }
 };
-inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight) {
-    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}};
+inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight, int beams = 0) {
+    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0};
 }

@@ -50,6 +50,13 @@ def add_runtime_arguments(parser):
     parser.add_argument("--samples_out", default=None, metavar="FILE.jsonl",
                         help="--samples_per_prompt: append one JSON line per task with all its samples (text, ids, logprob) and the index picked "
                              "(rank-local file `FILE.jsonl.rank<r>` when world > 1)")
+    parser.add_argument("--beams", type=int, default=1, metavar="K",
+                        help=f"beam search with K <= {MAX_BEAMS} beams per clip as HF's generate(num_beams=K) computes it, on the device (generate(beams=K)); "
+                             "--schedule group only, not with --do_sample or --samples_per_prompt; a group holds --batch clips x K sequences "
+                             "(--batch auto counts K decode slots per clip)")
+    parser.add_argument("--length_penalty", type=float, default=None, help="--beams: HF's length_penalty; default: the checkpoint's generation_config.json, else 1.0")
+    parser.add_argument("--early_stopping", choices=("false", "true", "never"), default=None,
+                        help="--beams: HF's early_stopping; default: the checkpoint's generation_config.json, else false")
     parser.add_argument("--timings", default=None, metavar="OUT.jsonl",
                         help="append one JSON line per answered task (rank-local file `OUT.jsonl.rank<r>` when world > 1): frame load, upload + ingest, "
                              "tower + pool, prefill, decode seconds, generated tokens, group size, feature-cache hit (SURVEY 5: per-clip stage timings)")
@@ -67,10 +74,39 @@ def add_runtime_arguments(parser):
             parser.error(f"--samples_per_prompt {ns.samples_per_prompt} needs --schedule refill --do_sample")
         if ns.batch != "auto" and ns.samples_per_prompt > ns.batch:
             parser.error(f"--samples_per_prompt {ns.samples_per_prompt} exceeds the --batch {ns.batch} decode slots")
+        try:
+            check_beam_args(ns)
+        except ValueError as e:
+            parser.error(str(e))
         return ns, rest
 
     parser.parse_known_args = parse_known_args
     return parser
+
+
+MAX_BEAMS = 8       # generation.MAX_BEAMS
+
+
+def check_beam_args(ns):
+    """--beams / --length_penalty / --early_stopping of a parsed command line -> (K, length_penalty or None, early_stopping or None) as generate()
+    takes them (None: the generation config decides); ValueError names the flag a beam search cannot run with."""
+    K = int(getattr(ns, "beams", 1))
+    if not 1 <= K <= MAX_BEAMS:
+        raise ValueError(f"--beams {K} outside [1, {MAX_BEAMS}]")
+    early = {None: None, "false": False, "true": True, "never": "never"}[getattr(ns, "early_stopping", None)]
+    lp = getattr(ns, "length_penalty", None)
+    if K == 1:
+        return K, lp, early
+    if getattr(ns, "do_sample", False):
+        raise ValueError(f"--beams {K} cannot be combined with --do_sample (beam search picks by score)")
+    if getattr(ns, "schedule", "group") == "refill":
+        raise ValueError(f"--beams {K} cannot be combined with --schedule refill (the beams of a clip are a fixed group of decode slots)")
+    if int(getattr(ns, "samples_per_prompt", 1)) > 1:
+        raise ValueError(f"--beams {K} cannot be combined with --samples_per_prompt {ns.samples_per_prompt}")
+    batch = getattr(ns, "batch", "auto")
+    if batch != "auto" and batch * K > MAX_BATCH:
+        raise ValueError(f"--batch {batch} clips x --beams {K} exceed the {MAX_BATCH} decode slots of a group")
+    return K, lp, early
 
 
 def _batch_arg(text):
@@ -307,6 +343,12 @@ class _Runner:
         def generate(part, timings=None):
             # a stop string that IS the EOS piece (pg-video-llava: "</s>") is already handled on the device by the EOS flag; the host check
             # is for conv modes whose stop is ordinary text (default: "###") -- without it every group decodes max_new_tokens steps
+            K, lp, early = check_beam_args(self.args)
+            if K > 1:
+                # a beam search ends on EOS or the budget; answer_tasks cuts a stop string that is ordinary text afterwards, as for any generate()
+                return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
+                                           do_sample=False, max_new_tokens=self.args.max_new_tokens, timings=timings, beams=K, length_penalty=lp,
+                                           early_stopping=early, **self.warpers()).cpu()
             return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
                                        do_sample=False, max_new_tokens=self.args.max_new_tokens, stop_strings=[s for _, _, _, s in part],
                                        tokenizer=self.tokenizer, timings=timings, **self.warpers()).cpu()
@@ -464,6 +506,9 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
             t = torch.tensor([args.batch], dtype=torch.int32, device=device if torch.distributed.get_backend() == "nccl" else "cpu")
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MIN)
             args.batch = int(t[0])
+        beams = int(getattr(args, "beams", 1))
+        if beams > 1:
+            args.batch = max(1, args.batch // beams)                   # a clip holds K decode slots: the same number of sequences per group
         if rank == 0:
             print(f"[pgv] --batch auto: {args.batch} clips per group ({free_b / 2 ** 30:.0f} GiB free on {device}, shared by {sharers})", flush=True)
     spill = os.path.join(args.output_dir, args.output_name) if getattr(args, "output_dir", None) and getattr(args, "output_name", None) else None

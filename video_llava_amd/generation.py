@@ -87,7 +87,8 @@ def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: s
         else:
             v, where = _config_get(generation_config, name), "generation_config field"
         if asks(v):
-            hint = "; several sampled answers per prompt: this package's own keyword `samples_per_prompt`" if name == "num_return_sequences" else ""
+            hint = {"num_return_sequences": "; several sampled answers per prompt: this package's own keyword `samples_per_prompt`",
+                    "num_beams": "; beam search: this package's own keyword `beams`"}.get(name, "")
             raise ValueError(f"{who}: {where} `{name}`={v!r} is not implemented by this package (it would change the result of HF's generate()); "
                              f"implemented: temperature, top_k, top_p, repetition_penalty{hint}")
     for name in ("output_scores", "output_attentions", "output_hidden_states", "return_dict_in_generate"):
@@ -133,6 +134,53 @@ def check_samples_per_prompt(n, batch: int, do_sample: bool, has_criteria: bool,
     if has_reuse_key:
         raise ValueError(f"{who}: `samples_per_prompt`={n} cannot be combined with `kv_reuse_key` (the kept cache would hold {n} different answers)")
     return n
+
+
+MAX_BEAMS = 8           # beams per prompt (pgv_beam_config.beams)
+HF_BEAM_DEFAULTS = {"length_penalty": 1.0, "early_stopping": False}
+
+
+def check_beams(beams, batch: int, do_sample: bool = False, samples_per_prompt=1, repetition_penalty: float = 1.0, output_logprobs: bool = False,
+                has_criteria: bool = False, has_stop_strings: bool = False, has_reuse_key: bool = False, length_penalty=None, early_stopping=None,
+                generation_config=None, who: str = "generate()") -> Tuple[int, float, object]:
+    """Validate generate(beams=K, ...) on the host, before any device work.  Returns (K, length_penalty, early_stopping): the latter two from the
+    call if given, else from the generation config, else HF's defaults (1.0, False).  K == 1 is greedy decoding and combines with everything."""
+    if isinstance(beams, bool) or int(beams) != beams or beams < 1 or beams > MAX_BEAMS:
+        raise ValueError(f"{who}: `beams`={beams!r} has to be an integer in [1, {MAX_BEAMS}]")
+    K = int(beams)
+    if K == 1:              # greedy decoding: the two beam parameters stay inert, as in a call without `beams`
+        return K, 1.0, False
+    lp = length_penalty if length_penalty is not None else _config_get(generation_config, "length_penalty")
+    lp = float(HF_BEAM_DEFAULTS["length_penalty"] if lp is None else lp)
+    es = early_stopping if early_stopping is not None else _config_get(generation_config, "early_stopping")
+    es = HF_BEAM_DEFAULTS["early_stopping"] if es is None else es
+    if not (isinstance(es, bool) or es == "never"):
+        raise ValueError(f"{who}: `early_stopping`={es!r} has to be False, True or \"never\"")
+    if lp != lp or lp in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: `length_penalty`={lp!r} has to be a finite float")
+    refused = [("do_sample", bool(do_sample), "beam search picks by score; HF's beam sampling is not implemented"),
+               ("samples_per_prompt", samples_per_prompt is not None and samples_per_prompt != 1, "the K beams of a prompt are its group of slots"),
+               ("repetition_penalty", float(repetition_penalty) != 1.0, "the beam pick applies no logits processor"),
+               ("output_logprobs", bool(output_logprobs), "a hypothesis' score is returned with `output_beam_scores=True`"),
+               ("stopping_criteria", bool(has_criteria), "they are evaluated on one running sequence"),
+               ("stop_strings", bool(has_stop_strings), "they cut one running sequence, not a set of hypotheses"),
+               ("kv_reuse_key", bool(has_reuse_key), f"the kept cache would hold {K} different beams")]
+    for name, bad, why in refused:
+        if bad:
+            raise ValueError(f"{who}: `{name}` cannot be combined with `beams`={K} ({why})")
+    if batch * K > MAX_GROUP:
+        raise ValueError(f"{who}: {batch} prompts x `beams`={K} = {batch * K} sequences exceed the {MAX_GROUP} of one decode group")
+    return K, lp, es
+
+
+@dataclass
+class GenerateBeamsOutput:
+    """What `generate(..., beams=K, output_beam_scores=True)` returns.  sequences: exactly what generate(beams=K) returns without the keyword -- the
+    best hypothesis of every prompt, prompt echoed, shorter rows padded.  sequences_scores: fp32 [B] on the host, HF's `sequences_scores` (the sum of
+    the hypothesis' token log-probabilities over length ** length_penalty).  new_lengths: int64 [B], the new tokens of every row."""
+    sequences: Any
+    sequences_scores: Any
+    new_lengths: Any = None
 
 
 def resolve_sampling(temperature=None, top_k=None, top_p=None, repetition_penalty=None, generation_config=None) -> Tuple[float, int, float, float]:

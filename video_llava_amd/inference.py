@@ -224,6 +224,33 @@ def video_chatgpt_infer_samples(video_frames, question, conv_mode, model, vision
     return res
 
 
+def video_chatgpt_infer_beams(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len, beams,
+                              transcript=None, length_penalty=None, early_stopping=None, max_new_tokens=1024, features=None, **generate_kwargs):
+    """The beam-search answer to one question about one clip (model.generate(beams=K): HF's generate(num_beams=K) on the device, K beams from ONE
+    CLIP pass and ONE prefill).  A beam ends on EOS or the budget; a stop string that is ordinary text is cut afterwards, as the reference's own
+    post-processing does (inference.py:119-123).  Returns a dict: "text", "ids" (the generated token ids of the best hypothesis, up to the cut)
+    and "score" (HF's sequences_scores of the uncut hypothesis: its summed token log-probabilities over length ** length_penalty).
+    `length_penalty` / `early_stopping`: None = the model's generation config, else HF's defaults; `features`: pooled features computed
+    earlier (skips the tower); `generate_kwargs` go to model.generate as they are."""
+    from .model.utils import first_stop_length
+    prompt, stop_str = build_prompt(question, conv_mode, video_token_len, model.get_model().vision_config.use_vid_start_end, transcript)
+    input_ids = torch.as_tensor(tokenizer([prompt]).input_ids)
+    feats = features if features is not None else video_features(video_frames, vision_tower, image_processor)
+    with torch.inference_mode():
+        out = model.generate(input_ids, video_spatio_temporal_features=feats.unsqueeze(0), do_sample=False, max_new_tokens=max_new_tokens, beams=beams,
+                             length_penalty=length_penalty, early_stopping=early_stopping, **dict(generate_kwargs, output_beam_scores=int(beams) > 1))
+    n_in = input_ids.shape[1]
+    if torch.is_tensor(out):                        # beams == 1: greedy decoding has no beam score
+        new_ids, score = out[0, n_in:].tolist(), None
+    else:
+        new_ids, score = out.sequences[0, n_in:n_in + int(out.new_lengths[0])].tolist(), float(out.sequences_scores[0])
+    n = first_stop_length(new_ids, tokenizer, [stop_str]) if stop_str else None
+    if n is not None:
+        new_ids = new_ids[:n]
+    text = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0].strip()
+    return {"text": text.rstrip(stop_str).strip() if stop_str else text, "ids": new_ids, "score": score}
+
+
 def best_sample(samples) -> int:
     """Index of the sample with the largest "logprob" (video_chatgpt_infer_samples' dicts); ties go to the first."""
     if not samples:

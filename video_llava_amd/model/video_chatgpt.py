@@ -21,7 +21,9 @@ import torch.nn as nn
 
 from .. import _lib
 from ..constants import CLIP_WIDTH
-from ..generation import GenerateLogprobsOutput, check_generate_kwargs, check_samples_per_prompt, fork_sources, load_generation_config, resolve_sampling
+from ..beam_reference import early_code
+from ..generation import (GenerateBeamsOutput, GenerateLogprobsOutput, check_beams, check_generate_kwargs, check_samples_per_prompt, fork_sources,
+                          load_generation_config, resolve_sampling)
 from ..scoring import ScoreOutput, id_rows, shift_labels
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
 from .utils import AnswerState
@@ -527,6 +529,76 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         self._kv_epoch += 1                 # a PastKeyValues object handed out earlier describes another group width
         return len(src)
 
+    def kv_gather(self, kv, K: int, src: Sequence[int], row0: Sequence[int]):
+        """pgv_kv_gather: inside every group of K consecutive slots of the live group, slot g * K + i receives the cache rows [row0[g], len) and the
+        current token of slot g * K + src[g * K + i] (the cache reorder of a beam step; rows below row0[g] are shared by the group and stay)."""
+        W, P = len(src), len(row0)
+        _lib.check(self.ctx.lib.pgv_kv_gather(self.ctx.handle, self.handle, kv, int(K), (C.c_int32 * W)(*[int(v) for v in src]),
+                                              (C.c_int32 * P)(*[int(v) for v in row0]), _lib.stream_ptr(self.device_)), "pgv_kv_gather")
+
+    def beam_begin(self, kv, beams: int, max_new_tokens: int, eos_id: int = -1, length_penalty: float = 1.0, early_stopping=False):
+        """pgv_beam_begin: start a beam search on the live group of `kv` (a prefill with capacity >= prompts x beams): every prompt is forked to
+        `beams` consecutive slots and the first pick runs on the prefill's logits."""
+        cfg = _lib.BeamConfig(int(beams), int(max_new_tokens), int(eos_id), float(length_penalty), early_code(early_stopping))
+        _lib.check(self.ctx.lib.pgv_beam_begin(self.ctx.handle, self.handle, kv, C.byref(cfg), _lib.stream_ptr(self.device_)), "pgv_beam_begin")
+        self._kv_epoch += 1                 # a PastKeyValues object handed out earlier describes another group width
+
+    def decode_beam(self, kv, n: int):
+        """pgv_llm_decode_beam: n beam steps on the device (trunk, lm_head, beam pick, in-group cache gather), no host round trip."""
+        _lib.check(self.ctx.lib.pgv_llm_decode_beam(self.ctx.handle, self.handle, kv, int(n), _lib.stream_ptr(self.device_)), "pgv_llm_decode_beam")
+
+    def beam_open(self, kv, prompts: int) -> List[bool]:
+        """pgv_beam_open: which prompts of the beam run can still improve (synchronises)."""
+        h = (C.c_int32 * int(prompts))()
+        _lib.check(self.ctx.lib.pgv_beam_open(kv, h, _lib.stream_ptr(self.device_)), "pgv_beam_open")
+        return [bool(v) for v in h]
+
+    def beam_result(self, kv, p: int, rank: int = 0):
+        """pgv_beam_result: (tokens, score, finished) of finished entry `rank` (0 = best) of prompt p; score is HF's sequences_scores."""
+        n, score, fin = C.c_int32(), C.c_float(), C.c_int32()
+        s = _lib.stream_ptr(self.device_)
+        _lib.check(self.ctx.lib.pgv_beam_result(kv, int(p), int(rank), None, 0, C.byref(n), C.byref(score), C.byref(fin), s), "pgv_beam_result")
+        toks = (C.c_int32 * max(1, n.value))()
+        if n.value:
+            _lib.check(self.ctx.lib.pgv_beam_result(kv, int(p), int(rank), toks, n.value, C.byref(n), C.byref(score), C.byref(fin), s), "pgv_beam_result")
+        return [int(toks[i]) for i in range(n.value)], float(score.value), bool(fin.value)
+
+    def _generate_beams(self, seqs, feats, K: int, length_penalty: float, early_stopping, max_new_tokens: int, max_seq: int, eos_i: int, chunk: int,
+                        output_beam_scores: bool, timings: Optional[dict]):
+        """generate(beams=K > 1): one prefill of the B prompts in a cache of B * K slots, pgv_beam_begin, then chunks of beam steps until no prompt
+        is open or the budget is spent.  The host reads one flag per prompt between chunks and the best hypothesis at the end."""
+        import time as _time
+        _t0 = _time.perf_counter()
+        B = len(seqs)
+        if max_new_tokens < 1:
+            new = [([], 0.0)] * B
+            _t1 = _t0
+            n_gen = 0
+        else:
+            kv, _nxt, _ = self.prefill(seqs, feats, max_seq, capacity=B * K)
+            self.beam_begin(kv, K, max_new_tokens, eos_i, length_penalty, early_stopping)
+            n_gen = 1
+            still = self.beam_open(kv, B)       # synchronises: the prefill and the first pick are done
+            _t1 = _time.perf_counter()
+            while n_gen < max_new_tokens and any(still):
+                n = min(max(1, int(chunk)), max_new_tokens - n_gen)
+                self.decode_beam(kv, n)
+                n_gen += n
+                still = self.beam_open(kv, B)
+            new = [self.beam_result(kv, b, 0)[:2] for b in range(B)]
+        if timings is not None:
+            timings.update(prefill_s=_t1 - _t0, decode_s=_time.perf_counter() - _t1, steps=n_gen, batch=B * K, reused_tokens=0, samples_per_prompt=1, beams=K)
+        width = max(len(s_) + len(n_[0]) for s_, n_ in zip(seqs, new))
+        pad = eos_i if eos_i >= 0 else 0
+        out = torch.full((B, width), pad, dtype=torch.long)
+        for b in range(B):
+            row = list(seqs[b]) + list(new[b][0])
+            out[b, :len(row)] = torch.tensor(row, dtype=torch.long)
+        out = out.to(self.device_)
+        if output_beam_scores:
+            return GenerateBeamsOutput(out, torch.tensor([n_[1] for n_ in new], dtype=torch.float32), torch.tensor([len(n_[0]) for n_ in new], dtype=torch.long))
+        return out
+
     def kv_peek(self, kv, layer: int, which: int, slot: int, row0: int, nrows: int) -> torch.Tensor:
         """pgv_kv_peek (tests / debugging): cache rows [row0, row0 + nrows) of `slot` in `layer`, which = 0 keys / 1 values ->
         [heads, nrows, 128] in the model's dtype."""
@@ -640,7 +712,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  chunk: int = 32, generator: Optional[torch.Generator] = None, top_k: Optional[int] = None,
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
-                 samples_per_prompt: int = 1, **_unused):
+                 samples_per_prompt: int = 1, beams: int = 1, length_penalty: Optional[float] = None, early_stopping=None,
+                 output_beam_scores: bool = False, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -681,7 +754,14 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         consecutive slots, and the loop above runs at width B * n -- the result is what generate() returns for the prompts repeated n times each
         (repeat_interleave: row b * n + j is sample j of prompt b) with the same generator, minus n - 1 prefills per prompt.  Uniforms are
         torch.rand(max_new_tokens, B * n); `stop_strings` and `video_spatio_temporal_features` stay per PROMPT.  Needs do_sample=True and
-        B * n <= 64; not combinable with `stopping_criteria` or `kv_reuse_key`.  n = 1 is the path above, unchanged."""
+        B * n <= 64; not combinable with `stopping_criteria` or `kv_reuse_key`.  n = 1 is the path above, unchanged.
+        `beams=K` (a keyword of this package; HF's `num_beams` stays refused): beam search as HF's generate(num_beams=K) computes it, K <= 8 beams per
+        prompt from ONE prefill, every step on the device (pgv.h: pgv_beam_begin states the rules; equal scores, which torch.topk leaves open, go to
+        the lower index).  `length_penalty` / `early_stopping` (False, True, "never"): from the call, else the generation config, else HF's defaults
+        (1.0, False); without `beams` they stay inert.  Returns the best hypothesis of every prompt in the shape above; `output_beam_scores=True`
+        returns generation.GenerateBeamsOutput with HF's `sequences_scores`.  The result does not depend on `chunk` (the steps between two looks at the
+        prompts' open flags).  B * K <= 64; not combinable with do_sample, samples_per_prompt > 1, a repetition penalty, output_logprobs,
+        stopping_criteria, stop_strings or kv_reuse_key (generation.check_beams).  K = 1 is greedy decoding, the path above, unchanged."""
         check_generate_kwargs(_unused, self.generation_config)
         temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
         if torch.is_tensor(input_ids):
@@ -689,6 +769,11 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         else:
             seqs = [list(s) for s in input_ids]
         B = len(seqs)
+        n_beams, length_penalty, early_stopping = check_beams(beams, B, bool(do_sample), samples_per_prompt, rep_pen, bool(output_logprobs), bool(stopping_criteria),
+                                                              stop_strings is not None and any(stop_strings), kv_reuse_key is not None, length_penalty, early_stopping,
+                                                              self.generation_config)
+        if output_beam_scores and n_beams == 1:
+            raise ValueError("generate(): `output_beam_scores` needs `beams` > 1 (a greedy answer's log-probabilities: `output_logprobs=True`)")
         n_samples = check_samples_per_prompt(samples_per_prompt, B, bool(do_sample), bool(stopping_criteria), kv_reuse_key is not None)
         eos = self.config.eos_token_id if eos_token_id == "config" else eos_token_id
         eos_i = -1 if eos is None else int(eos)
@@ -696,6 +781,9 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         if max_seq > self.config.max_position_embeddings:
             raise ValueError(f"prompt + max_new_tokens = {max_seq} exceeds max_position_embeddings {self.config.max_position_embeddings}")
         max_seq = (max_seq + 63) // 64 * 64
+        if n_beams > 1:
+            return self._generate_beams(seqs, video_spatio_temporal_features, n_beams, length_penalty, early_stopping, int(max_new_tokens), max_seq, eos_i, chunk,
+                                        bool(output_beam_scores), timings)
         if kv_reuse_key is not None and B == 1:
             max_seq = min(int(self.config.max_position_embeddings), 4096)      # one cache for the whole conversation: later turns grow into it
         criteria = list(stopping_criteria) if stopping_criteria else []
