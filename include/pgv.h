@@ -427,6 +427,68 @@ int pgv_beam_result(pgv_kv *kv, int p, int rank, int32_t *h_tokens, int cap, int
 int pgv_beam_pick_logits(pgv_ctx *ctx, const float *d_logits, int V, int P, const pgv_beam_config *cfg, int t, uint32_t *d_state, int32_t *d_tokens,
                          int32_t *d_parents, void *stream);
 
+/* Logit bans: HF's processors that set scores to -inf (HF generation/logits_process.py; built by GenerationMixin._get_logits_processor between
+ * the repetition penalty and the warpers).  Each writes -inf or nothing, so their order among themselves and against the penalty (-inf * p and
+ * -inf / p are -inf for p > 0) does not change the result.  With ids [0, L) the sequence of a slot -- its prompt as handed to the prefill, placeholder
+ * ids included, plus every token a covered pick returned and a later step consumed -- and P its prompt length (the length after the last prefill of the
+ * slot; for pgv_llm_prefill_append the total after the append: HF sees the whole conversation as the prompt):
+ *  - no_repeat_ngram = n > 0 (NoRepeatNGramLogitsProcessor.__call__ / _get_generated_ngrams): nothing while L < n; else every window ids[j : j + n),
+ *    0 <= j <= L - n, whose first n - 1 ids equal the suffix ids[L - n + 1 : L) bans ids[j + n - 1].  n = 1 bans every id of the sequence.
+ *  - bad word w of m ids (NoBadWordsLogitsProcessor = SequenceBiasLogitsProcessor.__call__, bias -inf): m = 1 always banned; m > 1: skipped while
+ *    m > L, else w[m - 1] is banned iff ids[L - m + 1 : L) == w[0 : m - 1).  (HF's constructor drops a word equal to [eos]: that filter is the
+ *    caller's, video_llava_amd/logit_bans.py applies it.)
+ *  - suppress (SuppressTokensLogitsProcessor): always banned.  begin_suppress (SuppressTokensAtBeginLogitsProcessor): banned iff L == P.
+ *  - min_length (MinLengthLogitsProcessor): eos_id is banned while L < min_length.  min_new_tokens (MinNewTokensLengthLogitsProcessor): eos_id is
+ *    banned while L - P < min_new_tokens.  eos_id < 0 makes both rules empty.  The eos_id of the configuration is the one banned; the eos_id argument
+ *    of the stepping calls keeps its own meaning (the sticky end of a sequence).
+ * Limits (refused with PGV_EINVAL, the message names the value): at most PGV_BAN_MAX_WORDS bad words of at most PGV_BAN_MAX_WORD_LEN ids each, at
+ * most PGV_BAN_MAX_IDS listed ids in total (suppress + begin_suppress + all bad-word ids), every listed id in [0, vocab)
+ * (SequenceBiasLogitsProcessor._prepare_bias_variables), no negative count; a vocabulary beyond 65536 (the ban set is an LDS bitmap).
+ *
+ * pgv_kv_set_bans (modelled on pgv_kv_set_warpers): the configuration of every later COVERED pick on this cache; NULL or a configuration that asks
+ *   nothing turns the feature off.  Set it before the prefill of the sequences it is meant for: while it is on, the prefill calls (pgv_llm_prefill,
+ *   _append, _slots, _slots_n, pgv_llm_score) write each slot's ids and prompt length to a per-cache record int32 [batch][max_seq], indexed by cache
+ *   position (so pgv_kv_truncate needs no action), and the ban kernel of a decode step appends the token the step consumes at the slot's position.
+ *   The record, a second logits buffer and the device copy of the lists are allocated by the first configuration that asks something; a cache that
+ *   never asks allocates nothing and launches nothing.  Synchronises the device (the lists may be read by work in flight); the captured decode graphs
+ *   are rebuilt when the configuration changes.
+ *   Covered picks: pgv_llm_sample, pgv_llm_pick_greedy, every step of pgv_llm_decode_greedy / _sample, and the first token of
+ *   pgv_llm_prefill_slots / _slots_n.  Greedy picks then take the route of a greedy pick under a repetition penalty (the lm_head's arg-max candidates
+ *   know no ban).  NOT covered, exactly as for the penalty: the greedy d_next of pgv_llm_prefill / _append (re-pick with pgv_llm_pick_greedy) and plain
+ *   pgv_llm_decode steps, which neither ban nor record the token they consume.  Beam runs: pgv_beam_begin on a cache with bans set returns PGV_ESTATE.
+ *   pgv_kv_fork copies a source's record rows [0, len) and prompt length to its destinations; pgv_llm_prefill_slots_n writes the prompt's ids to every
+ *   sample's slot.
+ *   RE-PICKED ROWS: the bans are written to a COPY of the logits row, which the pick reads; the cache's own logits (what d_logits returns, what
+ *   pgv_kv_fork copies, what a second pgv_llm_sample reads) are never modified and the row statistics of pgv_kv_set_logprobs are always taken from
+ *   them.  Log-probabilities under bans: `model` stays the raw logits' log-softmax (HF's `logits`); `pick` is normalised over what survives the bans
+ *   and the warpers (HF's `scores`) -- for a greedy pick the whole-vocabulary log-softmax of the banned (and penalised) logits at temperature 1.
+ *   Measured on one MI355X at 7B shapes, 8 sequences, 461-token prompt, 256 steps, no_repeat_ngram 3 + min_new_tokens 8 (scripts/bench_bans.py; LAB.md):
+ *   sampled 2.504 -> 2.517 ms per token step (+0.013 ms: the ban kernel); greedy 2.427 -> 2.508 ms (+0.082 ms, of which 0.072 ms is the pick route
+ *   that greedy under a repetition penalty already pays).  Off: the steps of the commit before, within run-to-run spread.
+ * pgv_ban_logits: the same kernel on caller buffers, in place: d_logits [B, V] fp32 (row stride V), row b's sequence = the d_lens[b] ids at
+ *   d_ids + b * ids_stride, its prompt length d_prompt_lens[b]; eos_id as an argument (cfg->eos_id is not read).  Entries outside the ban set keep their
+ *   bits (NaN and -inf included); a configuration that asks nothing launches nothing.  Every entry is written by at most one thread: the result does not
+ *   depend on B or on the row's index.  Synchronises the stream.
+ * pgv_kv_ids_peek (test read-back): the first n <= max_seq entries of slot's record -> d_out [n] int32 (may be NULL), the slot's prompt length ->
+ *   d_prompt_len [1] (may be NULL).  PGV_ESTATE while the cache has no record. */
+#define PGV_BAN_MAX_IDS 1024
+#define PGV_BAN_MAX_WORDS 256
+#define PGV_BAN_MAX_WORD_LEN 16
+typedef struct {
+    int no_repeat_ngram;                 /* n; 0: off */
+    const int32_t *h_bad_words;          /* the ids of all bad words, concatenated */
+    const int32_t *h_bad_word_lens;      /* [n_bad_words] ids per word */
+    int n_bad_words;
+    const int32_t *h_suppress; int n_suppress;
+    const int32_t *h_begin_suppress; int n_begin_suppress;
+    int min_length, min_new_tokens;      /* 0: off */
+    int eos_id;                          /* the id the two length rules ban; < 0: none */
+} pgv_ban_config;
+int pgv_kv_set_bans(pgv_kv *kv, const pgv_ban_config *cfg);
+int pgv_ban_logits(pgv_ctx *ctx, float *d_logits, int V, int B, const int32_t *d_ids, int ids_stride, const int32_t *d_lens,
+                   const int32_t *d_prompt_lens, int eos_id, const pgv_ban_config *cfg, void *stream);
+int pgv_kv_ids_peek(pgv_kv *kv, int slot, int n, int32_t *d_out, int32_t *d_prompt_len, void *stream);
+
 /* current length (tokens in cache) of sequence b, host-side bookkeeping */
 int pgv_kv_len(const pgv_kv *kv, int b);
 

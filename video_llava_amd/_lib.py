@@ -42,6 +42,27 @@ class BeamConfig(C.Structure):
     _fields_ = [("beams", _i), ("max_new_tokens", _i), ("eos_id", _i), ("length_penalty", _f), ("early_stopping", _i)]
 
 
+BAN_MAX_IDS, BAN_MAX_WORDS, BAN_MAX_WORD_LEN = 1024, 256, 16      # PGV_BAN_MAX_* of include/pgv.h
+
+
+class BanConfig(C.Structure):
+    """pgv_ban_config of include/pgv.h (pgv_kv_set_bans, pgv_ban_logits).  `from_bans` keeps the host arrays alive as attributes."""
+    _fields_ = [("no_repeat_ngram", _i), ("h_bad_words", C.POINTER(C.c_int32)), ("h_bad_word_lens", C.POINTER(C.c_int32)), ("n_bad_words", _i),
+                ("h_suppress", C.POINTER(C.c_int32)), ("n_suppress", _i), ("h_begin_suppress", C.POINTER(C.c_int32)), ("n_begin_suppress", _i),
+                ("min_length", _i), ("min_new_tokens", _i), ("eos_id", _i)]
+
+    @classmethod
+    def from_bans(cls, bans, eos_id: int = -1) -> "BanConfig":
+        """`bans`: logit_bans.LogitBans (already checked: the EOS filter of its bad words is the caller's)."""
+        flat = [int(t) for w in bans.bad_words for t in w]
+        lens = [len(w) for w in bans.bad_words]
+        arrs = [(C.c_int32 * max(1, len(v)))(*v) for v in (flat, lens, [int(t) for t in bans.suppress], [int(t) for t in bans.begin_suppress])]
+        cfg = cls(int(bans.no_repeat_ngram), arrs[0], arrs[1], len(lens), arrs[2], len(bans.suppress), arrs[3], len(bans.begin_suppress),
+                  int(bans.min_length), int(bans.min_new_tokens), int(eos_id))
+        cfg._keep = arrs
+        return cfg
+
+
 def beam_state_words(K: int) -> int:
     """PGV_BEAM_STATE_WORDS(K): 32-bit words of one prompt's beam state."""
     return 6 * int(K) + 2
@@ -125,6 +146,9 @@ PROTOTYPES = {
     "pgv_kv_logprobs_steps": (_i, [_vp, _i, _vp, _vp, _vp]),
     "pgv_llm_pick_greedy": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "pgv_sample_logits_lp": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "pgv_kv_set_bans": (_i, [_vp, C.POINTER(BanConfig)]),
+    "pgv_ban_logits": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(BanConfig), _vp]),
+    "pgv_kv_ids_peek": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "pgv_ingest_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pgv_gemm": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "pgv_gemm_ex": (_i, [_vp, _i, C.POINTER(GemmDesc), _vp]),
@@ -352,6 +376,20 @@ class Context:
                                             seen_lens.data_ptr() if seen_ids is not None else None, u.data_ptr(), out.data_ptr(),
                                             kept.data_ptr() if kept is not None else None, stream_ptr(logits.device)), "pgv_sample_logits_ex")
         return (out, kept) if want_kept else out
+
+    def ban_logits(self, logits: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor, prompt_lens: torch.Tensor, bans, eos_id: int = -1) -> torch.Tensor:
+        """pgv_ban_logits: HF's -inf processors (`bans`: logit_bans.LogitBans; the [eos] filter of its bad words is the caller's) on `logits`
+        [B, V] fp32 IN PLACE.  Row b's sequence: the first lens[b] entries of ids[b] (int32 [B, stride]); prompt_lens [B].  Returns `logits`."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+        B = logits.shape[0]
+        assert ids.is_cuda and ids.dtype == torch.int32 and ids.is_contiguous() and ids.dim() == 2 and ids.shape[0] == B
+        for t in (lens, prompt_lens):
+            assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+        assert B == 0 or int(lens.max()) <= ids.shape[1]
+        cfg = BanConfig.from_bans(bans, int(eos_id))
+        check(self.lib.pgv_ban_logits(self.handle, logits.data_ptr(), logits.shape[1], B, ids.data_ptr(), ids.shape[1], lens.data_ptr(),
+                                      prompt_lens.data_ptr(), int(eos_id), C.byref(cfg), stream_ptr(logits.device)), "pgv_ban_logits")
+        return logits
 
     def sample_logits_lp(self, logits: torch.Tensor, u: "torch.Tensor | None", temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                          repetition_penalty: float = 1.0, seen_ids: "torch.Tensor | None" = None, seen_lens: "torch.Tensor | None" = None,

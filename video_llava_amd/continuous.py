@@ -88,7 +88,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                         prompt_slack: int = 128, eos_token_id="config", seed: int = 0,
                         on_error: Callable[[Any, Exception], None] = _default_on_error,
                         timings: Optional[dict] = None, top_p: float = 1.0, repetition_penalty: float = 1.0,
-                        logprobs: Optional[dict] = None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
+                        logprobs: Optional[dict] = None, bans=None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
     """Yield (task_id, new_ids) as each task finishes; new_ids is None for a task that failed (`on_error(task_id, exc)` is told why) -- a failed
     task costs only itself.
 
@@ -114,7 +114,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     started it and the decode chunks it was live in).
     logprobs (a dict): logprobs[task_id] = {"token_logprobs": [...], "transition_scores": [...]} of each finished task, one entry per new id --
     what `generate(output_logprobs=True)` returns for the task on its own, bit for bit, whatever its slot and the group width (the values are
-    recorded on the device at pick time: pgv_kv_set_logprobs)."""
+    recorded on the device at pick time: pgv_kv_set_logprobs).
+    bans (logit_bans.LogitBans, a dict of its fields, or None): HF's -inf processors, one configuration for every task of the call, as in
+    `generate`; a task's sequence is its own prompt and answer -- a refilled slot's id record starts from its prompt (pgv_kv_set_bans)."""
     if not 1 <= width <= 64:
         raise ValueError(f"width {width} outside [1, 64]")
     if do_sample and not float(temperature) > 0.0:
@@ -128,6 +130,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     k_min = max(1, int(refill_min) if refill_min is not None else width // 8)
     eos = model.config.eos_token_id if eos_token_id == "config" else eos_token_id
     eos_i = -1 if eos is None else int(eos)
+    from .logit_bans import LogitBans, check_bans
+    ban = LogitBans() if bans is None else check_bans(bans, model.vocab_size, eos_i, who="generate_continuous()")      # on the host, before any device work
+    ban_on = not ban.effective_neutral(eos_i)
     dev = model.device_
 
     source = iter(tasks)
@@ -232,7 +237,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     t0 = time.perf_counter()
     want_lp = logprobs is not None
     kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq, **({"logprobs": True} if want_lp else {}),
-                               **({"capacity": W} if forked else {}))
+                               **({"capacity": W} if forked else {}), **({"bans": ban, "eos_id": eos_i} if ban_on else {}))
     try:
         slots: List[Optional[_Slot]] = [None] * W
         # slot s holds sample j of first[i]; j beyond the task's samples: an idle padding slot
@@ -244,8 +249,8 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         if do_sample:
             idle = torch.full((), 0.5, dtype=torch.float32, device=dev)
             nxt = model.sample_last(kv, torch.stack([u[0] if u is not None else idle for u in us]), temperature, top_k, **warp)
-        elif rep_pen != 1.0:
-            nxt = model.greedy_last(kv, W, **pen)                  # greedy over the penalised logits (as generate does)
+        elif rep_pen != 1.0 or ban_on:
+            nxt = model.greedy_last(kv, W, **pen)                  # greedy over the penalised / banned logits (as generate does)
         cur = nxt.clone()
         first_lp = model.logprobs_last(kv, W).cpu().numpy() if want_lp else None
         first_tok = nxt.cpu().numpy()
@@ -406,3 +411,5 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     finally:
         if want_lp:
             model.set_logprobs(kv, False)                           # the switch was on for this call only: also when the generator is closed early
+        if ban_on:
+            model.set_bans(kv, None)

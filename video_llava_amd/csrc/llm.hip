@@ -85,6 +85,14 @@ struct pgv_kv {
     unsigned* bm_state = nullptr; int *bm_map = nullptr, *bm_row0 = nullptr, *bm_t = nullptr, *bm_hist = nullptr; BeamParams* bm_prm = nullptr; float* bm_denom = nullptr;
     std::vector<unsigned> bm_stage;     // host staging of the initial state (kept alive across the async copy)
     int bm_K = 0, bm_P = 0, bm_N = 0, bm_steps = 0;      // the run in flight (bm_K 0: none): width K, prompts, token budget, picks done
+    // logit bans (pgv_kv_set_bans): one allocation by the first configuration that asks something -- the id record [B][max_seq] (indexed by cache
+    // position), the prompt lengths [B], the logits copy the bans are written to [B][vocab_cap] and the lists of the configuration
+    char* ban_blob = nullptr;
+    int *ban_ids = nullptr, *ban_plen = nullptr, *ban_lists = nullptr; float* ban_logits = nullptr;
+    BanLists ban_cfg; int ban_eos = -1;
+    std::vector<int> ban_host;          // the list words the device copy holds
+    bool ban_on = false;
+    int ban_gen = 0;                    // bumped by every pgv_kv_set_bans that changes the device copy: part of the decode graphs' key
 };
 // every call that changes what the slots of the live group hold ends a beam run
 static void beam_drop(pgv_kv* kv) { kv->bm_K = 0; }
@@ -368,6 +376,7 @@ extern "C" void pgv_kv_destroy(pgv_kv* kv) {
     for (auto g : kv->gexec) if (g) (void)hipGraphExecDestroy(g);
     if (kv->blob) (void)hipFree(kv->blob);
     if (kv->bm_blob) (void)hipFree(kv->bm_blob);
+    if (kv->ban_blob) (void)hipFree(kv->ban_blob);
     delete kv;
 }
 
@@ -375,6 +384,54 @@ extern "C" int pgv_kv_set_warpers(pgv_kv* kv, float top_p, float repetition_pena
     PGV_CHECK(kv != nullptr, "pgv_kv_set_warpers: null cache");
     PGV_TRY(pgv_check_warpers("pgv_kv_set_warpers", top_p, repetition_penalty));
     kv->warpers.top_p = top_p; kv->warpers.penalty = repetition_penalty;
+    return PGV_OK;
+}
+
+// HF's -inf processors (pgv.h).  The lists go to device memory owned by the cache, outside any capture: a captured decode step bakes in their
+// addresses and lengths, and the graphs' key carries the generation counter.
+extern "C" int pgv_kv_set_bans(pgv_kv* kv, const pgv_ban_config* cfg) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_set_bans: null cache");
+    if (!cfg) { kv->ban_on = false; return PGV_OK; }
+    std::vector<int> blob;
+    BanPacked at;
+    PGV_TRY(pgv_ban_pack("pgv_kv_set_bans", cfg, kv->llm->cfg.vocab, blob, at));
+    PGV_CHECK(cfg->eos_id < kv->llm->cfg.vocab, "pgv_kv_set_bans: eos_id %d outside the vocabulary (%d)", cfg->eos_id, kv->llm->cfg.vocab);
+    if (pgv_ban_neutral(cfg, cfg->eos_id)) { kv->ban_on = false; return PGV_OK; }
+    const size_t B = kv->B, n_lists = PGV_BAN_MAX_IDS + PGV_BAN_MAX_WORDS + 1;
+    if (!kv->ban_blob) {
+        const size_t b_ids = pgv_align(B * kv->max_seq * 4), b_plen = pgv_align(B * 4), b_lists = pgv_align(n_lists * 4),
+                     b_logits = pgv_align(B * (size_t)kv->llm->vocab_cap * 4);
+        hipError_t e = hipMalloc((void**)&kv->ban_blob, b_ids + b_plen + b_lists + b_logits);
+        if (e != hipSuccess) { kv->ban_blob = nullptr; pgv_set_error("pgv_kv_set_bans: hipMalloc(%zu KiB): %s", (b_ids + b_plen + b_lists + b_logits) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
+        kv->ban_ids = (int*)kv->ban_blob; kv->ban_plen = (int*)(kv->ban_blob + b_ids); kv->ban_lists = (int*)(kv->ban_blob + b_ids + b_plen);
+        kv->ban_logits = (float*)(kv->ban_blob + b_ids + b_plen + b_lists);
+        PGV_HIP(hipMemset(kv->ban_blob, 0, b_ids + b_plen + b_lists));
+    }
+    PGV_CHECK(blob.size() <= n_lists, "pgv_kv_set_bans: %zu list words exceed the %zu reserved", blob.size(), n_lists);
+    // the configuration the device copy already holds (a caller that sets and clears it around every run): nothing to upload, the graphs stay valid
+    const BanLists& o = kv->ban_cfg;
+    const BanLists& n = at.cfg;
+    const bool same = kv->ban_gen > 0 && blob == kv->ban_host && cfg->eos_id == kv->ban_eos && n.ngram == o.ngram && n.n_sup == o.n_sup && n.n_beg == o.n_beg &&
+                      n.n_words == o.n_words && n.min_length == o.min_length && n.min_new == o.min_new;
+    if (!same) {
+        PGV_HIP(hipDeviceSynchronize());          // a pick in flight may still read the lists of the configuration before
+        PGV_HIP(hipMemcpy(kv->ban_lists, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+        kv->ban_cfg = ban_lists(at, kv->ban_lists);
+        kv->ban_host = blob;
+        kv->ban_eos = cfg->eos_id;
+        kv->ban_gen += 1;
+    }
+    kv->ban_on = true;
+    return PGV_OK;
+}
+
+extern "C" int pgv_kv_ids_peek(pgv_kv* kv, int slot, int n, int32_t* d_out, int32_t* d_prompt_len, void* stream) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_ids_peek: null cache");
+    if (!kv->ban_ids) { pgv_set_error("pgv_kv_ids_peek: this cache has no id record (pgv_kv_set_bans allocates it)"); return PGV_ESTATE; }
+    PGV_CHECK(slot >= 0 && slot < kv->B, "pgv_kv_ids_peek: slot %d outside the %d of the cache", slot, kv->B);
+    PGV_CHECK(n >= 0 && n <= kv->max_seq, "pgv_kv_ids_peek: %d entries outside the cache's %d", n, kv->max_seq);
+    if (d_out && n > 0) PGV_HIP(hipMemcpyAsync(d_out, kv->ban_ids + (size_t)slot * kv->max_seq, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_prompt_len) PGV_HIP(hipMemcpyAsync(d_prompt_len, kv->ban_plen + slot, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PGV_OK;
 }
 
@@ -442,7 +499,13 @@ static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hip
 // and the uniforms u [B], or u [steps][B] indexed by the device-side step counter (u_by_step).  `st`: the cache's own state (kv_state) or a refill's
 // scratch.  Row b reads the seen-set of slot slot_map[b] (null: b) and, with pgv_kv_set_logprobs on, records its log-probabilities there.
 static PickState kv_state(pgv_kv* kv, int eos, int advance) { return {kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, eos, advance}; }
-static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u, bool u_by_step, const PickState& st, const int* slot_map, hipStream_t s) {
+// With pgv_kv_set_bans on, a sampled pick (the greedy ones take that route then, kv_greedy_sampled) reads a copy of the logits with HF's -inf
+// processors applied, made by logit_ban_kernel behind the row statistics: kv->logits itself stays raw for the statistics, a re-pick, a fork and the
+// d_logits outputs.  Row b's sequence is the record of its slot at length ban_lens[b] (null: the cache's positions) -- plus, for the pick of a decode
+// step (AM_INC_POS), the token that step consumed, which the kernel appends to the record.
+static bool kv_greedy_sampled(const pgv_kv* kv) { return kv->warpers.penalty != 1.f || kv->ban_on; }
+static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u, bool u_by_step, const PickState& st, const int* slot_map, hipStream_t s,
+                   const int* ban_lens = nullptr) {
     const int V = kv->llm->cfg.vocab;
     PickLp lp;
     if (kv->lp_on) {
@@ -451,9 +514,20 @@ static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u,
         PGV_TRY(pgv_launch_row_lse(kv->logits, V, V, B, kv->lp_stat, s));
     }
     if (!sampled) return pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (V + 15) / 16, kv->amax_ts, V, B, st, s, kv->logits, &lp);
+    const float* logits = kv->logits;
+    if (kv->ban_on) {
+        BanArgs a;
+        a.src = kv->logits; a.dst = kv->ban_logits; a.V = V;
+        a.ids = kv->ban_ids; a.ids_stride = kv->max_seq; a.slot_map = slot_map; a.lens = ban_lens ? ban_lens : kv->d_pos; a.prompt_lens = kv->ban_plen;
+        a.rec = kv->ban_ids; a.cur = kv->d_cur; a.inc = (st.advance & AM_INC_POS) ? 1 : 0;
+        a.done = (st.advance & AM_RECORD) ? st.done : nullptr;       // a pick that does not record must not look at a flag an earlier run left set
+        a.eos = kv->ban_eos; a.cfg = kv->ban_cfg;
+        PGV_TRY(pgv_launch_logit_ban(a, B, s));
+        logits = kv->ban_logits; lp.banned = 1;
+    }
     SampleWarp w;
     w.seen_bits = kv->d_seen; w.seen_words = kv->seen_words; w.seen_slot = slot_map;
-    return pgv_launch_sample(kv->logits, V, B, *sampled, u, B, u_by_step, st, s, &w, &lp);
+    return pgv_launch_sample(logits, V, B, *sampled, u, B, u_by_step, st, s, &w, &lp);
 }
 
 // The pick of a beam step on the logits of rows [0, P * K): row statistics, the beam pick (token -> d_cur, parent -> the gather map, both into the
@@ -626,6 +700,8 @@ static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefi
     // HF's repetition penalty sees the prompt ids as given, placeholder ids included: a new prompt starts its slot's set, an appended turn adds to it
     // (and every sample of a prompt starts from the prompt's ids alone: the pick adds its own token to the set of its own slot)
     PGV_TRY(pgv_launch_seen_mark(w.d.raw_ids, w.d.cu, w.t_slots, T, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s, q.h_counts ? w.d.samp_seq : nullptr));
+    // the ordered twin of the seen-set (pgv_kv_set_bans): each slot's ids at their cache positions and its prompt length, same indirection
+    if (kv->ban_on) PGV_TRY(pgv_launch_ids_write(w.d.raw_ids, w.d.cu, w.d.offs, w.t_slots, q.h_counts ? w.d.samp_seq : nullptr, T, kv->ban_ids, kv->max_seq, kv->ban_plen, s));
     if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
         PGV_HIP(hipMemcpyAsync(kv->d_pos, w.d.lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
         PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
@@ -709,7 +785,7 @@ static int prefill_last_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefill
         pgv_prof_begin(ctx, 6, s);
         const float* d_u = q.d_u;
         if (q.pick && q.pick->greedy) { d_u = kv->d_u; PGV_TRY(pgv_zero_uniforms(kv->d_u, B, s)); }
-        PGV_TRY(kv_pick(kv, B, q.pick, d_u, false, PickState{w.d_pick}, w.t_slots, s));      // in scratch rows [0, B): what it records lands at the slots
+        PGV_TRY(kv_pick(kv, B, q.pick, d_u, false, PickState{w.d_pick}, w.t_slots, s, w.t_lens));      // in scratch rows [0, B): what it records lands at the slots
         PGV_TRY(pgv_launch_slot_scatter(w.t_slots, w.d_pick, w.t_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
         pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
@@ -764,14 +840,14 @@ extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
                                      const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k, const float* d_u, float* d_logits,
                                      int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots, "pgv_llm_prefill_slots: null slot list");
-    // uniforms: sampled; none: greedy, from the lm_head candidates unless a penalty applies (prefill_check refuses a null cache)
+    // uniforms: sampled; none: greedy, from the lm_head candidates unless a penalty or a ban applies (prefill_check refuses a null cache)
     const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);
     PrefillReq q;
     q.who = "pgv_llm_prefill_slots"; q.mode = PREFILL_SLOTS;
     q.h_ids = h_ids; q.h_seq_lens = h_seq_lens; q.B = n;
     q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
     q.d_logits = d_logits; q.d_next = d_next;
-    q.h_slots = h_slots; q.pick = !d_u && p.penalty == 1.f ? nullptr : &p; q.d_u = d_u;
+    q.h_slots = h_slots; q.pick = !d_u && !(kv && kv_greedy_sampled(kv)) ? nullptr : &p; q.d_u = d_u;
     return prefill_impl(ctx, m, kv, q, stream);
 }
 
@@ -785,7 +861,7 @@ extern "C" int pgv_llm_prefill_slots_n(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, con
     q.h_ids = h_ids; q.h_seq_lens = h_seq_lens; q.B = n;
     q.d_video = d_video; q.Vt = Vt; q.h_vid_pos = h_vid_pos;
     q.d_logits = d_logits; q.d_next = d_next;
-    q.h_slots = h_slots; q.h_counts = h_counts; q.pick = !d_u && p.penalty == 1.f ? nullptr : &p; q.d_u = d_u;
+    q.h_slots = h_slots; q.h_counts = h_counts; q.pick = !d_u && !(kv && kv_greedy_sampled(kv)) ? nullptr : &p; q.d_u = d_u;
     return prefill_impl(ctx, m, kv, q, stream);
 }
 
@@ -856,6 +932,12 @@ extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* 
         if (c == 1 && base == p) continue;                 // the slot stays where it is
         a.src = p; a.d0 = base; a.nd = c; a.run_pieces = (unsigned)kv->h_len[p] * (kHD * 2 / 16);
         PGV_TRY(pgv_launch_kv_fork(a, s));
+        // the id record of pgv_kv_set_bans moves with the slot: rows [0, len) and the prompt length, in the same order as the cache rows
+        for (int i = 0; kv->ban_on && i < c; ++i) {
+            if (base + i == p) continue;
+            PGV_HIP(hipMemcpyAsync(kv->ban_ids + (size_t)(base + i) * kv->max_seq, kv->ban_ids + (size_t)p * kv->max_seq, (size_t)kv->h_len[p] * 4, hipMemcpyDeviceToDevice, s));
+            PGV_HIP(hipMemcpyAsync(kv->ban_plen + base + i, kv->ban_plen + p, 4, hipMemcpyDeviceToDevice, s));
+        }
     }
     for (int i = 0; i < (int)W; ++i) kv->h_len[i] = len[i];
     kv->active = (int)W;
@@ -943,7 +1025,7 @@ static bool graphs_enabled() {
 constexpr int kGraphSteps = 8;
 
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s) {
-    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K);
+    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K, kv->ban_on ? kv->ban_gen : 0);
     if (!(kv->gkey == key)) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->gkey = key;
@@ -1026,7 +1108,7 @@ extern "C" int pgv_llm_decode_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_CHECK(ctx && d_first && d_tokens, "pgv_llm_decode_greedy: null argument");
     PGV_CHECK(n >= 1, "pgv_llm_decode_greedy: n must be positive");
     PGV_TRY(check_decode(m, kv, n, "pgv_llm_decode_greedy"));
-    if (kv->warpers.penalty == 1.f) return decode_run(ctx, m, kv, d_first, n, eos_id, nullptr, d_tokens, (hipStream_t)stream);
+    if (!kv_greedy_sampled(kv)) return decode_run(ctx, m, kv, d_first, n, eos_id, nullptr, d_tokens, (hipStream_t)stream);
     const PickParams p = pick_greedy(kv->warpers.penalty);
     PGV_TRY(pgv_zero_uniforms(kv->d_u, (size_t)n * kv->active, (hipStream_t)stream));
     return decode_run(ctx, m, kv, d_first, n, eos_id, &p, d_tokens, (hipStream_t)stream);
@@ -1115,6 +1197,7 @@ extern "C" int pgv_beam_begin(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const pgv_be
     PGV_CHECK(kv->llm == m, "pgv_beam_begin: kv cache belongs to another model");
     PGV_TRY(beam_check_config("pgv_beam_begin", cfg, m->cfg.vocab));
     if (kv->active < 1) { pgv_set_error("pgv_beam_begin: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
+    if (kv->ban_on) { pgv_set_error("pgv_beam_begin: logit bans are set on this cache (pgv_kv_set_bans); the beam pick applies no logits processor"); return PGV_ESTATE; }
     const int P = kv->active, K = cfg->beams, N = cfg->max_new_tokens, B = kv->B;
     PGV_CHECK((long long)P * K <= B, "pgv_beam_begin: %d prompts x %d beams exceed the %d sequences the cache was created with", P, K, B);
     PGV_CHECK(N <= kv->max_seq, "pgv_beam_begin: max_new_tokens %d exceeds the cache's %d positions", N, kv->max_seq);

@@ -111,6 +111,7 @@ struct PickLp {
     float *hist_model = nullptr, *hist_pick = nullptr; int hist_stride = 0;
     const int* slot = nullptr;
     int greedy = 0;
+    int banned = 0;      // the logits the pick reads went through logit_ban_kernel: a greedy `pick` value is then their whole-vocabulary log-softmax, penalty or not
 };
 int pgv_check_warpers(const char* who, float top_p, float penalty);
 // n zeros: the uniforms of a pick_greedy pick
@@ -126,6 +127,41 @@ int pgv_launch_argmax_parts(const float* val, const int* idx, int nblk, int amax
                             const PickLp* lp = nullptr);
 // pgv_llm_prefill_slots: sequence i of the call becomes slot slots[i] -- cur = pick[i], pos = lens[i], step = done = 0
 int pgv_launch_slot_scatter(const int* slots, const int* pick, const int* lens, int n, int* cur, int* pos, int* step, int* done, hipStream_t s);
+
+// logit_ban.hip: HF's processors that set scores to -inf (pgv.h: pgv_kv_set_bans).
+// The lists of a configuration in DEVICE memory: suppress [n_sup], begin-suppress [n_beg], bad word w = word_ids[word_off[w] .. word_off[w + 1]).
+struct BanLists {
+    int ngram = 0, n_sup = 0, n_beg = 0, n_words = 0, min_length = 0, min_new = 0;
+    const int *sup = nullptr, *beg = nullptr, *word_off = nullptr, *word_ids = nullptr;
+};
+// One workgroup per logits row b: dst[b] = src[b] with -inf at every id the rules ban (src == dst: only those entries are written).  The row's
+// sequence is ids[slot * ids_stride .. + L) with slot = slot_map[b] (null: b) and L = lens[b]; with `inc` (the pick of a decode step, AM_INC_POS) the
+// token the step consumed, cur[b], is first stored at rec[slot * ids_stride + lens[b]] and L = lens[b] + 1.  prompt_lens is indexed by slot.
+// done (may be null): rows whose flag is set are copied without a ban.  eos < 0: the two length rules are empty.
+struct BanArgs {
+    const float* src = nullptr; float* dst = nullptr; int V = 0;
+    const int* ids = nullptr; int ids_stride = 0;
+    const int *slot_map = nullptr, *lens = nullptr, *prompt_lens = nullptr;
+    int* rec = nullptr; const int* cur = nullptr; int inc = 0;
+    const int* done = nullptr;
+    int eos = -1;
+    BanLists cfg;
+};
+int pgv_launch_logit_ban(const BanArgs& a, int B, hipStream_t s);
+// prefill: workgroup t writes the ids of sequence seq[t] (null: t; rows cu[q] .. cu[q + 1] of `ids`) to rec[slot * stride + offs[q] ..) with slot =
+// slots[t] (null: t), and prompt_lens[slot] = offs[q] + the row count -- the indirection of pgv_launch_seen_mark
+int pgv_launch_ids_write(const int* ids, const int* cu, const int* offs, const int* slots, const int* seq, int T, int* rec, int stride, int* prompt_lens,
+                         hipStream_t s);
+// validate a pgv_ban_config against the limits of pgv.h and the vocabulary and pack its lists into `blob` (offsets into it: sup / beg / word_off /
+// word_ids of `at`); ban_lists turns them into pointers behind a device copy of the blob
+struct BanPacked { BanLists cfg; size_t sup = 0, beg = 0, word_off = 0, word_ids = 0; };
+int pgv_ban_pack(const char* who, const pgv_ban_config* c, int V, std::vector<int>& blob, BanPacked& at);
+bool pgv_ban_neutral(const pgv_ban_config* c, int eos);
+inline BanLists ban_lists(const BanPacked& at, const int* d_blob) {
+    BanLists l = at.cfg;
+    l.sup = d_blob + at.sup; l.beg = d_blob + at.beg; l.word_off = d_blob + at.word_off; l.word_ids = d_blob + at.word_ids;
+    return l;
+}
 
 // score.hip: per-row log-probability of targets[r] / logsumexp / argmax over columns [0, V) of fp32 logits [R, ld]; row r writes at index
 // out_rows[r] (null: r).  Timed under family 6.

@@ -20,10 +20,11 @@ inline PickParams pick_greedy(float penalty) { return {1.f, 1, 1.f, penalty, tru
 struct DecodeGraphKey {
     int B = 0, eos = 0, flags = 0, generation = -1; bool logprobs = false; PickParams pick;
     int beams = 0;          // AM_BEAM: the group width K of the run (the grid of the gather and the slots a pick writes); every other beam parameter lives in device memory
+    int bans = 0;           // pgv_kv_set_bans: the generation counter of the cache's ban configuration (0: none) -- the ban kernel's launch and its list lengths are baked in
     bool operator==(const DecodeGraphKey& o) const {
-        return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick && beams == o.beams;
+        return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick && beams == o.beams && bans == o.bans;
     }
 };
-inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight, int beams = 0) {
-    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0};
+inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight, int beams = 0, int bans = 0) {
+    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0, bans};
 }

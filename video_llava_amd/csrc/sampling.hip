@@ -116,7 +116,8 @@ __global__ __launch_bounds__(256) void argmax_parts_lp_kernel(const float* __res
 //  * pick = (x'[t] - M) / T - ln S: the lane that holds the chosen entry has its (penalised) logit x', thread 0 publishes the total S of the kept
 //    weights through LDS.  From the logit, not as the log of the rounded weight.
 //  * greedy under a penalty: S is the sum over the WHOLE vocabulary of the penalised weights instead (one more pass, fixed order), not the sum
-//    above the top-1 threshold -- HF's greedy loop normalises the processed scores over everything.  Without a penalty the value is `model`.
+//    above the top-1 threshold -- HF's greedy loop normalises the processed scores over everything.  Without a penalty the value is `model`,
+//    unless the row went through logit_ban_kernel (PickLp::banned): then it is the whole-vocabulary sum of the banned row, -inf entries weight 0.
 //  * model = (x[t] - max x) - ln sum exp(x - max x) on the raw logits, the two statistics taken from row_lse_kernel (score.hip).
 // The seen-set it reads is the LDS copy made before the pick; the bit of the returned token is set in global memory afterwards.
 // ---------------------------------------------------------------------------------------------
@@ -326,7 +327,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, Sam
     };
     [[maybe_unused]] bool lp_whole = false;
     if constexpr (LP) {
-        lp_whole = p.lp.greedy && pen_on;
+        lp_whole = p.lp.greedy && (pen_on || p.lp.banned);      // banned: the -inf entries of the row carry weight 0, like NaN
         if (lp_whole) {        // whole-vocabulary sum of the penalised weights (NaN: weight 0): lane, wave, then the 16 wave totals in order
             float a = 0.f;
             for (int r = 0; r < rounds; ++r) {
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, Sam
             if (!lp_sticky) {
                 model = (lg[tok] - p.lp.stat[2 * b]) - p.lp.stat[2 * b + 1];
                 pick = ((lp_x - M) * p.c - __builtin_amdgcn_logf(lp_red[16])) * 0.6931471805599453f;        // v_log_f32 is log2; c = log2(e) / T
-                if (p.lp.greedy && !pen_on) pick = model;
+                if (p.lp.greedy && !pen_on && !p.lp.banned) pick = model;
             }
             lp_store(p.lp, b, lp_step, p.advance, model, pick);
         }

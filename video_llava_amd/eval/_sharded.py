@@ -34,6 +34,13 @@ def add_runtime_arguments(parser):
     parser.add_argument("--repetition_penalty", type=float, default=None,
                         help="HF RepetitionPenaltyLogitsProcessor over prompt + answer, greedy and sampled; default: the checkpoint's "
                              "generation_config.json, else 1.0")
+    parser.add_argument("--no_repeat_ngram", type=int, default=0, metavar="N",
+                        help="HF NoRepeatNGramLogitsProcessor (no_repeat_ngram_size=N) over prompt + answer, on the device (generate(bans=)): no n-gram of "
+                             "N tokens occurs twice -- the remedy for greedy answers that loop; 0 (default): off")
+    parser.add_argument("--min_new_tokens", type=int, default=0, metavar="N",
+                        help="HF MinNewTokensLengthLogitsProcessor: the end-of-sequence token is banned until the answer has N tokens; 0 (default): off")
+    parser.add_argument("--suppress_tokens", type=_id_list_arg, default=(), metavar="ID[,ID...]",
+                        help="HF SuppressTokensLogitsProcessor: token ids that are never generated; default: none")
     parser.add_argument("--schedule", choices=("group", "refill"), default="group",
                         help="group (default): answer the shard in static groups of --batch clips, each decoding until its longest answer ends; refill: keep "
                              "--batch decode slots busy and refill a slot with the next task as soon as its answer ends (continuous batching, "
@@ -75,7 +82,10 @@ def add_runtime_arguments(parser):
         if ns.batch != "auto" and ns.samples_per_prompt > ns.batch:
             parser.error(f"--samples_per_prompt {ns.samples_per_prompt} exceeds the --batch {ns.batch} decode slots")
         try:
-            check_beam_args(ns)
+            K, _, _ = check_beam_args(ns)
+            if bans_from_args(ns) and K > 1:        # validates the three flags, HF's wording
+                raise ValueError(f"--beams {K} cannot be combined with --no_repeat_ngram / --min_new_tokens / --suppress_tokens (the beam pick applies "
+                                 f"no logits processor)")
         except ValueError as e:
             parser.error(str(e))
         return ns, rest
@@ -107,6 +117,27 @@ def check_beam_args(ns):
     if batch != "auto" and batch * K > MAX_BATCH:
         raise ValueError(f"--batch {batch} clips x --beams {K} exceed the {MAX_BATCH} decode slots of a group")
     return K, lp, early
+
+
+def _id_list_arg(text):
+    try:
+        ids = tuple(int(t) for t in text.split(",") if t.strip() != "")
+    except ValueError:
+        ids = None
+    if ids is None or any(t < 0 for t in ids):
+        import argparse
+        raise argparse.ArgumentTypeError(f"--suppress_tokens {text!r} is not a comma-separated list of non-negative token ids")
+    return ids
+
+
+def bans_from_args(ns) -> dict:
+    """--no_repeat_ngram / --min_new_tokens / --suppress_tokens of a parsed command line as generate() / generate_continuous() keywords: {} when all
+    are off, else {"bans": LogitBans}.  (Bad words are not a flag: tokenising them, with the prefix-space pitfalls, belongs to the caller.)"""
+    from ..logit_bans import LogitBans
+    b = LogitBans(no_repeat_ngram=getattr(ns, "no_repeat_ngram", 0), min_new_tokens=getattr(ns, "min_new_tokens", 0),
+                  suppress=tuple(getattr(ns, "suppress_tokens", ()) or ()))
+    b.check(1 << 31)            # HF's wording for a negative value; the vocabulary is checked by generate()
+    return {} if b.neutral else {"bans": b}
 
 
 def _batch_arg(text):
@@ -351,7 +382,7 @@ class _Runner:
                                            early_stopping=early, **self.warpers()).cpu()
             return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
                                        do_sample=False, max_new_tokens=self.args.max_new_tokens, stop_strings=[s for _, _, _, s in part],
-                                       tokenizer=self.tokenizer, timings=timings, **self.warpers()).cpu()
+                                       tokenizer=self.tokenizer, timings=timings, **self.warpers(), **bans_from_args(self.args)).cpu()
 
         def record(part, out):
             for row, (j, ids, _, _) in zip(out, part):
@@ -419,7 +450,8 @@ class _Runner:
         warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
         lps = {} if many else None                                    # the samples are ranked by their log-probabilities
         for idx, new in generate_continuous(self.model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
-                                            tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp, **({"logprobs": lps} if many else {})):
+                                            tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp, **({"logprobs": lps} if many else {}),
+                                            **bans_from_args(args)):
             if new is not None and many:
                 new = self.pick_sample(idx, new, lps.pop(idx))
             if new is not None:
@@ -469,7 +501,7 @@ class _Runner:
                     raise clips[t["path"]]
                 new, stop = video_chatgpt_infer_ids(None, t["question"], self.args.conv_mode, self.model, self.vision_tower, self.tokenizer,
                                                     self.image_processor, self.video_token_len, None, max_new_tokens=self.args.max_new_tokens,
-                                                    features=feat_of[t["path"]], **self.warpers())
+                                                    features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args))
                 self.stop_strs[idx] = stop
                 self.record(toks, lens, j, new, strip_eos=False)       # the ids end where the reference's criterion stopped them
             except Exception as e:                                     # noqa: BLE001

@@ -42,6 +42,10 @@ REFUSED = {
 }
 
 
+# the refused HF arguments that `generate(bans=...)` covers under this package's own names (logit_bans.LogitBans): named in the refusal
+BANS_HINT = {"no_repeat_ngram_size": "no_repeat_ngram", "bad_words_ids": "bad_words", "min_length": "min_length", "min_new_tokens": "min_new_tokens"}
+
+
 class GenerationDefaults:
     """The fields of a checkpoint's generation_config.json, as attributes (`model.generation_config`).  An absent field reads as None."""
 
@@ -88,7 +92,9 @@ def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: s
             v, where = _config_get(generation_config, name), "generation_config field"
         if asks(v):
             hint = {"num_return_sequences": "; several sampled answers per prompt: this package's own keyword `samples_per_prompt`",
-                    "num_beams": "; beam search: this package's own keyword `beams`"}.get(name, "")
+                    "num_beams": "; beam search: this package's own keyword `beams`",
+                    **{hf: f"; HF's -inf processors: this package's own keyword `bans` (logit_bans.LogitBans({field}=...))"
+                       for hf, field in BANS_HINT.items()}}.get(name, "")
             raise ValueError(f"{who}: {where} `{name}`={v!r} is not implemented by this package (it would change the result of HF's generate()); "
                              f"implemented: temperature, top_k, top_p, repetition_penalty{hint}")
     for name in ("output_scores", "output_attentions", "output_hidden_states", "return_dict_in_generate"):

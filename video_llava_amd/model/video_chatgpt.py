@@ -24,6 +24,7 @@ from ..constants import CLIP_WIDTH
 from ..beam_reference import early_code
 from ..generation import (GenerateBeamsOutput, GenerateLogprobsOutput, check_beams, check_generate_kwargs, check_samples_per_prompt, fork_sources,
                           load_generation_config, resolve_sampling)
+from ..logit_bans import LogitBans, check_bans
 from ..scoring import ScoreOutput, id_rows, shift_labels
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
 from .utils import AnswerState
@@ -367,13 +368,15 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
 
     def prefill(self, seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor], max_seq: int,
                 want_logits: bool = False, want_all_logits: bool = False, append_to=None, logprobs: Optional[bool] = None,
-                capacity: Optional[int] = None):
+                capacity: Optional[int] = None, bans=None, eos_id: int = -1):
         """Run the prompt(s); returns (kv handle, next-token ids [B] int32 on device, logits [B, vocab] or None) -- with want_all_logits a fourth
         entry: the logits of EVERY position, [sum of lengths, vocab] fp32 (what the reference's forward returns, model/video_chatgpt.py:225-226).
         `append_to` = a kv handle this model filled before: the rows continue its sequences (pgv_llm_prefill_append; `max_seq` is ignored).
         `logprobs` (True / False): set the cache's log-probability switch (set_logprobs) before the prompt runs, so that the greedy first token is
         recorded too; None leaves the switch as it is.
-        `capacity`: the cache is created for max(B, capacity) sequences, so that fork() has slots to grow into (ignored with `append_to`)."""
+        `capacity`: the cache is created for max(B, capacity) sequences, so that fork() has slots to grow into (ignored with `append_to`).
+        `bans` (logit_bans.LogitBans, checked) with `eos_id`: set the cache's logit bans (set_bans) before the prompt runs, so that the slots' id
+        record holds it -- on the `append_to` path too; None leaves the cache's configuration as it is."""
         B = len(seqs)
         lens = [len(s) for s in seqs]
         feats = video_spatio_temporal_features
@@ -390,6 +393,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             kv = append_to
         if logprobs is not None:
             self.set_logprobs(kv, logprobs)
+        if bans is not None:
+            self.set_bans(kv, bans, eos_id)
         flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
         h_lens = (C.c_int32 * B)(*lens)
         h_pos = (C.c_int32 * B)(*vid_pos)
@@ -407,6 +412,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         except Exception:
             if logprobs:
                 self.set_logprobs(kv, False)               # a refused prompt never reaches the caller who would turn the switch off again
+            if bans is not None:
+                self.set_bans(kv, None)
             raise
         if want_all_logits:
             return kv, nxt, logits, all_logits[:, :self.vocab_size]
@@ -492,6 +499,24 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
     def set_warpers(self, kv, top_p: float = 1.0, repetition_penalty: float = 1.0):
         """pgv_kv_set_warpers: HF's TopPLogitsWarper / RepetitionPenaltyLogitsProcessor values for every later pick on this cache."""
         _lib.check(self.ctx.lib.pgv_kv_set_warpers(kv, float(top_p), float(repetition_penalty)), "pgv_kv_set_warpers")
+
+    def set_bans(self, kv, bans=None, eos_id: int = -1):
+        """pgv_kv_set_bans: HF's -inf processors (logit_bans.LogitBans; None or a neutral record: off) for every later covered pick on this cache.
+        Set them before the prefill of the sequences they are meant for (prefill(..., bans=) does).  `eos_id`: the id the two length rules ban."""
+        bans = LogitBans.coerce(bans).check(self.vocab_size, eos_id)
+        if bans.effective_neutral(eos_id):
+            _lib.check(self.ctx.lib.pgv_kv_set_bans(kv, None), "pgv_kv_set_bans")
+            return
+        cfg = _lib.BanConfig.from_bans(bans, -1 if eos_id is None else int(eos_id))
+        _lib.check(self.ctx.lib.pgv_kv_set_bans(kv, C.byref(cfg)), "pgv_kv_set_bans")
+
+    def ids_peek(self, kv, slot: int, n: int):
+        """pgv_kv_ids_peek (test read-back): (the first n ids of the slot's record as a list, the slot's prompt length)."""
+        out = torch.empty(int(n) + 1, dtype=torch.int32, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_kv_ids_peek(kv, int(slot), int(n), out.data_ptr(), out[int(n):].data_ptr(), _lib.stream_ptr(self.device_)),
+                   "pgv_kv_ids_peek")
+        h = out.cpu().tolist()
+        return h[:int(n)], h[int(n)]
 
     def set_logprobs(self, kv, on: bool = True):
         """pgv_kv_set_logprobs: record the two log-probabilities (`model`, `pick`: include/pgv.h) of every later pick on this cache."""
@@ -713,7 +738,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  samples_per_prompt: int = 1, beams: int = 1, length_penalty: Optional[float] = None, early_stopping=None,
-                 output_beam_scores: bool = False, **_unused):
+                 output_beam_scores: bool = False, bans=None, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -761,7 +786,16 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         (1.0, False); without `beams` they stay inert.  Returns the best hypothesis of every prompt in the shape above; `output_beam_scores=True`
         returns generation.GenerateBeamsOutput with HF's `sequences_scores`.  The result does not depend on `chunk` (the steps between two looks at the
         prompts' open flags).  B * K <= 64; not combinable with do_sample, samples_per_prompt > 1, a repetition penalty, output_logprobs,
-        stopping_criteria, stop_strings or kv_reuse_key (generation.check_beams).  K = 1 is greedy decoding, the path above, unchanged."""
+        stopping_criteria, stop_strings or kv_reuse_key (generation.check_beams).  K = 1 is greedy decoding, the path above, unchanged.
+        `bans` (a keyword of this package: logit_bans.LogitBans, a dict of its fields, or None; HF's argument names stay refused): HF's processors
+        that set scores to -inf -- no_repeat_ngram (HF: no_repeat_ngram_size), bad_words (bad_words_ids), suppress (suppress_tokens), begin_suppress
+        (begin_suppress_tokens), min_length, min_new_tokens -- applied on the device between the lm_head and the pick (pgv.h: pgv_kv_set_bans), at
+        HF's place in the chain: after the repetition penalty, before temperature / top-k / top-p.  They see the prompt ids as given plus every
+        generated token; the prompt length of min_new_tokens / begin_suppress is the length of the prompt.  Validated on the host before any device
+        work, with HF's wording; a bad word equal to [eos] is dropped, as HF does.  Greedy decoding under bans takes the route of greedy under a
+        repetition penalty.  With `output_logprobs`, token_logprobs stay the raw model's and transition_scores are normalised over what survives
+        (HF's `scores`).  Works with samples_per_prompt; `kv_reuse_key` falls back to the full prefill; `beams` > 1 is refused.  None or a record
+        that asks nothing is the call without the keyword; the cache's configuration is cleared when the call ends."""
         check_generate_kwargs(_unused, self.generation_config)
         temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
         if torch.is_tensor(input_ids):
@@ -777,6 +811,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         n_samples = check_samples_per_prompt(samples_per_prompt, B, bool(do_sample), bool(stopping_criteria), kv_reuse_key is not None)
         eos = self.config.eos_token_id if eos_token_id == "config" else eos_token_id
         eos_i = -1 if eos is None else int(eos)
+        ban = LogitBans() if bans is None else check_bans(bans, self.vocab_size, eos_i, n_beams)       # None: the call as it has always been
+        ban_on = not ban.effective_neutral(eos_i)
         max_seq = max(len(s) for s in seqs) + max_new_tokens
         if max_seq > self.config.max_position_embeddings:
             raise ValueError(f"prompt + max_new_tokens = {max_seq} exceeds max_position_embeddings {self.config.max_position_embeddings}")
@@ -806,8 +842,11 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
         pen = {} if rep_pen == 1.0 else {"repetition_penalty": rep_pen}
         lpk = {"logprobs": True} if output_logprobs else {}    # the switch is on for this call only (turned off again in the finally below)
+        if ban_on:
+            lpk.update(bans=ban, eos_id=eos_i)                 # likewise: set before the prompt runs, cleared in the finally below
         reused = 0
-        if kv_reuse_key is not None and B == 1 and rep_pen == 1.0:
+        if kv_reuse_key is not None and B == 1 and rep_pen == 1.0 and not ban_on:
+            # (and under bans the slot's id record has to be exactly prompt + answer, for the same reason)
             # (under a repetition penalty the slot's seen-set has to be exactly prompt + answer: the surplus steps a kept cache carries past a
             # stop string would stay in it, so such a turn runs the full prefill)
             reused = self._reusable_prefix(kv_reuse_key, seqs[0], max_new_tokens)
@@ -825,6 +864,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             except Exception:
                 if output_logprobs:
                     self.set_logprobs(kv, False)
+                if ban_on:
+                    self.set_bans(kv, None)
                 raise
             seqs = [seqs[i] for i in fork_sources([n_samples] * len(seqs))]
             if stops is not None:
@@ -837,8 +878,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             if do_sample and max_new_tokens >= 1:
                 u = torch.rand(max_new_tokens, B, device=self.device_, dtype=torch.float32, generator=generator)
                 nxt = self.sample_last(kv, u[0], temperature, top_k, **warp)
-            elif rep_pen != 1.0 and max_new_tokens >= 1:
-                # greedy under a penalty: the prefill's argmax knows no penalty -- re-pick over the penalised logits (first index on ties)
+            elif (rep_pen != 1.0 or ban_on) and max_new_tokens >= 1:
+                # greedy under a penalty or bans: the prefill's argmax knows neither -- re-pick over the processed logits (first index on ties)
                 nxt = self.greedy_last(kv, B, **pen)
             lp_parts = []                                      # output_logprobs: [2, B, steps] blocks in generation order (first token, then every chunk)
             if output_logprobs and max_new_tokens >= 1:
@@ -910,6 +951,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         finally:
             if output_logprobs:
                 self.set_logprobs(kv, False)                   # also when a criterion, the tokenizer or an interrupt ends the call early
+            if ban_on:
+                self.set_bans(kv, None)
 
 
 def _vision_config_from(mm_vision_tower) -> VisionConfig:
