@@ -380,6 +380,40 @@ int pgv_sample_logits_lp(pgv_ctx *ctx, const float *d_logits, int V, int B, floa
                          const int32_t *d_seen_ids, int seen_stride, const int32_t *d_seen_lens, const float *d_u, int32_t *d_next, int32_t *d_kept,
                          int greedy, float *d_lp_model, float *d_lp_pick, void *stream);
 
+/* The filter tail of a sampled pick: HF's four remaining sampling warpers (generation/logits_process.py: MinPLogitsWarper, TypicalLogitsWarper,
+ * EpsilonLogitsWarper, EtaLogitsWarper), in HF's order behind top-p:
+ *   repetition penalty -> temperature -> top-k -> top-p -> min_p -> typical_p -> epsilon_cutoff -> eta_cutoff -> softmax -> multinomial.
+ * y = the scores after penalty / temperature / top-k / top-p, -inf where removed.  Each stage works on the CURRENT survivors: p = their softmax,
+ * H = -sum p ln p their entropy, "top" = the largest current survivor.  Every stage keeps the top (HF's min_tokens_to_keep = 1).
+ *   min_p           on when > 0       keeps i iff p_i >= min_p * p_max
+ *   typical_p       on when < 1       d_i = |(-ln p_i) - H|; sorted ascending by d, last = min(#(cumulative p < typical_p), n - 1),
+ *                                     d* = d_sorted[last]; keeps i iff d_i <= d*.  TIE RULE: entries of equal d are kept or removed together (HF
+ *                                     removes `sorted_scores > threshold`), the entry that crosses the mass is kept, the smallest d always stays.
+ *                                     The survivors are a BAND in the logit, not a threshold: the row's largest logit is routinely removed, and
+ *                                     "the top" of the two stages behind it is the largest logit that is still there.
+ *   epsilon_cutoff  on when > 0       keeps i iff p_i >= epsilon, or i is the top
+ *   eta_cutoff      on when > 0       keeps i iff p_i >= min(eta, sqrt(eta) * exp(-H)), or i is the top
+ * On the device the mass of the typical stage is summed in 2^40 fixed point (order-free), every other sum in a fixed order: same logits, same
+ * seen-set, same u -> same token.  Entries whose weights are the same float are kept or removed together in every stage.
+ * Refused with PGV_EINVAL, in HF's words and with the value: min_p outside [0, 1] ("`min_p` has to be a float in the [0, 1] interval"), typical_p
+ * outside (0, 1] ("`typical_p` has to be a float > 0 and < 1"; 1 is this library's neutral value), epsilon_cutoff / eta_cutoff outside [0, 1)
+ * ("`epsilon_cutoff` / `eta_cutoff` has to be a float > 0 and < 1"; 0 is off).
+ *
+ * pgv_kv_set_filters: the values of every later SAMPLED pick on this cache -- pgv_llm_sample, pgv_llm_decode_sample, the first-token draw of
+ * pgv_llm_prefill_slots / _slots_n; NULL or the neutral record (0, 1, 0, 0) turns them off, and every launch is then what it is without this call.
+ * Greedy picks ignore them, as they ignore top_p.  pgv_kv_set_warpers leaves them alone.  With pgv_kv_set_logprobs the `pick` value is normalised
+ * over the FINAL survivors (HF: compute_transition_scores on `scores`).  The captured decode graphs are rebuilt when a value changes.
+ * pgv_sample_logits_filtered (building block, same kernels): pgv_sample_logits_lp plus the record (NULL: neutral) and d_kept_range [B, 2] (may be
+ * NULL): the smallest and the largest kept (penalised) logit of each row, (+inf, -inf) for a row that keeps nothing.  With d_kept it pins the kept
+ * SET: the survivors are the entries in that logit interval that passed top-k / top-p.  A neutral record gives the tokens, d_kept and both
+ * log-probabilities of pgv_sample_logits_lp bit for bit. */
+typedef struct pgv_filter_config { float min_p, typical_p, epsilon_cutoff, eta_cutoff; } pgv_filter_config;
+int pgv_kv_set_filters(pgv_kv *kv, const pgv_filter_config *cfg);
+int pgv_sample_logits_filtered(pgv_ctx *ctx, const float *d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                               const int32_t *d_seen_ids, int seen_stride, const int32_t *d_seen_lens, const float *d_u, int32_t *d_next,
+                               int32_t *d_kept, int greedy, float *d_lp_model, float *d_lp_pick, const pgv_filter_config *cfg, float *d_kept_range,
+                               void *stream);
+
 /* Beam search (HF: generate(num_beams = K); GenerationMixin._beam_search of transformers 5, steps b-g), K beams per prompt from ONE prefill, every
  * step on the device.  Per prompt, with t = tokens generated so far, N = max_new_tokens, all arithmetic fp32, NEG = -1e9f:
  *   start  running scores [0, NEG, ...]; finished scores all NEG, finished flags all 0; unsat = 1; open = 1.

@@ -63,6 +63,16 @@ class BanConfig(C.Structure):
         return cfg
 
 
+class FilterConfig(C.Structure):
+    """pgv_filter_config of include/pgv.h (pgv_kv_set_filters, pgv_sample_logits_filtered)."""
+    _fields_ = [("min_p", _f), ("typical_p", _f), ("epsilon_cutoff", _f), ("eta_cutoff", _f)]
+
+    @classmethod
+    def from_filters(cls, f) -> "FilterConfig":
+        """`f`: sample_filters.SampleFilters (min_p None: 0, the neutral value of the C layer)."""
+        return cls(0.0 if f.min_p is None else float(f.min_p), float(f.typical_p), float(f.epsilon_cutoff), float(f.eta_cutoff))
+
+
 def beam_state_words(K: int) -> int:
     """PGV_BEAM_STATE_WORDS(K): 32-bit words of one prompt's beam state."""
     return 6 * int(K) + 2
@@ -146,6 +156,8 @@ PROTOTYPES = {
     "pgv_kv_logprobs_steps": (_i, [_vp, _i, _vp, _vp, _vp]),
     "pgv_llm_pick_greedy": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "pgv_sample_logits_lp": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "pgv_kv_set_filters": (_i, [_vp, C.POINTER(FilterConfig)]),
+    "pgv_sample_logits_filtered": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.POINTER(FilterConfig), _vp, _vp]),
     "pgv_kv_set_bans": (_i, [_vp, C.POINTER(BanConfig)]),
     "pgv_ban_logits": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(BanConfig), _vp]),
     "pgv_kv_ids_peek": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
@@ -416,6 +428,37 @@ class Context:
                                             out.data_ptr(), kept.data_ptr(), 1 if greedy else 0, lp[0].data_ptr(), lp[1].data_ptr(),
                                             stream_ptr(logits.device)), "pgv_sample_logits_lp")
         return out, kept, lp[0], lp[1]
+
+    def sample_logits_filtered(self, logits: torch.Tensor, u: "torch.Tensor | None", temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
+                               repetition_penalty: float = 1.0, seen_ids: "torch.Tensor | None" = None, seen_lens: "torch.Tensor | None" = None,
+                               greedy: bool = False, filters=None, want_range: bool = True):
+        """pgv_sample_logits_filtered: sample_logits_lp behind HF's filter tail (`filters`: sample_filters.SampleFilters, a dict of its fields, or
+        None -- passed to the C layer unchecked, so that its refusals can be seen).  Returns (tokens, kept, model, pick, kept_range fp32 [B, 2] or
+        None): kept_range is the smallest / largest kept (penalised) logit of each row."""
+        from .sample_filters import SampleFilters
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+        B = logits.shape[0]
+        if not greedy:
+            assert u is not None and u.is_cuda and u.dtype == torch.float32 and u.is_contiguous() and u.numel() == B
+        stride = 0
+        if seen_ids is not None:
+            assert seen_ids.is_cuda and seen_ids.dtype == torch.int32 and seen_ids.is_contiguous() and seen_ids.dim() == 2 and seen_ids.shape[0] == B
+            stride = seen_ids.shape[1]
+            if seen_lens is None:
+                seen_lens = torch.full((B,), stride, dtype=torch.int32, device=logits.device)
+            assert seen_lens.is_cuda and seen_lens.dtype == torch.int32 and seen_lens.numel() == B and int(seen_lens.max()) <= stride
+        out = torch.empty(B, dtype=torch.int32, device=logits.device)
+        kept = torch.empty(B, dtype=torch.int32, device=logits.device)
+        lp = torch.empty(2, B, dtype=torch.float32, device=logits.device)
+        rng = torch.empty(B, 2, dtype=torch.float32, device=logits.device) if want_range else None
+        cfg = None if filters is None else FilterConfig.from_filters(SampleFilters.coerce(filters))
+        check(self.lib.pgv_sample_logits_filtered(self.handle, logits.data_ptr(), logits.shape[1], B, float(temperature), int(top_k), float(top_p),
+                                                  float(repetition_penalty), seen_ids.data_ptr() if seen_ids is not None else None, stride,
+                                                  seen_lens.data_ptr() if seen_ids is not None else None, u.data_ptr() if u is not None else None,
+                                                  out.data_ptr(), kept.data_ptr(), 1 if greedy else 0, lp[0].data_ptr(), lp[1].data_ptr(),
+                                                  C.byref(cfg) if cfg is not None else None, rng.data_ptr() if rng is not None else None,
+                                                  stream_ptr(logits.device)), "pgv_sample_logits_filtered")
+        return out, kept, lp[0], lp[1], rng
 
     def beam_pick_logits(self, logits: torch.Tensor, state: torch.Tensor, beams: int, t: int, max_new_tokens: int, eos_id: int = -1,
                          length_penalty: float = 1.0, early_stopping: int = 0):

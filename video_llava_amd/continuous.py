@@ -88,7 +88,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                         prompt_slack: int = 128, eos_token_id="config", seed: int = 0,
                         on_error: Callable[[Any, Exception], None] = _default_on_error,
                         timings: Optional[dict] = None, top_p: float = 1.0, repetition_penalty: float = 1.0,
-                        logprobs: Optional[dict] = None, bans=None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
+                        logprobs: Optional[dict] = None, bans=None, filters=None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
     """Yield (task_id, new_ids) as each task finishes; new_ids is None for a task that failed (`on_error(task_id, exc)` is told why) -- a failed
     task costs only itself.
 
@@ -116,7 +116,10 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     what `generate(output_logprobs=True)` returns for the task on its own, bit for bit, whatever its slot and the group width (the values are
     recorded on the device at pick time: pgv_kv_set_logprobs).
     bans (logit_bans.LogitBans, a dict of its fields, or None): HF's -inf processors, one configuration for every task of the call, as in
-    `generate`; a task's sequence is its own prompt and answer -- a refilled slot's id record starts from its prompt (pgv_kv_set_bans)."""
+    `generate`; a task's sequence is its own prompt and answer -- a refilled slot's id record starts from its prompt (pgv_kv_set_bans).
+    filters (sample_filters.SampleFilters, a dict of its fields, or None): HF's min_p / typical_p / epsilon_cutoff / eta_cutoff warpers behind top_p,
+    one record for every sampled pick of the call -- the opening draw, every refill's first-token draw and every decode step (pgv_kv_set_filters);
+    fields not given come from the model's generation config, as in `generate`.  Inert with do_sample=False."""
     if not 1 <= width <= 64:
         raise ValueError(f"width {width} outside [1, 64]")
     if do_sample and not float(temperature) > 0.0:
@@ -133,6 +136,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     from .logit_bans import LogitBans, check_bans
     ban = LogitBans() if bans is None else check_bans(bans, model.vocab_size, eos_i, who="generate_continuous()")      # on the host, before any device work
     ban_on = not ban.effective_neutral(eos_i)
+    from .sample_filters import check_filters
+    filt = check_filters(filters, getattr(model, "generation_config", None), who="generate_continuous()")
+    filt_on = bool(do_sample) and not filt.neutral
     dev = model.device_
 
     source = iter(tasks)
@@ -239,6 +245,8 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq, **({"logprobs": True} if want_lp else {}),
                                **({"capacity": W} if forked else {}), **({"bans": ban, "eos_id": eos_i} if ban_on else {}))
     try:
+        if filt_on:
+            model.set_filters(kv, filt)                             # for this call only: cleared in the finally below
         slots: List[Optional[_Slot]] = [None] * W
         # slot s holds sample j of first[i]; j beyond the task's samples: an idle padding slot
         owner = [(i, s - sum(counts[:i])) for s, i in enumerate(fork_sources(counts))]
@@ -413,3 +421,5 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
             model.set_logprobs(kv, False)                           # the switch was on for this call only: also when the generator is closed early
         if ban_on:
             model.set_bans(kv, None)
+        if filt_on:
+            model.set_filters(kv, None)

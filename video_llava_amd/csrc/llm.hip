@@ -387,6 +387,16 @@ extern "C" int pgv_kv_set_warpers(pgv_kv* kv, float top_p, float repetition_pena
     return PGV_OK;
 }
 
+// HF's four filter warpers behind top-p (pgv.h): stored next to top_p and the penalty, read by every later sampled pick (kv_sampled)
+extern "C" int pgv_kv_set_filters(pgv_kv* kv, const pgv_filter_config* cfg) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_set_filters: null cache");
+    const pgv_filter_config off{0.f, 1.f, 0.f, 0.f};
+    const pgv_filter_config& c = cfg ? *cfg : off;
+    PGV_TRY(pgv_check_filters("pgv_kv_set_filters", c.min_p, c.typical_p, c.epsilon_cutoff, c.eta_cutoff));
+    kv->warpers.min_p = c.min_p; kv->warpers.typical_p = c.typical_p; kv->warpers.epsilon = c.epsilon_cutoff; kv->warpers.eta = c.eta_cutoff;
+    return PGV_OK;
+}
+
 // HF's -inf processors (pgv.h).  The lists go to device memory owned by the cache, outside any capture: a captured decode step bakes in their
 // addresses and lengths, and the graphs' key carries the generation counter.
 extern "C" int pgv_kv_set_bans(pgv_kv* kv, const pgv_ban_config* cfg) {
@@ -436,7 +446,11 @@ extern "C" int pgv_kv_ids_peek(pgv_kv* kv, int slot, int n, int32_t* d_out, int3
 }
 
 // a sampled pick on this cache: the caller's temperature and top_k, the cache's warpers
-static PickParams kv_sampled(const pgv_kv* kv, float temperature, int top_k) { return {temperature, top_k, kv->warpers.top_p, kv->warpers.penalty, false}; }
+static PickParams kv_sampled(const pgv_kv* kv, float temperature, int top_k) {
+    PickParams p = kv->warpers;         // top_p, penalty and the filter tail (pgv_kv_set_filters)
+    p.temperature = temperature; p.top_k = top_k; p.greedy = false;
+    return p;
+}
 
 extern "C" int pgv_kv_set_logprobs(pgv_kv* kv, int on) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_logprobs: null cache");

@@ -117,7 +117,10 @@ int pgv_check_warpers(const char* who, float top_p, float penalty);
 // n zeros: the uniforms of a pick_greedy pick
 inline int pgv_zero_uniforms(float* u, size_t n, hipStream_t s) { PGV_HIP(hipMemsetAsync(u, 0, n * 4, s)); return PGV_OK; }
 int pgv_launch_sample(const float* logits, int V, int B, const PickParams& p, const float* u, int u_stride, int u_by_step, const PickState& st, hipStream_t s,
-                      const SampleWarp* warp = nullptr, const PickLp* lp = nullptr);
+                      const SampleWarp* warp = nullptr, const PickLp* lp = nullptr, float* kept_range = nullptr);
+// HF's constructor checks of the four filter warpers (pgv.h: pgv_kv_set_filters), their wording.  pgv_launch_sample runs the filter tail
+// (sample_kernel<true, LP, true>) only when PickParams::filtered() or kept_range [B][2] (the smallest / largest kept logit) asks for it.
+int pgv_check_filters(const char* who, float min_p, float typical_p, float epsilon, float eta);
 // prefill: ids [M] of sequences with row ranges cu -> block b marks the ids of sequence seq[b] (null: b) in the bitmap of slot slots[b] (null: b);
 // clear = start from an empty set
 int pgv_launch_seen_mark(const int* ids, const int* cu, const int* slots, int B, int V, unsigned* bits, int words, int clear, hipStream_t s,

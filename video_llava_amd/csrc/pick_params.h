@@ -7,9 +7,16 @@ enum { AM_INC_POS = 1, AM_RECORD = 2, AM_SAMPLE = 4, AM_BEAM = 8 };      // book
 
 // HF's processors in HF's order: repetition penalty, temperature, top-k, top-p (the defaults: none of them).  greedy: the pick is the arg-max of
 // the penalised logits and its log-probability their log-softmax over the WHOLE vocabulary, as HF's greedy loop has it.
+// min_p, typical_p, epsilon, eta: HF's four remaining sampling warpers, the tail behind top-p (pgv.h: pgv_kv_set_filters; neutral: 0, 1, 0, 0).  A greedy
+// pick ignores them, as it ignores top_p.
 struct PickParams {
     float temperature = 1.f; int top_k = 0; float top_p = 1.f, penalty = 1.f; bool greedy = false;
-    bool operator==(const PickParams& o) const { return temperature == o.temperature && top_k == o.top_k && top_p == o.top_p && penalty == o.penalty && greedy == o.greedy; }
+    float min_p = 0.f, typical_p = 1.f, epsilon = 0.f, eta = 0.f;
+    bool filtered() const { return !greedy && (min_p > 0.f || typical_p < 1.f || epsilon > 0.f || eta > 0.f); }
+    bool operator==(const PickParams& o) const {
+        return temperature == o.temperature && top_k == o.top_k && top_p == o.top_p && penalty == o.penalty && greedy == o.greedy && min_p == o.min_p &&
+               typical_p == o.typical_p && epsilon == o.epsilon && eta == o.eta;
+    }
 };
 // Greedy under a repetition penalty: the arg-max candidates of the lm_head GEMV know no penalty, so the pick is the sampled one over the penalised
 // logits with temperature 1, top_k = 1, no nucleus and a uniform of 0 (pgv_zero_uniforms) -- the largest value, the first index on ties.

@@ -120,6 +120,23 @@ __global__ __launch_bounds__(256) void argmax_parts_lp_kernel(const float* __res
 //    unless the row went through logit_ban_kernel (PickLp::banned): then it is the whole-vocabulary sum of the banned row, -inf entries weight 0.
 //  * model = (x[t] - max x) - ln sum exp(x - max x) on the raw logits, the two statistics taken from row_lse_kernel (score.hip).
 // The seen-set it reads is the LDS copy made before the pick; the bit of the returned token is set in global memory afterwards.
+//
+// sample_kernel<true, LP, true> (pgv_kv_set_filters) adds HF's remaining sampling warpers, the tail behind top-p in HF's order: MinPLogitsWarper,
+// TypicalLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper.  Each stage recomputes the softmax over what the stage before left, so each is one
+// statistics pass over the current survivors (S = sum e, A = sum e * t with t = (x - M) c = log2 e, and the largest surviving e: lane, wave, then
+// the 16 wave totals in order) followed by a tighter bound.  The survivor predicate becomes `key >= thr && key != 0 && e_lo <= e <= e_hi` on the
+// weight e the kernel computes anyway; the two bounds are row-uniform (every thread derives the same floats from the same LDS partials).  M stays the
+// row maximum: the weights stay <= 1.  With p = e / S, ln e = t ln 2, m = (A / S) ln 2 (the mean of ln e) and H = ln S - m:
+//  * min_p:    keep e >= min_p * e_max (independent of the normaliser).  It is the first stage, so e_max is the weight of the row maximum, 1: no pass.
+//  * typical:  d = |(-ln p) - H| = |t ln 2 - m|.  The smallest d* with mass{d <= d*} >= ceil(typical_p * S_fx) comes from a 4-pass radix select like
+//              the nucleus one -- ascending, keyed by the bits of the non-negative float d, over 2^40 fixed-point masses added with integer LDS
+//              atomics (order-free).  Entries with d <= d* stay: equal d are kept together (HF: `sorted_scores > threshold` removes), the entry that
+//              crosses the mass is kept, the smallest d always stays.  One more pass takes the smallest and largest weight among them: they become
+//              [e_lo, e_hi] -- a BAND in the logit, the row's largest logit is routinely outside.
+//  * epsilon:  keep e >= epsilon * S, or the largest CURRENT survivor: e_lo = max(e_lo, min(epsilon * S, e_max)).
+//  * eta:      the same with min(eta, sqrt(eta) * exp(-H)) in place of epsilon.
+// A row without a positive total skips the stages.  The final weight pass, the kept count, the CDF walk and the log-probability read the same
+// predicate: `pick` is normalised over the final survivors.  Greedy picks never take this form.
 // ---------------------------------------------------------------------------------------------
 struct SampleArgs {
     const float* logits; int V;
@@ -130,6 +147,9 @@ struct SampleArgs {
     SampleWarp w;            // sample_kernel<true> only
 };
 struct SampleArgsLp : SampleArgs { PickLp lp; };     // sample_kernel<true, true>: the other two keep the argument record they have always had
+// sample_kernel<true, LP, true>: HF's tail behind top-p (see below).  kept_range [B][2] (optional): the smallest and the largest kept (penalised) logit.
+struct SampleFilt { float min_p = 0.f, typical_p = 1.f, epsilon = 0.f, eta = 0.f; float* kept_range = nullptr; };
+struct SampleArgsF : SampleArgsLp { SampleFilt f; };
 
 __device__ __forceinline__ unsigned float_key(float x) {          // larger float <-> larger key; NaN -> 0 (below every number)
     if (x != x) return 0u;
@@ -143,9 +163,11 @@ constexpr float SAMPLE_FX = 1099511627776.f;     // 2^40: fixed-point scale of a
 
 __device__ __forceinline__ unsigned long long weight_fx(float e) { return e > 0.f ? (unsigned long long)(e * SAMPLE_FX) : 0ull; }     // NaN -> 0
 
-template <bool WARP, bool LP = false>
-__global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, SampleArgsLp, SampleArgs> p) {
+template <bool WARP, bool LP = false, bool FILT = false>
+__global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<FILT, SampleArgsF, std::conditional_t<LP, SampleArgsLp, SampleArgs>> p) {
     static_assert(WARP || !LP, "the log-probability form is built on the kernel with both processors");
+    static_assert(WARP || !FILT, "the filter tail is built on the kernel with both processors");
+    __shared__ float fred[FILT ? 3 : 1][16];   // FILT: per-wave partials of a statistics pass (S, A, e_max) or of the band pass (min e, max e)
     __shared__ float lp_red[LP ? 17 : 1];      // LP: the 16 wave totals of the whole-vocabulary sum, then the total the pick value is normalised by
     __shared__ int hist[256];
     __shared__ unsigned sbits[WARP ? 16 * 64 * SAMPLE_MAXR / 32 : 1];      // seen-set of the row
@@ -319,12 +341,133 @@ __global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, Sam
         }
     }
     // ---- weights e_i = exp2((x_i - M) c) of the kept entries; round and wave totals -------------------------
+    [[maybe_unused]] float e_lo = 0.f, e_hi = INFINITY;      // FILT: the bounds of the filter tail on a kept weight (row-uniform)
     auto weight = [&](int i) -> float {
         if (i >= V) return 0.f;
         const float x = load(i);
         const unsigned key = float_key(x);
+        if constexpr (FILT) {
+            const float e = (key >= thr && key != 0u) ? __builtin_amdgcn_exp2f((x - M) * p.c) : 0.f;
+            return (e >= e_lo && e <= e_hi) ? e : 0.f;
+        }
         return (key >= thr && key != 0u) ? __builtin_amdgcn_exp2f((x - M) * p.c) : 0.f;
     };
+    // ---- filter tail: min_p -> typical_p -> epsilon -> eta, each over the survivors of the stage before (header comment) ----------------
+    if constexpr (FILT) {
+        constexpr float LN2 = 0.6931471805599453f;
+        // a current survivor's weight (0: none) and its exponent t = log2 e
+        auto weight_t = [&](int i, float& t) -> float {
+            t = 0.f;
+            if (i >= V) return 0.f;
+            const float x = load(i);
+            const unsigned key = float_key(x);
+            if (!(key >= thr && key != 0u)) return 0.f;
+            t = (x - M) * p.c;
+            const float e = __builtin_amdgcn_exp2f(t);
+            return (e >= e_lo && e <= e_hi) ? e : 0.f;
+        };
+        float S = 0.f, A = 0.f, E = 0.f;
+        auto stats = [&]() {       // S, A and the largest weight of the current survivors: lane, wave, the 16 wave totals in order
+            float s = 0.f, a = 0.f, m = 0.f;
+            for (int r = 0; r < rounds; ++r) {
+                float t;
+                const float e = weight_t(base + r * 64 + lane, t);
+                if (e > 0.f) { s += e; a = __fmaf_rn(e, t, a); m = fmaxf(m, e); }
+            }
+            s = wave_sum(s); a = wave_sum(a); m = wave_max(m);
+            __syncthreads();                                  // the partials of the pass before have been read
+            if (lane == 0) { fred[0][w] = s; fred[1][w] = a; fred[2][w] = m; }
+            __syncthreads();
+            S = 0.f; A = 0.f; E = 0.f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { S += fred[0][i]; A += fred[1][i]; E = fmaxf(E, fred[2][i]); }
+        };
+        // min_p is the first stage: the largest survivor of top-k / top-p is the row maximum itself, whose weight is exp2(0) = 1 -- no pass needed
+        // (a row without a finite entry has M = -inf and keeps nothing either way).  min_p <= 1: the top passes its own bound.
+        if (p.f.min_p > 0.f && M > -INFINITY) e_lo = p.f.min_p;
+        if (p.f.typical_p < 1.f) {
+            stats();
+            if (S > 0.f) {
+                const float mean = (A / S) * LN2;                         // the mean of ln e under p: H = ln S - mean, (-ln p_i) - H = mean - t_i ln 2
+                auto dist = [&](float t) -> unsigned { return __float_as_uint(fabsf(__fmaf_rn(t, LN2, -mean))); };      // non-negative float: its bits order it
+                unsigned prefix = 0u, mask = 0u;
+                if (tid == 0) { sel_q[0] = 0ull; sel_q[1] = 0ull; }      // mass below the prefix; the limit ceil(typical_p * total) (set in the first pass)
+                for (int pass = 3; pass >= 0; --pass) {
+                    if (tid < 256) mass[tid] = 0ull;
+                    __syncthreads();
+                    for (int r = 0; r < rounds; ++r) {
+                        float t;
+                        const float e = weight_t(base + r * 64 + lane, t);
+                        const unsigned key = dist(t);
+                        unsigned long long q = (key & mask) == prefix ? weight_fx(e) : 0ull;
+                        const int bin = (int)((key >> (8 * pass)) & 255u);
+                        const unsigned long long act = __ballot(q != 0ull);
+                        if (act == 0ull) continue;
+                        const int bin0 = __shfl(bin, __builtin_ctzll(act), 64);
+                        if (__ballot(q != 0ull && bin != bin0) == 0ull) {   // one bin for the whole wave: one atomic (integer adds: any order, same sum)
+#pragma unroll
+                            for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+                            if (lane == 0) atomicAdd(&mass[bin0], q);
+                        } else if (q != 0ull) {
+                            atomicAdd(&mass[bin], q);
+                        }
+                    }
+                    __syncthreads();
+                    if (tid == 0) {
+                        if (pass == 3) {
+                            unsigned long long T = 0ull;
+                            for (int q = 0; q < 256; ++q) T += mass[q];
+                            sel_q[1] = (unsigned long long)ceil((double)p.f.typical_p * (double)T);     // <= T: some bin reaches it in every pass
+                        }
+                        // the lowest bin at which the mass of everything up to and including it reaches the limit: d* lies in it
+                        const unsigned long long limit = sel_q[1];
+                        unsigned long long cum = sel_q[0];
+                        int bin = -1;
+                        for (int q = 0; q < 256 && limit != 0ull; ++q) {
+                            const unsigned long long h = mass[q];
+                            if (h != 0ull && cum + h >= limit) { bin = q; sel_q[0] = cum; break; }
+                            cum += h;
+                        }
+                        sel_i[0] = bin;
+                    }
+                    __syncthreads();
+                    const int bin = sel_i[0];
+                    __syncthreads();
+                    if (bin < 0) { mask = 0u; break; }                    // no weight of 2^-40 or more among the survivors: the stage keeps them
+                    prefix |= (unsigned)bin << (8 * pass);
+                    mask |= 0xffu << (8 * pass);
+                }
+                if (mask == 0xffffffffu) {        // prefix = the bits of d*: the band of weights with d <= d*
+                    float lo = INFINITY, hi = 0.f;
+                    for (int r = 0; r < rounds; ++r) {
+                        float t;
+                        const float e = weight_t(base + r * 64 + lane, t);
+                        if (e > 0.f && dist(t) <= prefix) { lo = fminf(lo, e); hi = fmaxf(hi, e); }
+                    }
+                    lo = -wave_max(-lo); hi = wave_max(hi);
+                    __syncthreads();
+                    if (lane == 0) { fred[0][w] = lo; fred[1][w] = hi; }
+                    __syncthreads();
+                    lo = INFINITY; hi = 0.f;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) { lo = fminf(lo, fred[0][i]); hi = fmaxf(hi, fred[1][i]); }
+                    if (hi > 0.f) { e_lo = fmaxf(e_lo, lo); e_hi = hi; }
+                }
+            }
+        }
+        if (p.f.epsilon > 0.f) {
+            stats();
+            if (S > 0.f) e_lo = fmaxf(e_lo, fminf(p.f.epsilon * S, E));     // the largest current survivor always stays
+        }
+        if (p.f.eta > 0.f) {
+            stats();
+            if (S > 0.f) {
+                const float H = logf(S) - (A / S) * LN2;
+                e_lo = fmaxf(e_lo, fminf(fminf(p.f.eta, sqrtf(p.f.eta) * expf(-H)) * S, E));
+            }
+        }
+        __syncthreads();            // the last partials have been read before the passes below reuse LDS
+    }
     [[maybe_unused]] bool lp_whole = false;
     if constexpr (LP) {
         lp_whole = p.lp.greedy && (pen_on || p.lp.banned);      // banned: the -inf entries of the row carry weight 0, like NaN
@@ -342,13 +485,23 @@ __global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, Sam
         }
     }
     int nkept = 0;
+    [[maybe_unused]] float x_lo = INFINITY, x_hi = -INFINITY;      // FILT: the smallest / largest kept (penalised) logit
     for (int r = 0; r < rounds; ++r) {
         const float e = weight(base + r * 64 + lane);
         const float t = wave_sum(e);
         if (lane == 0) R[w][r] = t;
         if constexpr (WARP) nkept += __popcll(__ballot(e > 0.f));
+        if constexpr (FILT) {
+            if (p.f.kept_range && e > 0.f) { const float x = load(base + r * 64 + lane); x_lo = fminf(x_lo, x); x_hi = fmaxf(x_hi, x); }
+        }
     }
     if constexpr (WARP) { if (lane == 0) kc[w] = nkept; }
+    if constexpr (FILT) {
+        if (p.f.kept_range) {
+            x_lo = -wave_max(-x_lo); x_hi = wave_max(x_hi);
+            if (lane == 0) { fred[0][w] = x_lo; fred[1][w] = x_hi; }
+        }
+    }
     __syncthreads();
     if (tid < 16) {
         float t = 0.f;
@@ -361,6 +514,13 @@ __global__ __launch_bounds__(1024) void sample_kernel(std::conditional_t<LP, Sam
         for (int i = 0; i < 16; ++i) S += Wt[i];
         if constexpr (WARP) {
             if (p.w.kept) { int n = 0; for (int i = 0; i < 16; ++i) n += kc[i]; p.w.kept[b] = n; }
+        }
+        if constexpr (FILT) {
+            if (p.f.kept_range) {       // an empty row: (+inf, -inf)
+                float lo = INFINITY, hi = -INFINITY;
+                for (int i = 0; i < 16; ++i) { lo = fminf(lo, fred[0][i]); hi = fmaxf(hi, fred[1][i]); }
+                p.f.kept_range[2 * b] = lo; p.f.kept_range[2 * b + 1] = hi;
+            }
         }
         if constexpr (LP) {
             float G = S;
@@ -502,8 +662,18 @@ int pgv_check_warpers(const char* who, float top_p, float penalty) {
     return PGV_OK;
 }
 
+int pgv_check_filters(const char* who, float min_p, float typical_p, float epsilon, float eta) {
+    // HF's wording: generation/logits_process.py, the constructors of MinPLogitsWarper / TypicalLogitsWarper / EpsilonLogitsWarper / EtaLogitsWarper
+    // (here typical_p == 1 and a cutoff of 0 are the neutral values HF's generate() builds no warper for)
+    PGV_CHECK(min_p >= 0.f && min_p <= 1.f, "%s: `min_p` has to be a float in the [0, 1] interval, but is %g", who, (double)min_p);
+    PGV_CHECK(typical_p > 0.f && typical_p <= 1.f, "%s: `typical_p` has to be a float > 0 and < 1, but is %g", who, (double)typical_p);
+    PGV_CHECK(epsilon >= 0.f && epsilon < 1.f, "%s: `epsilon_cutoff` has to be a float > 0 and < 1, but is %g", who, (double)epsilon);
+    PGV_CHECK(eta >= 0.f && eta < 1.f, "%s: `eta_cutoff` has to be a float > 0 and < 1, but is %g", who, (double)eta);
+    return PGV_OK;
+}
+
 int pgv_launch_sample(const float* logits, int V, int B, const PickParams& p, const float* u, int u_stride, int u_by_step, const PickState& st, hipStream_t s,
-                      const SampleWarp* warp, const PickLp* lp) {
+                      const SampleWarp* warp, const PickLp* lp, float* kept_range) {
     PGV_CHECK(V >= 1 && V <= 16 * 64 * SAMPLE_MAXR, "sample: vocabulary %d outside [1, %d]", V, 16 * 64 * SAMPLE_MAXR);
     PGV_CHECK(p.temperature > 0.f, "sample: temperature must be positive (got %g); use the greedy path for temperature 0", (double)p.temperature);
     SampleArgsLp a;
@@ -515,6 +685,20 @@ int pgv_launch_sample(const float* logits, int V, int B, const PickParams& p, co
     a.lp = (lp && lp->stat) ? *lp : PickLp{};
     a.lp.greedy = p.greedy;
     if (a.lp.stat) PGV_TRY(check_lp("sample", a.lp, st.advance));
+    // the filter tail (min_p / typical_p / epsilon / eta) runs in an instantiation of its own, launched only when one of the four is on (or the
+    // kept range is asked for): with all four neutral everything below launches what it has always launched
+    if (p.filtered() || kept_range) {
+        PGV_TRY(pgv_check_warpers("sample", p.top_p, p.penalty));
+        PGV_TRY(pgv_check_filters("sample", p.min_p, p.typical_p, p.epsilon, p.eta));
+        PGV_CHECK(a.w.seen_bits == nullptr || a.w.seen_words * 32 >= V, "sample: seen-set bitmap of %d words for a vocabulary of %d", a.w.seen_words, V);
+        SampleArgsF f;
+        static_cast<SampleArgsLp&>(f) = a;
+        if (p.filtered()) { f.f.min_p = p.min_p; f.f.typical_p = p.typical_p; f.f.epsilon = p.epsilon; f.f.eta = p.eta; }      // a greedy pick ignores them
+        f.f.kept_range = kept_range;
+        if (a.lp.stat) hipLaunchKernelGGL((sample_kernel<true, true, true>), dim3(B), dim3(1024), 0, s, f);
+        else hipLaunchKernelGGL((sample_kernel<true, false, true>), dim3(B), dim3(1024), 0, s, f);
+        return PGV_OK;
+    }
     // the neutral values run the kernel without the two extra processors: bit for bit the tokens of the temperature / top-k chain alone
     if (p.top_p < 1.f || p.penalty != 1.f || a.w.kept) {
         PGV_TRY(pgv_check_warpers("sample", p.top_p, p.penalty));
@@ -531,10 +715,10 @@ int pgv_launch_sample(const float* logits, int V, int B, const PickParams& p, co
 
 // the pick of the three building blocks: the seen-set as id lists (none: no penalty applies), the token to d_next and nothing advanced
 static int sample_ids(const float* d_logits, int V, int B, const PickParams& p, const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u,
-                      int32_t* d_next, int32_t* d_kept, const PickLp* lp, hipStream_t s) {
+                      int32_t* d_next, int32_t* d_kept, const PickLp* lp, hipStream_t s, float* d_kept_range = nullptr) {
     SampleWarp w;
     w.seen_ids = d_seen_ids; w.seen_stride = seen_stride; w.seen_lens = d_seen_lens; w.kept = d_kept;
-    PGV_TRY(pgv_launch_sample(d_logits, V, B, p, d_u, B, 0, PickState{d_next}, s, &w, lp));
+    PGV_TRY(pgv_launch_sample(d_logits, V, B, p, d_u, B, 0, PickState{d_next}, s, &w, lp, d_kept_range));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
@@ -548,26 +732,45 @@ extern "C" int pgv_sample_logits_ex(pgv_ctx* ctx, const float* d_logits, int V, 
     return sample_ids(d_logits, V, B, {temperature, top_k, top_p, repetition_penalty}, d_seen_ids, seen_stride, d_seen_lens, d_u, d_next, d_kept, nullptr, (hipStream_t)stream);
 }
 
-extern "C" int pgv_sample_logits_lp(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
-                                    const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u, int32_t* d_next, int32_t* d_kept,
-                                    int greedy, float* d_lp_model, float* d_lp_pick, void* stream) {
-    PGV_CHECK(ctx && d_logits && (d_u || greedy) && d_next && B >= 1, "pgv_sample_logits_lp: bad arguments");
-    PGV_CHECK((d_seen_ids == nullptr) == (d_seen_lens == nullptr) && seen_stride >= 0, "pgv_sample_logits_lp: d_seen_ids and d_seen_lens go together");
-    const PickParams p = greedy ? pick_greedy(repetition_penalty) : PickParams{temperature, top_k, top_p, repetition_penalty};
-    PGV_TRY(pgv_check_warpers("pgv_sample_logits_lp", p.top_p, p.penalty));
+// pgv_sample_logits_lp and, with a filter record / a kept-range output, pgv_sample_logits_filtered
+static int sample_logits_lp(const char* who, pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                            const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u, int32_t* d_next, int32_t* d_kept,
+                            int greedy, float* d_lp_model, float* d_lp_pick, const pgv_filter_config* cfg, float* d_kept_range, void* stream) {
+    PGV_CHECK(ctx && d_logits && (d_u || greedy) && d_next && B >= 1, "%s: bad arguments", who);
+    PGV_CHECK((d_seen_ids == nullptr) == (d_seen_lens == nullptr) && seen_stride >= 0, "%s: d_seen_ids and d_seen_lens go together", who);
+    PickParams p = greedy ? pick_greedy(repetition_penalty) : PickParams{temperature, top_k, top_p, repetition_penalty};
+    PGV_TRY(pgv_check_warpers(who, p.top_p, p.penalty));
+    if (cfg) {
+        PGV_TRY(pgv_check_filters(who, cfg->min_p, cfg->typical_p, cfg->epsilon_cutoff, cfg->eta_cutoff));
+        p.min_p = cfg->min_p; p.typical_p = cfg->typical_p; p.epsilon = cfg->epsilon_cutoff; p.eta = cfg->eta_cutoff;
+    }
     hipStream_t s = (hipStream_t)stream;
     // row statistics [B][2] and, for the greedy form, its B uniforms
     PGV_TRY(pgv_ws_reserve(ctx, 2 * pgv_align((size_t)B * 8), s));
     float* stat = (float*)pgv_ws_alloc(ctx, (size_t)B * 8);
     float* zero = (float*)pgv_ws_alloc(ctx, (size_t)B * 4);
-    PGV_CHECK(stat && zero, "pgv_sample_logits_lp: workspace exhausted");
+    PGV_CHECK(stat && zero, "%s: workspace exhausted", who);
     if (greedy) PGV_TRY(pgv_zero_uniforms(zero, B, s));
     PGV_TRY(pgv_launch_row_lse(d_logits, V, V, B, stat, s));
     PickLp lp;
     lp.stat = stat; lp.last_model = d_lp_model; lp.last_pick = d_lp_pick;
-    PGV_TRY(sample_ids(d_logits, V, B, p, d_seen_ids, seen_stride, d_seen_lens, greedy ? zero : d_u, d_next, d_kept, &lp, s));
+    PGV_TRY(sample_ids(d_logits, V, B, p, d_seen_ids, seen_stride, d_seen_lens, greedy ? zero : d_u, d_next, d_kept, &lp, s, d_kept_range));
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
+}
+
+extern "C" int pgv_sample_logits_lp(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                                    const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u, int32_t* d_next, int32_t* d_kept,
+                                    int greedy, float* d_lp_model, float* d_lp_pick, void* stream) {
+    return sample_logits_lp("pgv_sample_logits_lp", ctx, d_logits, V, B, temperature, top_k, top_p, repetition_penalty, d_seen_ids, seen_stride, d_seen_lens, d_u, d_next,
+                            d_kept, greedy, d_lp_model, d_lp_pick, nullptr, nullptr, stream);
+}
+
+extern "C" int pgv_sample_logits_filtered(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, float top_p, float repetition_penalty,
+                                          const int32_t* d_seen_ids, int seen_stride, const int32_t* d_seen_lens, const float* d_u, int32_t* d_next, int32_t* d_kept,
+                                          int greedy, float* d_lp_model, float* d_lp_pick, const pgv_filter_config* cfg, float* d_kept_range, void* stream) {
+    return sample_logits_lp("pgv_sample_logits_filtered", ctx, d_logits, V, B, temperature, top_k, top_p, repetition_penalty, d_seen_ids, seen_stride, d_seen_lens, d_u,
+                            d_next, d_kept, greedy, d_lp_model, d_lp_pick, cfg, d_kept_range, stream);
 }
 
 extern "C" int pgv_sample_logits(pgv_ctx* ctx, const float* d_logits, int V, int B, float temperature, int top_k, const float* d_u, int32_t* d_next,

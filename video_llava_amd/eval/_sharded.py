@@ -34,6 +34,13 @@ def add_runtime_arguments(parser):
     parser.add_argument("--repetition_penalty", type=float, default=None,
                         help="HF RepetitionPenaltyLogitsProcessor over prompt + answer, greedy and sampled; default: the checkpoint's "
                              "generation_config.json, else 1.0")
+    parser.add_argument("--min_p", type=float, default=None, metavar="P",
+                        help="--do_sample: HF MinPLogitsWarper behind --top_p, on the device (generate(filters=)): keeps the tokens whose probability is at "
+                             "least P x the most likely token's; default: the checkpoint's generation_config.json when another of these four flags is "
+                             "given, else off")
+    parser.add_argument("--typical_p", type=float, default=None, metavar="P", help="--do_sample: HF TypicalLogitsWarper (locally typical mass P); 1: off")
+    parser.add_argument("--epsilon_cutoff", type=float, default=None, metavar="E", help="--do_sample: HF EpsilonLogitsWarper (probability floor E); 0: off")
+    parser.add_argument("--eta_cutoff", type=float, default=None, metavar="E", help="--do_sample: HF EtaLogitsWarper (entropy-dependent floor); 0: off")
     parser.add_argument("--no_repeat_ngram", type=int, default=0, metavar="N",
                         help="HF NoRepeatNGramLogitsProcessor (no_repeat_ngram_size=N) over prompt + answer, on the device (generate(bans=)): no n-gram of "
                              "N tokens occurs twice -- the remedy for greedy answers that loop; 0 (default): off")
@@ -82,6 +89,8 @@ def add_runtime_arguments(parser):
         if ns.batch != "auto" and ns.samples_per_prompt > ns.batch:
             parser.error(f"--samples_per_prompt {ns.samples_per_prompt} exceeds the --batch {ns.batch} decode slots")
         try:
+            if filters_from_args(ns) and not ns.do_sample:        # validates the four flags, HF's wording
+                raise ValueError("--min_p / --typical_p / --epsilon_cutoff / --eta_cutoff need --do_sample (they filter a sampled pick)")
             K, _, _ = check_beam_args(ns)
             if bans_from_args(ns) and K > 1:        # validates the three flags, HF's wording
                 raise ValueError(f"--beams {K} cannot be combined with --no_repeat_ngram / --min_new_tokens / --suppress_tokens (the beam pick applies "
@@ -138,6 +147,16 @@ def bans_from_args(ns) -> dict:
                   suppress=tuple(getattr(ns, "suppress_tokens", ()) or ()))
     b.check(1 << 31)            # HF's wording for a negative value; the vocabulary is checked by generate()
     return {} if b.neutral else {"bans": b}
+
+
+def filters_from_args(ns) -> dict:
+    """--min_p / --typical_p / --epsilon_cutoff / --eta_cutoff of a parsed command line as generate() / generate_continuous() keywords: {} when none
+    is given, else {"filters": {flag: value}} with the flags given only -- the rest comes from the model's generation config."""
+    from ..sample_filters import HF_ARGUMENTS, SampleFilters
+    given = {name: getattr(ns, name, None) for name in HF_ARGUMENTS}
+    given = {k: v for k, v in given.items() if v is not None}
+    SampleFilters.coerce(given).check()
+    return {"filters": given} if given else {}
 
 
 def _batch_arg(text):
@@ -451,7 +470,7 @@ class _Runner:
         lps = {} if many else None                                    # the samples are ranked by their log-probabilities
         for idx, new in generate_continuous(self.model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
                                             tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp, **({"logprobs": lps} if many else {}),
-                                            **bans_from_args(args)):
+                                            **bans_from_args(args), **filters_from_args(args)):
             if new is not None and many:
                 new = self.pick_sample(idx, new, lps.pop(idx))
             if new is not None:
@@ -501,7 +520,7 @@ class _Runner:
                     raise clips[t["path"]]
                 new, stop = video_chatgpt_infer_ids(None, t["question"], self.args.conv_mode, self.model, self.vision_tower, self.tokenizer,
                                                     self.image_processor, self.video_token_len, None, max_new_tokens=self.args.max_new_tokens,
-                                                    features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args))
+                                                    features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args), **filters_from_args(self.args))
                 self.stop_strs[idx] = stop
                 self.record(toks, lens, j, new, strip_eos=False)       # the ids end where the reference's criterion stopped them
             except Exception as e:                                     # noqa: BLE001

@@ -46,6 +46,10 @@ REFUSED = {
 BANS_HINT = {"no_repeat_ngram_size": "no_repeat_ngram", "bad_words_ids": "bad_words", "min_length": "min_length", "min_new_tokens": "min_new_tokens"}
 
 
+# the refused HF arguments that `generate(filters=...)` covers (sample_filters.SampleFilters, HF's own field names): named in the refusal
+FILTERS_HINT = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+
+
 class GenerationDefaults:
     """The fields of a checkpoint's generation_config.json, as attributes (`model.generation_config`).  An absent field reads as None."""
 
@@ -81,20 +85,25 @@ def _config_get(generation_config, name):
     return getattr(generation_config, name, None)
 
 
-def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: str = "generate()") -> None:
+def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: str = "generate()", filters_given: bool = False) -> None:
     """Raise ValueError naming the first argument -- of the call, else of the model's generation config -- that changes what HF's generate()
     returns and that this package does not implement.  Everything else in `kwargs` is inert here (use_cache, pad_token_id, an all-ones
-    attention_mask, output_scores=False, ...) and stays ignored."""
+    attention_mask, output_scores=False, ...) and stays ignored.  filters_given: the call passes `filters=`, which takes over the four
+    FILTERS_HINT fields of the generation config (sample_filters.resolve_filters); as arguments of the call they stay refused."""
     for name, asks in REFUSED.items():
         if name in kwargs:
             v, where = kwargs[name], "argument"
+        elif filters_given and name in FILTERS_HINT:
+            continue
         else:
             v, where = _config_get(generation_config, name), "generation_config field"
         if asks(v):
             hint = {"num_return_sequences": "; several sampled answers per prompt: this package's own keyword `samples_per_prompt`",
                     "num_beams": "; beam search: this package's own keyword `beams`",
                     **{hf: f"; HF's -inf processors: this package's own keyword `bans` (logit_bans.LogitBans({field}=...))"
-                       for hf, field in BANS_HINT.items()}}.get(name, "")
+                       for hf, field in BANS_HINT.items()},
+                    **{hf: f"; HF's sampling warpers behind top_p: this package's own keyword `filters` (sample_filters.SampleFilters({hf}=...))"
+                       for hf in FILTERS_HINT}}.get(name, "")
             raise ValueError(f"{who}: {where} `{name}`={v!r} is not implemented by this package (it would change the result of HF's generate()); "
                              f"implemented: temperature, top_k, top_p, repetition_penalty{hint}")
     for name in ("output_scores", "output_attentions", "output_hidden_states", "return_dict_in_generate"):

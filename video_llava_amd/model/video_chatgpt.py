@@ -25,6 +25,7 @@ from ..beam_reference import early_code
 from ..generation import (GenerateBeamsOutput, GenerateLogprobsOutput, check_beams, check_generate_kwargs, check_samples_per_prompt, fork_sources,
                           load_generation_config, resolve_sampling)
 from ..logit_bans import LogitBans, check_bans
+from ..sample_filters import SampleFilters, check_filters
 from ..scoring import ScoreOutput, id_rows, shift_labels
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
 from .utils import AnswerState
@@ -458,7 +459,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
 
     def prefill_slots(self, kv, slots: Sequence[int], seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor],
                       want_logits: bool = False, u: Optional[torch.Tensor] = None, temperature: float = 1.0, top_k: int = 50,
-                      top_p: float = 1.0, repetition_penalty: float = 1.0, counts: Optional[Sequence[int]] = None):
+                      top_p: float = 1.0, repetition_penalty: float = 1.0, counts: Optional[Sequence[int]] = None, filters=None):
         """Prefill NEW prompts `seqs` into cache slots `slots` of the live group `kv` (a handle prefill() returned) while the other slots keep
         their state (pgv_llm_prefill_slots: continuous batching).  `video_spatio_temporal_features` [n, V, C] (None: text only; a text-only
         prompt next to video ones takes any [V, C] block, it is not read).  u [n] (optional): draw each first token as sample_last does,
@@ -466,9 +467,13 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         of their own prompt only.  Returns (first tokens [n] int32 on device, logits [n, vocab] or None).
         `counts` (pgv_llm_prefill_slots_n): prompt i gets counts[i] >= 1 sampled answers from ONE prefill -- `slots` and `u` then have
         S = sum(counts) entries, prompt 0's first, and S first tokens / logits rows come back; bit for bit the call with prompt i repeated
-        counts[i] times."""
+        counts[i] times.
+        `filters` (sample_filters.SampleFilters or a dict of its fields): the cache's filter tail from this call on (set_filters); None leaves the
+        cache's values as they are."""
         n = len(seqs)
         self.set_warpers(kv, top_p, repetition_penalty)
+        if filters is not None:
+            self.set_filters(kv, filters)
         if counts is not None and len(counts) != n:
             raise ValueError(f"{len(counts)} counts for {n} prompts")
         S = n if counts is None else sum(int(c) for c in counts)
@@ -499,6 +504,16 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
     def set_warpers(self, kv, top_p: float = 1.0, repetition_penalty: float = 1.0):
         """pgv_kv_set_warpers: HF's TopPLogitsWarper / RepetitionPenaltyLogitsProcessor values for every later pick on this cache."""
         _lib.check(self.ctx.lib.pgv_kv_set_warpers(kv, float(top_p), float(repetition_penalty)), "pgv_kv_set_warpers")
+
+    def set_filters(self, kv, filters=None):
+        """pgv_kv_set_filters: HF's min_p / typical_p / epsilon_cutoff / eta_cutoff warpers (sample_filters.SampleFilters or a dict of its fields;
+        None or a neutral record: off) for every later SAMPLED pick on this cache; set_warpers leaves them alone, greedy picks ignore them."""
+        f = SampleFilters.coerce(filters).check()
+        if f.neutral:
+            _lib.check(self.ctx.lib.pgv_kv_set_filters(kv, None), "pgv_kv_set_filters")
+            return
+        cfg = _lib.FilterConfig.from_filters(f)
+        _lib.check(self.ctx.lib.pgv_kv_set_filters(kv, C.byref(cfg)), "pgv_kv_set_filters")
 
     def set_bans(self, kv, bans=None, eos_id: int = -1):
         """pgv_kv_set_bans: HF's -inf processors (logit_bans.LogitBans; None or a neutral record: off) for every later covered pick on this cache.
@@ -738,7 +753,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  samples_per_prompt: int = 1, beams: int = 1, length_penalty: Optional[float] = None, early_stopping=None,
-                 output_beam_scores: bool = False, bans=None, **_unused):
+                 output_beam_scores: bool = False, bans=None, filters=None, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -795,8 +810,15 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         work, with HF's wording; a bad word equal to [eos] is dropped, as HF does.  Greedy decoding under bans takes the route of greedy under a
         repetition penalty.  With `output_logprobs`, token_logprobs stay the raw model's and transition_scores are normalised over what survives
         (HF's `scores`).  Works with samples_per_prompt; `kv_reuse_key` falls back to the full prefill; `beams` > 1 is refused.  None or a record
-        that asks nothing is the call without the keyword; the cache's configuration is cleared when the call ends."""
-        check_generate_kwargs(_unused, self.generation_config)
+        that asks nothing is the call without the keyword; the cache's configuration is cleared when the call ends.
+        `filters` (a keyword of this package: sample_filters.SampleFilters, a dict of its fields, or None; HF's four argument names stay refused):
+        HF's sampling warpers behind top-p -- min_p, typical_p, epsilon_cutoff, eta_cutoff -- inside the device pick, in HF's order (pgv.h:
+        pgv_kv_set_filters).  Each field comes from the call if given (a key of the dict / a field that differs from its neutral value), else from
+        `self.generation_config` under the same name, else it is neutral; a checkpoint whose generation_config.json carries one of them runs when
+        the call passes `filters` (an empty dict takes the file's values) and is refused without it.  Validated on the host before any device
+        work, with HF's wording.  Inert with do_sample=False, as top_p is; `beams` > 1 is refused.  With `output_logprobs`, transition_scores are
+        normalised over the final survivors.  None or a neutral record is the call without the keyword, bit for bit."""
+        check_generate_kwargs(_unused, self.generation_config, filters_given=filters is not None)
         temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
         if torch.is_tensor(input_ids):
             seqs = [row.tolist() for row in input_ids.cpu()]
@@ -813,6 +835,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         eos_i = -1 if eos is None else int(eos)
         ban = LogitBans() if bans is None else check_bans(bans, self.vocab_size, eos_i, n_beams)       # None: the call as it has always been
         ban_on = not ban.effective_neutral(eos_i)
+        filt = check_filters(filters, self.generation_config, n_beams)
+        filt_on = bool(do_sample) and not filt.neutral
         max_seq = max(len(s) for s in seqs) + max_new_tokens
         if max_seq > self.config.max_position_embeddings:
             raise ValueError(f"prompt + max_new_tokens = {max_seq} exceeds max_position_embeddings {self.config.max_position_embeddings}")
@@ -875,6 +899,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         try:
             raw: List[int] = []                                # B == 1: every token the device emitted, stop cuts ignored (= what the cache holds, shifted by one)
             u = None
+            if filt_on:
+                self.set_filters(kv, filt)                     # for this call only: cleared in the finally below
             if do_sample and max_new_tokens >= 1:
                 u = torch.rand(max_new_tokens, B, device=self.device_, dtype=torch.float32, generator=generator)
                 nxt = self.sample_last(kv, u[0], temperature, top_k, **warp)
@@ -953,6 +979,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 self.set_logprobs(kv, False)                   # also when a criterion, the tokenizer or an interrupt ends the call early
             if ban_on:
                 self.set_bans(kv, None)
+            if filt_on:
+                self.set_filters(kv, None)
 
 
 def _vision_config_from(mm_vision_tower) -> VisionConfig:
