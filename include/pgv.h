@@ -290,6 +290,33 @@ int pgv_kv_peek(pgv_kv *kv, int layer, int which, int slot, int row0, int nrows,
 /* One decode step for all B sequences (the `input_ids.shape[1] == 1` branch, :103): consumes
  * d_last [B] token ids, appends to the KV cache, writes d_logits [B, vocab] and/or d_next [B]. */
 int pgv_llm_decode(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *d_last, float *d_logits, int32_t *d_next, void *stream);
+/* Prompt-lookup speculative decoding (greedy, token-exact) and its building block, the row-wise decode step: several consecutive positions of a
+ * sequence in ONE pass over the weights.  A row is bit for bit the plain step at its position (the decode GEMVs are batch-invariant, the row form
+ * of the attention keeps the plain kernels' key order), so a lookup run emits exactly the tokens pgv_llm_decode_greedy emits.
+ * pgv_kv_set_lookup(kv, D, n): D drafts per sequence and step, 0 <= D <= 15 (0: off, the default; n is ignored then), ngram size 1 <= n <= 4
+ *   (the stepping calls need sequences x (1 + D) <= 64).  The first call with D > 0 allocates the cache's row scratch (a second set of the per-row decode buffers, for
+ *   min(64, 16 x batch) rows) and, unless pgv_kv_set_bans has, the id record.  Set it BEFORE pgv_llm_prefill: while it is on, the prefill writes
+ *   each slot's ids to the record, as under bans.  A call that is refused changes nothing.
+ * pgv_llm_decode_rows: h_slots [R] lists the sequence of every row, the rows of one sequence consecutively (at most 1 + D of them).  Row j of a
+ *   sequence's run consumes d_tokens[r] at position pgv_kv_len + j: its K / V go to that cache row and d_logits [R, vocab] receives its logits --
+ *   those of the j-th of consecutive pgv_llm_decode calls fed the same tokens.  Lengths, current tokens and step counters do NOT advance: the
+ *   caller keeps a prefix of the rows by stepping on.  Runs eagerly.  PGV_ESTATE without lookup set or prefilled sequences; PGV_EINVAL for a slot
+ *   outside the live group, a sequence listed twice, too many rows, or a row past max_seq; nothing is launched then.
+ * pgv_llm_decode_lookup: `steps` lookup steps from d_first [B] (as pgv_llm_decode_greedy takes it).  A step drafts up to D tokens per sequence by
+ *   HF's prompt-lookup rule (PromptLookupCandidateGenerator.get_candidates with num_output_tokens = D, max_matching_ngram_size = n, on the slot's ids
+ *   as given plus everything emitted; cut before eos_id), runs current token + drafts as rows, and emits the model's token behind the current one
+ *   plus one per leading draft the model agrees with: between 1 and 1 + D tokens.  eos_id (< 0: none) ends a sequence behind the token that emits
+ *   it; h_budget [B] bounds what each sequence may emit in this call (pgv_kv_len + h_budget <= max_seq).  A finished sequence emits nothing more.
+ *   d_tokens [B, steps x (1 + D)]: each sequence's emitted tokens, packed from column 0; d_counts [steps, B]: tokens emitted per step.  On return
+ *   pgv_kv_len is true again (one blocking copy) and the cache's current tokens are the last emitted ones (d_first NULL continues from them); cache rows at or beyond pgv_kv_len are
+ *   stale: never read, overwritten later.  Eager the first time, then captured graphs of 1 and 8 steps keyed by (D, n).  Refused with PGV_ESTATE and
+ *   nothing launched: lookup off, a cache whose record does not cover its sequences (prefilled before pgv_kv_set_lookup, or stepped / forked /
+ *   refilled since), a repetition penalty, bans, log-probabilities on, a beam run in flight.  Sampling has no lookup form. */
+int pgv_kv_set_lookup(pgv_kv *kv, int D, int n);
+int pgv_kv_lookup(const pgv_kv *kv);        /* the D in force (0: off) */
+int pgv_llm_decode_rows(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_slots, const int32_t *d_tokens, int R, float *d_logits, void *stream);
+int pgv_llm_decode_lookup(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *d_first, int steps, int eos_id, const int32_t *h_budget,
+                          int32_t *d_tokens, int32_t *d_counts, void *stream);
 
 /* n greedy steps without host round trips: step i consumes the previous argmax (step 0 consumes
  * d_first [B]); token of step i of sequence b is written to d_tokens[b * n + i].  A sequence that
@@ -648,6 +675,15 @@ int pgv_gemv_prep(pgv_ctx *ctx, int dtype, const int32_t *d_tok, const void *d_e
  * d_ticket (B * heads, zeroed by the caller; every launch leaves it zero) are the split merge's scratch.  Synchronises the stream once. */
 int pgv_decode_attention(pgv_ctx *ctx, pgv_llm *llm, const void *d_qkv, const int32_t *h_pos, void *d_Kc, void *d_Vc, void *d_out, int B, int max_seq,
                          int split, float *d_part, uint32_t *d_ticket, void *stream);
+/* Its row form, the kernels and launcher pgv_llm_decode_rows runs: row r of R is the pair (slot h_row_slot[r] of S, offset h_row_j[r]) and sits at
+ * position p = h_pos[slot] + h_row_j[r].  The rotated k and the v of d_qkv[r] ([R, 3H]) are written to cache row p of the slot (by a launch in front
+ * of the attention), the row attends to cache rows [0, p] and writes d_out[r] ([R, H]).  With the rows of a slot at offsets 0 .. n - 1, output and
+ * cache rows are bit for bit those of n consecutive pgv_decode_attention calls at h_pos, h_pos + 1, ... on the same q / k / v (same `split`).
+ * h_row_slot[r] == -1: no row -- nothing of it is read or written.  Host-checked: 1 <= S, R <= 64, every position below max_seq, no two rows at
+ * one (slot, offset).  d_part (R * heads * 8 * 130 floats) and d_ticket (R * heads, zeroed by the caller; left zero).  Synchronises the stream once. */
+int pgv_decode_attention_rows(pgv_ctx *ctx, pgv_llm *llm, const void *d_qkv, const int32_t *h_pos, int S, const int32_t *h_row_slot,
+                              const int32_t *h_row_j, void *d_Kc, void *d_Vc, void *d_out, int R, int max_seq, int split, float *d_part,
+                              uint32_t *d_ticket, void *stream);
 /* LLaMA prefill attention on caller buffers: the kernels pgv_llm_prefill / pgv_llm_prefill_append run.  Sequence b has h_seq_lens[b] rows,
  * concatenated in d_qkv [M, 3H]; row i sits at position koff + i (h_koff[b], or 0 when h_koff is NULL).  q is rotated in place in d_qkv,
  * the rotated k and v are written to cache rows koff + i, and row i attends to keys [0, koff + i].  d_out [M, H].  Host-checked:

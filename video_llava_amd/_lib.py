@@ -145,6 +145,10 @@ PROTOTYPES = {
     "pgv_beam_result": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(_f), C.POINTER(C.c_int32), _vp]),
     "pgv_beam_pick_logits": (_i, [_vp, _vp, _i, _i, C.POINTER(BeamConfig), _i, _vp, _vp, _vp, _vp]),
     "pgv_llm_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pgv_kv_set_lookup": (_i, [_vp, _i, _i]),
+    "pgv_kv_lookup": (_i, [_vp]),
+    "pgv_llm_decode_lookup": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    "pgv_llm_decode_rows": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _vp, _vp]),
     "pgv_llm_decode_greedy": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "pgv_llm_sample": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     "pgv_llm_decode_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp]),
@@ -182,6 +186,7 @@ PROTOTYPES = {
     "pgv_gemv_prep": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "pgv_llm_get_weight": (_i, [_vp, _vp, C.c_char_p, _vp, _vp]),
     "pgv_decode_attention": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "pgv_decode_attention_rows": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "pgv_prefill_attention": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _i, _i, _vp]),
     "pgv_layernorm": (_i, [_vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _vp]),
     "pgv_rmsnorm": (_i, [_vp, _i, _vp, _vp, _f, _vp, _i, _i, _vp]),

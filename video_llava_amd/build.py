@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libpgv.so")
-SOURCES = ["api.hip", "gemm.hip", "elementwise.hip", "vit_attn.hip", "weights.hip", "fp8.hip", "w12.hip", "vit.hip", "llm_prefill.hip", "kv_fork.hip", "beam.hip", "gemv.hip", "decode_attn.hip", "sampling.hip", "logit_ban.hip", "score.hip", "llm.hip"]
+SOURCES = ["api.hip", "gemm.hip", "elementwise.hip", "vit_attn.hip", "weights.hip", "fp8.hip", "w12.hip", "vit.hip", "llm_prefill.hip", "kv_fork.hip", "beam.hip", "gemv.hip", "decode_attn.hip", "sampling.hip", "lookup.hip", "logit_ban.hip", "score.hip", "llm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast"]
 # Attention kernels run VALU softmax on the MFMA results every chunk: keep their accumulators in the VGPR file (hipcc otherwise puts
@@ -134,7 +134,7 @@ def check_isa() -> dict:
     """Build-time check of the one place where the code leans on the gfx950 LOWERING rather than on the HIP memory model: the
     cross-workgroup merge of decode_attn_split_kernel moves every shared byte with relaxed agent-scope atomics and no fences, which is correct
     only while those lower to write-through stores / memory-side loads (`sc1`).  Compiles csrc/decode_attn.hip to device assembly and requires,
-    in every instantiation of the kernel: the partial-state and ticket stores and the merge loads carry sc1, there is exactly one ticket
+    in every instantiation of the kernel (plain and row form: the `ROWS` template flag): the partial-state and ticket stores and the merge loads carry sc1, there is exactly one ticket
     atomic, and no cache write-back / invalidate was inserted.  Raises RuntimeError otherwise (a compiler upgrade that changes the lowering
     fails the build instead of silently reading stale partial states; PGV_DATTN_SPLIT=1 is the run-time fallback).  Returns the counts."""
     import re
@@ -153,13 +153,14 @@ def check_isa() -> dict:
         ld = len(re.findall(r"global_load_dword\b.*\bsc1\b", body))
         at = len(re.findall(r"global_atomic_add\b", body))
         bad = len(re.findall(r"buffer_wbl2|buffer_inv", body))
-        found[(dt, split)] = dict(sc1_stores=st, sc1_loads=ld, atomics=at, cache_maintenance=bad)
+        n = found.get((dt, split), {}).get("instantiations", 0) + 1        # the plain and the row form share an entry; each is checked below
+        found[(dt, split)] = dict(sc1_stores=st, sc1_loads=ld, atomics=at, cache_maintenance=bad, instantiations=n)
         if st < 4 or ld < 3 * split or at != 1 or bad:
             raise RuntimeError(f"check_isa: {name}: sc1 stores {st} (need >= 4), sc1 loads {ld} (need >= {3 * split}), ticket atomics {at} (need 1), "
                                f"cache maintenance instructions {bad} (need 0): the fence-free merge of the split decode attention is not safe with this "
                                "compiler's lowering -- set PGV_DATTN_SPLIT=1 and fix csrc/decode_attn.hip")
-    if len(found) != 6:
-        raise RuntimeError(f"check_isa: expected 6 instantiations of decode_attn_split_kernel (2 dtypes x splits 2/4/8), found {sorted(found)}")
+    if len(found) != 6 or any(v["instantiations"] != 2 for v in found.values()):
+        raise RuntimeError(f"check_isa: expected 12 instantiations of decode_attn_split_kernel (2 dtypes x splits 2/4/8 x plain / rows), found {found}")
     found.update(_check_isa_vit_attn())
     return found
 

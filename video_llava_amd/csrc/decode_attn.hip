@@ -9,6 +9,11 @@ namespace {
 
 constexpr int HD = kHD;
 
+// One element of the rotate-half RoPE, rounded to the activation dtype: the ONE expression behind every rotated q and k of the decode path (the fresh
+// key the attention kernels keep in registers and the cache rows kv_rows_append_kernel writes are the same bits because they are this function)
+template <typename T>
+__device__ __forceinline__ typename T::elem rope_rot(typename T::elem own, typename T::elem oth, float c, float s) { return T::from_f32((float)own * c + (float)oth * s); }
+
 // ---------------------------------------------------------------------------------------------
 // decode attention: one workgroup of 8 waves per (sequence, head); lane = (key slot 0..3, 16-B d chunk 0..15), so a
 // wave-load covers 4 consecutive cache rows = 1 KiB contiguous.  Each lane keeps TWO independent online-softmax states
@@ -19,17 +24,27 @@ constexpr int HD = kHD;
 // registers (the loop only streams keys [0, pos)), so nothing waits for that store; partial states are merged inside each wave
 // with shuffles before 8 (not 64) states meet in LDS.
 // ---------------------------------------------------------------------------------------------
-template <typename T, int NW>
+// ROWS (the verify step of prompt-lookup decoding, llm.hip): blockIdx.y is a ROW r = (slot row_slot[r], offset row_j[r]) instead of a slot.  The row reads
+// q / k / v of qkv[r], attends to cache rows [0, p) of its slot with p = pos[slot] + row_j[r] and takes the key at p from registers exactly where the
+// plain kernel takes its fresh token (read back from the cache row the append wrote); it writes out[r] and NO cache row (kv_rows_append_kernel has written rows pos .. pos + j of every slot in a
+// launch of its own in front, so no workgroup reads a row another one of the same launch writes).  Key-to-lane assignment, ring, merge trees and
+// split partition are those of the plain form: row j of a verify step is bit for bit the plain step at that position.  row_slot[r] < 0: no row
+// (the workgroup leaves before it issues a load).  !ROWS: row_slot / row_j are not read and the instruction stream is the one of the kernel before
+// the row map existed.
+template <typename T, int NW, bool ROWS = false>
 __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const typename T::elem* __restrict__ qkv, const int* __restrict__ pos_arr,
                                                           const float2* __restrict__ rope, typename T::elem* __restrict__ Kc,
                                                           typename T::elem* __restrict__ Vc, typename T::elem* __restrict__ out, int H, int heads,
-                                                          int max_seq, float scale_log2e) {
+                                                          int max_seq, float scale_log2e, const int* __restrict__ row_slot,
+                                                          const int* __restrict__ row_j) {
     __shared__ float st_m[NW], st_l[NW];
     __shared__ float st_o[NW][HD];
     constexpr int KPR = NW * 8;                        // keys per round: NW waves x 4 slots x 2 states
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int h = blockIdx.x, b = blockIdx.y;
-    const typename T::elem* q = qkv + (size_t)b * 3 * H + h * HD;
+    const int h = blockIdx.x, r = blockIdx.y;
+    int b = r;
+    if constexpr (ROWS) { b = row_slot[r]; if (b < 0) return; }
+    const typename T::elem* q = qkv + (size_t)r * 3 * H + h * HD;
     const typename T::elem* k = q + H;
     const typename T::elem* v = q + 2 * H;
     typename T::elem* kcache = Kc + ((size_t)b * heads + h) * max_seq * HD;
@@ -56,7 +71,8 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const typename T::
     }
     const typename T::v8 q_own = *(const typename T::v8*)(q + dc * 8), q_oth = *(const typename T::v8*)(q + (dc ^ 8) * 8);     // needs no position either
     __builtin_amdgcn_sched_barrier(0);                 // keeps the (scalar) position load and everything that hangs off it behind the loads above
-    const int pos = pos_arr[b];
+    int pos = pos_arr[b];
+    if constexpr (ROWS) pos += row_j[r];
     const int n_keys = pos;                            // cached keys; the fresh key (index pos) is handled from registers below
     auto load = [&](int key, typename T::v8& kk_, typename T::v8& vv_) { load_row(max(0, min(key, n_keys - 1)), kk_, vv_); };   // clamped rows are masked below
 
@@ -68,7 +84,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const typename T::
     for (int e = 0; e < 8; ++e) { const float2 cs = rope[(size_t)pos * 64 + j0 + e]; cs_c[e] = cs.x; cs_s[e] = dc < 8 ? -cs.y : cs.y; }
     auto rotate = [&](const typename T::v8& own, const typename T::v8& oth, float (&r)[8]) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) r[e] = (float)T::from_f32((float)own[e] * cs_c[e] + (float)oth[e] * cs_s[e]);
+        for (int e = 0; e < 8; ++e) r[e] = (float)rope_rot<T>(own[e], oth[e], cs_c[e], cs_s[e]);
     };
     auto rotated = [&](const typename T::elem* x, float (&r)[8]) {
         rotate(*(const typename T::v8*)(x + dc * 8), *(const typename T::v8*)(x + (dc ^ 8) * 8), r);
@@ -101,14 +117,19 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const typename T::
     // fresh token (overlaps the first loads): wave 0 appends the rotated k and v to the cache; its slot-0 lanes also keep them for the softmax
     typename T::v8 knew, vnew;
     if (w == 0) {
-        float kr[8];
-        rotated(k, kr);
+        if constexpr (ROWS) {      // the row kv_rows_append_kernel wrote: the bits the plain kernel holds here, whatever the compiler contracts in this instantiation
+            knew = *(const typename T::v8*)(kcache + (size_t)pos * HD + dc * 8);
+            vnew = *(const typename T::v8*)(vcache + (size_t)pos * HD + dc * 8);
+        } else {
+            float kr[8];
+            rotated(k, kr);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) knew[e] = T::from_f32(kr[e]);
-        vnew = *(const typename T::v8*)(v + dc * 8);
-        if (slot == 0) {
-            *(typename T::v8*)(kcache + (size_t)pos * HD + dc * 8) = knew;
-            *(typename T::v8*)(vcache + (size_t)pos * HD + dc * 8) = vnew;
+            for (int e = 0; e < 8; ++e) knew[e] = T::from_f32(kr[e]);
+            vnew = *(const typename T::v8*)(v + dc * 8);
+            if (slot == 0) {
+                *(typename T::v8*)(kcache + (size_t)pos * HD + dc * 8) = knew;
+                *(typename T::v8*)(vcache + (size_t)pos * HD + dc * 8) = vnew;
+            }
         }
     }
 
@@ -158,7 +179,7 @@ __global__ __launch_bounds__(NW * 64) void decode_attn_kernel(const typename T::
             L += st_l[i] * f;
             acc += st_o[i][tid] * f;
         }
-        out[(size_t)b * H + h * HD + tid] = T::from_f32(acc / L);
+        out[(size_t)r * H + h * HD + tid] = T::from_f32(acc / L);
     }
 }
 
@@ -181,18 +202,22 @@ constexpr int DPART = HD + 2;                            // floats per partial s
 #ifndef PGV_LAB_DATTN_WAVES_PER_EU
 #define PGV_LAB_DATTN_WAVES_PER_EU 6      // lab A/B: -DPGV_LAB_DATTN_WAVES_PER_EU=5 restores two workgroups per CU
 #endif
-template <typename T, int SPLIT>
+// ROWS: as decode_attn_kernel; the partial states and tickets are those of unit (row, head), so `part` / `ticket` hold one entry per ROW and head.
+template <typename T, int SPLIT, bool ROWS = false>
 __global__ __launch_bounds__(512, PGV_LAB_DATTN_WAVES_PER_EU) void decode_attn_split_kernel(const typename T::elem* __restrict__ qkv, const int* __restrict__ pos_arr,
                                                                 const float2* __restrict__ rope, typename T::elem* __restrict__ Kc,
                                                                 typename T::elem* __restrict__ Vc, typename T::elem* __restrict__ out, int H, int heads,
-                                                                int max_seq, float scale_log2e, float* __restrict__ part, unsigned* __restrict__ ticket) {
+                                                                int max_seq, float scale_log2e, float* __restrict__ part, unsigned* __restrict__ ticket,
+                                                                const int* __restrict__ row_slot, const int* __restrict__ row_j) {
     constexpr int NW = 8, DEPTH = 2;
     __shared__ float st_m[NW], st_l[NW];
     __shared__ float st_o[NW][HD];
     __shared__ unsigned s_ticket;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int h = blockIdx.x, b = blockIdx.y, sp = blockIdx.z;
-    const typename T::elem* q = qkv + (size_t)b * 3 * H + h * HD;
+    const int h = blockIdx.x, r = blockIdx.y, sp = blockIdx.z;
+    int b = r;
+    if constexpr (ROWS) { b = row_slot[r]; if (b < 0) return; }     // every workgroup of the unit leaves: its ticket stays armed at 0
+    const typename T::elem* q = qkv + (size_t)r * 3 * H + h * HD;
     const typename T::elem* k = q + H;
     const typename T::elem* v = q + 2 * H;
     typename T::elem* kcache = Kc + ((size_t)b * heads + h) * max_seq * HD;
@@ -212,7 +237,8 @@ __global__ __launch_bounds__(512, PGV_LAB_DATTN_WAVES_PER_EU) void decode_attn_s
         for (int u = 0; u < 2; ++u) load_row(min(key_of(d, u), max_seq - 1), kq[d][u], vq[d][u]);
     const typename T::v8 q_own = *(const typename T::v8*)(q + dc * 8), q_oth = *(const typename T::v8*)(q + (dc ^ 8) * 8);
     __builtin_amdgcn_sched_barrier(0);
-    const int pos = pos_arr[b];
+    int pos = pos_arr[b];
+    if constexpr (ROWS) pos += row_j[r];
     const int n_keys = pos;
     const int j0 = (dc & 7) * 8;
     float cs_c[8], cs_s[8];
@@ -220,7 +246,7 @@ __global__ __launch_bounds__(512, PGV_LAB_DATTN_WAVES_PER_EU) void decode_attn_s
     for (int e = 0; e < 8; ++e) { const float2 cs = rope[(size_t)pos * 64 + j0 + e]; cs_c[e] = cs.x; cs_s[e] = dc < 8 ? -cs.y : cs.y; }
     auto rotate = [&](const typename T::v8& own, const typename T::v8& oth, float (&r)[8]) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) r[e] = (float)T::from_f32((float)own[e] * cs_c[e] + (float)oth[e] * cs_s[e]);
+        for (int e = 0; e < 8; ++e) r[e] = (float)rope_rot<T>(own[e], oth[e], cs_c[e], cs_s[e]);
     };
     float qr[8];
     rotate(q_own, q_oth, qr);
@@ -259,14 +285,18 @@ __global__ __launch_bounds__(512, PGV_LAB_DATTN_WAVES_PER_EU) void decode_attn_s
     // (round 5), when the ring of prefetched keys is dead: rotating k up front kept 96 VGPRs live, 5 waves per SIMD = two workgroups per CU, so
     // 13B's 640 workgroups ran as 512 + 128; with the block here the kernel fits 80 VGPRs = three workgroups per CU, all 640 resident at once.
     // Same values in the same order (the fresh key always entered the softmax last): bitwise the former result.
-    if (fresh) {
+    if (ROWS && fresh) {           // the row kv_rows_append_kernel wrote: the bits the plain kernel holds here (see decode_attn_kernel)
+        const typename T::v8 knew = *(const typename T::v8*)(kcache + (size_t)pos * HD + dc * 8), vnew = *(const typename T::v8*)(vcache + (size_t)pos * HD + dc * 8);
+        update(0, knew, vnew, slot == 0);
+    }
+    if (!ROWS && fresh) {
         typename T::v8 knew, vnew;
         float cs_c[8], cs_s[8], kr[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) { const float2 cs = rope[(size_t)pos * 64 + j0 + e]; cs_c[e] = cs.x; cs_s[e] = dc < 8 ? -cs.y : cs.y; }
         const typename T::v8 k_own = *(const typename T::v8*)(k + dc * 8), k_oth = *(const typename T::v8*)(k + (dc ^ 8) * 8);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) kr[e] = (float)T::from_f32((float)k_own[e] * cs_c[e] + (float)k_oth[e] * cs_s[e]);
+        for (int e = 0; e < 8; ++e) kr[e] = (float)rope_rot<T>(k_own[e], k_oth[e], cs_c[e], cs_s[e]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) knew[e] = T::from_f32(kr[e]);
         vnew = *(const typename T::v8*)(v + dc * 8);
@@ -311,7 +341,7 @@ __global__ __launch_bounds__(512, PGV_LAB_DATTN_WAVES_PER_EU) void decode_attn_s
             acc += st_o[i][tid] * f;
         }
     }
-    const int unit = b * heads + h;
+    const int unit = r * heads + h;
     float* mine = part + ((size_t)unit * SPLIT + sp) * DPART;
     if (tid < HD) {
         __hip_atomic_store(mine + tid, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -345,9 +375,38 @@ __global__ __launch_bounds__(512, PGV_LAB_DATTN_WAVES_PER_EU) void decode_attn_s
             LL += ls[s_] * f;
             A += os[s_] * f;
         }
-        out[(size_t)b * H + h * HD + tid] = T::from_f32(A / LL);
+        out[(size_t)r * H + h * HD + tid] = T::from_f32(A / LL);
     }
 }
+
+// The cache append of a row-wise step: row r = (slot, j) writes the rotated k and the v of qkv[r] to cache row pos[slot] + j of its slot, the bits
+// the plain kernels store for their fresh token (rope_rot, same lane layout: 16 lanes x 8 dims per head).  One wave per (4 heads, row); rows
+// with row_slot[r] < 0 write nothing.  Plain vector stores.
+template <typename T>
+__global__ __launch_bounds__(64) void kv_rows_append_kernel(const typename T::elem* __restrict__ qkv, const int* __restrict__ pos_arr,
+                                                           const int* __restrict__ row_slot, const int* __restrict__ row_j,
+                                                           const float2* __restrict__ rope, typename T::elem* __restrict__ Kc,
+                                                           typename T::elem* __restrict__ Vc, int H, int heads, int max_seq) {
+    const int r = blockIdx.y, b = row_slot[r];
+    if (b < 0) return;
+    const int lane = threadIdx.x, h = blockIdx.x * 4 + (lane >> 4), dc = lane & 15;
+    if (h >= heads) return;
+    const int pos = pos_arr[b] + row_j[r];
+    const typename T::elem* k = qkv + (size_t)r * 3 * H + H + h * HD;
+    const typename T::elem* v = k + H;
+    const int j0 = (dc & 7) * 8;
+    const typename T::v8 k_own = *(const typename T::v8*)(k + dc * 8), k_oth = *(const typename T::v8*)(k + (dc ^ 8) * 8);
+    typename T::v8 knew;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float2 cs = rope[(size_t)pos * 64 + j0 + e];
+        knew[e] = rope_rot<T>(k_own[e], k_oth[e], cs.x, dc < 8 ? -cs.y : cs.y);
+    }
+    const size_t row = (((size_t)b * heads + h) * max_seq + pos) * HD + dc * 8;
+    *(typename T::v8*)(Kc + row) = knew;
+    *(typename T::v8*)(Vc + row) = *(const typename T::v8*)(v + dc * 8);
+}
+
 
 }  // namespace
 
@@ -382,7 +441,7 @@ int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* 
 #define PGV_DATTN_SPLIT_LAUNCH(S_) \
         PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_attn_split_kernel<T, S_>), dim3(heads, B, S_), dim3(512), 0, s, (const typename T::elem*)qkv, pos, \
                                                         (const float2*)rope, (typename T::elem*)Kc, (typename T::elem*)Vc, (typename T::elem*)out, H, heads, \
-                                                        max_seq, sc, part, ticket))
+                                                        max_seq, sc, part, ticket, (const int*)nullptr, (const int*)nullptr))
     if (split == 2) PGV_DATTN_SPLIT_LAUNCH(2);
     else if (split == 4) PGV_DATTN_SPLIT_LAUNCH(4);
     else if (split == 8) PGV_DATTN_SPLIT_LAUNCH(8);
@@ -390,11 +449,37 @@ int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* 
     else if (nw == 16)
         PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_attn_kernel<T, 16>), dim3(heads, B), dim3(1024), 0, s, (const typename T::elem*)qkv, pos,
                                                         (const float2*)rope, (typename T::elem*)Kc, (typename T::elem*)Vc, (typename T::elem*)out, H, heads,
-                                                        max_seq, sc));
+                                                        max_seq, sc, (const int*)nullptr, (const int*)nullptr));
     else
         PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_attn_kernel<T, 8>), dim3(heads, B), dim3(512), 0, s, (const typename T::elem*)qkv, pos,
                                                         (const float2*)rope, (typename T::elem*)Kc, (typename T::elem*)Vc, (typename T::elem*)out, H, heads,
-                                                        max_seq, sc));
+                                                        max_seq, sc, (const int*)nullptr, (const int*)nullptr));
+    pgv_prof_end(ctx, 4, s, 0.0, bytes);
+    return PGV_OK;
+}
+
+// A row-wise step's attention: the append launch, then the row form of the kernel the model's split choice picks (split_force as above).  `part` /
+// `ticket` hold R * heads units.
+int pgv_launch_decode_attn_rows(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const int* row_slot, const int* row_j, const void* rope, void* Kc,
+                                void* Vc, void* out, int R, int H, int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket,
+                                int split_force) {
+    const float sc = 0.08838834764831845f * 1.4426950408889634f;
+    const int split = split_force ? split_force : (part && ticket) ? decode_attn_split(heads, ctx->num_cu) : 1;
+    pgv_prof_begin(ctx, 4, s);
+    PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((kv_rows_append_kernel<T>), dim3((heads + 3) / 4, R), dim3(64), 0, s, (const typename T::elem*)qkv, pos, row_slot,
+                                                    row_j, (const float2*)rope, (typename T::elem*)Kc, (typename T::elem*)Vc, H, heads, max_seq));
+#define PGV_DATTN_SPLIT_LAUNCH(S_) \
+        PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_attn_split_kernel<T, S_, true>), dim3(heads, R, S_), dim3(512), 0, s, (const typename T::elem*)qkv, pos, \
+                                                        (const float2*)rope, (typename T::elem*)Kc, (typename T::elem*)Vc, (typename T::elem*)out, H, heads, \
+                                                        max_seq, sc, part, ticket, row_slot, row_j))
+    if (split == 2) PGV_DATTN_SPLIT_LAUNCH(2);
+    else if (split == 4) PGV_DATTN_SPLIT_LAUNCH(4);
+    else if (split == 8) PGV_DATTN_SPLIT_LAUNCH(8);
+#undef PGV_DATTN_SPLIT_LAUNCH
+    else
+        PGV_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((decode_attn_kernel<T, 8, true>), dim3(heads, R), dim3(512), 0, s, (const typename T::elem*)qkv, pos,
+                                                        (const float2*)rope, (typename T::elem*)Kc, (typename T::elem*)Vc, (typename T::elem*)out, H, heads,
+                                                        max_seq, sc, row_slot, row_j));
     pgv_prof_end(ctx, 4, s, 0.0, bytes);
     return PGV_OK;
 }

@@ -46,6 +46,14 @@ struct pgv_llm {
 };
 static const LlmMat& layer_mat(const pgv_llm* m, int layer, int kind) { return m->mats[llm_mat_index(layer, kind)]; }
 
+// The fixed-address buffers one decode step works in, one entry per ROW of the step: the cache's own (kv_scratch: row b is slot b) or the row
+// scratch of pgv_kv_set_lookup, whose rows are (slot, offset) pairs.  What pgv_kv documents for its members of these names holds here.
+struct DecodeScratch {
+    float* resid = nullptr; void *xn = nullptr, *qkv = nullptr, *ao = nullptr, *act = nullptr; float* logits = nullptr;
+    float* amax_val = nullptr; int* amax_idx = nullptr; float* ssq = nullptr; int ssq_ts = 0, amax_ts = 0;
+    void* k8_part = nullptr; float* dattn_part = nullptr; unsigned* dattn_ticket = nullptr;
+};
+
 struct pgv_kv {
     pgv_llm* llm;
     int B, max_seq;
@@ -93,7 +101,26 @@ struct pgv_kv {
     std::vector<int> ban_host;          // the list words the device copy holds
     bool ban_on = false;
     int ban_gen = 0;                    // bumped by every pgv_kv_set_bans that changes the device copy: part of the decode graphs' key
+    // row-wise steps (pgv_kv_set_lookup): one allocation by the first call that asks -- a second set of the per-row decode buffers above for up to
+    // lk_rows rows that are (slot, offset) pairs, and the row maps (slot [lk_rows] | offset [lk_rows])
+    char* lk_blob = nullptr;
+    DecodeScratch lk;
+    int *lk_slot = nullptr, *lk_j = nullptr;
+    int lk_rows = 0, lk_D = 0, lk_n = 0;
+    std::vector<int> lk_stage;          // host staging of the row maps / the budgets (kept alive across the async copy)
+    // prompt-lookup steps (pgv_llm_decode_lookup): row tokens and row arg-max [lk_rows], drafts and budget per slot [B], the run's step counter and the
+    // emit counts [max_seq][B]
+    int *lk_tok = nullptr, *lk_t = nullptr, *lk_ndraft = nullptr, *lk_budget = nullptr, *lk_k = nullptr, *lk_counts = nullptr;
+    bool lk_warmed = false;             // a lookup step has run eagerly (code objects loaded) before the first capture
+    bool lk_valid = false;              // the id record holds exactly the ids behind cache rows [0, len) of every live slot (a plain prefill wrote it, only lookup steps since)
 };
+static DecodeScratch kv_scratch(const pgv_kv* kv) {
+    DecodeScratch sc;
+    sc.resid = kv->resid; sc.xn = kv->xn; sc.qkv = kv->qkv; sc.ao = kv->ao; sc.act = kv->act; sc.logits = kv->logits;
+    sc.amax_val = kv->amax_val; sc.amax_idx = kv->amax_idx; sc.ssq = kv->ssq; sc.ssq_ts = kv->ssq_ts; sc.amax_ts = kv->amax_ts;
+    sc.k8_part = kv->k8_part; sc.dattn_part = kv->dattn_part; sc.dattn_ticket = kv->dattn_ticket;
+    return sc;
+}
 // every call that changes what the slots of the live group hold ends a beam run
 static void beam_drop(pgv_kv* kv) { kv->bm_K = 0; }
 
@@ -324,23 +351,51 @@ extern "C" int pgv_llm_get_weight(pgv_ctx* ctx, pgv_llm* m, const char* name_in,
 // ---------------------------------------------------------------------------------------------
 // KV cache
 // ---------------------------------------------------------------------------------------------
+// The ONE list of what a decode step keeps per row (DecodeScratch), laid out for `rows` rows with the caller's `take`: the cache's own buffers
+// (rows = its batch) and the row scratch of pgv_kv_set_lookup come from here.  CT = the column tiles the decode GEMVs run with at that width (1 / 2 /
+// 4): every tile's slice of the side arrays is written, also the empty ones.
+struct ScratchLayout { size_t resid, xn, qkv, ao, act, logits, ssq, av, ai, dpart, dtick, k8, xn_bytes, ssq_bytes, dtick_bytes; };
+template <class Take>
+static ScratchLayout scratch_layout(const pgv_llm* llm, size_t rows, Take&& take) {
+    const size_t H = llm->cfg.hidden, I = llm->cfg.inter, V = llm->vocab_cap, heads = llm->cfg.heads, CT = gemv_col_tiles((int)rows);
+    ScratchLayout o{};
+    o.xn_bytes = CT * 16 * H * 2; o.ssq_bytes = CT * H * 4; o.dtick_bytes = rows * heads * 4;
+    o.resid = take(rows * H * 4);
+    o.xn = take(o.xn_bytes);            // row-major [rows][H] up to 8 rows, fragment-blocked [H / 32][CT][4][16][8] beyond (gv_xblk_offset)
+    o.qkv = take(rows * 3 * H * 2); o.ao = take(rows * H * 2); o.act = take(rows * I * 2); o.logits = take(rows * V * 4);
+    o.ssq = take(o.ssq_bytes); o.av = take(CT * V * 4); o.ai = take(CT * V * 4);
+    o.dpart = take(rows * heads * (size_t)kDattnSplitMax * kDattnPart * 4); o.dtick = take(o.dtick_bytes);
+    o.k8 = take(gemv_k8_part_bytes((int)(H / 16), (int)CT));
+    return o;
+}
+static DecodeScratch scratch_bind(char* b, const ScratchLayout& o, const pgv_llm* llm) {
+    DecodeScratch sc;
+    sc.resid = (float*)(b + o.resid); sc.xn = b + o.xn; sc.qkv = b + o.qkv; sc.ao = b + o.ao; sc.act = b + o.act; sc.logits = (float*)(b + o.logits);
+    sc.ssq = (float*)(b + o.ssq); sc.amax_val = (float*)(b + o.av); sc.amax_idx = (int*)(b + o.ai); sc.ssq_ts = llm->cfg.hidden; sc.amax_ts = llm->vocab_cap;
+    sc.dattn_part = (float*)(b + o.dpart); sc.dattn_ticket = (unsigned*)(b + o.dtick); sc.k8_part = b + o.k8;
+    return sc;
+}
+// tickets armed at 0; the xn columns / ssq partials of absent rows are read (never stored): finite
+static hipError_t scratch_clear(const DecodeScratch& sc, const ScratchLayout& o) {
+    hipError_t e = hipMemset(sc.dattn_ticket, 0, o.dtick_bytes);
+    if (e == hipSuccess) e = hipMemset(sc.ssq, 0, o.ssq_bytes);
+    if (e == hipSuccess) e = hipMemset(sc.xn, 0, o.xn_bytes);
+    return e;
+}
+
 extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq, pgv_kv** out) {
     PGV_CHECK(ctx && llm && out, "pgv_kv_create: null argument");
     PGV_CHECK(batch >= 1 && batch <= kMaxBatch, "pgv_kv_create: batch %d outside [1,%d] (the decode GEMVs tile up to 4 x 16 sequences)", batch, kMaxBatch);
     PGV_CHECK(max_seq >= 1 && max_seq <= kMaxPos, "pgv_kv_create: max_seq %d outside [1,%d]", max_seq, kMaxPos);
     pgv_kv* kv = new pgv_kv();
     kv->llm = llm; kv->B = batch; kv->max_seq = max_seq;
-    const size_t H = llm->cfg.hidden, I = llm->cfg.inter, V = llm->vocab_cap, L = llm->cfg.layers, B = batch;
+    const size_t V = llm->vocab_cap, L = llm->cfg.layers, B = batch;
     const size_t per = pgv_align(B * llm->cfg.heads * (size_t)max_seq * kHD * 2);
-    const size_t CTn = gemv_col_tiles(batch);                // column tiles the decode GEMVs run with (1 / 2 / 4): every tile's slice of the side arrays is written, also the empty ones
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
     const size_t o_cache = take(per * 2 * L);
-    const size_t o_resid = take(B * H * 4), o_xn = take(CTn * 16 * H * 2),      // xn: row-major [B][H] up to 8 sequences, fragment-blocked [H / 32][CTn][4][16][8] beyond (gv_xblk_offset)
-                 o_qkv = take(B * 3 * H * 2), o_ao = take(B * H * 2), o_act = take(B * I * 2),
-                 o_logits = take(B * V * 4), o_ssq = take(CTn * H * 4), o_av = take(CTn * V * 4), o_ai = take(CTn * V * 4), o_ints = take((4 * B + B * (size_t)max_seq) * 4),
-                 o_u = take(B * (size_t)max_seq * 4), o_dpart = take(B * llm->cfg.heads * (size_t)kDattnSplitMax * kDattnPart * 4), o_dtick = take(B * llm->cfg.heads * 4),
-                 o_k8 = take(gemv_k8_part_bytes((int)(H / 16), (int)CTn));
+    const ScratchLayout so = scratch_layout(llm, B, take);
+    const size_t o_ints = take((4 * B + B * (size_t)max_seq) * 4), o_u = take(B * (size_t)max_seq * 4);
     kv->seen_words = (int)(V / 32);                          // vocab_cap is a multiple of 16: round up
     if ((size_t)kv->seen_words * 32 < V) kv->seen_words += 1;
     const size_t o_seen = take(B * (size_t)kv->seen_words * 4);
@@ -350,21 +405,18 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
     char* b = kv->blob;
     for (size_t i = 0; i < L; ++i) { kv->Kc.push_back(b + o_cache + per * 2 * i); kv->Vc.push_back(b + o_cache + per * (2 * i + 1)); }
     kv->plane_bytes = per;
-    kv->resid = (float*)(b + o_resid); kv->xn = b + o_xn; kv->qkv = b + o_qkv; kv->ao = b + o_ao; kv->act = b + o_act; kv->logits = (float*)(b + o_logits); kv->ssq = (float*)(b + o_ssq); kv->amax_val = (float*)(b + o_av); kv->amax_idx = (int*)(b + o_ai);
+    const DecodeScratch sc = scratch_bind(b, so, llm);
+    kv->resid = sc.resid; kv->xn = sc.xn; kv->qkv = sc.qkv; kv->ao = sc.ao; kv->act = sc.act; kv->logits = sc.logits; kv->ssq = sc.ssq; kv->amax_val = sc.amax_val; kv->amax_idx = sc.amax_idx;
+    kv->ssq_ts = sc.ssq_ts; kv->amax_ts = sc.amax_ts; kv->dattn_part = sc.dattn_part; kv->dattn_ticket = sc.dattn_ticket; kv->k8_part = sc.k8_part;
     int* ints = (int*)(b + o_ints);
     kv->d_pos = ints; kv->d_cur = ints + B; kv->d_step = ints + 2 * B; kv->d_done = ints + 3 * B; kv->d_hist = ints + 4 * B;
     kv->d_u = (float*)(b + o_u);
-    kv->dattn_part = (float*)(b + o_dpart); kv->dattn_ticket = (unsigned*)(b + o_dtick);
-    kv->k8_part = (void*)(b + o_k8);
     kv->d_seen = (unsigned*)(b + o_seen);
     kv->lp_stat = (float*)(b + o_lp); kv->lp_last = kv->lp_stat + 2 * B; kv->lp_hist = kv->lp_last + 2 * B;
     e = hipMemset(ints, 0, (4 * B + B * (size_t)max_seq) * 4);
     if (e == hipSuccess) e = hipMemset(kv->d_seen, 0, B * (size_t)kv->seen_words * 4);
     if (e == hipSuccess) e = hipMemset(kv->lp_stat, 0, n_lp * 4);
-    if (e == hipSuccess) e = hipMemset(kv->dattn_ticket, 0, B * llm->cfg.heads * 4);
-    if (e == hipSuccess) e = hipMemset(kv->ssq, 0, CTn * H * 4);
-    if (e == hipSuccess) e = hipMemset(kv->xn, 0, CTn * 16 * H * 2);            // the columns of absent sequences are read (never stored): finite
-    kv->ssq_ts = (int)H; kv->amax_ts = (int)V;
+    if (e == hipSuccess) e = scratch_clear(sc, so);
     if (e != hipSuccess) { (void)hipFree(kv->blob); delete kv; pgv_set_error("pgv_kv_create: memset: %s", hipGetErrorString(e)); return PGV_EHIP; }
     kv->h_len.assign(batch, 0);
     *out = kv;
@@ -377,6 +429,7 @@ extern "C" void pgv_kv_destroy(pgv_kv* kv) {
     if (kv->blob) (void)hipFree(kv->blob);
     if (kv->bm_blob) (void)hipFree(kv->bm_blob);
     if (kv->ban_blob) (void)hipFree(kv->ban_blob);
+    if (kv->lk_blob) (void)hipFree(kv->lk_blob);
     delete kv;
 }
 
@@ -384,6 +437,22 @@ extern "C" int pgv_kv_set_warpers(pgv_kv* kv, float top_p, float repetition_pena
     PGV_CHECK(kv != nullptr, "pgv_kv_set_warpers: null cache");
     PGV_TRY(pgv_check_warpers("pgv_kv_set_warpers", top_p, repetition_penalty));
     kv->warpers.top_p = top_p; kv->warpers.penalty = repetition_penalty;
+    return PGV_OK;
+}
+
+// The id record of a cache -- each slot's ids at their cache positions [B][max_seq] and its prompt length [B] -- with the ban lists and the banned
+// logits copy behind it: one allocation by the first configuration that needs the record (pgv_kv_set_bans, pgv_kv_set_lookup)
+constexpr size_t kBanListWords = PGV_BAN_MAX_IDS + PGV_BAN_MAX_WORDS + 1;
+static int kv_ids_alloc(pgv_kv* kv, const char* who) {
+    if (kv->ban_blob) return PGV_OK;
+    const size_t B = kv->B;
+    const size_t b_ids = pgv_align(B * kv->max_seq * 4), b_plen = pgv_align(B * 4), b_lists = pgv_align(kBanListWords * 4),
+                 b_logits = pgv_align(B * (size_t)kv->llm->vocab_cap * 4);
+    hipError_t e = hipMalloc((void**)&kv->ban_blob, b_ids + b_plen + b_lists + b_logits);
+    if (e != hipSuccess) { kv->ban_blob = nullptr; pgv_set_error("%s: hipMalloc(%zu KiB): %s", who, (b_ids + b_plen + b_lists + b_logits) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
+    kv->ban_ids = (int*)kv->ban_blob; kv->ban_plen = (int*)(kv->ban_blob + b_ids); kv->ban_lists = (int*)(kv->ban_blob + b_ids + b_plen);
+    kv->ban_logits = (float*)(kv->ban_blob + b_ids + b_plen + b_lists);
+    PGV_HIP(hipMemset(kv->ban_blob, 0, b_ids + b_plen + b_lists));
     return PGV_OK;
 }
 
@@ -407,16 +476,8 @@ extern "C" int pgv_kv_set_bans(pgv_kv* kv, const pgv_ban_config* cfg) {
     PGV_TRY(pgv_ban_pack("pgv_kv_set_bans", cfg, kv->llm->cfg.vocab, blob, at));
     PGV_CHECK(cfg->eos_id < kv->llm->cfg.vocab, "pgv_kv_set_bans: eos_id %d outside the vocabulary (%d)", cfg->eos_id, kv->llm->cfg.vocab);
     if (pgv_ban_neutral(cfg, cfg->eos_id)) { kv->ban_on = false; return PGV_OK; }
-    const size_t B = kv->B, n_lists = PGV_BAN_MAX_IDS + PGV_BAN_MAX_WORDS + 1;
-    if (!kv->ban_blob) {
-        const size_t b_ids = pgv_align(B * kv->max_seq * 4), b_plen = pgv_align(B * 4), b_lists = pgv_align(n_lists * 4),
-                     b_logits = pgv_align(B * (size_t)kv->llm->vocab_cap * 4);
-        hipError_t e = hipMalloc((void**)&kv->ban_blob, b_ids + b_plen + b_lists + b_logits);
-        if (e != hipSuccess) { kv->ban_blob = nullptr; pgv_set_error("pgv_kv_set_bans: hipMalloc(%zu KiB): %s", (b_ids + b_plen + b_lists + b_logits) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
-        kv->ban_ids = (int*)kv->ban_blob; kv->ban_plen = (int*)(kv->ban_blob + b_ids); kv->ban_lists = (int*)(kv->ban_blob + b_ids + b_plen);
-        kv->ban_logits = (float*)(kv->ban_blob + b_ids + b_plen + b_lists);
-        PGV_HIP(hipMemset(kv->ban_blob, 0, b_ids + b_plen + b_lists));
-    }
+    const size_t n_lists = kBanListWords;
+    PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_bans"));
     PGV_CHECK(blob.size() <= n_lists, "pgv_kv_set_bans: %zu list words exceed the %zu reserved", blob.size(), n_lists);
     // the configuration the device copy already holds (a caller that sets and clears it around every run): nothing to upload, the graphs stay valid
     const BanLists& o = kv->ban_cfg;
@@ -499,15 +560,16 @@ static int gemv_mat(pgv_ctx* ctx, const pgv_llm* m, int mode, const LlmMat& w, c
     return pgv_launch_gemv(ctx, m->dtype, mode, m->fp8 ? w.w8 : w.w16, x, (int)w.K, out, ldo, (int)w.N, (int)w.K, B, s, m->fp8 ? w.scale : nullptr, nm, z12(m, w.z));
 }
 
-// lm_head GEMV on kv->xn (B rows) -> kv->logits and, for a greedy pick, the per-workgroup argmax candidates
-static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hipStream_t s, int nparts) {
+// lm_head GEMV on sc.xn (B rows) -> sc.logits and, for a greedy pick, the per-workgroup argmax candidates
+static int lm_head_rows(pgv_ctx* ctx, pgv_llm* m, const DecodeScratch& sc, int B, bool greedy, hipStream_t s, int nparts) {
     const int H = m->cfg.hidden, V = m->cfg.vocab;
-    GemvNorm nm; nm.ssq_in = nparts > 0 ? kv->ssq : nullptr; nm.nparts_in = nparts; nm.hidden = H; nm.eps = m->cfg.eps;     // nparts 0: kv->xn is already normalised
-    nm.ssq_ts = kv->ssq_ts; nm.amax_ts = kv->amax_ts;
-    nm.x_blocked = nparts > 0;                       // the folded path hands kv->xn over blocked at batches beyond 16 (pgv_gemv_xblk_tiles)
-    if (greedy) { nm.amax_val = kv->amax_val; nm.amax_idx = kv->amax_idx; }
-    return gemv_mat(ctx, m, GV_F32, m->mats[0], kv->xn, kv->logits, V, B, s, &nm);
+    GemvNorm nm; nm.ssq_in = nparts > 0 ? sc.ssq : nullptr; nm.nparts_in = nparts; nm.hidden = H; nm.eps = m->cfg.eps;     // nparts 0: sc.xn is already normalised
+    nm.ssq_ts = sc.ssq_ts; nm.amax_ts = sc.amax_ts;
+    nm.x_blocked = nparts > 0;                       // the folded path hands sc.xn over blocked at batches beyond 16 (pgv_gemv_xblk_tiles)
+    if (greedy) { nm.amax_val = sc.amax_val; nm.amax_idx = sc.amax_idx; }
+    return gemv_mat(ctx, m, GV_F32, m->mats[0], sc.xn, sc.logits, V, B, s, &nm);
 }
+static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hipStream_t s, int nparts) { return lm_head_rows(ctx, m, kv_scratch(kv), B, greedy, s, nparts); }
 
 // Every pick on rows [0, B) of kv->logits.  `sampled` null: the arg-max of the candidates lm_head left; else the sampled pick with those parameters
 // and the uniforms u [B], or u [steps][B] indexed by the device-side step counter (u_by_step).  `st`: the cache's own state (kv_state) or a refill's
@@ -715,7 +777,7 @@ static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefi
     // (and every sample of a prompt starts from the prompt's ids alone: the pick adds its own token to the set of its own slot)
     PGV_TRY(pgv_launch_seen_mark(w.d.raw_ids, w.d.cu, w.t_slots, T, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s, q.h_counts ? w.d.samp_seq : nullptr));
     // the ordered twin of the seen-set (pgv_kv_set_bans): each slot's ids at their cache positions and its prompt length, same indirection
-    if (kv->ban_on) PGV_TRY(pgv_launch_ids_write(w.d.raw_ids, w.d.cu, w.d.offs, w.t_slots, q.h_counts ? w.d.samp_seq : nullptr, T, kv->ban_ids, kv->max_seq, kv->ban_plen, s));
+    if (kv->ban_on || kv->lk_D > 0) PGV_TRY(pgv_launch_ids_write(w.d.raw_ids, w.d.cu, w.d.offs, w.t_slots, q.h_counts ? w.d.samp_seq : nullptr, T, kv->ban_ids, kv->max_seq, kv->ban_plen, s));
     if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
         PGV_HIP(hipMemcpyAsync(kv->d_pos, w.d.lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
         PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
@@ -819,12 +881,14 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& 
     PrefillWork w;
     PGV_TRY(prefill_check(ctx, m, kv, q));
     beam_drop(kv);
+    kv->lk_valid = false;
     PGV_TRY(prefill_plan_upload(ctx, m, kv, q, w, s));
     PGV_TRY(prefill_trunk(ctx, m, kv, q, w, s));
     if (q.h_counts) PGV_TRY(prefill_fork_runs(m, kv, q, w, s));
     if (q.d_all_logits) PGV_TRY(prefill_all_logits(ctx, m, q, w, s));
     if (q.mode == PREFILL_SCORE) PGV_TRY(prefill_score(ctx, m, q.score, w, s));
     PGV_TRY(prefill_last_rows(ctx, m, kv, q, w, s));
+    kv->lk_valid = kv->lk_D > 0 && q.mode == PREFILL_PLAIN;
     PGV_HIP(hipGetLastError());
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
@@ -928,6 +992,7 @@ extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* 
     PGV_CHECK(W <= kv->B, "pgv_kv_fork: new width %lld exceeds the %d sequences the cache was created with", W, kv->B);
     if (W == P) return PGV_OK;            // every count is 1: the group is its own fork
     beam_drop(kv);
+    kv->lk_valid = false;
     hipStream_t s = (hipStream_t)stream;
     const int heads = m->cfg.heads, L = m->cfg.layers;
     KvForkArgs a;
@@ -975,55 +1040,81 @@ extern "C" int pgv_kv_peek(pgv_kv* kv, int layer, int which, int slot, int row0,
 // ---------------------------------------------------------------------------------------------
 // decode
 // ---------------------------------------------------------------------------------------------
-static int decode_enqueue_unfolded(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s) {
-    const int H = m->cfg.hidden, I = m->cfg.inter, heads = m->cfg.heads, B = kv->active, L = m->cfg.layers;
+// One token step up to the input of lm_head, over `rows` rows of the scratch `sc` fed the tokens tok [rows]: the cache's B slots on its own scratch
+// (row_slot null: row b is slot b at d_pos[b], the launches and arguments of every release so far), or mapped rows on the row scratch (row r is
+// slot row_slot[r] at d_pos[slot] + row_j[r]; a negative slot: no row).  The GEMVs only see another batch, so every row's arithmetic is the one of
+// a plain step at its position (choose_gemv picks the shape by batch; the results are batch-invariant).  *nparts: what lm_head takes.
+struct RowMap { const int *d_slot = nullptr, *d_j = nullptr, *h_slot = nullptr, *h_j = nullptr; };     // device maps for the kernels; host copies for the byte count of the profile
+static double step_kv_bytes(const pgv_kv* kv, int rows, const RowMap& rm, int H) {
+    if (rm.d_slot && !rm.h_slot) return 0.0;       // a lookup step: its rows are drawn on the device
+    double bytes = 0;
+    for (int r = 0; r < rows; ++r) {
+        const int b = rm.h_slot ? rm.h_slot[r] : r;
+        if (b >= 0) bytes += 2.0 * 2.0 * (double)(kv->h_len[b] + (rm.h_j ? rm.h_j[r] : 0) + 1) * H;
+    }
+    return bytes;
+}
+static int step_attn(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const DecodeScratch& sc, int li, int rows, const RowMap& rm, double kv_bytes, hipStream_t s) {
+    const int H = m->cfg.hidden, heads = m->cfg.heads;
+    if (!rm.d_slot)
+        return pgv_launch_decode_attn(ctx, m->dtype, sc.qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], sc.ao, rows, H, heads, kv->max_seq, kv_bytes, s, sc.dattn_part, sc.dattn_ticket, 0);
+    return pgv_launch_decode_attn_rows(ctx, m->dtype, sc.qkv, kv->d_pos, rm.d_slot, rm.d_j, m->rope, kv->Kc[li], kv->Vc[li], sc.ao, rows, H, heads, kv->max_seq, kv_bytes, s,
+                                       sc.dattn_part, sc.dattn_ticket, 0);
+}
+static int decode_trunk_unfolded(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const DecodeScratch& sc, const int* tok, int rows, const RowMap& rm, hipStream_t s, int* nparts_out) {
+    const int H = m->cfg.hidden, I = m->cfg.inter, B = rows, L = m->cfg.layers;
     pgv_prof_begin(ctx, 6, s);
-    PGV_TRY(pgv_launch_embed_tok_norm(m->dtype, kv->d_cur, m->embed, kv->resid, L > 0 ? m->layers[0].in_g : m->norm_g, kv->xn, kv->ssq, B, H, s, false));   // resid is what matters here
+    PGV_TRY(pgv_launch_embed_tok_norm(m->dtype, tok, m->embed, sc.resid, L > 0 ? m->layers[0].in_g : m->norm_g, sc.xn, sc.ssq, B, H, s, false));   // resid is what matters here
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
-    double kv_bytes = 0;
-    for (int b = 0; b < B; ++b) kv_bytes += 2.0 * 2.0 * (double)(kv->h_len[b] + 1) * H;
+    const double kv_bytes = step_kv_bytes(kv, rows, rm, H);
     for (int li = 0; li < L; ++li) {
         const LlmLayer& l = m->layers[li];
-        PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.in_g, m->cfg.eps, kv->xn, B, H, s));
-        PGV_TRY(gemv_mat(ctx, m, GV_STORE16, layer_mat(m, li, MAT_QKV), kv->xn, kv->qkv, 3 * H, B, s, nullptr));
-        PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket, 0));
-        PGV_TRY(gemv_mat(ctx, m, GV_RESID, layer_mat(m, li, MAT_O), kv->ao, kv->resid, H, B, s, nullptr));
-        PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, l.post_g, m->cfg.eps, kv->xn, B, H, s));
-        PGV_TRY(gemv_mat(ctx, m, GV_SWIGLU, layer_mat(m, li, MAT_GU), kv->xn, kv->act, I, B, s, nullptr));
-        PGV_TRY(gemv_mat(ctx, m, GV_RESID, layer_mat(m, li, MAT_DOWN), kv->act, kv->resid, H, B, s, nullptr));
+        PGV_TRY(pgv_launch_rmsnorm(m->dtype, sc.resid, l.in_g, m->cfg.eps, sc.xn, B, H, s));
+        PGV_TRY(gemv_mat(ctx, m, GV_STORE16, layer_mat(m, li, MAT_QKV), sc.xn, sc.qkv, 3 * H, B, s, nullptr));
+        PGV_TRY(step_attn(ctx, m, kv, sc, li, rows, rm, kv_bytes, s));
+        PGV_TRY(gemv_mat(ctx, m, GV_RESID, layer_mat(m, li, MAT_O), sc.ao, sc.resid, H, B, s, nullptr));
+        PGV_TRY(pgv_launch_rmsnorm(m->dtype, sc.resid, l.post_g, m->cfg.eps, sc.xn, B, H, s));
+        PGV_TRY(gemv_mat(ctx, m, GV_SWIGLU, layer_mat(m, li, MAT_GU), sc.xn, sc.act, I, B, s, nullptr));
+        PGV_TRY(gemv_mat(ctx, m, GV_RESID, layer_mat(m, li, MAT_DOWN), sc.act, sc.resid, H, B, s, nullptr));
     }
-    PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
-    PGV_TRY(lm_head_and_pick(ctx, m, kv, B, eos, flags, s, 0));
+    PGV_TRY(pgv_launch_rmsnorm(m->dtype, sc.resid, m->norm_g, m->cfg.eps, sc.xn, B, H, s));
+    *nparts_out = 0;
     return PGV_OK;
 }
 
-static int decode_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s) {
-    if (!norm_fold_enabled()) return decode_enqueue_unfolded(ctx, m, kv, eos, flags, s);
-    const int H = m->cfg.hidden, I = m->cfg.inter, heads = m->cfg.heads, B = kv->active, L = m->cfg.layers;
+static int decode_trunk(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const DecodeScratch& sc, const int* tok, int rows, const RowMap& rm, hipStream_t s, int* nparts_out) {
+    if (!norm_fold_enabled()) return decode_trunk_unfolded(ctx, m, kv, sc, tok, rows, rm, s, nparts_out);
+    const int H = m->cfg.hidden, I = m->cfg.inter, B = rows, L = m->cfg.layers;
     const int nparts = H / 16;                     // one sum-of-squares partial per 16-row workgroup of a residual producer
     // RMSNorm has no launch of its own in decode (GemvArgs, gemv.hip): the kernel that completes the residual also writes
     // xg = round16(resid * gamma_next) and sum-of-squares partials; the consumer GEMV scales its accumulators by rstd.
     pgv_prof_begin(ctx, 6, s);
-    PGV_TRY(pgv_launch_embed_tok_norm(m->dtype, kv->d_cur, m->embed, kv->resid, L > 0 ? m->layers[0].in_g : m->norm_g, kv->xn, kv->ssq, B, H, s, true));
+    PGV_TRY(pgv_launch_embed_tok_norm(m->dtype, tok, m->embed, sc.resid, L > 0 ? m->layers[0].in_g : m->norm_g, sc.xn, sc.ssq, B, H, s, true));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
-    double kv_bytes = 0;
-    for (int b = 0; b < B; ++b) kv_bytes += 2.0 * 2.0 * (double)(kv->h_len[b] + 1) * H;
+    const double kv_bytes = step_kv_bytes(kv, rows, rm, H);
     int parts_in = 1;                              // the embedding kernel leaves one partial per sequence
     for (int li = 0; li < L; ++li) {
         const LlmLayer& l = m->layers[li];
-        GemvNorm cons; cons.ssq_in = kv->ssq; cons.nparts_in = parts_in; cons.hidden = H; cons.eps = m->cfg.eps; cons.ssq_ts = kv->ssq_ts; cons.x_blocked = true;
-        PGV_TRY(gemv_mat(ctx, m, GV_STORE16, layer_mat(m, li, MAT_QKV), kv->xn, kv->qkv, 3 * H, B, s, &cons));
-        PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, kv->qkv, kv->d_pos, m->rope, kv->Kc[li], kv->Vc[li], kv->ao, B, H, heads, kv->max_seq, kv_bytes, s, kv->dattn_part, kv->dattn_ticket, 0));
-        GemvNorm prod; prod.gamma = l.post_g; prod.xg = kv->xn; prod.ssq_out = kv->ssq; prod.ssq_ts = kv->ssq_ts; prod.k8_part = kv->k8_part; prod.x_blocked = true;
-        PGV_TRY(gemv_mat(ctx, m, GV_RESIDNORM, layer_mat(m, li, MAT_O), kv->ao, kv->resid, H, B, s, &prod));
+        GemvNorm cons; cons.ssq_in = sc.ssq; cons.nparts_in = parts_in; cons.hidden = H; cons.eps = m->cfg.eps; cons.ssq_ts = sc.ssq_ts; cons.x_blocked = true;
+        PGV_TRY(gemv_mat(ctx, m, GV_STORE16, layer_mat(m, li, MAT_QKV), sc.xn, sc.qkv, 3 * H, B, s, &cons));
+        PGV_TRY(step_attn(ctx, m, kv, sc, li, rows, rm, kv_bytes, s));
+        GemvNorm prod; prod.gamma = l.post_g; prod.xg = sc.xn; prod.ssq_out = sc.ssq; prod.ssq_ts = sc.ssq_ts; prod.k8_part = sc.k8_part; prod.x_blocked = true;
+        PGV_TRY(gemv_mat(ctx, m, GV_RESIDNORM, layer_mat(m, li, MAT_O), sc.ao, sc.resid, H, B, s, &prod));
         cons.nparts_in = nparts;
-        PGV_TRY(gemv_mat(ctx, m, GV_SWIGLU, layer_mat(m, li, MAT_GU), kv->xn, kv->act, I, B, s, &cons));
+        PGV_TRY(gemv_mat(ctx, m, GV_SWIGLU, layer_mat(m, li, MAT_GU), sc.xn, sc.act, I, B, s, &cons));
         prod.gamma = li + 1 < L ? m->layers[li + 1].in_g : m->norm_g;
-        PGV_TRY(gemv_mat(ctx, m, GV_RESIDNORM, layer_mat(m, li, MAT_DOWN), kv->act, kv->resid, H, B, s, &prod));
+        PGV_TRY(gemv_mat(ctx, m, GV_RESIDNORM, layer_mat(m, li, MAT_DOWN), sc.act, sc.resid, H, B, s, &prod));
         parts_in = nparts;
     }
-    PGV_TRY(lm_head_and_pick(ctx, m, kv, B, eos, flags, s, parts_in));
+    *nparts_out = parts_in;
     return PGV_OK;
+}
+
+// a plain token step: the trunk over the live slots on the cache's own scratch, then lm_head and the pick
+static int decode_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s) {
+    int nparts = 0;
+    PGV_TRY(decode_trunk(ctx, m, kv, kv_scratch(kv), kv->d_cur, kv->active, RowMap{}, s, &nparts));
+    return lm_head_and_pick(ctx, m, kv, kv->active, eos, flags, s, nparts);
 }
 
 static bool graphs_enabled() {
@@ -1038,8 +1129,11 @@ static bool graphs_enabled() {
 // launches, so profiling disables the graphs.
 constexpr int kGraphSteps = 8;
 
-static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s) {
-    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K, kv->ban_on ? kv->ban_gen : 0);
+static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, hipStream_t s);      // below: one prompt-lookup step
+// lookup: the captured steps are lookup steps (pgv_llm_decode_lookup) with the cache's D and n, which join the key
+static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s, bool lookup = false) {
+    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K, kv->ban_on ? kv->ban_gen : 0, lookup ? kv->lk_D : 0,
+                                                lookup ? kv->lk_n : 0);
     if (!(kv->gkey == key)) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->gkey = key;
@@ -1051,7 +1145,7 @@ static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags
         if (!ctx->cap_stream) PGV_HIP(hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking));
         PGV_HIP(hipStreamBeginCapture(ctx->cap_stream, hipStreamCaptureModeRelaxed));
         int rc = PGV_OK;
-        for (int i = 0; i < steps && rc == PGV_OK; ++i) rc = decode_enqueue(ctx, m, kv, eos, flags, ctx->cap_stream);
+        for (int i = 0; i < steps && rc == PGV_OK; ++i) rc = lookup ? lookup_enqueue(ctx, m, kv, eos, ctx->cap_stream) : decode_enqueue(ctx, m, kv, eos, flags, ctx->cap_stream);
         hipError_t e = hipStreamEndCapture(ctx->cap_stream, &graph);
         if (rc != PGV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess) { pgv_set_error("decode graph capture failed: %s", hipGetErrorString(e)); return PGV_EHIP; }
@@ -1065,6 +1159,7 @@ static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags
 
 static int decode_steps(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int n, hipStream_t s) {
     const int B = kv->active;
+    kv->lk_valid = false;               // a plain step appends nothing to the id record
     while (n > 0) {
         int k = 1;
         if (ctx->prof || !graphs_enabled() || !kv->warmed) {
@@ -1349,6 +1444,142 @@ extern "C" int pgv_beam_pick_logits(pgv_ctx* ctx, const float* d_logits, int V, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// row-wise steps (pgv.h: pgv_kv_set_lookup, pgv_llm_decode_rows)
+// ---------------------------------------------------------------------------------------------
+extern "C" int pgv_kv_set_lookup(pgv_kv* kv, int D, int n) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_set_lookup: null cache");
+    PGV_CHECK(D >= 0 && D <= 15, "pgv_kv_set_lookup: %d draft rows per slot outside [0,15]", D);
+    if (D == 0) { kv->lk_D = 0; kv->lk_valid = false; return PGV_OK; }
+    PGV_CHECK(n >= 1 && n <= 4, "pgv_kv_set_lookup: ngram size %d outside [1,4]", n);
+    PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_lookup"));
+    if (!kv->lk_blob) {
+        // sized once for the most rows any setting can ask of this cache: the per-row decode buffers for R rows, then the lookup ints
+        const size_t B = kv->B, R = kMaxBatch < kv->B * 16 ? kMaxBatch : kv->B * 16;
+        size_t off = 0;
+        auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
+        const ScratchLayout so = scratch_layout(kv->llm, R, take);
+        const size_t o_ints = take((4 * R + 2 * B + 1 + B * (size_t)kv->max_seq) * 4);
+        char* b = nullptr;
+        hipError_t e = hipMalloc((void**)&b, off);
+        if (e != hipSuccess) { pgv_set_error("pgv_kv_set_lookup: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
+        e = hipMemset(b, 0, off);                 // beyond scratch_clear: rows no step has written yet are read by the GEMVs of a step with absent rows
+        if (e != hipSuccess) { (void)hipFree(b); pgv_set_error("pgv_kv_set_lookup: memset: %s", hipGetErrorString(e)); return PGV_EHIP; }
+        kv->lk = scratch_bind(b, so, kv->llm);
+        int* ints = (int*)(b + o_ints);
+        kv->lk_slot = ints; kv->lk_j = ints + R; kv->lk_tok = ints + 2 * R; kv->lk_t = ints + 3 * R;
+        kv->lk_ndraft = ints + 4 * R; kv->lk_budget = kv->lk_ndraft + B; kv->lk_k = kv->lk_budget + B; kv->lk_counts = kv->lk_k + 1;
+        kv->lk_blob = b; kv->lk_rows = (int)R;
+    }
+    kv->lk_D = D; kv->lk_n = n;
+    return PGV_OK;
+}
+
+extern "C" int pgv_kv_lookup(const pgv_kv* kv) { return kv ? kv->lk_D : -1; }
+
+// One prompt-lookup step over the live slots: draft -> row-wise trunk -> lm_head with candidates -> row-wise arg-max -> accept
+static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, hipStream_t s) {
+    const int B = kv->active, R = B * (1 + kv->lk_D), V = m->cfg.vocab;
+    LookupArgs a;
+    a.D = kv->lk_D; a.n = kv->lk_n; a.eos = eos; a.max_seq = kv->max_seq;
+    a.pos = kv->d_pos; a.cur = kv->d_cur; a.step = kv->d_step; a.done = kv->d_done; a.hist = kv->d_hist; a.hist_stride = kv->max_seq;
+    a.rec = kv->ban_ids; a.budget = kv->lk_budget;
+    a.tok = kv->lk_tok; a.row_slot = kv->lk_slot; a.row_j = kv->lk_j; a.n_draft = kv->lk_ndraft; a.t = kv->lk_t;
+    a.counts = kv->lk_counts; a.counts_stride = kv->B; a.k = kv->lk_k;
+    pgv_prof_begin(ctx, 6, s);
+    PGV_TRY(pgv_launch_lookup_draft(a, B, s));
+    pgv_prof_end(ctx, 6, s, 0.0, 0.0);
+    RowMap rm; rm.d_slot = kv->lk_slot; rm.d_j = kv->lk_j;
+    int nparts = 0;
+    PGV_TRY(decode_trunk(ctx, m, kv, kv->lk, kv->lk_tok, R, rm, s, &nparts));
+    PGV_TRY(lm_head_rows(ctx, m, kv->lk, R, true, s, nparts));
+    pgv_prof_begin(ctx, 6, s);
+    PGV_TRY(pgv_launch_argmax_parts(kv->lk.amax_val, kv->lk.amax_idx, (V + 15) / 16, kv->lk.amax_ts, V, R, PickState{kv->lk_t}, s));
+    PGV_TRY(pgv_launch_lookup_accept(a, B, s));
+    pgv_prof_end(ctx, 6, s, 0.0, 0.0);
+    return PGV_OK;
+}
+
+extern "C" int pgv_llm_decode_lookup(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int steps, int eos_id, const int32_t* h_budget,
+                                     int32_t* d_tokens, int32_t* d_counts, void* stream) {
+    PGV_CHECK(ctx && h_budget && d_tokens && d_counts, "pgv_llm_decode_lookup: null argument");
+    PGV_TRY(check_decode(m, kv, 0, "pgv_llm_decode_lookup"));
+    const int B = kv->active, D = kv->lk_D, W = 1 + D;
+    if (D < 1) { pgv_set_error("pgv_llm_decode_lookup: lookup is off on this cache (pgv_kv_set_lookup)"); return PGV_ESTATE; }
+    if (!kv->lk_valid) { pgv_set_error("pgv_llm_decode_lookup: the cache's id record does not cover its sequences: set pgv_kv_set_lookup before pgv_llm_prefill and step with pgv_llm_decode_lookup only"); return PGV_ESTATE; }
+    if (kv->warpers.penalty != 1.f) { pgv_set_error("pgv_llm_decode_lookup: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify the plain arg-max"); return PGV_ESTATE; }
+    if (kv->ban_on) { pgv_set_error("pgv_llm_decode_lookup: logit bans are set on this cache (pgv_kv_set_bans); lookup steps verify the plain arg-max"); return PGV_ESTATE; }
+    if (kv->lp_on) { pgv_set_error("pgv_llm_decode_lookup: log-probabilities are on (pgv_kv_set_logprobs); lookup steps record none"); return PGV_ESTATE; }
+    if (kv->bm_K > 0) { pgv_set_error("pgv_llm_decode_lookup: a beam run is in flight on this cache"); return PGV_ESTATE; }
+    PGV_CHECK(B * W <= kv->lk_rows && B * W <= kMaxBatch, "pgv_llm_decode_lookup: %d sequences x %d rows exceed the %d rows of a step", B, W, kv->lk_rows < kMaxBatch ? kv->lk_rows : kMaxBatch);
+    PGV_CHECK(steps >= 1 && steps <= kv->max_seq, "pgv_llm_decode_lookup: %d steps outside [1,%d]", steps, kv->max_seq);
+    PGV_CHECK(eos_id < m->cfg.vocab, "pgv_llm_decode_lookup: eos_id %d outside the vocabulary (%d)", eos_id, m->cfg.vocab);
+    for (int b = 0; b < B; ++b)
+        PGV_CHECK(h_budget[b] >= 0 && kv->h_len[b] + h_budget[b] <= kv->max_seq, "pgv_llm_decode_lookup: sequence %d would grow to %d tokens (cache holds %d)", b,
+                  kv->h_len[b] + h_budget[b], kv->max_seq);
+    hipStream_t s = (hipStream_t)stream;
+    PGV_HIP(hipStreamSynchronize(s));             // an earlier call's copy of the staging may still be in flight
+    kv->lk_stage.assign(h_budget, h_budget + B);
+    PGV_HIP(hipMemcpyAsync(kv->lk_budget, kv->lk_stage.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    if (d_first && d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));      // null: the cache's current tokens
+    PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
+    PGV_HIP(hipMemsetAsync(kv->lk_k, 0, 4, s));
+    PGV_HIP(hipMemsetAsync(kv->lk.dattn_ticket, 0, (size_t)B * W * m->cfg.heads * sizeof(unsigned), s));
+    for (int n = steps; n > 0;) {
+        int k = 1;
+        if (ctx->prof || !graphs_enabled() || !kv->lk_warmed) {
+            kv->lk_warmed = true;
+            PGV_TRY(lookup_enqueue(ctx, m, kv, eos_id, s));
+        } else if (n >= kGraphSteps) {
+            k = kGraphSteps;
+            PGV_TRY(decode_graph(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD, 1, kGraphSteps, s, true));
+        } else {
+            PGV_TRY(decode_graph(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD, 0, 1, s, true));
+        }
+        n -= k;
+    }
+    kv->lp_steps = -1;
+    const int cap = steps * W < kv->max_seq ? steps * W : kv->max_seq;
+    PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)steps * W * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)cap * 4, B, hipMemcpyDeviceToDevice, s));
+    PGV_HIP(hipMemcpy2DAsync(d_counts, (size_t)B * 4, kv->lk_counts, (size_t)kv->B * 4, (size_t)B * 4, steps, hipMemcpyDeviceToDevice, s));
+    // the lengths now live on the device only: one blocking copy makes h_len true again (the caller reads the tokens at this point anyway)
+    PGV_HIP(hipMemcpyAsync(kv->h_len.data(), kv->d_pos, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    PGV_HIP(hipStreamSynchronize(s));
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+extern "C" int pgv_llm_decode_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_slots, const int32_t* d_tokens, int R, float* d_logits, void* stream) {
+    PGV_CHECK(ctx && h_slots && d_tokens && d_logits, "pgv_llm_decode_rows: null argument");
+    PGV_TRY(check_decode(m, kv, 0, "pgv_llm_decode_rows"));
+    if (kv->lk_D < 1) { pgv_set_error("pgv_llm_decode_rows: this cache has no row scratch (pgv_kv_set_lookup allocates it)"); return PGV_ESTATE; }
+    PGV_CHECK(R >= 1 && R <= kv->lk_rows, "pgv_llm_decode_rows: %d rows outside [1,%d]", R, kv->lk_rows);
+    // rows are listed per slot in order: row j of a slot's run sits at position h_len + j
+    std::vector<int>& map = kv->lk_stage;
+    std::vector<int> count((size_t)kv->active, 0);
+    map.assign((size_t)2 * R, 0);
+    for (int r = 0; r < R; ++r) {
+        const int b = h_slots[r];
+        PGV_CHECK(b >= 0 && b < kv->active, "pgv_llm_decode_rows: slot %d of row %d outside the %d prefilled sequences", b, r, kv->active);
+        PGV_CHECK(count[b] == 0 || h_slots[r - 1] == b, "pgv_llm_decode_rows: the rows of slot %d are not consecutive (row %d)", b, r);
+        PGV_CHECK(count[b] <= kv->lk_D, "pgv_llm_decode_rows: more than the %d rows per slot pgv_kv_set_lookup set (slot %d)", 1 + kv->lk_D, b);
+        PGV_CHECK(kv->h_len[b] + count[b] < kv->max_seq, "pgv_llm_decode_rows: sequence %d would grow to %d tokens (cache holds %d)", b, kv->h_len[b] + count[b] + 1, kv->max_seq);
+        map[r] = b; map[(size_t)R + r] = count[b]++;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    PGV_HIP(hipStreamSynchronize(s));             // an earlier call's copy of the staging may still be in flight
+    PGV_HIP(hipMemcpyAsync(kv->lk_slot, map.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->lk_j, map.data() + R, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemsetAsync(kv->lk.dattn_ticket, 0, (size_t)R * m->cfg.heads * sizeof(unsigned), s));      // as every prefill does for the cache's own
+    RowMap rm; rm.d_slot = kv->lk_slot; rm.d_j = kv->lk_j; rm.h_slot = map.data(); rm.h_j = map.data() + R;
+    int nparts = 0;
+    PGV_TRY(decode_trunk(ctx, m, kv, kv->lk, d_tokens, R, rm, s, &nparts));
+    PGV_TRY(lm_head_rows(ctx, m, kv->lk, R, false, s, nparts));
+    PGV_HIP(hipMemcpyAsync(d_logits, kv->lk.logits, (size_t)R * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // attention building blocks (pgv.h): the launchers of prefill_impl / decode_enqueue* on caller buffers, for unit parity tests
 // ---------------------------------------------------------------------------------------------
 // Host values reach the device through the workspace arena; the stream is synchronised once after the upload so the host staging need not
@@ -1380,6 +1611,39 @@ extern "C" int pgv_decode_attention(pgv_ctx* ctx, pgv_llm* m, const void* d_qkv,
     PGV_TRY(upload_ints(ctx, pos, &d_pos, s));
     PGV_TRY(pgv_launch_decode_attn(ctx, m->dtype, d_qkv, d_pos, m->rope, d_Kc, d_Vc, d_out, B, m->cfg.hidden, m->cfg.heads, max_seq, bytes, s, d_part,
                                    d_ticket, split));
+    PGV_HIP(hipGetLastError());
+    PGV_TRY(pgv_ws_release(ctx, s));
+    return PGV_OK;
+}
+
+extern "C" int pgv_decode_attention_rows(pgv_ctx* ctx, pgv_llm* m, const void* d_qkv, const int32_t* h_pos, int S, const int32_t* h_row_slot,
+                                         const int32_t* h_row_j, void* d_Kc, void* d_Vc, void* d_out, int R, int max_seq, int split, float* d_part,
+                                         uint32_t* d_ticket, void* stream) {
+    PGV_CHECK(ctx && m && d_qkv && h_pos && h_row_slot && h_row_j && d_Kc && d_Vc && d_out && d_part && d_ticket, "pgv_decode_attention_rows: null argument");
+    PGV_CHECK(S >= 1 && S <= kMaxBatch && R >= 1 && R <= kMaxBatch, "pgv_decode_attention_rows: %d slots / %d rows outside [1,%d]", S, R, kMaxBatch);
+    PGV_CHECK(max_seq >= 1 && max_seq <= kMaxPos, "pgv_decode_attention_rows: max_seq %d outside [1,%d]", max_seq, kMaxPos);
+    PGV_CHECK(split == 0 || split == 1 || split == 2 || split == 4 || split == 8, "pgv_decode_attention_rows: split %d is not 0, 1, 2, 4 or 8", split);
+    std::vector<int> up((size_t)S + 2 * R);       // positions | row slots | row offsets
+    std::set<std::pair<int, int>> seen;
+    double bytes = 0;
+    for (int b = 0; b < S; ++b) {
+        PGV_CHECK(h_pos[b] >= 0 && h_pos[b] < max_seq, "pgv_decode_attention_rows: position %d of slot %d outside [0,%d)", h_pos[b], b, max_seq);
+        up[b] = h_pos[b];
+    }
+    for (int r = 0; r < R; ++r) {
+        const int b = h_row_slot[r], j = h_row_j[r];
+        PGV_CHECK(b >= -1 && b < S, "pgv_decode_attention_rows: slot %d of row %d outside [-1,%d)", b, r, S);
+        up[(size_t)S + r] = b; up[(size_t)S + R + r] = j;
+        if (b < 0) continue;
+        PGV_CHECK(j >= 0 && h_pos[b] + j < max_seq, "pgv_decode_attention_rows: row %d sits at position %d + %d, outside [0,%d)", r, h_pos[b], j, max_seq);
+        PGV_CHECK(seen.insert({b, j}).second, "pgv_decode_attention_rows: two rows write cache row %d + %d of slot %d", h_pos[b], j, b);
+        bytes += 2.0 * 2.0 * (h_pos[b] + j + 1.0) * m->cfg.hidden;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int* d_up = nullptr;
+    PGV_TRY(upload_ints(ctx, up, &d_up, s));
+    PGV_TRY(pgv_launch_decode_attn_rows(ctx, m->dtype, d_qkv, d_up, d_up + S, d_up + S + R, m->rope, d_Kc, d_Vc, d_out, R, m->cfg.hidden, m->cfg.heads, max_seq, bytes,
+                                        s, d_part, d_ticket, split));
     PGV_HIP(hipGetLastError());
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;

@@ -84,6 +84,23 @@ int pgv_launch_unpack_blocked(int dtype, const void* src, float* dst, long long 
 // decode_attn.hip
 int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const void* rope, void* Kc, void* Vc, void* out, int B, int H,
                            int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket, int split_force);
+// the row form (decode_attn.hip): row r = (slot row_slot[r], offset row_j[r]) of R reads qkv[r], appends its k / v at cache row pos[slot] + row_j[r] (a
+// launch of its own in front) and attends to rows [0, that]; row_slot[r] < 0: no row.  part / ticket: R * heads units.
+int pgv_launch_decode_attn_rows(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const int* row_slot, const int* row_j, const void* rope, void* Kc,
+                                void* Vc, void* out, int R, int H, int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket,
+                                int split_force);
+// lookup.hip: the draft and accept kernels of a prompt-lookup step (pgv.h: pgv_llm_decode_lookup).  Slot b owns rows b * (1 + D) + j, j = 0 .. D.
+struct LookupArgs {
+    int D = 0, n = 0, eos = -1, max_seq = 0;
+    int *pos = nullptr, *cur = nullptr, *step = nullptr, *done = nullptr, *hist = nullptr; int hist_stride = 0;   // the cache's pick state (PickState)
+    int* rec = nullptr;                       // id record [slots][max_seq], indexed by cache position
+    const int* budget = nullptr;              // [slots] tokens the run may still emit per slot
+    int *tok = nullptr, *row_slot = nullptr, *row_j = nullptr, *n_draft = nullptr;      // rows: token, slot (-1: no row), offset; drafts per slot
+    const int* t = nullptr;                   // [rows] the arg-max behind every row
+    int *counts = nullptr, counts_stride = 0, *k = nullptr;                            // emit counts [steps][counts_stride], the run's step counter
+};
+int pgv_launch_lookup_draft(const LookupArgs& a, int B, hipStream_t s);
+int pgv_launch_lookup_accept(const LookupArgs& a, int B, hipStream_t s);
 // sampling.hip
 // Where a pick puts the token of row b and what it advances (the defaults: the caller's `next` only).  advance: AM_INC_POS does pos[b]++;
 // AM_RECORD does hist[b * hist_stride + step[b]++] = token and keeps EOS sticky through done[b] (eos < 0: no EOS).

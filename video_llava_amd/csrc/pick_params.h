@@ -28,10 +28,13 @@ struct DecodeGraphKey {
     int B = 0, eos = 0, flags = 0, generation = -1; bool logprobs = false; PickParams pick;
     int beams = 0;          // AM_BEAM: the group width K of the run (the grid of the gather and the slots a pick writes); every other beam parameter lives in device memory
     int bans = 0;           // pgv_kv_set_bans: the generation counter of the cache's ban configuration (0: none) -- the ban kernel's launch and its list lengths are baked in
+    int lookup_D = 0, lookup_n = 0;      // pgv_llm_decode_lookup: drafts per slot and ngram size of the captured lookup steps (0: plain token steps)
     bool operator==(const DecodeGraphKey& o) const {
-        return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick && beams == o.beams && bans == o.bans;
+        return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick && beams == o.beams && bans == o.bans &&
+               lookup_D == o.lookup_D && lookup_n == o.lookup_n;
     }
 };
-inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight, int beams = 0, int bans = 0) {
-    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0, bans};
+inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight, int beams = 0, int bans = 0,
+                                       int lookup_D = 0, int lookup_n = 0) {
+    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0, bans, lookup_D, lookup_n};
 }

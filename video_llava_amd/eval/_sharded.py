@@ -71,6 +71,12 @@ def add_runtime_arguments(parser):
     parser.add_argument("--length_penalty", type=float, default=None, help="--beams: HF's length_penalty; default: the checkpoint's generation_config.json, else 1.0")
     parser.add_argument("--early_stopping", choices=("false", "true", "never"), default=None,
                         help="--beams: HF's early_stopping; default: the checkpoint's generation_config.json, else false")
+    parser.add_argument("--lookup", type=int, default=0, metavar="D",
+                        help=f"greedy decoding as prompt-lookup speculative decoding with D <= {MAX_LOOKUP} drafts per sequence and step (generate(lookup=D)): the "
+                             "greedy answers, bit for bit, in fewer passes over the weights when answers repeat themselves or quote the prompt; --schedule group "
+                             "only, not with --do_sample, --beams, --samples_per_prompt, --repetition_penalty or the ban flags; a group holds --batch clips x "
+                             "(1 + D) rows (--batch auto counts 1 + D rows per clip); --timings lines gain lookup_steps_group / lookup_emitted_group")
+    parser.add_argument("--lookup_ngram", type=int, default=2, metavar="N", help="--lookup: the largest n-gram matched, 1 .. 4 (HF: max_matching_ngram_size)")
     parser.add_argument("--timings", default=None, metavar="OUT.jsonl",
                         help="append one JSON line per answered task (rank-local file `OUT.jsonl.rank<r>` when world > 1): frame load, upload + ingest, "
                              "tower + pool, prefill, decode seconds, generated tokens, group size, feature-cache hit (SURVEY 5: per-clip stage timings)")
@@ -92,6 +98,7 @@ def add_runtime_arguments(parser):
             if filters_from_args(ns) and not ns.do_sample:        # validates the four flags, HF's wording
                 raise ValueError("--min_p / --typical_p / --epsilon_cutoff / --eta_cutoff need --do_sample (they filter a sampled pick)")
             K, _, _ = check_beam_args(ns)
+            lookup_from_args(ns)
             if bans_from_args(ns) and K > 1:        # validates the three flags, HF's wording
                 raise ValueError(f"--beams {K} cannot be combined with --no_repeat_ngram / --min_new_tokens / --suppress_tokens (the beam pick applies "
                                  f"no logits processor)")
@@ -104,6 +111,34 @@ def add_runtime_arguments(parser):
 
 
 MAX_BEAMS = 8       # generation.MAX_BEAMS
+MAX_LOOKUP = 15     # generation.MAX_LOOKUP
+
+
+def lookup_from_args(ns) -> dict:
+    """--lookup / --lookup_ngram of a parsed command line as generate() arguments ({}: off); ValueError names the flag lookup cannot run with."""
+    from ..generation import check_lookup
+    D = int(getattr(ns, "lookup", 0) or 0)
+    if D == 0:
+        return {}
+    D, n = check_lookup(D, getattr(ns, "lookup_ngram", 2), who="--lookup")
+    if getattr(ns, "do_sample", False):
+        raise ValueError(f"--lookup {D} cannot be combined with --do_sample (a sampled token has no draft to verify)")
+    if int(getattr(ns, "beams", 1)) > 1:
+        raise ValueError(f"--lookup {D} cannot be combined with --beams {ns.beams} (a beam step already runs K rows per prompt)")
+    if getattr(ns, "schedule", "group") == "refill":
+        raise ValueError(f"--lookup {D} cannot be combined with --schedule refill (refill needs per-slot lengths on the host between chunks)")
+    if int(getattr(ns, "samples_per_prompt", 1)) > 1:
+        raise ValueError(f"--lookup {D} cannot be combined with --samples_per_prompt {ns.samples_per_prompt}")
+    rp = getattr(ns, "repetition_penalty", None)
+    if rp is not None and float(rp) != 1.0:
+        raise ValueError(f"--lookup {D} cannot be combined with --repetition_penalty {rp} (the drafts are verified against the plain arg-max)")
+    if bans_from_args(ns):
+        raise ValueError(f"--lookup {D} cannot be combined with --no_repeat_ngram / --min_new_tokens / --suppress_tokens (the drafts are verified against "
+                         f"the plain arg-max)")
+    batch = getattr(ns, "batch", "auto")
+    if batch != "auto" and batch * (1 + D) > MAX_BATCH:
+        raise ValueError(f"--batch {batch} clips x (1 + --lookup {D}) rows exceed the {MAX_BATCH} rows of a decode step")
+    return {"lookup": D, "lookup_ngram": n}
 
 
 def check_beam_args(ns):
@@ -370,7 +405,9 @@ class _Runner:
                                      "load_s": host["load_s"].get(t["path"], 0.0), "upload_ingest_s_group": host["tm_v"].get("upload_ingest_s", 0.0),
                                      "tower_pool_s_group": host["tm_v"].get("tower_pool_s", 0.0), "clips_in_tower_pass": host["n_fresh"],
                                      "prefill_s_group": tm_g.get("prefill_s"), "decode_s_group": tm_g.get("decode_s"),
-                                     "decode_steps_group": tm_g.get("steps")}) + "\n")
+                                     "decode_steps_group": tm_g.get("steps"),
+                                     **({"lookup_steps_group": tm_g["lookup_steps"], "lookup_emitted_group": tm_g["lookup_emitted"]} if "lookup_steps" in tm_g else {})})
+                         + "\n")
 
     def warpers(self):
         """--top_p / --repetition_penalty as generate() arguments: only the ones given, so the rest comes from the model's generation config."""
@@ -401,7 +438,8 @@ class _Runner:
                                            early_stopping=early, **self.warpers()).cpu()
             return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
                                        do_sample=False, max_new_tokens=self.args.max_new_tokens, stop_strings=[s for _, _, _, s in part],
-                                       tokenizer=self.tokenizer, timings=timings, **self.warpers(), **bans_from_args(self.args)).cpu()
+                                       tokenizer=self.tokenizer, timings=timings, **self.warpers(), **bans_from_args(self.args),
+                                       **lookup_from_args(self.args)).cpu()
 
         def record(part, out):
             for row, (j, ids, _, _) in zip(out, part):
@@ -560,6 +598,8 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
         beams = int(getattr(args, "beams", 1))
         if beams > 1:
             args.batch = max(1, args.batch // beams)                   # a clip holds K decode slots: the same number of sequences per group
+        if int(getattr(args, "lookup", 0) or 0) > 0:
+            args.batch = max(1, min(args.batch, MAX_BATCH // (1 + int(args.lookup))))      # a clip holds 1 + D rows of a lookup step
         if rank == 0:
             print(f"[pgv] --batch auto: {args.batch} clips per group ({free_b / 2 ** 30:.0f} GiB free on {device}, shared by {sharers})", flush=True)
     spill = os.path.join(args.output_dir, args.output_name) if getattr(args, "output_dir", None) and getattr(args, "output_name", None) else None

@@ -151,6 +151,34 @@ def check_samples_per_prompt(n, batch: int, do_sample: bool, has_criteria: bool,
     return n
 
 
+MAX_LOOKUP, MAX_LOOKUP_NGRAM = 15, 4           # drafts per step / ngram size (pgv_kv_set_lookup)
+
+
+def check_lookup(lookup, lookup_ngram=2, batch: int = 1, do_sample: bool = False, beams=1, samples_per_prompt=1, repetition_penalty: float = 1.0,
+                 has_bans: bool = False, output_logprobs: bool = False, who: str = "generate()") -> Tuple[int, int]:
+    """Validate generate(lookup=D, lookup_ngram=n) on the host, before any device work; returns (D, n).  D == 0 (or None) is the call without the
+    keyword and combines with everything.  Lookup steps verify drafts against the plain arg-max, so whatever changes the pick is refused."""
+    if lookup is None or (not isinstance(lookup, bool) and lookup == 0):
+        return 0, 0
+    if isinstance(lookup, bool) or int(lookup) != lookup or lookup < 0 or lookup > MAX_LOOKUP:
+        raise ValueError(f"{who}: `lookup`={lookup!r} has to be an integer in [0, {MAX_LOOKUP}]")
+    if isinstance(lookup_ngram, bool) or int(lookup_ngram) != lookup_ngram or lookup_ngram < 1 or lookup_ngram > MAX_LOOKUP_NGRAM:
+        raise ValueError(f"{who}: `lookup_ngram`={lookup_ngram!r} has to be an integer in [1, {MAX_LOOKUP_NGRAM}]")
+    D, n = int(lookup), int(lookup_ngram)
+    refused = [("do_sample", bool(do_sample), "a sampled token has no draft to verify; speculative sampling is not implemented"),
+               ("beams", beams is not None and beams != 1, "a beam step already runs K rows per prompt"),
+               ("samples_per_prompt", samples_per_prompt is not None and samples_per_prompt != 1, "it needs do_sample"),
+               ("repetition_penalty", float(repetition_penalty) != 1.0, "the drafts are verified against the plain arg-max"),
+               ("bans", bool(has_bans), "the drafts are verified against the plain arg-max"),
+               ("output_logprobs", bool(output_logprobs), "lookup steps record no log-probabilities")]
+    for name, bad, why in refused:
+        if bad:
+            raise ValueError(f"{who}: `{name}` cannot be combined with `lookup`={D} ({why})")
+    if batch * (1 + D) > MAX_GROUP:
+        raise ValueError(f"{who}: {batch} prompts x (1 + `lookup`={D}) = {batch * (1 + D)} rows exceed the {MAX_GROUP} of one decode step")
+    return D, n
+
+
 MAX_BEAMS = 8           # beams per prompt (pgv_beam_config.beams)
 HF_BEAM_DEFAULTS = {"length_penalty": 1.0, "early_stopping": False}
 

@@ -22,7 +22,7 @@ import torch.nn as nn
 from .. import _lib
 from ..constants import CLIP_WIDTH
 from ..beam_reference import early_code
-from ..generation import (GenerateBeamsOutput, GenerateLogprobsOutput, check_beams, check_generate_kwargs, check_samples_per_prompt, fork_sources,
+from ..generation import (GenerateBeamsOutput, GenerateLogprobsOutput, check_beams, check_generate_kwargs, check_lookup, check_samples_per_prompt, fork_sources,
                           load_generation_config, resolve_sampling)
 from ..logit_bans import LogitBans, check_bans
 from ..sample_filters import SampleFilters, check_filters
@@ -369,7 +369,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
 
     def prefill(self, seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor], max_seq: int,
                 want_logits: bool = False, want_all_logits: bool = False, append_to=None, logprobs: Optional[bool] = None,
-                capacity: Optional[int] = None, bans=None, eos_id: int = -1):
+                capacity: Optional[int] = None, bans=None, eos_id: int = -1, lookup=None):
         """Run the prompt(s); returns (kv handle, next-token ids [B] int32 on device, logits [B, vocab] or None) -- with want_all_logits a fourth
         entry: the logits of EVERY position, [sum of lengths, vocab] fp32 (what the reference's forward returns, model/video_chatgpt.py:225-226).
         `append_to` = a kv handle this model filled before: the rows continue its sequences (pgv_llm_prefill_append; `max_seq` is ignored).
@@ -377,7 +377,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         recorded too; None leaves the switch as it is.
         `capacity`: the cache is created for max(B, capacity) sequences, so that fork() has slots to grow into (ignored with `append_to`).
         `bans` (logit_bans.LogitBans, checked) with `eos_id`: set the cache's logit bans (set_bans) before the prompt runs, so that the slots' id
-        record holds it -- on the `append_to` path too; None leaves the cache's configuration as it is."""
+        record holds it -- on the `append_to` path too; None leaves the cache's configuration as it is.
+        `lookup` (D, n): set_lookup before the prompt runs, for the same reason; None leaves the setting as it is."""
         B = len(seqs)
         lens = [len(s) for s in seqs]
         feats = video_spatio_temporal_features
@@ -396,6 +397,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             self.set_logprobs(kv, logprobs)
         if bans is not None:
             self.set_bans(kv, bans, eos_id)
+        if lookup is not None:
+            self.set_lookup(kv, *lookup)
         flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
         h_lens = (C.c_int32 * B)(*lens)
         h_pos = (C.c_int32 * B)(*vid_pos)
@@ -415,6 +418,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 self.set_logprobs(kv, False)               # a refused prompt never reaches the caller who would turn the switch off again
             if bans is not None:
                 self.set_bans(kv, None)
+            if lookup is not None:
+                self.set_lookup(kv, 0)
             raise
         if want_all_logits:
             return kv, nxt, logits, all_logits[:, :self.vocab_size]
@@ -662,6 +667,37 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                                                _lib.stream_ptr(self.device_)), "pgv_llm_decode")
         return nxt, logits
 
+    def set_lookup(self, kv, D: int, n: int = 2):
+        """pgv_kv_set_lookup: D drafts per sequence and step by n-gram lookup (`decode_lookup`), up to 1 + D rows per sequence in `decode_rows`; 0
+        turns it off.  Set it before the prompt runs (`prefill(lookup=(D, n))`), so that the cache's id record holds the prompt."""
+        _lib.check(self.ctx.lib.pgv_kv_set_lookup(kv, int(D), int(n)), "pgv_kv_set_lookup")
+
+    def decode_lookup(self, kv, first: Optional[torch.Tensor], steps: int, eos_id: int, budget: Sequence[int]):
+        """pgv_llm_decode_lookup: `steps` prompt-lookup steps from `first` [B] (None: from the cache's current tokens, where the last call
+        stopped); budget [B]: tokens each sequence may still emit.  Returns (tokens int32 [B, steps * (1 + D)] on the device, each row's emitted
+        tokens packed from column 0; counts int32 [steps, B] on the HOST: tokens emitted per step).  The tokens are those of decode_greedy, in
+        fewer passes over the weights."""
+        B = len(budget)
+        D = max(0, int(self.ctx.lib.pgv_kv_lookup(kv)))
+        toks = torch.zeros(B, int(steps) * (1 + D), dtype=torch.int32, device=self.device_)
+        counts = torch.zeros(int(steps), B, dtype=torch.int32, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_llm_decode_lookup(self.ctx.handle, self.handle, kv, first.data_ptr() if first is not None else None, int(steps), int(eos_id),
+                                                      (C.c_int32 * B)(*[int(x) for x in budget]), toks.data_ptr(), counts.data_ptr(),
+                                                      _lib.stream_ptr(self.device_)), "pgv_llm_decode_lookup")
+        return toks, counts.cpu().numpy()
+
+    def decode_rows(self, kv, slots, tokens: torch.Tensor) -> torch.Tensor:
+        """pgv_llm_decode_rows: one pass over the weights for several consecutive positions per sequence.  `slots` lists the sequence of every row
+        (a sequence's rows consecutively), `tokens` [R] int32 the token each row consumes; row j of a sequence runs at position kv_len + j.  Returns
+        the fp32 logits [R, vocab], bit for bit those of consecutive `decode_step` calls fed the same tokens.  Nothing advances."""
+        slots = [int(b) for b in slots]
+        tokens = tokens.to(device=self.device_, dtype=torch.int32).contiguous()
+        assert tokens.numel() == len(slots), "one token per row"
+        logits = torch.empty(len(slots), self.vocab_size, dtype=torch.float32, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_llm_decode_rows(self.ctx.handle, self.handle, kv, (C.c_int32 * len(slots))(*slots), tokens.data_ptr(), len(slots),
+                                                    logits.data_ptr(), _lib.stream_ptr(self.device_)), "pgv_llm_decode_rows")
+        return logits
+
     def decode_greedy(self, kv, first: torch.Tensor, n: int, eos_id: int = -1, repetition_penalty: float = 1.0) -> torch.Tensor:
         """n greedy steps on the device; repetition_penalty != 1: the argmax of the penalised logits (the cache's seen-set)."""
         B = first.shape[0]
@@ -753,7 +789,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  samples_per_prompt: int = 1, beams: int = 1, length_penalty: Optional[float] = None, early_stopping=None,
-                 output_beam_scores: bool = False, bans=None, filters=None, **_unused):
+                 output_beam_scores: bool = False, bans=None, filters=None, lookup: int = 0, lookup_ngram: int = 2, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -817,7 +853,15 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         `self.generation_config` under the same name, else it is neutral; a checkpoint whose generation_config.json carries one of them runs when
         the call passes `filters` (an empty dict takes the file's values) and is refused without it.  Validated on the host before any device
         work, with HF's wording.  Inert with do_sample=False, as top_p is; `beams` > 1 is refused.  With `output_logprobs`, transition_scores are
-        normalised over the final survivors.  None or a neutral record is the call without the keyword, bit for bit."""
+        normalised over the final survivors.  None or a neutral record is the call without the keyword, bit for bit.
+        `lookup=D`, `lookup_ngram=n` (keywords of this package; HF's `prompt_lookup_num_tokens` / `max_matching_ngram_size` name the same two
+        numbers and stay ignored, being inert for a greedy result): prompt-lookup speculative decoding.  Every step drafts up to D tokens per
+        sequence by n-gram lookup in prompt + answer (HF's PromptLookupCandidateGenerator rule, on the device), verifies them in ONE pass over the
+        weights and keeps the longest prefix the model agrees with -- the returned tensor is bit for bit the one of the call without the keyword,
+        in fewer passes when the answer repeats itself or quotes the prompt.  `chunk` counts lookup steps.  Any B with B * (1 + D) <= 64; ragged
+        prompts, `eos_token_id`, `max_new_tokens`, `stopping_criteria`, `stop_strings` and `timings` (which gains `lookup_steps` and
+        `lookup_emitted`: tokens per pass = their quotient) work as without it; `kv_reuse_key` falls back to the full prefill.  Refused with
+        do_sample, beams > 1, samples_per_prompt > 1, a repetition penalty, bans and output_logprobs (generation.check_lookup)."""
         check_generate_kwargs(_unused, self.generation_config, filters_given=filters is not None)
         temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
         if torch.is_tensor(input_ids):
@@ -835,6 +879,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         eos_i = -1 if eos is None else int(eos)
         ban = LogitBans() if bans is None else check_bans(bans, self.vocab_size, eos_i, n_beams)       # None: the call as it has always been
         ban_on = not ban.effective_neutral(eos_i)
+        look_D, look_n = check_lookup(lookup, lookup_ngram, B, bool(do_sample), n_beams, n_samples, rep_pen, ban_on, bool(output_logprobs))
         filt = check_filters(filters, self.generation_config, n_beams)
         filt_on = bool(do_sample) and not filt.neutral
         max_seq = max(len(s) for s in seqs) + max_new_tokens
@@ -868,8 +913,10 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         lpk = {"logprobs": True} if output_logprobs else {}    # the switch is on for this call only (turned off again in the finally below)
         if ban_on:
             lpk.update(bans=ban, eos_id=eos_i)                 # likewise: set before the prompt runs, cleared in the finally below
+        if look_D:
+            lpk.update(lookup=(look_D, look_n))                # likewise
         reused = 0
-        if kv_reuse_key is not None and B == 1 and rep_pen == 1.0 and not ban_on:
+        if kv_reuse_key is not None and B == 1 and rep_pen == 1.0 and not ban_on and not look_D:
             # (and under bans the slot's id record has to be exactly prompt + answer, for the same reason)
             # (under a repetition penalty the slot's seen-set has to be exactly prompt + answer: the surplus steps a kept cache carries past a
             # stop string would stay in it, so such a turn runs the full prefill)
@@ -919,6 +966,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 return any(c(cur, None) for c in criteria)
 
             n_gen = 0
+            look_steps = look_emitted = 0
             _t1 = _t0
             if max_new_tokens >= 1:
                 first = nxt.cpu().numpy()
@@ -928,6 +976,29 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 stop = all(st.done for st in states) or (bool(criteria) and criterion_fires())
                 _t1 = _time.perf_counter()
                 n_gen = 1
+                if look_D:
+                    # chunks of lookup steps: every sequence emits a run of its own length; a sequence the host has finished gets no budget.  The
+                    # cache keeps the current tokens between chunks (first = None), so only the first chunk hands them in
+                    while not stop:
+                        left = [0 if st.done else max_new_tokens - len(st.new) for st in states]
+                        toks, counts = self.decode_lookup(kv, nxt if n_gen == 1 else None, min(chunk, max(left)), eos_i, left)
+                        h = toks.cpu().numpy()
+                        runs = counts.sum(axis=0)
+                        look_steps += int((counts.sum(axis=1) > 0).sum())     # steps behind the last token of the chunk emitted nothing
+                        look_emitted += int(runs.sum())
+                        raw.extend(h[0, :int(runs[0])].tolist())
+                        for b, st in enumerate(states):
+                            if st.done or not runs[b]:
+                                continue
+                            if criteria:
+                                for i in range(int(runs[b])):
+                                    if st.take(h[b, i:i + 1]) or criterion_fires():
+                                        stop = True
+                                        break
+                            else:
+                                st.take(h[b, :int(runs[b])])
+                        stop = stop or all(st.done for st in states)
+                        n_gen = max(2, max(len(st.new) for st in states))
                 while not stop and n_gen < max_new_tokens:
                     n = min(chunk, max_new_tokens - n_gen)
                     if do_sample:
@@ -959,6 +1030,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             if timings is not None:
                 _t2 = _time.perf_counter()
                 timings.update(prefill_s=_t1 - _t0, decode_s=_t2 - _t1, steps=n_gen, batch=B, reused_tokens=reused, samples_per_prompt=n_samples)
+                if look_D:
+                    timings.update(lookup_steps=look_steps, lookup_emitted=look_emitted)
             if kv_reuse_key is not None and B == 1:
                 # the cache holds the prompt and every emitted token that was fed back (all but the last one)
                 self._reuse = (kv_reuse_key, kv, max_seq, list(seqs[0]) + raw[:-1])
@@ -981,6 +1054,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 self.set_bans(kv, None)
             if filt_on:
                 self.set_filters(kv, None)
+            if look_D:
+                self.set_lookup(kv, 0)
 
 
 def _vision_config_from(mm_vision_tower) -> VisionConfig:
