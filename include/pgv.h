@@ -290,7 +290,7 @@ int pgv_kv_peek(pgv_kv *kv, int layer, int which, int slot, int row0, int nrows,
 /* One decode step for all B sequences (the `input_ids.shape[1] == 1` branch, :103): consumes
  * d_last [B] token ids, appends to the KV cache, writes d_logits [B, vocab] and/or d_next [B]. */
 int pgv_llm_decode(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *d_last, float *d_logits, int32_t *d_next, void *stream);
-/* Prompt-lookup speculative decoding (greedy, token-exact) and its building block, the row-wise decode step: several consecutive positions of a
+/* Prompt-lookup speculative decoding (token-exact; greedy and sampled) and its building block, the row-wise decode step: several consecutive positions of a
  * sequence in ONE pass over the weights.  A row is bit for bit the plain step at its position (the decode GEMVs are batch-invariant, the row form
  * of the attention keeps the plain kernels' key order), so a lookup run emits exactly the tokens pgv_llm_decode_greedy emits.
  * pgv_kv_set_lookup(kv, D, n): D drafts per sequence and step, 0 <= D <= 15 (0: off, the default; n is ignored then), ngram size 1 <= n <= 4
@@ -311,12 +311,23 @@ int pgv_llm_decode(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *d_last
  *   pgv_kv_len is true again (one blocking copy) and the cache's current tokens are the last emitted ones (d_first NULL continues from them); cache rows at or beyond pgv_kv_len are
  *   stale: never read, overwritten later.  Eager the first time, then captured graphs of 1 and 8 steps keyed by (D, n).  Refused with PGV_ESTATE and
  *   nothing launched: lookup off, a cache whose record does not cover its sequences (prefilled before pgv_kv_set_lookup, or stepped / forked /
- *   refilled since), a repetition penalty, bans, log-probabilities on, a beam run in flight.  Sampling has no lookup form. */
+ *   refilled since), a repetition penalty, bans, log-probabilities on, a beam run in flight.
+ * pgv_llm_decode_lookup_sample: the same steps for a sampled run, bit for bit the tokens pgv_llm_decode_sample emits from the same uniforms.  d_u is
+ *   fp32 [u_rows][B], B the active width, row i holding the uniforms of the run's i-th new token (copied into the cache's, so u_rows <= max_seq);
+ *   h_u_base [B]: tokens sequence b has emitted before this call in the current generation.  The uniform indexing rule: the row for (sequence b,
+ *   offset j) of a step is picked with u[h_u_base[b] + e + j][b], e = tokens b has emitted so far in this call -- the uniform the plain run picks
+ *   that token with.  The pick is pgv_llm_decode_sample's (temperature, top_k, the cache's top_p and pgv_kv_set_filters values) on the row's logits,
+ *   and a draft is accepted exactly when it equals the pick behind the row in front of it.  Everything else is pgv_llm_decode_lookup's, the
+ *   refusals included; also PGV_EINVAL for temperature <= 0, a null d_u / h_u_base, h_u_base[b] < 0 or h_u_base[b] + h_budget[b] > u_rows.
+ *   Captured graphs are keyed by the pick parameters besides (D, n). */
 int pgv_kv_set_lookup(pgv_kv *kv, int D, int n);
 int pgv_kv_lookup(const pgv_kv *kv);        /* the D in force (0: off) */
 int pgv_llm_decode_rows(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *h_slots, const int32_t *d_tokens, int R, float *d_logits, void *stream);
 int pgv_llm_decode_lookup(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *d_first, int steps, int eos_id, const int32_t *h_budget,
                           int32_t *d_tokens, int32_t *d_counts, void *stream);
+int pgv_llm_decode_lookup_sample(pgv_ctx *ctx, pgv_llm *llm, pgv_kv *kv, const int32_t *d_first, int steps, int eos_id, const int32_t *h_budget,
+                                 const int32_t *h_u_base, float temperature, int top_k, const float *d_u, int u_rows, int32_t *d_tokens,
+                                 int32_t *d_counts, void *stream);
 
 /* n greedy steps without host round trips: step i consumes the previous argmax (step 0 consumes
  * d_first [B]); token of step i of sequence b is written to d_tokens[b * n + i].  A sequence that

@@ -19,9 +19,14 @@ draft + embedding + row-wise arg-max + accept in (c); the draft and the accept k
 scripts/bench_lookup.py --child 8:7 --layers 2 --repeats 1` (their time does not depend on the depth).
 Every (B, D) pair runs in a child process of its own under `--pair-timeout` seconds; a pair that fails or runs out of time ends the run.
 `--plain-only B`: only (a) at width B over 256 steps, one figure -- for A/B runs of the plain path against another build of the library.
+`--sampled`: the same (B, D) table for sampled runs (temperature 0.2, top_k 50: the reference's defaults), every row live, one step per call as
+above: ms per plain sampled step (pgv_llm_decode_sample) at width B, per sampled lookup step (pgv_llm_decode_lookup_sample) and, beside it, per greedy
+lookup step at the same (B, D); the break-even is in tokens beyond the first (sampled lookup / plain sampled at B - 1).  Plain greedy and plain
+sampled steps at width R say what the sampled pick costs over the arg-max at the width the lookup step picks at.  Random weights accept next to no
+draft: tokens per step on real answers stays unmeasured.
 One JSON line on stdout.
 
-    python scripts/bench_lookup.py [--repeats 3] [--layers 32] [--pairs 1:3,1:7,1:15,8:1,8:3,8:7] [--steps 64] [--pair-timeout 240]
+    python scripts/bench_lookup.py [--sampled] [--repeats 3] [--layers 32] [--pairs 1:3,1:7,1:15,8:1,8:3,8:7] [--steps 64] [--pair-timeout 240]
 """
 from __future__ import annotations
 
@@ -40,6 +45,7 @@ from scripts.bench_fork import PROMPT_TOKENS, make_prompt        # noqa: E402
 from scripts.refill_bench import V_ROWS, build_model             # noqa: E402
 
 MAX_SEQ = 2048
+TEMPERATURE, TOP_K = 0.2, 50          # --sampled: the reference's sampling defaults
 
 
 def main(argv=None):
@@ -51,18 +57,19 @@ def main(argv=None):
     ap.add_argument("--pair-timeout", type=int, default=240)
     ap.add_argument("--child", default=None, metavar="B:D", help="measure this pair in this process (what the parent starts per pair)")
     ap.add_argument("--plain-only", type=int, default=0, metavar="B")
+    ap.add_argument("--sampled", action="store_true", help="the sampled table: plain sampled step, sampled lookup step, greedy lookup step (every row live)")
     a = ap.parse_args(argv)
     if not a.child and not a.plain_only:
         rows = []
         for pair in a.pairs.split(","):
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", pair, "--repeats", str(a.repeats), "--layers", str(a.layers), "--steps",
-                                str(a.steps)], stdout=subprocess.PIPE, text=True, timeout=a.pair_timeout)
+                                str(a.steps)] + (["--sampled"] if a.sampled else []), stdout=subprocess.PIPE, text=True, timeout=a.pair_timeout)
             if r.returncode != 0:
                 print(f"[bench_lookup] pair {pair} ended with status {r.returncode}: stopping", file=sys.stderr)
                 return 1
             rows += json.loads(r.stdout.strip().splitlines()[-1])["rows"]
         print(json.dumps({"prompt_tokens": PROMPT_TOKENS, "video_rows": V_ROWS, "layers": a.layers, "repeats": a.repeats, "steps": a.steps, "max_seq": MAX_SEQ,
-                          "rows": rows}))
+                          **({"sampled": {"temperature": TEMPERATURE, "top_k": TOP_K}} if a.sampled else {}), "rows": rows}))
         return 0
     dev = torch.device("cuda", 0)
     m = build_model(a.layers, dev)
@@ -114,25 +121,59 @@ def main(argv=None):
     seed_tok = ids[10]                      # occurs early in the prompt: a 1-gram match with a full continuation behind it
 
     def one_step_calls(kind, B, D):
-        """N calls of ONE step each, a stream synchronise behind every call: plain at width B (kind 'plain'), or a lookup step whose 1 + D rows per
-        slot are all live (kind 'lookup')."""
-        if kind == "plain":
+        """N calls of ONE step each, a stream synchronise behind every call: plain at width B (kind 'plain': greedy, 'plain_s': sampled), or a
+        lookup step whose 1 + D rows per slot are all live (kind 'lookup': greedy, 'lookup_s': sampled)."""
+        g = torch.Generator(device=dev).manual_seed(17)
+        if kind in ("plain", "plain_s"):
             kv, nxt, _ = m.prefill([ids], feats, MAX_SEQ, capacity=B)
             m.fork(kv, [B])
             first = nxt.repeat(B).contiguous()
-            step = lambda: (m.decode_greedy(kv, first, 1), torch.cuda.synchronize())
+            u = torch.rand(1, B, device=dev, generator=g)
+            if kind == "plain":
+                step = lambda: (m.decode_greedy(kv, first, 1), torch.cuda.synchronize())
+            else:
+                step = lambda: (m.decode_sample(kv, first, 1, -1, TEMPERATURE, TOP_K, u), torch.cuda.synchronize())
         else:
             kv, _, _ = m.prefill([ids] * B, feats.expand(B, -1, -1).contiguous(), MAX_SEQ, lookup=(D, 1))
             first = torch.full((B,), seed_tok, dtype=torch.int32, device=dev)
             # ngram size 1: the leftmost occurrence of the token, in the prompt's head, whatever the calls before appended behind the prompt
             assert len(lookup_candidates(ids + [seed_tok] * 3, D, 1)) == D
-            step = lambda: m.decode_lookup(kv, first, 1, -1, [1 + D] * B)
+            u = torch.rand(1 + D, B, device=dev, generator=g)
+            if kind == "lookup":
+                step = lambda: m.decode_lookup(kv, first, 1, -1, [1 + D] * B)
+            else:
+                step = lambda: m.decode_lookup_sample(kv, first, 1, -1, [1 + D] * B, [0] * B, TEMPERATURE, TOP_K, u)
         for _ in range(3):
             step()
         ms = timed(lambda: [step() for _ in range(N)])[0]
-        if kind != "plain":
+        if kind in ("lookup", "lookup_s"):
             m.set_lookup(kv, 0)
         return ms
+
+    if a.sampled:
+        B, D = (int(x) for x in a.child.split(":"))
+        R = B * (1 + D)
+        kinds = [("plain_s", B), ("lookup_s", B), ("lookup", B), ("plain", R), ("plain_s", R)]
+        t = {k: [] for k in kinds}
+        for rnd in range(a.repeats + 1):
+            for k in kinds:
+                ms = one_step_calls(k[0], k[1], D)
+                if rnd > 0:
+                    t[k].append(ms)
+        med = {k: statistics.median(v) for k, v in t.items()}
+        span = lambda k: [round(min(t[k]), 4), round(max(t[k]), 4)]
+        ps, ls, lg, gr, sr = (med[k] for k in kinds)
+        row = {"B": B, "D": D, "rows": R, "plain_sampled_B_1": round(ps, 4), "lookup_sampled_live_1": round(ls, 4), "lookup_greedy_live_1": round(lg, 4),
+               "break_even_live": round(ls / ps - 1, 4), "sampled_over_greedy_lookup": round(ls - lg, 4), "plain_greedy_R_1": round(gr, 4),
+               "plain_sampled_R_1": round(sr, 4), "sampled_over_greedy_plain_R": round(sr - gr, 4),
+               "plain_sampled_B_1_min_max": span(kinds[0]), "lookup_sampled_live_1_min_max": span(kinds[1]), "lookup_greedy_live_1_min_max": span(kinds[2]),
+               "plain_greedy_R_1_min_max": span(kinds[3]), "plain_sampled_R_1_min_max": span(kinds[4])}
+        res["rows"].append(row)
+        res["sampled"] = {"temperature": TEMPERATURE, "top_k": TOP_K}
+        print(f"[bench_lookup] sampled B={B} D={D}, every row live, one step per call: plain sampled@{B} {ps:.4f}, sampled lookup {ls:.4f}, greedy lookup {lg:.4f} "
+              f"ms/step -> break-even +{ls / ps - 1:.3f} tokens; sampled - greedy: lookup {ls - lg:+.4f}, plain@{R} {sr - gr:+.4f}", file=sys.stderr, flush=True)
+        print(json.dumps(res))
+        return 0
 
     for pair in [a.child]:
         B, D = (int(x) for x in pair.split(":"))

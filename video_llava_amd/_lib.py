@@ -148,6 +148,7 @@ PROTOTYPES = {
     "pgv_kv_set_lookup": (_i, [_vp, _i, _i]),
     "pgv_kv_lookup": (_i, [_vp]),
     "pgv_llm_decode_lookup": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp]),
+    "pgv_llm_decode_lookup_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f, _i, _vp, _i, _vp, _vp, _vp]),
     "pgv_llm_decode_rows": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32), _vp, _i, _vp, _vp]),
     "pgv_llm_decode_greedy": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "pgv_llm_sample": (_i, [_vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),

@@ -25,7 +25,7 @@ from .video_conversation import SeparatorStyle, conv_templates, default_conversa
 class VideoChatGPTInterface:
     def __init__(self, args_model_name, args_projection_path, use_asr=False, conv_mode="pg-video-llava", temperature=0.2,
                  max_output_tokens=1024, components=None, do_sample=True, reuse_kv=True, top_p=None, repetition_penalty=None, lookup=0,
-                 lookup_ngram=2) -> None:
+                 lookup_ngram=2, lookup_sample=False) -> None:
         if use_asr:
             raise NotImplementedError("--use_asr needs the WhisperX transcript stack, which is outside this package's hot path")
         self.use_asr = use_asr
@@ -39,8 +39,10 @@ class VideoChatGPTInterface:
         self.top_p, self.repetition_penalty = top_p, repetition_penalty      # None: the checkpoint's generation_config.json, else HF's default
         self.max_new_tokens = max_output_tokens
         self.do_sample = do_sample
-        # prompt-lookup speculative decoding (generate(lookup=D, lookup_ngram=n)): greedy only, refused here as generate() would refuse it
-        self.lookup = check_lookup(lookup, lookup_ngram, 1, bool(do_sample), who="VideoChatGPTInterface")
+        # prompt-lookup speculative decoding (generate(lookup=D, lookup_ngram=n)): greedy, or with lookup_sample the sampled run's own answer;
+        # refused here as generate() would refuse it
+        self.lookup = check_lookup(lookup, lookup_ngram, 1, bool(do_sample), who="VideoChatGPTInterface", lookup_sample=bool(lookup_sample))
+        self.lookup_sample = bool(lookup_sample)
         self.reuse_kv = reuse_kv
         self.frame_size = (image_processor.crop_size["height"], image_processor.crop_size["width"])
         if self.model.get_model().vision_config.use_vid_start_end:
@@ -118,7 +120,8 @@ class VideoChatGPTInterface:
                                              max_new_tokens=min(int(self.max_new_tokens), 1536), stopping_criteria=[stopping_criteria],
                                              kv_reuse_key=self.kv_key, timings=self.last_timings, top_p=self.top_p,
                                              repetition_penalty=self.repetition_penalty,
-                                             **({"lookup": self.lookup[0], "lookup_ngram": self.lookup[1]} if self.lookup[0] else {}))
+                                             **({"lookup": self.lookup[0], "lookup_ngram": self.lookup[1]} if self.lookup[0] else {}),
+                                             **({"lookup_sample": True} if self.lookup_sample else {}))
         n_in = input_ids.shape[1]
         n_diff = int((input_ids.to(output_ids.device) != output_ids[:, :n_in]).sum())
         if n_diff > 0:
@@ -175,10 +178,16 @@ def parse_args(argv=None):
     parser.add_argument("--do_sample", action="store_true", help="the reference's temperature-0.2 sampling (the default unless --lookup is given)")
     parser.add_argument("--lookup", type=int, default=0, metavar="D",
                         help="greedy decoding as prompt-lookup speculative decoding with D <= 15 drafts per step (generate(lookup=D)): the greedy answer, "
-                             "bit for bit, in fewer passes over the weights; not with --do_sample")
+                             "bit for bit, in fewer passes over the weights; not with --do_sample unless --lookup_sample is given")
     parser.add_argument("--lookup_ngram", type=int, default=2, metavar="N", help="--lookup: the largest n-gram matched, 1 .. 4 (HF: max_matching_ngram_size)")
+    parser.add_argument("--lookup_sample", action="store_true",
+                        help="--lookup D --do_sample: lookup steps for the sampled run (generate(lookup_sample=True)): bit for bit the answer of --do_sample alone")
     args = parser.parse_args(argv)
-    if args.lookup and args.do_sample:
+    if args.lookup_sample and not args.do_sample:
+        parser.error("--lookup_sample needs --do_sample (greedy lookup is --lookup D alone)")
+    if args.lookup_sample and not args.lookup:
+        parser.error("--lookup_sample needs --lookup D with D >= 1 drafts per step")
+    if args.lookup and args.do_sample and not args.lookup_sample:
         parser.error(f"--lookup {args.lookup} cannot be combined with --do_sample (a sampled token has no draft to verify)")
     try:
         check_lookup(args.lookup, args.lookup_ngram, 1, who="chat.py")
@@ -192,4 +201,5 @@ if __name__ == "__main__":
     if args.with_grounding:
         raise NotImplementedError("the grounding stack (GroundingDINO / SAM / DEVA / RAM) is outside this package's hot path")
     VideoChatGPTInterface(args_model_name=args.model_name, args_projection_path=args.projection_path, use_asr=args.use_asr,
-                          conv_mode=args.conv_mode, do_sample=not args.lookup, lookup=args.lookup, lookup_ngram=args.lookup_ngram).interact()
+                          conv_mode=args.conv_mode, do_sample=args.lookup_sample or not args.lookup, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
+                          lookup_sample=args.lookup_sample).interact()

@@ -111,7 +111,10 @@ struct pgv_kv {
     // prompt-lookup steps (pgv_llm_decode_lookup): row tokens and row arg-max [lk_rows], drafts and budget per slot [B], the run's step counter and the
     // emit counts [max_seq][B]
     int *lk_tok = nullptr, *lk_t = nullptr, *lk_ndraft = nullptr, *lk_budget = nullptr, *lk_k = nullptr, *lk_counts = nullptr;
+    // their sampled form (pgv_llm_decode_lookup_sample): the uniform of every row [lk_rows], tokens emitted before the call per slot [B] (behind lk_budget)
+    float* lk_u = nullptr; int* lk_ubase = nullptr;
     bool lk_warmed = false;             // a lookup step has run eagerly (code objects loaded) before the first capture
+    bool lk_warmed_s = false;           // likewise a sampled lookup step
     bool lk_valid = false;              // the id record holds exactly the ids behind cache rows [0, len) of every live slot (a plain prefill wrote it, only lookup steps since)
 };
 static DecodeScratch kv_scratch(const pgv_kv* kv) {
@@ -1129,8 +1132,8 @@ static bool graphs_enabled() {
 // launches, so profiling disables the graphs.
 constexpr int kGraphSteps = 8;
 
-static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, hipStream_t s);      // below: one prompt-lookup step
-// lookup: the captured steps are lookup steps (pgv_llm_decode_lookup) with the cache's D and n, which join the key
+static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s);      // below: one prompt-lookup step
+// lookup: the captured steps are lookup steps (pgv_llm_decode_lookup, with AM_SAMPLE pgv_llm_decode_lookup_sample) with the cache's D and n, which join the key
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s, bool lookup = false) {
     const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K, kv->ban_on ? kv->ban_gen : 0, lookup ? kv->lk_D : 0,
                                                 lookup ? kv->lk_n : 0);
@@ -1145,7 +1148,7 @@ static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags
         if (!ctx->cap_stream) PGV_HIP(hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking));
         PGV_HIP(hipStreamBeginCapture(ctx->cap_stream, hipStreamCaptureModeRelaxed));
         int rc = PGV_OK;
-        for (int i = 0; i < steps && rc == PGV_OK; ++i) rc = lookup ? lookup_enqueue(ctx, m, kv, eos, ctx->cap_stream) : decode_enqueue(ctx, m, kv, eos, flags, ctx->cap_stream);
+        for (int i = 0; i < steps && rc == PGV_OK; ++i) rc = lookup ? lookup_enqueue(ctx, m, kv, eos, flags, ctx->cap_stream) : decode_enqueue(ctx, m, kv, eos, flags, ctx->cap_stream);
         hipError_t e = hipStreamEndCapture(ctx->cap_stream, &graph);
         if (rc != PGV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess) { pgv_set_error("decode graph capture failed: %s", hipGetErrorString(e)); return PGV_EHIP; }
@@ -1458,7 +1461,7 @@ extern "C" int pgv_kv_set_lookup(pgv_kv* kv, int D, int n) {
         size_t off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
         const ScratchLayout so = scratch_layout(kv->llm, R, take);
-        const size_t o_ints = take((4 * R + 2 * B + 1 + B * (size_t)kv->max_seq) * 4);
+        const size_t o_ints = take((5 * R + 3 * B + 1 + B * (size_t)kv->max_seq) * 4);
         char* b = nullptr;
         hipError_t e = hipMalloc((void**)&b, off);
         if (e != hipSuccess) { pgv_set_error("pgv_kv_set_lookup: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
@@ -1467,7 +1470,8 @@ extern "C" int pgv_kv_set_lookup(pgv_kv* kv, int D, int n) {
         kv->lk = scratch_bind(b, so, kv->llm);
         int* ints = (int*)(b + o_ints);
         kv->lk_slot = ints; kv->lk_j = ints + R; kv->lk_tok = ints + 2 * R; kv->lk_t = ints + 3 * R;
-        kv->lk_ndraft = ints + 4 * R; kv->lk_budget = kv->lk_ndraft + B; kv->lk_k = kv->lk_budget + B; kv->lk_counts = kv->lk_k + 1;
+        kv->lk_u = (float*)(ints + 4 * R);
+        kv->lk_ndraft = ints + 5 * R; kv->lk_budget = kv->lk_ndraft + B; kv->lk_ubase = kv->lk_budget + B; kv->lk_k = kv->lk_ubase + B; kv->lk_counts = kv->lk_k + 1;
         kv->lk_blob = b; kv->lk_rows = (int)R;
     }
     kv->lk_D = D; kv->lk_n = n;
@@ -1476,64 +1480,87 @@ extern "C" int pgv_kv_set_lookup(pgv_kv* kv, int D, int n) {
 
 extern "C" int pgv_kv_lookup(const pgv_kv* kv) { return kv ? kv->lk_D : -1; }
 
-// One prompt-lookup step over the live slots: draft -> row-wise trunk -> lm_head with candidates -> row-wise arg-max -> accept
-static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, hipStream_t s) {
+// One prompt-lookup step over the live slots: draft -> row-wise trunk -> lm_head -> row-wise pick -> accept.  The pick is the arg-max of the lm_head
+// candidates, or with AM_SAMPLE the sampled pick with kv->run over the full logits of every row, fed the uniform the draft kernel gathered for the
+// row (pgv.h: u[u_base + step + j][b]).  Either pick writes the row's token and nothing else: the accept kernel keeps the slots' state.
+static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s) {
     const int B = kv->active, R = B * (1 + kv->lk_D), V = m->cfg.vocab;
+    const bool sampled = flags & AM_SAMPLE;
     LookupArgs a;
     a.D = kv->lk_D; a.n = kv->lk_n; a.eos = eos; a.max_seq = kv->max_seq;
     a.pos = kv->d_pos; a.cur = kv->d_cur; a.step = kv->d_step; a.done = kv->d_done; a.hist = kv->d_hist; a.hist_stride = kv->max_seq;
     a.rec = kv->ban_ids; a.budget = kv->lk_budget;
     a.tok = kv->lk_tok; a.row_slot = kv->lk_slot; a.row_j = kv->lk_j; a.n_draft = kv->lk_ndraft; a.t = kv->lk_t;
     a.counts = kv->lk_counts; a.counts_stride = kv->B; a.k = kv->lk_k;
+    if (sampled) {
+        a.u = kv->d_u; a.u_stride = B; a.u_base = kv->lk_ubase; a.u_row = kv->lk_u;
+        // a plain sampled step marks the token it returns in the slot's seen-set in the instantiations that carry the set (pgv_launch_sample)
+        if (kv->run.filtered() || kv->run.top_p < 1.f) { a.seen = kv->d_seen; a.seen_words = kv->seen_words; a.vocab = V; }
+    }
     pgv_prof_begin(ctx, 6, s);
     PGV_TRY(pgv_launch_lookup_draft(a, B, s));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     RowMap rm; rm.d_slot = kv->lk_slot; rm.d_j = kv->lk_j;
     int nparts = 0;
     PGV_TRY(decode_trunk(ctx, m, kv, kv->lk, kv->lk_tok, R, rm, s, &nparts));
-    PGV_TRY(lm_head_rows(ctx, m, kv->lk, R, true, s, nparts));
+    PGV_TRY(lm_head_rows(ctx, m, kv->lk, R, !sampled, s, nparts));
     pgv_prof_begin(ctx, 6, s);
-    PGV_TRY(pgv_launch_argmax_parts(kv->lk.amax_val, kv->lk.amax_idx, (V + 15) / 16, kv->lk.amax_ts, V, R, PickState{kv->lk_t}, s));
+    if (sampled) PGV_TRY(pgv_launch_sample(kv->lk.logits, V, R, kv->run, kv->lk_u, R, false, PickState{kv->lk_t}, s));
+    else PGV_TRY(pgv_launch_argmax_parts(kv->lk.amax_val, kv->lk.amax_idx, (V + 15) / 16, kv->lk.amax_ts, V, R, PickState{kv->lk_t}, s));
     PGV_TRY(pgv_launch_lookup_accept(a, B, s));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     return PGV_OK;
 }
 
-extern "C" int pgv_llm_decode_lookup(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int steps, int eos_id, const int32_t* h_budget,
-                                     int32_t* d_tokens, int32_t* d_counts, void* stream) {
-    PGV_CHECK(ctx && h_budget && d_tokens && d_counts, "pgv_llm_decode_lookup: null argument");
-    PGV_TRY(check_decode(m, kv, 0, "pgv_llm_decode_lookup"));
+// what both lookup entries refuse, before any device work
+static int check_lookup_run(pgv_llm* m, pgv_kv* kv, int steps, int eos_id, const int32_t* h_budget, const char* who, const char* verifies) {
+    PGV_TRY(check_decode(m, kv, 0, who));
     const int B = kv->active, D = kv->lk_D, W = 1 + D;
-    if (D < 1) { pgv_set_error("pgv_llm_decode_lookup: lookup is off on this cache (pgv_kv_set_lookup)"); return PGV_ESTATE; }
-    if (!kv->lk_valid) { pgv_set_error("pgv_llm_decode_lookup: the cache's id record does not cover its sequences: set pgv_kv_set_lookup before pgv_llm_prefill and step with pgv_llm_decode_lookup only"); return PGV_ESTATE; }
-    if (kv->warpers.penalty != 1.f) { pgv_set_error("pgv_llm_decode_lookup: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify the plain arg-max"); return PGV_ESTATE; }
-    if (kv->ban_on) { pgv_set_error("pgv_llm_decode_lookup: logit bans are set on this cache (pgv_kv_set_bans); lookup steps verify the plain arg-max"); return PGV_ESTATE; }
-    if (kv->lp_on) { pgv_set_error("pgv_llm_decode_lookup: log-probabilities are on (pgv_kv_set_logprobs); lookup steps record none"); return PGV_ESTATE; }
-    if (kv->bm_K > 0) { pgv_set_error("pgv_llm_decode_lookup: a beam run is in flight on this cache"); return PGV_ESTATE; }
-    PGV_CHECK(B * W <= kv->lk_rows && B * W <= kMaxBatch, "pgv_llm_decode_lookup: %d sequences x %d rows exceed the %d rows of a step", B, W, kv->lk_rows < kMaxBatch ? kv->lk_rows : kMaxBatch);
-    PGV_CHECK(steps >= 1 && steps <= kv->max_seq, "pgv_llm_decode_lookup: %d steps outside [1,%d]", steps, kv->max_seq);
-    PGV_CHECK(eos_id < m->cfg.vocab, "pgv_llm_decode_lookup: eos_id %d outside the vocabulary (%d)", eos_id, m->cfg.vocab);
+    if (D < 1) { pgv_set_error("%s: lookup is off on this cache (pgv_kv_set_lookup)", who); return PGV_ESTATE; }
+    if (!kv->lk_valid) { pgv_set_error("%s: the cache's id record does not cover its sequences: set pgv_kv_set_lookup before pgv_llm_prefill and step with pgv_llm_decode_lookup only", who); return PGV_ESTATE; }
+    if (kv->warpers.penalty != 1.f) { pgv_set_error("%s: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
+    if (kv->ban_on) { pgv_set_error("%s: logit bans are set on this cache (pgv_kv_set_bans); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
+    if (kv->lp_on) { pgv_set_error("%s: log-probabilities are on (pgv_kv_set_logprobs); lookup steps record none", who); return PGV_ESTATE; }
+    if (kv->bm_K > 0) { pgv_set_error("%s: a beam run is in flight on this cache", who); return PGV_ESTATE; }
+    PGV_CHECK(B * W <= kv->lk_rows && B * W <= kMaxBatch, "%s: %d sequences x %d rows exceed the %d rows of a step", who, B, W, kv->lk_rows < kMaxBatch ? kv->lk_rows : kMaxBatch);
+    PGV_CHECK(steps >= 1 && steps <= kv->max_seq, "%s: %d steps outside [1,%d]", who, steps, kv->max_seq);
+    PGV_CHECK(eos_id < m->cfg.vocab, "%s: eos_id %d outside the vocabulary (%d)", who, eos_id, m->cfg.vocab);
     for (int b = 0; b < B; ++b)
-        PGV_CHECK(h_budget[b] >= 0 && kv->h_len[b] + h_budget[b] <= kv->max_seq, "pgv_llm_decode_lookup: sequence %d would grow to %d tokens (cache holds %d)", b,
+        PGV_CHECK(h_budget[b] >= 0 && kv->h_len[b] + h_budget[b] <= kv->max_seq, "%s: sequence %d would grow to %d tokens (cache holds %d)", who, b,
                   kv->h_len[b] + h_budget[b], kv->max_seq);
-    hipStream_t s = (hipStream_t)stream;
+    return PGV_OK;
+}
+
+// `steps` lookup steps behind the checks.  run null: the greedy form; else the sampled one, picking with *run from the uniforms d_u [u_rows][B]
+// (copied into the cache's) at the rows h_u_base counts from.
+static int lookup_run(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int steps, int eos_id, const int32_t* h_budget, const int32_t* h_u_base,
+                      const PickParams* run, const float* d_u, int u_rows, int32_t* d_tokens, int32_t* d_counts, hipStream_t s) {
+    const int B = kv->active, W = 1 + kv->lk_D;
+    const int flags = AM_INC_POS | AM_RECORD | (run ? AM_SAMPLE : 0);
     PGV_HIP(hipStreamSynchronize(s));             // an earlier call's copy of the staging may still be in flight
     kv->lk_stage.assign(h_budget, h_budget + B);
+    if (run) kv->lk_stage.insert(kv->lk_stage.end(), h_u_base, h_u_base + B);
     PGV_HIP(hipMemcpyAsync(kv->lk_budget, kv->lk_stage.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    if (run) {
+        PGV_HIP(hipMemcpyAsync(kv->lk_ubase, kv->lk_stage.data() + B, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)u_rows * B * 4, hipMemcpyDeviceToDevice, s));      // u_rows <= max_seq (checked by the entry)
+        kv->run = *run;
+    }
     if (d_first && d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));      // null: the cache's current tokens
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
     PGV_HIP(hipMemsetAsync(kv->lk_k, 0, 4, s));
     PGV_HIP(hipMemsetAsync(kv->lk.dattn_ticket, 0, (size_t)B * W * m->cfg.heads * sizeof(unsigned), s));
+    bool& warmed = run ? kv->lk_warmed_s : kv->lk_warmed;
     for (int n = steps; n > 0;) {
         int k = 1;
-        if (ctx->prof || !graphs_enabled() || !kv->lk_warmed) {
-            kv->lk_warmed = true;
-            PGV_TRY(lookup_enqueue(ctx, m, kv, eos_id, s));
+        if (ctx->prof || !graphs_enabled() || !warmed) {
+            warmed = true;
+            PGV_TRY(lookup_enqueue(ctx, m, kv, eos_id, flags, s));
         } else if (n >= kGraphSteps) {
             k = kGraphSteps;
-            PGV_TRY(decode_graph(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD, 1, kGraphSteps, s, true));
+            PGV_TRY(decode_graph(ctx, m, kv, eos_id, flags, 1, kGraphSteps, s, true));
         } else {
-            PGV_TRY(decode_graph(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD, 0, 1, s, true));
+            PGV_TRY(decode_graph(ctx, m, kv, eos_id, flags, 0, 1, s, true));
         }
         n -= k;
     }
@@ -1546,6 +1573,28 @@ extern "C" int pgv_llm_decode_lookup(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_HIP(hipStreamSynchronize(s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
+}
+
+extern "C" int pgv_llm_decode_lookup(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int steps, int eos_id, const int32_t* h_budget,
+                                     int32_t* d_tokens, int32_t* d_counts, void* stream) {
+    PGV_CHECK(ctx && h_budget && d_tokens && d_counts, "pgv_llm_decode_lookup: null argument");
+    PGV_TRY(check_lookup_run(m, kv, steps, eos_id, h_budget, "pgv_llm_decode_lookup", "the plain arg-max"));
+    return lookup_run(ctx, m, kv, d_first, steps, eos_id, h_budget, nullptr, nullptr, nullptr, 0, d_tokens, d_counts, (hipStream_t)stream);
+}
+
+extern "C" int pgv_llm_decode_lookup_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int steps, int eos_id, const int32_t* h_budget,
+                                            const int32_t* h_u_base, float temperature, int top_k, const float* d_u, int u_rows, int32_t* d_tokens,
+                                            int32_t* d_counts, void* stream) {
+    const char* who = "pgv_llm_decode_lookup_sample";
+    PGV_CHECK(ctx && h_budget && h_u_base && d_u && d_tokens && d_counts, "%s: null argument", who);
+    PGV_CHECK(temperature > 0.f, "%s: temperature must be positive (got %g)", who, (double)temperature);
+    PGV_TRY(check_lookup_run(m, kv, steps, eos_id, h_budget, who, "the plain pick without them"));
+    PGV_CHECK(u_rows >= 1 && u_rows <= kv->max_seq, "%s: %d rows of uniforms outside [1,%d]", who, u_rows, kv->max_seq);
+    for (int b = 0; b < kv->active; ++b)
+        PGV_CHECK(h_u_base[b] >= 0 && (long long)h_u_base[b] + h_budget[b] <= u_rows, "%s: sequence %d would read uniform rows [%d,%lld) of %d", who, b, h_u_base[b],
+                  (long long)h_u_base[b] + h_budget[b], u_rows);
+    const PickParams p = kv_sampled(kv, temperature, top_k);
+    return lookup_run(ctx, m, kv, d_first, steps, eos_id, h_budget, h_u_base, &p, d_u, u_rows, d_tokens, d_counts, (hipStream_t)stream);
 }
 
 extern "C" int pgv_llm_decode_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_slots, const int32_t* d_tokens, int R, float* d_logits, void* stream) {

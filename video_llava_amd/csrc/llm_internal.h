@@ -89,7 +89,7 @@ int pgv_launch_decode_attn(pgv_ctx* ctx, int dtype, const void* qkv, const int* 
 int pgv_launch_decode_attn_rows(pgv_ctx* ctx, int dtype, const void* qkv, const int* pos, const int* row_slot, const int* row_j, const void* rope, void* Kc,
                                 void* Vc, void* out, int R, int H, int heads, int max_seq, double bytes, hipStream_t s, float* part, unsigned* ticket,
                                 int split_force);
-// lookup.hip: the draft and accept kernels of a prompt-lookup step (pgv.h: pgv_llm_decode_lookup).  Slot b owns rows b * (1 + D) + j, j = 0 .. D.
+// lookup.hip: the draft and accept kernels of a prompt-lookup step (pgv.h: pgv_llm_decode_lookup, pgv_llm_decode_lookup_sample).  Slot b owns rows b * (1 + D) + j, j = 0 .. D.
 struct LookupArgs {
     int D = 0, n = 0, eos = -1, max_seq = 0;
     int *pos = nullptr, *cur = nullptr, *step = nullptr, *done = nullptr, *hist = nullptr; int hist_stride = 0;   // the cache's pick state (PickState)
@@ -98,6 +98,11 @@ struct LookupArgs {
     int *tok = nullptr, *row_slot = nullptr, *row_j = nullptr, *n_draft = nullptr;      // rows: token, slot (-1: no row), offset; drafts per slot
     const int* t = nullptr;                   // [rows] the arg-max behind every row
     int *counts = nullptr, counts_stride = 0, *k = nullptr;                            // emit counts [steps][counts_stride], the run's step counter
+    // the sampled form (null u: the greedy form, which reads and writes none of these).  Row (b, j) is picked with the uniform the plain run uses for
+    // that token, u[(u_base[b] + step[b] + j) * u_stride + b]: the draft kernel gathers it into u_row [rows] (0 for a row that is none).
+    const float* u = nullptr; int u_stride = 0; const int* u_base = nullptr; float* u_row = nullptr;
+    // seen-set bitmaps [slots][seen_words] (null: not kept): the accept kernel marks every emitted token below `vocab`, as a plain sampled pick does
+    unsigned* seen = nullptr; int seen_words = 0, vocab = 0;
 };
 int pgv_launch_lookup_draft(const LookupArgs& a, int B, hipStream_t s);
 int pgv_launch_lookup_accept(const LookupArgs& a, int B, hipStream_t s);

@@ -1,7 +1,8 @@
 // Prompt-lookup speculative decoding, the two small kernels around the row-wise decode step (llm.hip: pgv_llm_decode_lookup): drafting by n-gram
-// lookup in the slot's own ids, and acceptance of the longest draft prefix the model agrees with.  Greedy only: a lookup step emits exactly the
-// tokens consecutive plain steps would.  The drafting rule is HF's PromptLookupCandidateGenerator.get_candidates (transformers/generation/
-// candidate_generator.py); video_llava_amd/lookup_reference.py states it and the step trace in numpy, and the kernels reproduce those.
+// lookup in the slot's own ids, and acceptance of the longest draft prefix the model agrees with.  A lookup step emits exactly the tokens
+// consecutive plain steps would: the rows are picked by arg-max, or (sampled form) each with the uniform the plain run draws for its token.
+// The drafting rule is HF's PromptLookupCandidateGenerator.get_candidates (transformers/generation/candidate_generator.py);
+// video_llava_amd/lookup_reference.py states it and the step trace in numpy, and the kernels reproduce those.
 #include "llm_internal.h"
 
 namespace {
@@ -54,11 +55,13 @@ __global__ __launch_bounds__(256) void lookup_draft_kernel(LookupArgs a) {
         a.row_slot[r] = row ? b : -1;
         a.row_j[r] = tid;
         a.tok[r] = (row && tid > 0) ? rec[start + tid - 1] : cur;
+        // sampled: a live row j has step + j < budget (nd <= left - 1), so its uniform lies inside the rows the entry checked
+        if (a.u) a.u_row[r] = row ? a.u[(size_t)(a.u_base[b] + a.step[b] + tid) * a.u_stride + b] : 0.f;
     }
 }
 
-// One thread per slot b behind the row-wise arg-max t[r].  a = the leading drafts j = 1 .. n_draft with draft_j == t[row j - 1]; the slot emits
-// t[row 0 .. a] with the bookkeeping of a recording pick, token by token: history and step++, an eos raises done and ends the emission, the
+// One thread per slot b behind the row-wise pick t[r] (arg-max, or the sampled pick).  a = the leading drafts j = 1 .. n_draft with
+// draft_j == t[row j - 1]; the slot emits t[row 0 .. a] with the bookkeeping of a recording pick, token by token: history and step++, an eos raises done and ends the emission, the
 // budget ends it too.  pos += emitted, cur = the last emitted token, the emitted tokens go into the id record behind cur, counts[k][b] = emitted
 // with k the run's step counter (advanced here).  Cache rows at or beyond the new pos are stale: never read, overwritten by later steps.
 __global__ __launch_bounds__(64) void lookup_accept_kernel(LookupArgs a, int B) {
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(64) void lookup_accept_kernel(LookupArgs a, int B) 
             last = a.t[b * W + j];
             a.hist[(size_t)b * a.hist_stride + st++] = last;
             if (pos + 1 + j < a.max_seq) a.rec[(size_t)b * a.max_seq + pos + 1 + j] = last;
+            if (a.seen && last >= 0 && last < a.vocab) a.seen[(size_t)b * a.seen_words + (last >> 5)] |= 1u << (last & 31);
             ++emitted;
             if (a.eos >= 0 && last == a.eos) { a.done[b] = 1; break; }
         }

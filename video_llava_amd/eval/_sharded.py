@@ -74,9 +74,13 @@ def add_runtime_arguments(parser):
     parser.add_argument("--lookup", type=int, default=0, metavar="D",
                         help=f"greedy decoding as prompt-lookup speculative decoding with D <= {MAX_LOOKUP} drafts per sequence and step (generate(lookup=D)): the "
                              "greedy answers, bit for bit, in fewer passes over the weights when answers repeat themselves or quote the prompt; --schedule group "
-                             "only, not with --do_sample, --beams, --samples_per_prompt, --repetition_penalty or the ban flags; a group holds --batch clips x "
+                             "only, not with --do_sample (unless --lookup_sample), --beams, --samples_per_prompt, --repetition_penalty or the ban flags; a group holds --batch clips x "
                              "(1 + D) rows (--batch auto counts 1 + D rows per clip); --timings lines gain lookup_steps_group / lookup_emitted_group")
     parser.add_argument("--lookup_ngram", type=int, default=2, metavar="N", help="--lookup: the largest n-gram matched, 1 .. 4 (HF: max_matching_ngram_size)")
+    parser.add_argument("--lookup_sample", action="store_true",
+                        help="--lookup D --do_sample: lookup steps for the sampled run (generate(lookup_sample=True)) -- every draft is verified against the "
+                             "pick from the uniform the plain run draws for that token, so the answers are bit for bit those of --do_sample alone; lifts "
+                             "only the --do_sample refusal of --lookup")
     parser.add_argument("--timings", default=None, metavar="OUT.jsonl",
                         help="append one JSON line per answered task (rank-local file `OUT.jsonl.rank<r>` when world > 1): frame load, upload + ingest, "
                              "tower + pool, prefill, decode seconds, generated tokens, group size, feature-cache hit (SURVEY 5: per-clip stage timings)")
@@ -115,13 +119,18 @@ MAX_LOOKUP = 15     # generation.MAX_LOOKUP
 
 
 def lookup_from_args(ns) -> dict:
-    """--lookup / --lookup_ngram of a parsed command line as generate() arguments ({}: off); ValueError names the flag lookup cannot run with."""
+    """--lookup / --lookup_ngram / --lookup_sample of a parsed command line as generate() arguments ({}: off); ValueError names the flag lookup cannot run with."""
     from ..generation import check_lookup
     D = int(getattr(ns, "lookup", 0) or 0)
+    sampled = bool(getattr(ns, "lookup_sample", False))
+    if sampled and not getattr(ns, "do_sample", False):
+        raise ValueError("--lookup_sample needs --do_sample (greedy lookup is --lookup D alone)")
+    if sampled and D == 0:
+        raise ValueError("--lookup_sample needs --lookup D with D >= 1 drafts per step")
     if D == 0:
         return {}
     D, n = check_lookup(D, getattr(ns, "lookup_ngram", 2), who="--lookup")
-    if getattr(ns, "do_sample", False):
+    if getattr(ns, "do_sample", False) and not sampled:
         raise ValueError(f"--lookup {D} cannot be combined with --do_sample (a sampled token has no draft to verify)")
     if int(getattr(ns, "beams", 1)) > 1:
         raise ValueError(f"--lookup {D} cannot be combined with --beams {ns.beams} (a beam step already runs K rows per prompt)")
@@ -138,7 +147,7 @@ def lookup_from_args(ns) -> dict:
     batch = getattr(ns, "batch", "auto")
     if batch != "auto" and batch * (1 + D) > MAX_BATCH:
         raise ValueError(f"--batch {batch} clips x (1 + --lookup {D}) rows exceed the {MAX_BATCH} rows of a decode step")
-    return {"lookup": D, "lookup_ngram": n}
+    return {"lookup": D, "lookup_ngram": n, **({"lookup_sample": True} if sampled else {})}
 
 
 def check_beam_args(ns):
@@ -558,7 +567,8 @@ class _Runner:
                     raise clips[t["path"]]
                 new, stop = video_chatgpt_infer_ids(None, t["question"], self.args.conv_mode, self.model, self.vision_tower, self.tokenizer,
                                                     self.image_processor, self.video_token_len, None, max_new_tokens=self.args.max_new_tokens,
-                                                    features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args), **filters_from_args(self.args))
+                                                    features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args), **filters_from_args(self.args),
+                                                    **lookup_from_args(self.args))      # --lookup D --lookup_sample: the same ids in fewer passes
                 self.stop_strs[idx] = stop
                 self.record(toks, lens, j, new, strip_eos=False)       # the ids end where the reference's criterion stopped them
             except Exception as e:                                     # noqa: BLE001

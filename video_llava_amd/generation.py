@@ -155,21 +155,30 @@ MAX_LOOKUP, MAX_LOOKUP_NGRAM = 15, 4           # drafts per step / ngram size (p
 
 
 def check_lookup(lookup, lookup_ngram=2, batch: int = 1, do_sample: bool = False, beams=1, samples_per_prompt=1, repetition_penalty: float = 1.0,
-                 has_bans: bool = False, output_logprobs: bool = False, who: str = "generate()") -> Tuple[int, int]:
-    """Validate generate(lookup=D, lookup_ngram=n) on the host, before any device work; returns (D, n).  D == 0 (or None) is the call without the
-    keyword and combines with everything.  Lookup steps verify drafts against the plain arg-max, so whatever changes the pick is refused."""
+                 has_bans: bool = False, output_logprobs: bool = False, who: str = "generate()", lookup_sample: bool = False) -> Tuple[int, int]:
+    """Validate generate(lookup=D, lookup_ngram=n, lookup_sample=) on the host, before any device work; returns (D, n).  D == 0 (or None) is the
+    call without the keyword and combines with everything.  Lookup steps verify drafts against the plain pick -- the arg-max, or with
+    `lookup_sample` the sampled pick from the uniform the plain run uses for that token -- so whatever else changes the pick is refused.
+    `lookup_sample` needs do_sample and a D >= 1; without it do_sample is refused as before."""
+    if lookup_sample and not do_sample:
+        raise ValueError(f"{who}: `lookup_sample` needs `do_sample` (the greedy form is `lookup` alone)")
     if lookup is None or (not isinstance(lookup, bool) and lookup == 0):
+        if lookup_sample:
+            raise ValueError(f"{who}: `lookup_sample` needs `lookup` >= 1 drafts per step")
         return 0, 0
     if isinstance(lookup, bool) or int(lookup) != lookup or lookup < 0 or lookup > MAX_LOOKUP:
         raise ValueError(f"{who}: `lookup`={lookup!r} has to be an integer in [0, {MAX_LOOKUP}]")
     if isinstance(lookup_ngram, bool) or int(lookup_ngram) != lookup_ngram or lookup_ngram < 1 or lookup_ngram > MAX_LOOKUP_NGRAM:
         raise ValueError(f"{who}: `lookup_ngram`={lookup_ngram!r} has to be an integer in [1, {MAX_LOOKUP_NGRAM}]")
     D, n = int(lookup), int(lookup_ngram)
-    refused = [("do_sample", bool(do_sample), "a sampled token has no draft to verify; speculative sampling is not implemented"),
+    verified = "the plain pick without it" if lookup_sample else "the plain arg-max"
+    refused = [("do_sample", bool(do_sample) and not lookup_sample,
+                "a sampled token has no draft to verify; speculative sampling is not implemented -- `lookup_sample`=True verifies against the run's own uniforms"),
                ("beams", beams is not None and beams != 1, "a beam step already runs K rows per prompt"),
-               ("samples_per_prompt", samples_per_prompt is not None and samples_per_prompt != 1, "it needs do_sample"),
-               ("repetition_penalty", float(repetition_penalty) != 1.0, "the drafts are verified against the plain arg-max"),
-               ("bans", bool(has_bans), "the drafts are verified against the plain arg-max"),
+               ("samples_per_prompt", samples_per_prompt is not None and samples_per_prompt != 1,
+                "the samples share no uniforms with a plain run" if lookup_sample else "it needs do_sample"),
+               ("repetition_penalty", float(repetition_penalty) != 1.0, f"the drafts are verified against {verified}"),
+               ("bans", bool(has_bans), f"the drafts are verified against {verified}"),
                ("output_logprobs", bool(output_logprobs), "lookup steps record no log-probabilities")]
     for name, bad, why in refused:
         if bad:

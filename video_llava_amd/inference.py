@@ -173,33 +173,38 @@ def video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tow
 
 def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                         transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, bans=None, filters=None, lookup=0,
-                        lookup_ngram=2):
+                        lookup_ngram=2, lookup_sample=False):
     """Answer `question` about one clip.  Same positional signature and defaults as the reference
     (video_chatgpt/inference.py:47; do_sample=True, temperature=0.2, max_new_tokens=1024 at :109-111); pass
     do_sample=False for deterministic greedy decoding.  `features`: pooled features computed earlier (skips the tower).  `bans`
     (logit_bans.LogitBans or a dict of its fields): HF's -inf processors -- no_repeat_ngram, bad_words, suppress, begin_suppress, min_length,
     min_new_tokens -- passed to model.generate(bans=) as it is.  `filters` (sample_filters.SampleFilters or a dict of its fields): HF's sampling warpers
     behind top_p -- min_p, typical_p, epsilon_cutoff, eta_cutoff -- passed to model.generate(filters=) as it is.  `lookup` = D > 0 (needs
-    do_sample=False): prompt-lookup speculative decoding, model.generate(lookup=D, lookup_ngram=n) -- the same answer in fewer passes over the weights."""
+    do_sample=False): prompt-lookup speculative decoding, model.generate(lookup=D, lookup_ngram=n) -- the same answer in fewer passes over the weights.
+    `lookup_sample=True` (with lookup = D > 0 and do_sample=True): the sampled form, model.generate(lookup_sample=True) -- bit for bit the sampled
+    answer of the call without the two keywords for the same generator state."""
     new_ids, stop_str = video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                                 transcript, do_sample, temperature, max_new_tokens, features, **({} if bans is None else {"bans": bans}),
                                                 **({} if filters is None else {"filters": filters}),
-                                                **({} if not lookup else {"lookup": lookup, "lookup_ngram": lookup_ngram}))
+                                                **({} if not lookup else {"lookup": lookup, "lookup_ngram": lookup_ngram}),
+                                                **({} if not lookup_sample else {"lookup_sample": True}))
     outputs = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0]
     return outputs.strip().rstrip(stop_str).strip()
 
 
 def video_chatgpt_infer_logprobs(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                  transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, bans=None, filters=None, lookup=0,
-                                 lookup_ngram=2, **generate_kwargs):
+                                 lookup_ngram=2, lookup_sample=False, **generate_kwargs):
     """`video_chatgpt_infer` that also says how probable the answer it produced was (model.generate(output_logprobs=True): recorded on the device
     at pick time, no second prefill).  Returns a dict: "text" (what video_chatgpt_infer returns), "ids" (the generated token ids),
     "token_logprobs" (per id, the model's own log-probability: HF's compute_transition_scores on the raw logits -- what video_chatgpt_score
     gives for the same ids), "transition_scores" (per id, the log of the probability the pick used, after repetition penalty / temperature /
-    top-k / top-p) and "logprob" (the fp64 sum of token_logprobs).  `lookup` keeps the signature of
-    video_chatgpt_infer; lookup steps record no log-probabilities, so anything but 0 is refused by generate()."""
+    top-k / top-p) and "logprob" (the fp64 sum of token_logprobs).  `lookup` / `lookup_sample` keep the signature of
+    video_chatgpt_infer; lookup steps record no log-probabilities, so anything but 0 / False is refused by generate()."""
     if lookup:
         generate_kwargs = dict(generate_kwargs, lookup=lookup, lookup_ngram=lookup_ngram)
+    if lookup_sample:
+        generate_kwargs = dict(generate_kwargs, lookup_sample=True)
     out, output_ids, n_in, stop_str = _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                                       transcript, do_sample, temperature, max_new_tokens, features,
                                                       dict(generate_kwargs, output_logprobs=True, **({} if bans is None else {"bans": bans}),

@@ -686,6 +686,26 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                                                       _lib.stream_ptr(self.device_)), "pgv_llm_decode_lookup")
         return toks, counts.cpu().numpy()
 
+    def decode_lookup_sample(self, kv, first: Optional[torch.Tensor], steps: int, eos_id: int, budget: Sequence[int], u_base: Sequence[int],
+                             temperature: float, top_k: int, u: torch.Tensor):
+        """pgv_llm_decode_lookup_sample: `decode_lookup` for a sampled run.  u [rows, B]: the uniforms of the whole run, row i those of its i-th new
+        token; u_base [B]: tokens each sequence has emitted before this call.  Row (b, j) of a step is picked with u[u_base[b] + e + j][b], e = tokens
+        b has emitted in this call, by the pick of `decode_sample` (the cache's top_p and filters included; `set_warpers` / `set_filters` beforehand).
+        Returns what decode_lookup returns; the tokens are bit for bit those of decode_sample from the same uniforms."""
+        B = len(budget)
+        assert len(u_base) == B, "one uniform base per sequence"
+        D = max(0, int(self.ctx.lib.pgv_kv_lookup(kv)))
+        u = u.to(device=self.device_, dtype=torch.float32).contiguous()
+        assert u.dim() == 2 and u.shape[1] == B, "u is [rows, B]"
+        toks = torch.zeros(B, int(steps) * (1 + D), dtype=torch.int32, device=self.device_)
+        counts = torch.zeros(int(steps), B, dtype=torch.int32, device=self.device_)
+        ints = lambda xs: (C.c_int32 * B)(*[int(x) for x in xs])      # noqa: E731
+        _lib.check(self.ctx.lib.pgv_llm_decode_lookup_sample(self.ctx.handle, self.handle, kv, first.data_ptr() if first is not None else None, int(steps),
+                                                             int(eos_id), ints(budget), ints(u_base), float(temperature), int(top_k), u.data_ptr(),
+                                                             int(u.shape[0]), toks.data_ptr(), counts.data_ptr(), _lib.stream_ptr(self.device_)),
+                   "pgv_llm_decode_lookup_sample")
+        return toks, counts.cpu().numpy()
+
     def decode_rows(self, kv, slots, tokens: torch.Tensor) -> torch.Tensor:
         """pgv_llm_decode_rows: one pass over the weights for several consecutive positions per sequence.  `slots` lists the sequence of every row
         (a sequence's rows consecutively), `tokens` [R] int32 the token each row consumes; row j of a sequence runs at position kv_len + j.  Returns
@@ -789,7 +809,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  samples_per_prompt: int = 1, beams: int = 1, length_penalty: Optional[float] = None, early_stopping=None,
-                 output_beam_scores: bool = False, bans=None, filters=None, lookup: int = 0, lookup_ngram: int = 2, **_unused):
+                 output_beam_scores: bool = False, bans=None, filters=None, lookup: int = 0, lookup_ngram: int = 2, lookup_sample: bool = False, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -861,7 +881,13 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         in fewer passes when the answer repeats itself or quotes the prompt.  `chunk` counts lookup steps.  Any B with B * (1 + D) <= 64; ragged
         prompts, `eos_token_id`, `max_new_tokens`, `stopping_criteria`, `stop_strings` and `timings` (which gains `lookup_steps` and
         `lookup_emitted`: tokens per pass = their quotient) work as without it; `kv_reuse_key` falls back to the full prefill.  Refused with
-        do_sample, beams > 1, samples_per_prompt > 1, a repetition penalty, bans and output_logprobs (generation.check_lookup)."""
+        do_sample, beams > 1, samples_per_prompt > 1, a repetition penalty, bans and output_logprobs (generation.check_lookup).
+        `lookup_sample=True` (with `lookup=D` and do_sample=True): the same steps for a sampled run.  The uniforms are drawn as without it, one
+        torch.rand(max_new_tokens, B) from `generator`; every row of a step is picked by the device pick from the uniform the plain run uses for that
+        token (pgv.h: pgv_llm_decode_lookup_sample), and a draft is kept exactly when it equals that pick.  The returned tensor is therefore bit for
+        bit the one of generate(do_sample=True) with the same generator -- not merely equal in distribution -- under any temperature, top_k, top_p
+        and `filters`.  A draft x is kept with the probability p(x) the pick gives it, which is HF's speculative acceptance min(1, p / q) for a
+        one-hot draft distribution q; how often that happens on real answers is unmeasured.  The other refusals of `lookup` stay."""
         check_generate_kwargs(_unused, self.generation_config, filters_given=filters is not None)
         temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
         if torch.is_tensor(input_ids):
@@ -879,7 +905,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         eos_i = -1 if eos is None else int(eos)
         ban = LogitBans() if bans is None else check_bans(bans, self.vocab_size, eos_i, n_beams)       # None: the call as it has always been
         ban_on = not ban.effective_neutral(eos_i)
-        look_D, look_n = check_lookup(lookup, lookup_ngram, B, bool(do_sample), n_beams, n_samples, rep_pen, ban_on, bool(output_logprobs))
+        look_D, look_n = check_lookup(lookup, lookup_ngram, B, bool(do_sample), n_beams, n_samples, rep_pen, ban_on, bool(output_logprobs),
+                                       lookup_sample=bool(lookup_sample))
         filt = check_filters(filters, self.generation_config, n_beams)
         filt_on = bool(do_sample) and not filt.neutral
         max_seq = max(len(s) for s in seqs) + max_new_tokens
@@ -979,9 +1006,15 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                 if look_D:
                     # chunks of lookup steps: every sequence emits a run of its own length; a sequence the host has finished gets no budget.  The
                     # cache keeps the current tokens between chunks (first = None), so only the first chunk hands them in
+                    def lookup_chunk(first_, steps_, left_):
+                        if not do_sample:
+                            return self.decode_lookup(kv, first_, steps_, eos_i, left_)
+                        # sampled: the whole table of uniforms, and per sequence the row its next token draws from
+                        return self.decode_lookup_sample(kv, first_, steps_, eos_i, left_, [len(st.new) for st in states], temperature, top_k, u)
+
                     while not stop:
                         left = [0 if st.done else max_new_tokens - len(st.new) for st in states]
-                        toks, counts = self.decode_lookup(kv, nxt if n_gen == 1 else None, min(chunk, max(left)), eos_i, left)
+                        toks, counts = lookup_chunk(nxt if n_gen == 1 else None, min(chunk, max(left)), left)
                         h = toks.cpu().numpy()
                         runs = counts.sum(axis=0)
                         look_steps += int((counts.sum(axis=1) > 0).sum())     # steps behind the last token of the chunk emitted nothing
