@@ -17,7 +17,7 @@ import argparse
 import torch
 
 from .constants import DEFAULT_TRANSCRIPT_START, DEFAULT_VID_END_TOKEN, DEFAULT_VID_START_TOKEN, DEFAULT_VIDEO_PATCH_TOKEN
-from .generation import check_lookup
+from .generation import check_lookup, given
 from .model.utils import KeywordsStoppingCriteria
 from .video_conversation import SeparatorStyle, conv_templates, default_conversation
 
@@ -120,8 +120,7 @@ class VideoChatGPTInterface:
                                              max_new_tokens=min(int(self.max_new_tokens), 1536), stopping_criteria=[stopping_criteria],
                                              kv_reuse_key=self.kv_key, timings=self.last_timings, top_p=self.top_p,
                                              repetition_penalty=self.repetition_penalty,
-                                             **({"lookup": self.lookup[0], "lookup_ngram": self.lookup[1]} if self.lookup[0] else {}),
-                                             **({"lookup_sample": True} if self.lookup_sample else {}))
+                                             **given(lookup=self.lookup[0], lookup_ngram=self.lookup[1], lookup_sample=self.lookup_sample))
         n_in = input_ids.shape[1]
         n_diff = int((input_ids.to(output_ids.device) != output_ids[:, :n_in]).sum())
         if n_diff > 0:

@@ -124,11 +124,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         raise ValueError(f"width {width} outside [1, 64]")
     if do_sample and not float(temperature) > 0.0:
         raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float; use do_sample=False for greedy decoding")
-    from .generation import check_samples_per_prompt, fork_sources, resolve_sampling
+    from .generation import CacheSettings, check_samples_per_prompt, fork_sources, resolve_sampling, step_kwargs
     _, _, top_p, rep_pen = resolve_sampling(temperature if do_sample else 1.0, top_k, top_p, repetition_penalty)      # validates, HF's wording
-    # passed on only when they differ from the neutral values: the model calls below then keep the argument lists they have always had
-    warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
-    pen = {} if rep_pen == 1.0 else {"repetition_penalty": rep_pen}
+    warp, pen = step_kwargs(top_p, rep_pen)     # empty when neutral: the model calls below then keep the argument lists they have always had
     chunk = max(1, int(chunk))
     k_min = max(1, int(refill_min) if refill_min is not None else width // 8)
     eos = model.config.eos_token_id if eos_token_id == "config" else eos_token_id
@@ -138,7 +136,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     ban_on = not ban.effective_neutral(eos_i)
     from .sample_filters import check_filters
     filt = check_filters(filters, getattr(model, "generation_config", None), who="generate_continuous()")
-    filt_on = bool(do_sample) and not filt.neutral
+    want_lp = logprobs is not None
+    # on for this call only: cleared in the finally below, also when the generator is closed early
+    on = CacheSettings(True if want_lp else None, ban if ban_on else None, eos_i, filt if do_sample and not filt.neutral else None)
     dev = model.device_
 
     source = iter(tasks)
@@ -241,12 +241,10 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     counts[-1] += W - taken
     forked = W != len(first)
     t0 = time.perf_counter()
-    want_lp = logprobs is not None
-    kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq, **({"logprobs": True} if want_lp else {}),
-                               **({"capacity": W} if forked else {}), **({"bans": ban, "eos_id": eos_i} if ban_on else {}))
+    kv, nxt, _ = model.prefill([t.ids for _, t in first], feats_for([t for _, t in first]), max_seq, **({"capacity": W} if forked else {}),
+                               **on.prefill_kwargs())
     try:
-        if filt_on:
-            model.set_filters(kv, filt)                             # for this call only: cleared in the finally below
+        on.apply(model, kv, prefilled=True)
         slots: List[Optional[_Slot]] = [None] * W
         # slot s holds sample j of first[i]; j beyond the task's samples: an idle padding slot
         owner = [(i, s - sum(counts[:i])) for s, i in enumerate(fork_sources(counts))]
@@ -417,9 +415,4 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                     if done is not None:
                         yield done
     finally:
-        if want_lp:
-            model.set_logprobs(kv, False)                           # the switch was on for this call only: also when the generator is closed early
-        if ban_on:
-            model.set_bans(kv, None)
-        if filt_on:
-            model.set_filters(kv, None)
+        on.clear(model, kv)

@@ -511,9 +511,8 @@ class _Runner:
 
         tm = {} if self.tfile else None
         # temperature 0.2, top_k 50: the reference's call (inference.py:106-112 + HF's default); the two warpers by generate()'s precedence
-        from ..generation import resolve_sampling
-        _, _, top_p, rep_pen = resolve_sampling(0.2, 50, generation_config=getattr(self.model, "generation_config", None), **self.warpers())
-        warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
+        from ..generation import resolve_sampling, step_kwargs
+        warp, _ = step_kwargs(*resolve_sampling(0.2, 50, generation_config=getattr(self.model, "generation_config", None), **self.warpers())[2:])
         lps = {} if many else None                                    # the samples are ranked by their log-probabilities
         for idx, new in generate_continuous(self.model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
                                             tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp, **({"logprobs": lps} if many else {}),

@@ -13,10 +13,24 @@ import os
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Sequence, Tuple
 
+from .logit_bans import LogitBans, check_bans
+from .sample_filters import check_filters
+
 GENERATION_CONFIG_NAME = "generation_config.json"
 
 # HF's GenerationConfig defaults (generation/configuration_utils.py) of the parameters the pick implements
 HF_DEFAULTS = {"temperature": 1.0, "top_k": 50, "top_p": 1.0, "repetition_penalty": 1.0}
+# keyword of generate() -> the value at which it asks nothing, where that is not None / 0 / False (given)
+NEUTRAL = {"beams": 1, "samples_per_prompt": 1}
+
+
+def given(**kw) -> Dict[str, Any]:
+    """The keywords of a generate() call that ask something: an entry at its neutral value (None, 0, False; NEUTRAL) is dropped, so a caller
+    hands on only what it was given and the call stays the call it has always been.  `lookup_ngram` only qualifies `lookup`: it is kept, its
+    default included, exactly when `lookup` is."""
+    def asks(k, v):
+        return not (v is None or (isinstance(v, (bool, int, float)) and v == NEUTRAL.get(k, 0)))
+    return {k: v for k, v in kw.items() if (asks("lookup", kw.get("lookup")) if k == "lookup_ngram" else asks(k, v))}
 
 
 def _positive(v) -> bool:
@@ -283,3 +297,143 @@ class GenerateLogprobsOutput:
                 out[k, b, :n] = row[:n]
         return cls(sequences, torch.from_numpy(out[0]), torch.from_numpy(out[1]), torch.from_numpy(out[0].astype(np.float64).sum(axis=1)),
                    torch.tensor([int(n) for n in n_kept], dtype=torch.long))
+
+
+def step_kwargs(top_p: float, repetition_penalty: float) -> Tuple[dict, dict]:
+    """(warp, pen): what the sampled / the greedy step methods of the model take as keywords -- passed on only when they differ from the neutral
+    values the methods default to, so a plain call keeps the argument lists it has always had."""
+    warp = {} if (top_p == 1.0 and repetition_penalty == 1.0) else {"top_p": top_p, "repetition_penalty": repetition_penalty}
+    return warp, ({} if repetition_penalty == 1.0 else {"repetition_penalty": repetition_penalty})
+
+
+@dataclass(frozen=True)
+class CacheSettings:
+    """What a KV cache is switched to for the length of ONE call, and the one scope that does it: `apply` (or the prefill, for what it takes)
+    switches on what is on, `clear` switches off exactly that.  logprobs: True records log-probabilities (False: `apply` turns the switch off, None
+    leaves it).  bans: a checked LogitBans with the `eos_id` its length rules ban; filters: a checked SampleFilters; lookup: (D, n).  None: off."""
+    logprobs: Optional[bool] = None
+    bans: Any = None
+    eos_id: int = -1
+    filters: Any = None
+    lookup: Optional[Tuple[int, int]] = None
+
+    def prefill_kwargs(self) -> dict:
+        """The keywords of model.prefill that are on: it sets them before the prompt runs, so that the first pick and the id record see them."""
+        kw = {"logprobs": True} if self.logprobs else {}
+        if self.bans is not None:
+            kw.update(bans=self.bans, eos_id=self.eos_id)
+        if self.lookup is not None:
+            kw.update(lookup=self.lookup)
+        return kw
+
+    def apply(self, model, kv, prefilled: bool = False):
+        """prefilled: `kv` comes from model.prefill(**prefill_kwargs()), which applied those; the filters, which no prefill takes, are left."""
+        if not prefilled:
+            if self.logprobs is not None:
+                model.set_logprobs(kv, self.logprobs)
+            if self.bans is not None:
+                model.set_bans(kv, self.bans, self.eos_id)
+            if self.lookup is not None:
+                model.set_lookup(kv, *self.lookup)
+        if self.filters is not None:
+            model.set_filters(kv, self.filters)
+
+    def clear(self, model, kv):
+        if self.logprobs:
+            model.set_logprobs(kv, False)
+        if self.bans is not None:
+            model.set_bans(kv, None)
+        if self.filters is not None:
+            model.set_filters(kv, None)
+        if self.lookup is not None:
+            model.set_lookup(kv, 0)
+
+
+@dataclass(frozen=True)
+class GenerationPlan:
+    """Everything one generate() call derives on the host before it touches the device (plan_generate).  bans / filters: the checked records,
+    `bans_on` / `filters_on`: whether they change a pick of this call; lookup: (D, n), (0, 0) off; stops: one stop string per prompt or None;
+    chunk: already capped under stopping criteria; max_seq: the cache positions to allocate."""
+    do_sample: bool
+    temperature: float
+    top_k: int
+    top_p: float
+    repetition_penalty: float
+    max_new_tokens: int
+    eos_id: int
+    chunk: int
+    max_seq: int
+    beams: int
+    length_penalty: float
+    early_stopping: Any
+    output_beam_scores: bool
+    samples_per_prompt: int
+    output_logprobs: bool
+    bans: LogitBans
+    bans_on: bool
+    filters: Any
+    filters_on: bool
+    lookup: Tuple[int, int]
+    lookup_sample: bool
+    criteria: tuple = ()
+    stops: Optional[list] = None
+
+    @property
+    def warp(self) -> dict:
+        return step_kwargs(self.top_p, self.repetition_penalty)[0]
+
+    @property
+    def pen(self) -> dict:
+        return step_kwargs(self.top_p, self.repetition_penalty)[1]
+
+    @property
+    def settings(self) -> CacheSettings:
+        return CacheSettings(True if self.output_logprobs else None, self.bans if self.bans_on else None, self.eos_id,
+                             self.filters if self.filters_on else None, self.lookup if self.lookup[0] else None)
+
+
+def plan_generate(model, seqs, do_sample=False, temperature=None, max_new_tokens=1024, stopping_criteria=None, eos_token_id="config", chunk=32,
+                  top_k=None, stop_strings=None, tokenizer=None, kv_reuse_key=None, top_p=None, repetition_penalty=None, output_logprobs=False,
+                  samples_per_prompt=1, beams=1, length_penalty=None, early_stopping=None, output_beam_scores=False, bans=None, filters=None,
+                  lookup=0, lookup_ngram=2, lookup_sample=False, unused=None) -> GenerationPlan:
+    """The plan of generate(seqs, ...) -- its keywords under their own names, `unused` what fell into **_unused -- or the first ValueError of the
+    call: every check in the order generate() has always made them, on the host.  Of `model` only generation_config, config and (under `bans`)
+    vocab_size are read."""
+    gc, B = model.generation_config, len(seqs)       # `model.config` is read where it is needed: a call refused before that needs none
+    check_generate_kwargs(unused or {}, gc, filters_given=filters is not None)
+    temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, gc)
+    reuse, sample = kv_reuse_key is not None, bool(do_sample)
+    K, length_penalty, early_stopping = check_beams(beams, B, sample, samples_per_prompt, rep_pen, bool(output_logprobs), bool(stopping_criteria),
+                                                    stop_strings is not None and any(stop_strings), reuse, length_penalty, early_stopping, gc)
+    if output_beam_scores and K == 1:
+        raise ValueError("generate(): `output_beam_scores` needs `beams` > 1 (a greedy answer's log-probabilities: `output_logprobs=True`)")
+    n_samples = check_samples_per_prompt(samples_per_prompt, B, sample, bool(stopping_criteria), reuse)
+    eos = model.config.eos_token_id if eos_token_id == "config" else eos_token_id
+    eos_i = -1 if eos is None else int(eos)
+    ban = LogitBans() if bans is None else check_bans(bans, model.vocab_size, eos_i, K)       # None: the call as it has always been
+    ban_on = not ban.effective_neutral(eos_i)
+    look = check_lookup(lookup, lookup_ngram, B, sample, K, n_samples, rep_pen, ban_on, bool(output_logprobs), lookup_sample=bool(lookup_sample))
+    filt = check_filters(filters, gc, K)
+    max_seq = max(len(s) for s in seqs) + max_new_tokens
+    if max_seq > model.config.max_position_embeddings:
+        raise ValueError(f"prompt + max_new_tokens = {max_seq} exceeds max_position_embeddings {model.config.max_position_embeddings}")
+    max_seq = (max_seq + 63) // 64 * 64
+    criteria, stops = [], None
+    if K == 1:              # a beam search takes none of these (check_beams)
+        if reuse and B == 1:
+            max_seq = min(int(model.config.max_position_embeddings), 4096)      # one cache for the whole conversation: later turns grow into it
+        criteria = list(stopping_criteria) if stopping_criteria else []
+        if criteria and B != 1:
+            raise ValueError("stopping_criteria are evaluated on one sequence (the reference passes them with batch size 1 only)")
+        if sample and not float(temperature) > 0.0:
+            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float; use do_sample=False for greedy decoding")
+        if criteria:
+            chunk = min(chunk, 16)                         # at most 15 surplus steps past a stop string
+        stops = list(stop_strings) if stop_strings is not None else None
+        if stops is not None:
+            if len(stops) != B or tokenizer is None:
+                raise ValueError("stop_strings needs one entry per sequence and the tokenizer that decodes them")
+            stops = stops if any(stops) else None
+    return GenerationPlan(sample, temperature, top_k, top_p, rep_pen, max_new_tokens, eos_i, chunk, max_seq, K, length_penalty, early_stopping,
+                          bool(output_beam_scores), n_samples, bool(output_logprobs), ban, ban_on, filt, sample and not filt.neutral, look,
+                          bool(lookup_sample), tuple(criteria), stops)

@@ -12,6 +12,7 @@ import torch
 from . import _lib
 from .constants import (DEFAULT_TRANSCRIPT_START, DEFAULT_VID_END_TOKEN, DEFAULT_VID_START_TOKEN, DEFAULT_VIDEO_PATCH_TOKEN,
                         DEFAULT_VIDEO_TOKEN, NUM_TEMPORAL_TOKENS)
+from .generation import given
 from .model.utils import KeywordsStoppingCriteria
 from .scoring import continuation_labels
 from .video_conversation import SeparatorStyle, conv_templates
@@ -184,10 +185,8 @@ def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, 
     `lookup_sample=True` (with lookup = D > 0 and do_sample=True): the sampled form, model.generate(lookup_sample=True) -- bit for bit the sampled
     answer of the call without the two keywords for the same generator state."""
     new_ids, stop_str = video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
-                                                transcript, do_sample, temperature, max_new_tokens, features, **({} if bans is None else {"bans": bans}),
-                                                **({} if filters is None else {"filters": filters}),
-                                                **({} if not lookup else {"lookup": lookup, "lookup_ngram": lookup_ngram}),
-                                                **({} if not lookup_sample else {"lookup_sample": True}))
+                                                transcript, do_sample, temperature, max_new_tokens, features,
+                                                **given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample))
     outputs = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0]
     return outputs.strip().rstrip(stop_str).strip()
 
@@ -201,14 +200,10 @@ def video_chatgpt_infer_logprobs(video_frames, question, conv_mode, model, visio
     gives for the same ids), "transition_scores" (per id, the log of the probability the pick used, after repetition penalty / temperature /
     top-k / top-p) and "logprob" (the fp64 sum of token_logprobs).  `lookup` / `lookup_sample` keep the signature of
     video_chatgpt_infer; lookup steps record no log-probabilities, so anything but 0 / False is refused by generate()."""
-    if lookup:
-        generate_kwargs = dict(generate_kwargs, lookup=lookup, lookup_ngram=lookup_ngram)
-    if lookup_sample:
-        generate_kwargs = dict(generate_kwargs, lookup_sample=True)
+    asked = given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample)
     out, output_ids, n_in, stop_str = _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                                       transcript, do_sample, temperature, max_new_tokens, features,
-                                                      dict(generate_kwargs, output_logprobs=True, **({} if bans is None else {"bans": bans}),
-                                                           **({} if filters is None else {"filters": filters})))
+                                                      dict(generate_kwargs, output_logprobs=True, **asked))
     new_ids = output_ids[0, n_in:].tolist()
     text = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0].strip().rstrip(stop_str).strip()
     n = len(new_ids)

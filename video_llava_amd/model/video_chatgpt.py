@@ -5,8 +5,8 @@ stopping_criteria)` (reference: video_chatgpt/model/video_chatgpt.py:16-325; cal
 video_chatgpt/inference.py:67,105-112, chat.py:148-154, eval/model_utils.py:104-144).
 
 The decoder stack, the video splice, lm_head and greedy picking run in libpgv (hand-written gfx950 kernels);
-this file is host orchestration only: placeholder validation (same ValueErrors as the reference), the
-token loop, stopping criteria and sampling glue.
+this file is host orchestration only: placeholder validation (same ValueErrors as the reference) and the
+step methods; generate()'s checks are generation.plan_generate, its token loop is generate_loop.
 """
 from __future__ import annotations
 
@@ -19,16 +19,14 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, generate_loop
 from ..constants import CLIP_WIDTH
 from ..beam_reference import early_code
-from ..generation import (GenerateBeamsOutput, GenerateLogprobsOutput, check_beams, check_generate_kwargs, check_lookup, check_samples_per_prompt, fork_sources,
-                          load_generation_config, resolve_sampling)
-from ..logit_bans import LogitBans, check_bans
-from ..sample_filters import SampleFilters, check_filters
+from ..generation import CacheSettings, fork_sources, load_generation_config, plan_generate
+from ..logit_bans import LogitBans
+from ..sample_filters import SampleFilters
 from ..scoring import ScoreOutput, id_rows, shift_labels
 from .multimodal_projector.builder import HipLinear, IdentityMap, build_vision_projector
-from .utils import AnswerState
 
 DEFAULT_VIDEO_TOKEN = "<video>"
 DEFAULT_VIDEO_PATCH_TOKEN = "<vid_patch>"
@@ -393,12 +391,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             self._reuse = None
         else:
             kv = append_to
-        if logprobs is not None:
-            self.set_logprobs(kv, logprobs)
-        if bans is not None:
-            self.set_bans(kv, bans, eos_id)
-        if lookup is not None:
-            self.set_lookup(kv, *lookup)
+        on = CacheSettings(logprobs, bans, eos_id, lookup=lookup)
+        on.apply(self, kv)
         flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
         h_lens = (C.c_int32 * B)(*lens)
         h_pos = (C.c_int32 * B)(*vid_pos)
@@ -414,12 +408,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                           all_logits.data_ptr() if all_logits is not None else None, ld_all,
                           _lib.stream_ptr(self.device_)), who)
         except Exception:
-            if logprobs:
-                self.set_logprobs(kv, False)               # a refused prompt never reaches the caller who would turn the switch off again
-            if bans is not None:
-                self.set_bans(kv, None)
-            if lookup is not None:
-                self.set_lookup(kv, 0)
+            on.clear(self, kv)                             # a refused prompt never reaches the caller who would turn the switches off again
             raise
         if want_all_logits:
             return kv, nxt, logits, all_logits[:, :self.vocab_size]
@@ -607,42 +596,6 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         if n.value:
             _lib.check(self.ctx.lib.pgv_beam_result(kv, int(p), int(rank), toks, n.value, C.byref(n), C.byref(score), C.byref(fin), s), "pgv_beam_result")
         return [int(toks[i]) for i in range(n.value)], float(score.value), bool(fin.value)
-
-    def _generate_beams(self, seqs, feats, K: int, length_penalty: float, early_stopping, max_new_tokens: int, max_seq: int, eos_i: int, chunk: int,
-                        output_beam_scores: bool, timings: Optional[dict]):
-        """generate(beams=K > 1): one prefill of the B prompts in a cache of B * K slots, pgv_beam_begin, then chunks of beam steps until no prompt
-        is open or the budget is spent.  The host reads one flag per prompt between chunks and the best hypothesis at the end."""
-        import time as _time
-        _t0 = _time.perf_counter()
-        B = len(seqs)
-        if max_new_tokens < 1:
-            new = [([], 0.0)] * B
-            _t1 = _t0
-            n_gen = 0
-        else:
-            kv, _nxt, _ = self.prefill(seqs, feats, max_seq, capacity=B * K)
-            self.beam_begin(kv, K, max_new_tokens, eos_i, length_penalty, early_stopping)
-            n_gen = 1
-            still = self.beam_open(kv, B)       # synchronises: the prefill and the first pick are done
-            _t1 = _time.perf_counter()
-            while n_gen < max_new_tokens and any(still):
-                n = min(max(1, int(chunk)), max_new_tokens - n_gen)
-                self.decode_beam(kv, n)
-                n_gen += n
-                still = self.beam_open(kv, B)
-            new = [self.beam_result(kv, b, 0)[:2] for b in range(B)]
-        if timings is not None:
-            timings.update(prefill_s=_t1 - _t0, decode_s=_time.perf_counter() - _t1, steps=n_gen, batch=B * K, reused_tokens=0, samples_per_prompt=1, beams=K)
-        width = max(len(s_) + len(n_[0]) for s_, n_ in zip(seqs, new))
-        pad = eos_i if eos_i >= 0 else 0
-        out = torch.full((B, width), pad, dtype=torch.long)
-        for b in range(B):
-            row = list(seqs[b]) + list(new[b][0])
-            out[b, :len(row)] = torch.tensor(row, dtype=torch.long)
-        out = out.to(self.device_)
-        if output_beam_scores:
-            return GenerateBeamsOutput(out, torch.tensor([n_[1] for n_ in new], dtype=torch.float32), torch.tensor([len(n_[0]) for n_ in new], dtype=torch.long))
-        return out
 
     def kv_peek(self, kv, layer: int, which: int, slot: int, row0: int, nrows: int) -> torch.Tensor:
         """pgv_kv_peek (tests / debugging): cache rows [row0, row0 + nrows) of `slot` in `layer`, which = 0 keys / 1 values ->
@@ -888,207 +841,13 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         bit the one of generate(do_sample=True) with the same generator -- not merely equal in distribution -- under any temperature, top_k, top_p
         and `filters`.  A draft x is kept with the probability p(x) the pick gives it, which is HF's speculative acceptance min(1, p / q) for a
         one-hot draft distribution q; how often that happens on real answers is unmeasured.  The other refusals of `lookup` stay."""
-        check_generate_kwargs(_unused, self.generation_config, filters_given=filters is not None)
-        temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, self.generation_config)
-        if torch.is_tensor(input_ids):
-            seqs = [row.tolist() for row in input_ids.cpu()]
-        else:
-            seqs = [list(s) for s in input_ids]
-        B = len(seqs)
-        n_beams, length_penalty, early_stopping = check_beams(beams, B, bool(do_sample), samples_per_prompt, rep_pen, bool(output_logprobs), bool(stopping_criteria),
-                                                              stop_strings is not None and any(stop_strings), kv_reuse_key is not None, length_penalty, early_stopping,
-                                                              self.generation_config)
-        if output_beam_scores and n_beams == 1:
-            raise ValueError("generate(): `output_beam_scores` needs `beams` > 1 (a greedy answer's log-probabilities: `output_logprobs=True`)")
-        n_samples = check_samples_per_prompt(samples_per_prompt, B, bool(do_sample), bool(stopping_criteria), kv_reuse_key is not None)
-        eos = self.config.eos_token_id if eos_token_id == "config" else eos_token_id
-        eos_i = -1 if eos is None else int(eos)
-        ban = LogitBans() if bans is None else check_bans(bans, self.vocab_size, eos_i, n_beams)       # None: the call as it has always been
-        ban_on = not ban.effective_neutral(eos_i)
-        look_D, look_n = check_lookup(lookup, lookup_ngram, B, bool(do_sample), n_beams, n_samples, rep_pen, ban_on, bool(output_logprobs),
-                                       lookup_sample=bool(lookup_sample))
-        filt = check_filters(filters, self.generation_config, n_beams)
-        filt_on = bool(do_sample) and not filt.neutral
-        max_seq = max(len(s) for s in seqs) + max_new_tokens
-        if max_seq > self.config.max_position_embeddings:
-            raise ValueError(f"prompt + max_new_tokens = {max_seq} exceeds max_position_embeddings {self.config.max_position_embeddings}")
-        max_seq = (max_seq + 63) // 64 * 64
-        if n_beams > 1:
-            return self._generate_beams(seqs, video_spatio_temporal_features, n_beams, length_penalty, early_stopping, int(max_new_tokens), max_seq, eos_i, chunk,
-                                        bool(output_beam_scores), timings)
-        if kv_reuse_key is not None and B == 1:
-            max_seq = min(int(self.config.max_position_embeddings), 4096)      # one cache for the whole conversation: later turns grow into it
-        criteria = list(stopping_criteria) if stopping_criteria else []
-        if criteria and B != 1:
-            raise ValueError("stopping_criteria are evaluated on one sequence (the reference passes them with batch size 1 only)")
-        if do_sample and not float(temperature) > 0.0:
-            raise ValueError(f"`temperature` (={temperature}) has to be a strictly positive float; use do_sample=False for greedy decoding")
-        if criteria:
-            chunk = min(chunk, 16)                         # at most 15 surplus steps past a stop string
-        stops = list(stop_strings) if stop_strings is not None else None
-        if stops is not None:
-            if len(stops) != B or tokenizer is None:
-                raise ValueError("stop_strings needs one entry per sequence and the tokenizer that decodes them")
-            if not any(stops):
-                stops = None
-        import time as _time
-        _t0 = _time.perf_counter()
-
-        # passed on only when they differ from the neutral values (the step methods default to them)
-        warp = {} if (top_p == 1.0 and rep_pen == 1.0) else {"top_p": top_p, "repetition_penalty": rep_pen}
-        pen = {} if rep_pen == 1.0 else {"repetition_penalty": rep_pen}
-        lpk = {"logprobs": True} if output_logprobs else {}    # the switch is on for this call only (turned off again in the finally below)
-        if ban_on:
-            lpk.update(bans=ban, eos_id=eos_i)                 # likewise: set before the prompt runs, cleared in the finally below
-        if look_D:
-            lpk.update(lookup=(look_D, look_n))                # likewise
-        reused = 0
-        if kv_reuse_key is not None and B == 1 and rep_pen == 1.0 and not ban_on and not look_D:
-            # (and under bans the slot's id record has to be exactly prompt + answer, for the same reason)
-            # (under a repetition penalty the slot's seen-set has to be exactly prompt + answer: the surplus steps a kept cache carries past a
-            # stop string would stay in it, so such a turn runs the full prefill)
-            reused = self._reusable_prefix(kv_reuse_key, seqs[0], max_new_tokens)
-        if reused:
-            kv = self._reuse[1]
-            if reused < len(self._reuse[3]):
-                _lib.check(self.ctx.lib.pgv_kv_truncate(kv, 0, reused, _lib.stream_ptr(self.device_)), "pgv_kv_truncate")
-            _kv, nxt, _ = self.prefill([seqs[0][reused:]], None, 0, append_to=kv, **lpk)
-        elif n_samples > 1:
-            # one prefill of the B prompts, then every prompt's slot becomes n consecutive slots: from here on the call IS the call on the
-            # prompts repeated n times each (the prefill's own greedy first token is replaced by the draw below, per slot)
-            kv, _nxt, _ = self.prefill(seqs, video_spatio_temporal_features, max_seq, capacity=B * n_samples, **lpk)
-            try:
-                B = self.fork(kv, [n_samples] * B)
-            except Exception:
-                if output_logprobs:
-                    self.set_logprobs(kv, False)
-                if ban_on:
-                    self.set_bans(kv, None)
-                raise
-            seqs = [seqs[i] for i in fork_sources([n_samples] * len(seqs))]
-            if stops is not None:
-                stops = [stops[i // n_samples] for i in range(B)]
-        else:
-            kv, nxt, _ = self.prefill(seqs, video_spatio_temporal_features, max_seq, **lpk)
-        try:
-            raw: List[int] = []                                # B == 1: every token the device emitted, stop cuts ignored (= what the cache holds, shifted by one)
-            u = None
-            if filt_on:
-                self.set_filters(kv, filt)                     # for this call only: cleared in the finally below
-            if do_sample and max_new_tokens >= 1:
-                u = torch.rand(max_new_tokens, B, device=self.device_, dtype=torch.float32, generator=generator)
-                nxt = self.sample_last(kv, u[0], temperature, top_k, **warp)
-            elif (rep_pen != 1.0 or ban_on) and max_new_tokens >= 1:
-                # greedy under a penalty or bans: the prefill's argmax knows neither -- re-pick over the processed logits (first index on ties)
-                nxt = self.greedy_last(kv, B, **pen)
-            lp_parts = []                                      # output_logprobs: [2, B, steps] blocks in generation order (first token, then every chunk)
-            if output_logprobs and max_new_tokens >= 1:
-                lp_parts.append(self.logprobs_last(kv, B)[:, :, None])
-            states = [AnswerState(max_new_tokens, eos_i, stops[b] if stops is not None else None, tokenizer) for b in range(B)]
-            prompt_t = torch.tensor(seqs[0], dtype=torch.long)
-
-            def criterion_fires() -> bool:
-                """HF: a stopping criterion is asked after every appended token (B == 1)."""
-                cur = torch.cat([prompt_t, torch.tensor(states[0].new, dtype=torch.long)])[None]
-                return any(c(cur, None) for c in criteria)
-
-            n_gen = 0
-            look_steps = look_emitted = 0
-            _t1 = _t0
-            if max_new_tokens >= 1:
-                first = nxt.cpu().numpy()
-                raw.append(int(first[0]))
-                for b, st in enumerate(states):
-                    st.take(first[b:b + 1])
-                stop = all(st.done for st in states) or (bool(criteria) and criterion_fires())
-                _t1 = _time.perf_counter()
-                n_gen = 1
-                if look_D:
-                    # chunks of lookup steps: every sequence emits a run of its own length; a sequence the host has finished gets no budget.  The
-                    # cache keeps the current tokens between chunks (first = None), so only the first chunk hands them in
-                    def lookup_chunk(first_, steps_, left_):
-                        if not do_sample:
-                            return self.decode_lookup(kv, first_, steps_, eos_i, left_)
-                        # sampled: the whole table of uniforms, and per sequence the row its next token draws from
-                        return self.decode_lookup_sample(kv, first_, steps_, eos_i, left_, [len(st.new) for st in states], temperature, top_k, u)
-
-                    while not stop:
-                        left = [0 if st.done else max_new_tokens - len(st.new) for st in states]
-                        toks, counts = lookup_chunk(nxt if n_gen == 1 else None, min(chunk, max(left)), left)
-                        h = toks.cpu().numpy()
-                        runs = counts.sum(axis=0)
-                        look_steps += int((counts.sum(axis=1) > 0).sum())     # steps behind the last token of the chunk emitted nothing
-                        look_emitted += int(runs.sum())
-                        raw.extend(h[0, :int(runs[0])].tolist())
-                        for b, st in enumerate(states):
-                            if st.done or not runs[b]:
-                                continue
-                            if criteria:
-                                for i in range(int(runs[b])):
-                                    if st.take(h[b, i:i + 1]) or criterion_fires():
-                                        stop = True
-                                        break
-                            else:
-                                st.take(h[b, :int(runs[b])])
-                        stop = stop or all(st.done for st in states)
-                        n_gen = max(2, max(len(st.new) for st in states))
-                while not stop and n_gen < max_new_tokens:
-                    n = min(chunk, max_new_tokens - n_gen)
-                    if do_sample:
-                        toks = self.decode_sample(kv, nxt, n, eos_i, temperature, top_k, u[n_gen:n_gen + n], **warp)
-                    else:
-                        toks = self.decode_greedy(kv, nxt, n, eos_i, **pen)
-                    if output_logprobs:
-                        lp_parts.append(self.logprobs_steps(kv, B, n))
-                    h = toks.cpu().numpy()
-                    raw.extend(h[0].tolist())
-                    if criteria:
-                        for i in range(n):
-                            stop = states[0].take(h[0, i:i + 1]) or criterion_fires()
-                            n_gen += 1
-                            if stop:
-                                break
-                    else:
-                        # per SEQUENCE, not per step (a chunk of 64 steps x 8 sequences cost ~0.6 ms of Python between two decode launches, with the
-                        # GPU idle): AnswerState.take absorbs a live sequence's whole run at once
-                        last = 0
-                        for b, st in enumerate(states):
-                            if not st.done:
-                                st.take(h[b])
-                                last = max(last, st.taken)
-                        stop = all(st.done for st in states)
-                        n_gen += last if stop else n
-                    nxt = toks[:, n - 1].contiguous()
-            new = [st.new for st in states]
-            if timings is not None:
-                _t2 = _time.perf_counter()
-                timings.update(prefill_s=_t1 - _t0, decode_s=_t2 - _t1, steps=n_gen, batch=B, reused_tokens=reused, samples_per_prompt=n_samples)
-                if look_D:
-                    timings.update(lookup_steps=look_steps, lookup_emitted=look_emitted)
-            if kv_reuse_key is not None and B == 1:
-                # the cache holds the prompt and every emitted token that was fed back (all but the last one)
-                self._reuse = (kv_reuse_key, kv, max_seq, list(seqs[0]) + raw[:-1])
-                assert self.ctx.lib.pgv_kv_len(kv, 0) == len(self._reuse[3]), (self.ctx.lib.pgv_kv_len(kv, 0), len(self._reuse[3]))
-            width = max(len(s) + len(n_) for s, n_ in zip(seqs, new))
-            pad = eos_i if eos_i >= 0 else 0
-            out = torch.full((B, width), pad, dtype=torch.long)
-            for b in range(B):
-                row = seqs[b] + new[b]
-                out[b, :len(row)] = torch.tensor(row, dtype=torch.long)
-            if output_logprobs:
-                # a sequence's kept ids are a prefix of what the device emitted for it: the same cut applies to the values
-                lp = torch.cat(lp_parts, dim=2).cpu().numpy() if lp_parts else np.zeros((2, B, 0), dtype=np.float32)
-                return GenerateLogprobsOutput.assemble(out.to(self.device_), [len(n_) for n_ in new], lp[0], lp[1])
-            return out.to(self.device_)
-        finally:
-            if output_logprobs:
-                self.set_logprobs(kv, False)                   # also when a criterion, the tokenizer or an interrupt ends the call early
-            if ban_on:
-                self.set_bans(kv, None)
-            if filt_on:
-                self.set_filters(kv, None)
-            if look_D:
-                self.set_lookup(kv, 0)
+        seqs = [row.tolist() for row in input_ids.cpu()] if torch.is_tensor(input_ids) else [list(s) for s in input_ids]
+        plan = plan_generate(self, seqs, do_sample, temperature, max_new_tokens, stopping_criteria, eos_token_id, chunk, top_k, stop_strings, tokenizer,
+                             kv_reuse_key, top_p, repetition_penalty, output_logprobs, samples_per_prompt, beams, length_penalty, early_stopping,
+                             output_beam_scores, bans, filters, lookup, lookup_ngram, lookup_sample, unused=_unused)
+        if plan.beams > 1:
+            return generate_loop.generate_beams(self, plan, seqs, video_spatio_temporal_features, timings)
+        return generate_loop.generate_chunks(self, plan, seqs, video_spatio_temporal_features, generator, tokenizer, timings, kv_reuse_key)
 
 
 def _vision_config_from(mm_vision_tower) -> VisionConfig:
