@@ -561,6 +561,41 @@ int pgv_ban_logits(pgv_ctx *ctx, float *d_logits, int V, int B, const int32_t *d
                    const int32_t *d_prompt_lens, int eos_id, const pgv_ban_config *cfg, void *stream);
 int pgv_kv_ids_peek(pgv_kv *kv, int slot, int n, int32_t *d_out, int32_t *d_prompt_len, void *stream);
 
+/* Classifier-free guidance: HF's UnbatchedClassifierFreeGuidanceLogitsProcessor (generation/logits_process.py; generate(guidance_scale = s,
+ * negative_prompt_ids = ...), the FIRST processor GenerationMixin._get_logits_processor builds).  HF runs the model a second time on the negative
+ * prompt and hands the rest of the chain
+ *     guided = s * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond).
+ * Here the unconditional stream is P more rows of the same decode step: a live group of width 2P whose slots [0, P) are the conditional sequences
+ * and whose slot P + p is the unconditional twin of p (the caller prefills prompts + negatives as ONE ragged pgv_llm_prefill of 2P rows).  The trunk
+ * and the lm_head run over all 2P rows, unchanged; between the lm_head and the pick, per pair p and vocabulary index v, in fp32 and in this order:
+ *     lc = (xc[v] - Mc) - lsc,   lu = (xu[v] - Mu) - lsu,   out[v] = s * (lc - lu) + lu,
+ * M the row's maximum and ls = ln sum exp(x - M), the row statistics of pgv_logprob_rows in its reduction order ((x[v] - M) - ls is bit for bit its
+ * log-probability of target v).  A pair's result depends on its two rows alone: not on P, the pair's index or the launch.  IEEE results stand: a -inf
+ * in the conditional row gives -inf under s > 0; what is NaN in HF's tensor arithmetic (0 * inf, inf - inf) is NaN here.
+ *
+ * pgv_guidance_logits (building block, the same kernel on caller buffers): rows p of d_cond / d_uncond [P, ld] -> d_out [P, ld_out], columns [0, V).
+ *   Any ld, ld_out >= V; 4-byte alignment is all that is required (the decode logits are `vocab` floats apart: 32003 is odd).  d_uncond may equal
+ *   d_cond: the output is then the row's log-softmax.  PGV_EINVAL for a stride below V or a scale that is not finite.
+ * pgv_kv_set_guidance(kv, scale, pairs): the state of every later COVERED pick on this cache; pairs == 0 or scale == 1 is off, the default, and
+ *   every launch, captured graph and token is then what it is without this call.  The guided rows go to a buffer [batch / 2, vocab] that the first
+ *   call that switches guidance on allocates; the cache's own logits (d_logits of pgv_llm_decode, what a second pick reads) stay raw.  Refused, and
+ *   nothing changes: a scale that is not finite, 2 * pairs beyond the cache's batch (PGV_EINVAL); log-probabilities or lookup on, a beam run in flight
+ *   (PGV_ESTATE).  pgv_kv_guidance: the pairs in force (0: off).
+ *   Covered picks: pgv_llm_sample, pgv_llm_pick_greedy and every step of pgv_llm_decode_greedy / _sample.  They need a live group of exactly
+ *   2 * pairs sequences, else PGV_ESTATE.  The pick runs over P rows reading the guided buffer, with the conditional slot's seen-set (repetition
+ *   penalty: HF applies it to the guided scores, as here) and, under pgv_kv_set_bans, the ban copy made from the guided row with the conditional
+ *   slot's id record; greedy takes the route of greedy under a penalty.  d_u keeps the group's width 2P as its row length, only columns [0, P) are
+ *   read.  Behind the pick the twin follows: current token and done flag of slot P + p become those of slot p and its device position advances
+ *   exactly when slot p's does, so rows [P, 2P) of d_next / d_tokens repeat rows [0, P); EOS ends both.  A guided step adds two launches (mix,
+ *   follow), inside the captured decode graphs, whose key carries (pairs, scale).
+ *   NOT covered, as for the penalty and bans: the greedy d_next of pgv_llm_prefill / _append and plain pgv_llm_decode steps (all 2P rows, unguided).
+ *   Refused with PGV_ESTATE while guidance is on: pgv_kv_fork, pgv_llm_prefill_slots / _slots_n, pgv_beam_begin, pgv_kv_set_lookup (D > 0) and the
+ *   lookup calls, pgv_kv_set_logprobs(on). */
+int pgv_guidance_logits(pgv_ctx *ctx, const float *d_cond, const float *d_uncond, int ld, int V, int P, float scale, float *d_out, int ld_out,
+                        void *stream);
+int pgv_kv_set_guidance(pgv_kv *kv, float scale, int pairs);
+int pgv_kv_guidance(const pgv_kv *kv);
+
 /* current length (tokens in cache) of sequence b, host-side bookkeeping */
 int pgv_kv_len(const pgv_kv *kv, int b);
 

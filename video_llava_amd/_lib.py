@@ -166,6 +166,9 @@ PROTOTYPES = {
     "pgv_kv_set_bans": (_i, [_vp, C.POINTER(BanConfig)]),
     "pgv_ban_logits": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(BanConfig), _vp]),
     "pgv_kv_ids_peek": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "pgv_guidance_logits": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _i, _vp]),
+    "pgv_kv_set_guidance": (_i, [_vp, _f, _i]),
+    "pgv_kv_guidance": (_i, [_vp]),
     "pgv_ingest_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pgv_gemm": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "pgv_gemm_ex": (_i, [_vp, _i, C.POINTER(GemmDesc), _vp]),
@@ -408,6 +411,23 @@ class Context:
         check(self.lib.pgv_ban_logits(self.handle, logits.data_ptr(), logits.shape[1], B, ids.data_ptr(), ids.shape[1], lens.data_ptr(),
                                       prompt_lens.data_ptr(), int(eos_id), C.byref(cfg), stream_ptr(logits.device)), "pgv_ban_logits")
         return logits
+
+    def guidance_logits(self, cond: torch.Tensor, uncond: torch.Tensor, scale: float, V: "int | None" = None, out: "torch.Tensor | None" = None) -> torch.Tensor:
+        """pgv_guidance_logits: HF's classifier-free guidance rule on fp32 rows cond / uncond [P, ld] (unit column stride, any row stride >= V, one
+        stride for both; they may be the same tensor) over columns [0, V) (default: all) -> fp32 [P, V] (or `out`, any row stride >= V)."""
+        for t in (cond, uncond):
+            assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
+        assert cond.shape == uncond.shape
+        P = cond.shape[0]
+        V = cond.shape[1] if V is None else int(V)
+        ld = max(cond.stride(0), cond.shape[1]) if P > 1 else cond.shape[1]
+        assert P <= 1 or uncond.stride(0) == cond.stride(0), "cond and uncond need one row stride"
+        if out is None:
+            out = torch.empty(P, V, dtype=torch.float32, device=cond.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == P and out.shape[1] >= V
+        check(self.lib.pgv_guidance_logits(self.handle, cond.data_ptr(), uncond.data_ptr(), ld, V, P, float(scale), out.data_ptr(),
+                                           max(out.stride(0), out.shape[1]) if P > 1 else out.shape[1], stream_ptr(cond.device)), "pgv_guidance_logits")
+        return out
 
     def sample_logits_lp(self, logits: torch.Tensor, u: "torch.Tensor | None", temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                          repetition_penalty: float = 1.0, seen_ids: "torch.Tensor | None" = None, seen_lens: "torch.Tensor | None" = None,

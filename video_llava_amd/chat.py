@@ -25,7 +25,7 @@ from .video_conversation import SeparatorStyle, conv_templates, default_conversa
 class VideoChatGPTInterface:
     def __init__(self, args_model_name, args_projection_path, use_asr=False, conv_mode="pg-video-llava", temperature=0.2,
                  max_output_tokens=1024, components=None, do_sample=True, reuse_kv=True, top_p=None, repetition_penalty=None, lookup=0,
-                 lookup_ngram=2, lookup_sample=False) -> None:
+                 lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video") -> None:
         if use_asr:
             raise NotImplementedError("--use_asr needs the WhisperX transcript stack, which is outside this package's hot path")
         self.use_asr = use_asr
@@ -43,7 +43,11 @@ class VideoChatGPTInterface:
         # refused here as generate() would refuse it
         self.lookup = check_lookup(lookup, lookup_ngram, 1, bool(do_sample), who="VideoChatGPTInterface", lookup_sample=bool(lookup_sample))
         self.lookup_sample = bool(lookup_sample)
-        self.reuse_kv = reuse_kv
+        # classifier-free guidance (generate(guidance=)): every turn runs the conversation a second time without the clip ("no_video") or from
+        # its last token (HF's default negative) as B more rows of the decode steps; such a turn keeps no KV cache for the next one
+        self.guidance_scale = guidance_from_flags(guidance_scale, guidance_negative, lookup=self.lookup[0], who="VideoChatGPTInterface")
+        self.guidance_negative = guidance_negative
+        self.reuse_kv = reuse_kv and self.guidance_scale is None
         self.frame_size = (image_processor.crop_size["height"], image_processor.crop_size["width"])
         if self.model.get_model().vision_config.use_vid_start_end:
             self.replace_token = DEFAULT_VID_START_TOKEN + DEFAULT_VIDEO_PATCH_TOKEN * video_token_len + DEFAULT_VID_END_TOKEN
@@ -106,10 +110,18 @@ class VideoChatGPTInterface:
             self.state.append_message(self.state.roles[0], first_user_turn)
             self.state.append_message(self.state.roles[1], None)
             self.first_run = False
-        prompt = self.state.get_prompt()
-        prompt = prompt.replace("<video>", self.replace_token, 1)
+        raw = self.state.get_prompt()
+        prompt = raw.replace("<video>", self.replace_token, 1)
         prompt = prompt.replace("<audio_transcript>", f'{DEFAULT_TRANSCRIPT_START}\n"{self.transcript_text}"', 1)
         inputs = self.tokenizer([prompt])
+        guide = {}
+        if self.guidance_scale is not None:
+            from .guidance import Guidance
+            negative = "last_token"
+            if self.guidance_negative == "no_video":        # the same conversation without the video tokens
+                no_video = raw.replace("<video>", "", 1).replace("<audio_transcript>", f'{DEFAULT_TRANSCRIPT_START}\n"{self.transcript_text}"', 1)
+                negative = [list(self.tokenizer([no_video]).input_ids[0])]
+            guide = {"guidance": Guidance(self.guidance_scale, negative)}
         input_ids = torch.as_tensor(inputs.input_ids)
         stop_str = self.state.sep if self.state.sep_style != SeparatorStyle.TWO else self.state.sep2
         stopping_criteria = KeywordsStoppingCriteria([stop_str], self.tokenizer, input_ids)
@@ -120,7 +132,7 @@ class VideoChatGPTInterface:
                                              max_new_tokens=min(int(self.max_new_tokens), 1536), stopping_criteria=[stopping_criteria],
                                              kv_reuse_key=self.kv_key, timings=self.last_timings, top_p=self.top_p,
                                              repetition_penalty=self.repetition_penalty,
-                                             **given(lookup=self.lookup[0], lookup_ngram=self.lookup[1], lookup_sample=self.lookup_sample))
+                                             **given(lookup=self.lookup[0], lookup_ngram=self.lookup[1], lookup_sample=self.lookup_sample), **guide)
         n_in = input_ids.shape[1]
         n_diff = int((input_ids.to(output_ids.device) != output_ids[:, :n_in]).sum())
         if n_diff > 0:
@@ -167,6 +179,38 @@ class VideoChatGPTInterface:
         return fence.join(parts)
 
 
+def guidance_from_flags(scale, negative, lookup=0, beams=1, samples_per_prompt=1, schedule="group", who="--guidance_scale"):
+    """--guidance_scale S / --guidance_negative of a command line -> the scale as a float, or None when nothing is asked (no flag, or 1);
+    ValueError names the flag guidance cannot run with, as generate() would refuse it."""
+    import math
+    if negative not in ("no_video", "last_token"):
+        raise ValueError(f"{who}: --guidance_negative has to be no_video or last_token, but is {negative!r}")
+    if scale is None:
+        return None
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"{who}: --guidance_scale has to be a finite float, but is {scale!r}")
+    if scale == 1.0:
+        return None
+    for flag, bad, why in (("--schedule refill", schedule == "refill", "a refill would separate the twins from their prompts"),
+                           (f"--beams {beams}", int(beams or 1) > 1, "a beam step already runs K rows per prompt and applies no logits processor"),
+                           (f"--lookup {lookup}", int(lookup or 0) > 0, "the drafts are verified against the unguided pick"),
+                           (f"--samples_per_prompt {samples_per_prompt}", int(samples_per_prompt or 1) > 1, "a fork would separate the twins from their prompts")):
+        if bad:
+            raise ValueError(f"--guidance_scale {scale:g} cannot be combined with {flag} ({why})")
+    return scale
+
+
+def add_guidance_flags(parser):
+    parser.add_argument("--guidance_scale", type=float, default=None, metavar="S",
+                        help="classifier-free guidance (generate(guidance=); HF: guidance_scale): every pick reads S * (log_softmax(cond) - "
+                             "log_softmax(uncond)) + log_softmax(uncond), uncond the logits of the negative prompt, which runs as one more row per clip of "
+                             "every decode step; 1 (default): off; not with --schedule refill, --beams, --lookup or --samples_per_prompt")
+    parser.add_argument("--guidance_negative", choices=("no_video", "last_token"), default="no_video",
+                        help="--guidance_scale: the negative prompt -- no_video (default): the same conversation without the video tokens, i.e. contrast "
+                             "decoding against the language prior; last_token: HF's default, the prompt's last token")
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="Demo")
     parser.add_argument("--model-name", type=str, required=True)
@@ -181,6 +225,7 @@ def parse_args(argv=None):
     parser.add_argument("--lookup_ngram", type=int, default=2, metavar="N", help="--lookup: the largest n-gram matched, 1 .. 4 (HF: max_matching_ngram_size)")
     parser.add_argument("--lookup_sample", action="store_true",
                         help="--lookup D --do_sample: lookup steps for the sampled run (generate(lookup_sample=True)): bit for bit the answer of --do_sample alone")
+    add_guidance_flags(parser)
     args = parser.parse_args(argv)
     if args.lookup_sample and not args.do_sample:
         parser.error("--lookup_sample needs --do_sample (greedy lookup is --lookup D alone)")
@@ -190,6 +235,7 @@ def parse_args(argv=None):
         parser.error(f"--lookup {args.lookup} cannot be combined with --do_sample (a sampled token has no draft to verify)")
     try:
         check_lookup(args.lookup, args.lookup_ngram, 1, who="chat.py")
+        guidance_from_flags(args.guidance_scale, args.guidance_negative, lookup=args.lookup)
     except ValueError as e:
         parser.error(str(e))
     return args
@@ -201,4 +247,4 @@ if __name__ == "__main__":
         raise NotImplementedError("the grounding stack (GroundingDINO / SAM / DEVA / RAM) is outside this package's hot path")
     VideoChatGPTInterface(args_model_name=args.model_name, args_projection_path=args.projection_path, use_asr=args.use_asr,
                           conv_mode=args.conv_mode, do_sample=args.lookup_sample or not args.lookup, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
-                          lookup_sample=args.lookup_sample).interact()
+                          lookup_sample=args.lookup_sample, guidance_scale=args.guidance_scale, guidance_negative=args.guidance_negative).interact()

@@ -101,6 +101,11 @@ struct pgv_kv {
     std::vector<int> ban_host;          // the list words the device copy holds
     bool ban_on = false;
     int ban_gen = 0;                    // bumped by every pgv_kv_set_bans that changes the device copy: part of the decode graphs' key
+    // classifier-free guidance (pgv_kv_set_guidance): slots [0, g_pairs) of a live group of 2 * g_pairs are conditional, slot g_pairs + p is the
+    // unconditional twin of p.  g_logits [B / 2][vocab] (row stride vocab) holds the guided rows the pick reads; allocated when guidance is first
+    // switched on.  g_pairs 0: off
+    float* g_logits = nullptr;
+    int g_pairs = 0; float g_scale = 1.f;
     // row-wise steps (pgv_kv_set_lookup): one allocation by the first call that asks -- a second set of the per-row decode buffers above for up to
     // lk_rows rows that are (slot, offset) pairs, and the row maps (slot [lk_rows] | offset [lk_rows])
     char* lk_blob = nullptr;
@@ -433,6 +438,7 @@ extern "C" void pgv_kv_destroy(pgv_kv* kv) {
     if (kv->bm_blob) (void)hipFree(kv->bm_blob);
     if (kv->ban_blob) (void)hipFree(kv->ban_blob);
     if (kv->lk_blob) (void)hipFree(kv->lk_blob);
+    if (kv->g_logits) (void)hipFree(kv->g_logits);
     delete kv;
 }
 
@@ -518,7 +524,39 @@ static PickParams kv_sampled(const pgv_kv* kv, float temperature, int top_k) {
 
 extern "C" int pgv_kv_set_logprobs(pgv_kv* kv, int on) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_logprobs: null cache");
+    if (on && kv->g_pairs > 0) { pgv_set_error("pgv_kv_set_logprobs: guidance is on in this cache (a guided pick records no log-probabilities)"); return PGV_ESTATE; }
     if (kv->lp_on != (on != 0)) { kv->lp_on = on != 0; kv->lp_steps = -1; }
+    return PGV_OK;
+}
+
+// Classifier-free guidance (pgv.h).  Nothing is copied: the next covered pick reads the two values, and the decode graphs' key carries them.
+extern "C" int pgv_kv_set_guidance(pgv_kv* kv, float scale, int pairs) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_set_guidance: null cache");
+    PGV_CHECK(scale == scale && scale - scale == 0.f, "pgv_kv_set_guidance: scale %g is not finite", (double)scale);
+    PGV_CHECK(pairs >= 0 && 2 * (long long)pairs <= kv->B, "pgv_kv_set_guidance: %d pairs need %lld slots, outside the cache's %d", pairs, 2 * (long long)pairs, kv->B);
+    if (pairs == 0 || scale == 1.f) { kv->g_pairs = 0; kv->g_scale = 1.f; return PGV_OK; }
+    if (kv->lp_on) { pgv_set_error("pgv_kv_set_guidance: pgv_kv_set_logprobs is on in this cache (a guided pick records no log-probabilities)"); return PGV_ESTATE; }
+    if (kv->bm_K > 0) { pgv_set_error("pgv_kv_set_guidance: a beam run is in flight in this cache"); return PGV_ESTATE; }
+    if (kv->lk_D > 0) { pgv_set_error("pgv_kv_set_guidance: pgv_kv_set_lookup is on in this cache (lookup steps verify drafts against the unguided pick)"); return PGV_ESTATE; }
+    if (!kv->g_logits) {
+        const size_t bytes = (size_t)(kv->B / 2) * kv->llm->vocab_cap * 4;
+        hipError_t e = hipMalloc((void**)&kv->g_logits, bytes);
+        if (e != hipSuccess) { kv->g_logits = nullptr; pgv_set_error("pgv_kv_set_guidance: hipMalloc(%zu KiB): %s", bytes >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
+    }
+    kv->g_pairs = pairs; kv->g_scale = scale;
+    return PGV_OK;
+}
+extern "C" int pgv_kv_guidance(const pgv_kv* kv) { return kv ? kv->g_pairs : -1; }
+// a covered call under guidance needs the live group to be exactly the pairs; a call that guidance does not cover is refused outright
+static int guidance_width(const pgv_kv* kv, const char* who) {
+    if (kv->g_pairs > 0 && kv->active != 2 * kv->g_pairs) {
+        pgv_set_error("%s: guidance is on for %d pairs, the live group has %d sequences (need %d)", who, kv->g_pairs, kv->active, 2 * kv->g_pairs);
+        return PGV_ESTATE;
+    }
+    return PGV_OK;
+}
+static int guidance_refuses(const pgv_kv* kv, const char* who) {
+    if (kv && kv->g_pairs > 0) { pgv_set_error("%s: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)", who); return PGV_ESTATE; }
     return PGV_OK;
 }
 
@@ -582,7 +620,7 @@ static PickState kv_state(pgv_kv* kv, int eos, int advance) { return {kv->d_cur,
 // processors applied, made by logit_ban_kernel behind the row statistics: kv->logits itself stays raw for the statistics, a re-pick, a fork and the
 // d_logits outputs.  Row b's sequence is the record of its slot at length ban_lens[b] (null: the cache's positions) -- plus, for the pick of a decode
 // step (AM_INC_POS), the token that step consumed, which the kernel appends to the record.
-static bool kv_greedy_sampled(const pgv_kv* kv) { return kv->warpers.penalty != 1.f || kv->ban_on; }
+static bool kv_greedy_sampled(const pgv_kv* kv) { return kv->warpers.penalty != 1.f || kv->ban_on || kv->g_pairs > 0; }
 static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u, bool u_by_step, const PickState& st, const int* slot_map, hipStream_t s,
                    const int* ban_lens = nullptr) {
     const int V = kv->llm->cfg.vocab;
@@ -594,19 +632,29 @@ static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u,
     }
     if (!sampled) return pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (V + 15) / 16, kv->amax_ts, V, B, st, s, kv->logits, &lp);
     const float* logits = kv->logits;
+    // Guidance: the B = 2P rows of the group become P guided rows -- scale * (log_softmax(row p) - log_softmax(row P + p)) + log_softmax(row P + p) --
+    // in a buffer of their own (kv->logits stays raw); bans, penalty and pick run over those P rows with the conditional slots' records and
+    // seen-sets, the uniforms keep the group's width as their stride, and the follow kernel hands the outcome to the twins.
+    const int P = (kv->g_pairs > 0 && !slot_map) ? kv->g_pairs : 0, rows = P > 0 ? P : B;
+    if (P > 0) {
+        PGV_CHECK(B == 2 * P && st.next == kv->d_cur, "kv_pick: a guided pick runs on the cache's own state at width 2 x pairs");
+        PGV_TRY(pgv_launch_guidance_mix(kv->logits, kv->logits + (size_t)P * V, V, V, P, kv->g_scale, kv->g_logits, V, s));
+        logits = kv->g_logits;
+    }
     if (kv->ban_on) {
         BanArgs a;
-        a.src = kv->logits; a.dst = kv->ban_logits; a.V = V;
+        a.src = logits; a.dst = kv->ban_logits; a.V = V;
         a.ids = kv->ban_ids; a.ids_stride = kv->max_seq; a.slot_map = slot_map; a.lens = ban_lens ? ban_lens : kv->d_pos; a.prompt_lens = kv->ban_plen;
         a.rec = kv->ban_ids; a.cur = kv->d_cur; a.inc = (st.advance & AM_INC_POS) ? 1 : 0;
         a.done = (st.advance & AM_RECORD) ? st.done : nullptr;       // a pick that does not record must not look at a flag an earlier run left set
         a.eos = kv->ban_eos; a.cfg = kv->ban_cfg;
-        PGV_TRY(pgv_launch_logit_ban(a, B, s));
+        PGV_TRY(pgv_launch_logit_ban(a, rows, s));
         logits = kv->ban_logits; lp.banned = 1;
     }
     SampleWarp w;
     w.seen_bits = kv->d_seen; w.seen_words = kv->seen_words; w.seen_slot = slot_map;
-    return pgv_launch_sample(logits, V, B, *sampled, u, B, u_by_step, st, s, &w, &lp);
+    PGV_TRY(pgv_launch_sample(logits, V, rows, *sampled, u, B, u_by_step, st, s, &w, &lp));
+    return P > 0 ? pgv_launch_guidance_follow(P, st, s) : PGV_OK;
 }
 
 // The pick of a beam step on the logits of rows [0, P * K): row statistics, the beam pick (token -> d_cur, parent -> the gather map, both into the
@@ -921,6 +969,7 @@ extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
                                      const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k, const float* d_u, float* d_logits,
                                      int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots, "pgv_llm_prefill_slots: null slot list");
+    PGV_TRY(guidance_refuses(kv, "pgv_llm_prefill_slots"));
     // uniforms: sampled; none: greedy, from the lm_head candidates unless a penalty or a ban applies (prefill_check refuses a null cache)
     const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);
     PrefillReq q;
@@ -936,6 +985,7 @@ extern "C" int pgv_llm_prefill_slots_n(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, con
                                        const int32_t* h_seq_lens, const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k,
                                        const float* d_u, float* d_logits, int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots && h_counts, "pgv_llm_prefill_slots_n: null slot or count list");
+    PGV_TRY(guidance_refuses(kv, "pgv_llm_prefill_slots_n"));
     const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);       // as pgv_llm_prefill_slots
     PrefillReq q;
     q.who = "pgv_llm_prefill_slots_n"; q.mode = PREFILL_SLOTS;
@@ -985,6 +1035,7 @@ extern "C" int pgv_kv_truncate(pgv_kv* kv, int b, int len, void* stream) {
 extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_counts, int P, void* stream) {
     PGV_CHECK(ctx && m && kv && h_counts, "pgv_kv_fork: null argument");
     PGV_CHECK(kv->llm == m, "pgv_kv_fork: kv cache belongs to another model");
+    PGV_TRY(guidance_refuses(kv, "pgv_kv_fork"));
     if (kv->active < 1) { pgv_set_error("pgv_kv_fork: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
     PGV_CHECK(P == kv->active, "pgv_kv_fork: %d counts for a live group of %d sequences", P, kv->active);
     long long W = 0;
@@ -1136,7 +1187,7 @@ static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int fla
 // lookup: the captured steps are lookup steps (pgv_llm_decode_lookup, with AM_SAMPLE pgv_llm_decode_lookup_sample) with the cache's D and n, which join the key
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s, bool lookup = false) {
     const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K, kv->ban_on ? kv->ban_gen : 0, lookup ? kv->lk_D : 0,
-                                                lookup ? kv->lk_n : 0);
+                                                lookup ? kv->lk_n : 0, kv->g_pairs, kv->g_scale);
     if (!(kv->gkey == key)) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->gkey = key;
@@ -1220,6 +1271,7 @@ extern "C" int pgv_llm_decode_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_CHECK(ctx && d_first && d_tokens, "pgv_llm_decode_greedy: null argument");
     PGV_CHECK(n >= 1, "pgv_llm_decode_greedy: n must be positive");
     PGV_TRY(check_decode(m, kv, n, "pgv_llm_decode_greedy"));
+    PGV_TRY(guidance_width(kv, "pgv_llm_decode_greedy"));
     if (!kv_greedy_sampled(kv)) return decode_run(ctx, m, kv, d_first, n, eos_id, nullptr, d_tokens, (hipStream_t)stream);
     const PickParams p = pick_greedy(kv->warpers.penalty);
     PGV_TRY(pgv_zero_uniforms(kv->d_u, (size_t)n * kv->active, (hipStream_t)stream));
@@ -1238,12 +1290,14 @@ static int pick_last(pgv_kv* kv, const PickParams& p, const float* d_u, int32_t*
 extern "C" int pgv_llm_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, float temperature, int top_k, const float* d_u, int32_t* d_next, void* stream) {
     PGV_CHECK(ctx && d_u, "pgv_llm_sample: null argument");
     PGV_TRY(check_decode(m, kv, 0, "pgv_llm_sample"));
+    PGV_TRY(guidance_width(kv, "pgv_llm_sample"));
     return pick_last(kv, kv_sampled(kv, temperature, top_k), d_u, d_next, (hipStream_t)stream);
 }
 
 extern "C" int pgv_llm_pick_greedy(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int32_t* d_next, void* stream) {
     PGV_CHECK(ctx != nullptr, "pgv_llm_pick_greedy: null argument");
     PGV_TRY(check_decode(m, kv, 0, "pgv_llm_pick_greedy"));
+    PGV_TRY(guidance_width(kv, "pgv_llm_pick_greedy"));
     PGV_TRY(pgv_zero_uniforms(kv->d_u, kv->active, (hipStream_t)stream));
     return pick_last(kv, pick_greedy(kv->warpers.penalty), kv->d_u, d_next, (hipStream_t)stream);      // as pgv_llm_decode_greedy steps under a penalty
 }
@@ -1254,6 +1308,7 @@ extern "C" int pgv_llm_decode_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
     PGV_CHECK(n >= 1, "pgv_llm_decode_sample: n must be positive");
     PGV_CHECK(temperature > 0.f, "pgv_llm_decode_sample: temperature must be positive (got %g)", (double)temperature);
     PGV_TRY(check_decode(m, kv, n, "pgv_llm_decode_sample"));
+    PGV_TRY(guidance_width(kv, "pgv_llm_decode_sample"));
     PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)n * kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));     // n <= max_seq (check_decode)
     const PickParams p = kv_sampled(kv, temperature, top_k);
     return decode_run(ctx, m, kv, d_first, n, eos_id, &p, d_tokens, (hipStream_t)stream);
@@ -1308,6 +1363,7 @@ extern "C" int pgv_beam_begin(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const pgv_be
     PGV_CHECK(ctx && m && kv, "pgv_beam_begin: null argument");
     PGV_CHECK(kv->llm == m, "pgv_beam_begin: kv cache belongs to another model");
     PGV_TRY(beam_check_config("pgv_beam_begin", cfg, m->cfg.vocab));
+    PGV_TRY(guidance_refuses(kv, "pgv_beam_begin"));
     if (kv->active < 1) { pgv_set_error("pgv_beam_begin: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
     if (kv->ban_on) { pgv_set_error("pgv_beam_begin: logit bans are set on this cache (pgv_kv_set_bans); the beam pick applies no logits processor"); return PGV_ESTATE; }
     const int P = kv->active, K = cfg->beams, N = cfg->max_new_tokens, B = kv->B;
@@ -1453,6 +1509,7 @@ extern "C" int pgv_kv_set_lookup(pgv_kv* kv, int D, int n) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_lookup: null cache");
     PGV_CHECK(D >= 0 && D <= 15, "pgv_kv_set_lookup: %d draft rows per slot outside [0,15]", D);
     if (D == 0) { kv->lk_D = 0; kv->lk_valid = false; return PGV_OK; }
+    PGV_TRY(guidance_refuses(kv, "pgv_kv_set_lookup"));
     PGV_CHECK(n >= 1 && n <= 4, "pgv_kv_set_lookup: ngram size %d outside [1,4]", n);
     PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_lookup"));
     if (!kv->lk_blob) {
@@ -1515,6 +1572,7 @@ static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int fla
 // what both lookup entries refuse, before any device work
 static int check_lookup_run(pgv_llm* m, pgv_kv* kv, int steps, int eos_id, const int32_t* h_budget, const char* who, const char* verifies) {
     PGV_TRY(check_decode(m, kv, 0, who));
+    PGV_TRY(guidance_refuses(kv, who));
     const int B = kv->active, D = kv->lk_D, W = 1 + D;
     if (D < 1) { pgv_set_error("%s: lookup is off on this cache (pgv_kv_set_lookup)", who); return PGV_ESTATE; }
     if (!kv->lk_valid) { pgv_set_error("%s: the cache's id record does not cover its sequences: set pgv_kv_set_lookup before pgv_llm_prefill and step with pgv_llm_decode_lookup only", who); return PGV_ESTATE; }

@@ -188,6 +188,13 @@ inline BanLists ban_lists(const BanPacked& at, const int* d_blob) {
     return l;
 }
 
+// guidance.hip: classifier-free guidance (pgv.h: pgv_kv_set_guidance).
+// mix: pair p of P reads cond[p * ld ..) and uncond[p * ld ..) over columns [0, V) and writes out[p * ld_out ..) = scale * (lc - lu) + lu with lc / lu
+// the rows' log-softmax (row_lse_kernel's statistics, bit for bit).  Any strides >= V, 4-byte alignment.
+int pgv_launch_guidance_mix(const float* cond, const float* uncond, int ld, int V, int P, float scale, float* out, int ld_out, hipStream_t s);
+// follow: behind a pick on rows [0, P) with state `st` (the cache's own), slot P + p takes slot p's token and done flag and advances as st.advance says
+int pgv_launch_guidance_follow(int P, const PickState& st, hipStream_t s);
+
 // score.hip: per-row log-probability of targets[r] / logsumexp / argmax over columns [0, V) of fp32 logits [R, ld]; row r writes at index
 // out_rows[r] (null: r).  Timed under family 6.
 int pgv_launch_logprob_rows(pgv_ctx* ctx, const float* logits, int ld, int V, int R, const int* targets, const int* out_rows, float* logprob, float* lse,

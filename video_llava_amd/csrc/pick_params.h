@@ -29,12 +29,14 @@ struct DecodeGraphKey {
     int beams = 0;          // AM_BEAM: the group width K of the run (the grid of the gather and the slots a pick writes); every other beam parameter lives in device memory
     int bans = 0;           // pgv_kv_set_bans: the generation counter of the cache's ban configuration (0: none) -- the ban kernel's launch and its list lengths are baked in
     int lookup_D = 0, lookup_n = 0;      // pgv_llm_decode_lookup: drafts per slot and ngram size of the captured lookup steps (0: plain token steps)
+    int guide_pairs = 0; float guide_scale = 1.f;      // pgv_kv_set_guidance: the mix and follow launches bake in the pair count and the scale (0, 1: off)
     bool operator==(const DecodeGraphKey& o) const {
         return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick && beams == o.beams && bans == o.bans &&
-               lookup_D == o.lookup_D && lookup_n == o.lookup_n;
+               lookup_D == o.lookup_D && lookup_n == o.lookup_n && guide_pairs == o.guide_pairs && guide_scale == o.guide_scale;
     }
 };
 inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight, int beams = 0, int bans = 0,
-                                       int lookup_D = 0, int lookup_n = 0) {
-    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0, bans, lookup_D, lookup_n};
+                                       int lookup_D = 0, int lookup_n = 0, int guide_pairs = 0, float guide_scale = 1.f) {
+    return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0, bans, lookup_D, lookup_n,
+            guide_pairs, guide_pairs > 0 ? guide_scale : 1.f};
 }

@@ -81,6 +81,8 @@ def add_runtime_arguments(parser):
                         help="--lookup D --do_sample: lookup steps for the sampled run (generate(lookup_sample=True)) -- every draft is verified against the "
                              "pick from the uniform the plain run draws for that token, so the answers are bit for bit those of --do_sample alone; lifts "
                              "only the --do_sample refusal of --lookup")
+    from ..chat import add_guidance_flags
+    add_guidance_flags(parser)          # --guidance_scale S / --guidance_negative: --batch and --batch auto count two rows per clip
     parser.add_argument("--timings", default=None, metavar="OUT.jsonl",
                         help="append one JSON line per answered task (rank-local file `OUT.jsonl.rank<r>` when world > 1): frame load, upload + ingest, "
                              "tower + pool, prefill, decode seconds, generated tokens, group size, feature-cache hit (SURVEY 5: per-clip stage timings)")
@@ -103,6 +105,7 @@ def add_runtime_arguments(parser):
                 raise ValueError("--min_p / --typical_p / --epsilon_cutoff / --eta_cutoff need --do_sample (they filter a sampled pick)")
             K, _, _ = check_beam_args(ns)
             lookup_from_args(ns)
+            guidance_scale_from_args(ns)
             if bans_from_args(ns) and K > 1:        # validates the three flags, HF's wording
                 raise ValueError(f"--beams {K} cannot be combined with --no_repeat_ngram / --min_new_tokens / --suppress_tokens (the beam pick applies "
                                  f"no logits processor)")
@@ -148,6 +151,18 @@ def lookup_from_args(ns) -> dict:
     if batch != "auto" and batch * (1 + D) > MAX_BATCH:
         raise ValueError(f"--batch {batch} clips x (1 + --lookup {D}) rows exceed the {MAX_BATCH} rows of a decode step")
     return {"lookup": D, "lookup_ngram": n, **({"lookup_sample": True} if sampled else {})}
+
+
+def guidance_scale_from_args(ns):
+    """--guidance_scale / --guidance_negative of a parsed command line -> the scale (None: off); ValueError names the flag guidance cannot run
+    with.  A group holds --batch clips x 2 rows: the clip's prompt and its negative."""
+    from ..chat import guidance_from_flags
+    scale = guidance_from_flags(getattr(ns, "guidance_scale", None), getattr(ns, "guidance_negative", "no_video"), getattr(ns, "lookup", 0),
+                                getattr(ns, "beams", 1), getattr(ns, "samples_per_prompt", 1), getattr(ns, "schedule", "group"))
+    batch = getattr(ns, "batch", "auto")
+    if scale is not None and batch != "auto" and 2 * batch > MAX_BATCH:
+        raise ValueError(f"--batch {batch} clips x 2 rows under --guidance_scale exceed the {MAX_BATCH} rows of a decode step")
+    return scale
 
 
 def check_beam_args(ns):
@@ -423,6 +438,19 @@ class _Runner:
         given = {"top_p": getattr(self.args, "top_p", None), "repetition_penalty": getattr(self.args, "repetition_penalty", None)}
         return {k: v for k, v in given.items() if v is not None}
 
+    def guidance(self, idxs) -> dict:
+        """--guidance_scale / --guidance_negative as generate()'s `guidance` for the tasks idxs ({}: off): the "no_video" negative of a task is its
+        conversation prompt built without the video tokens."""
+        from ..guidance import Guidance
+        from ..inference import build_prompt
+        scale = guidance_scale_from_args(self.args)
+        if scale is None:
+            return {}
+        if getattr(self.args, "guidance_negative", "no_video") == "last_token":
+            return {"guidance": Guidance(scale, "last_token")}
+        texts = [build_prompt(self.tasks[i]["question"], self.args.conv_mode, self.video_token_len, self.use_se, video=False)[0] for i in idxs]
+        return {"guidance": Guidance(scale, [list(self.tokenizer([t]).input_ids[0]) for t in texts])}
+
     def infer_batch(self, indices, clips=None):
         """--schedule group -> (tokens [n, <= max_new] int32, lengths).  DEVICE half of a group: ONE tower pass over the frames of all distinct
         uncached clips of the group, then batched prefill + decode with the per-chunk stop-string check."""
@@ -448,7 +476,7 @@ class _Runner:
             return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
                                        do_sample=False, max_new_tokens=self.args.max_new_tokens, stop_strings=[s for _, _, _, s in part],
                                        tokenizer=self.tokenizer, timings=timings, **self.warpers(), **bans_from_args(self.args),
-                                       **lookup_from_args(self.args)).cpu()
+                                       **lookup_from_args(self.args), **self.guidance([indices[j] for j, _, _, _ in part])).cpu()
 
         def record(part, out):
             for row, (j, ids, _, _) in zip(out, part):
@@ -551,7 +579,7 @@ class _Runner:
     def infer_sampled(self, indices, clips=None):
         """--do_sample (--schedule group): the reference's temperature-0.2 sampling with its stopping criterion, one task at a time
         (video_chatgpt_infer's path up to the detokenisation); the ids travel through the same fixed-shape collation as the greedy answers."""
-        from ..inference import video_chatgpt_infer_ids
+        from ..inference import guidance_kwargs, video_chatgpt_infer_ids
         if clips is None:
             clips = self.prepare(indices)
         clips.pop("__load_s__", None)
@@ -567,7 +595,8 @@ class _Runner:
                 new, stop = video_chatgpt_infer_ids(None, t["question"], self.args.conv_mode, self.model, self.vision_tower, self.tokenizer,
                                                     self.image_processor, self.video_token_len, None, max_new_tokens=self.args.max_new_tokens,
                                                     features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args), **filters_from_args(self.args),
-                                                    **lookup_from_args(self.args))      # --lookup D --lookup_sample: the same ids in fewer passes
+                                                    **lookup_from_args(self.args),      # --lookup D --lookup_sample: the same ids in fewer passes
+                                                    **guidance_kwargs(guidance_scale_from_args(self.args), getattr(self.args, "guidance_negative", "no_video")))
                 self.stop_strs[idx] = stop
                 self.record(toks, lens, j, new, strip_eos=False)       # the ids end where the reference's criterion stopped them
             except Exception as e:                                     # noqa: BLE001
@@ -609,6 +638,8 @@ def answer_tasks(args, tasks, components, load_frames, rank, world):
             args.batch = max(1, args.batch // beams)                   # a clip holds K decode slots: the same number of sequences per group
         if int(getattr(args, "lookup", 0) or 0) > 0:
             args.batch = max(1, min(args.batch, MAX_BATCH // (1 + int(args.lookup))))      # a clip holds 1 + D rows of a lookup step
+        if guidance_scale_from_args(args) is not None:
+            args.batch = max(1, args.batch // 2)                       # a clip holds two decode slots: its prompt and its negative
         if rank == 0:
             print(f"[pgv] --batch auto: {args.batch} clips per group ({free_b / 2 ** 30:.0f} GiB free on {device}, shared by {sharers})", flush=True)
     spill = os.path.join(args.output_dir, args.output_name) if getattr(args, "output_dir", None) and getattr(args, "output_name", None) else None

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .generation import GenerateBeamsOutput, GenerateLogprobsOutput, fork_sources
+from .guidance import stack_features
 from .model.utils import AnswerState
 
 
@@ -30,9 +31,10 @@ def fill_timings(timings, t0: float, t1: float, steps: int, batch: int, **more):
 
 @contextmanager
 def open_cache(model, plan, seqs, feats, kv_reuse_key):
-    """The filled cache of the call -> (kv, the prefill's first tokens, B, seqs, stops, reused), by one of three routes: the cache kept under
+    """The filled cache of the call -> (kv, the prefill's first tokens, B, seqs, stops, reused), by one of four routes: the cache kept under
     `kv_reuse_key` truncated to the common prefix plus an append of the new tokens; one prefill at capacity B * n forked n ways (from there on
-    the call IS the call on the prompts repeated n times each); or a plain prefill.  It is the scope of the cache's settings: on from the
+    the call IS the call on the prompts repeated n times each); under guidance one ragged prefill of the B prompts and their B negatives (slot
+    B + b is the unconditional twin of b; B stays the number of answers); or a plain prefill.  It is the scope of the cache's settings: on from the
     prefill, off again however the call ends -- a refused fork, a criterion, the tokenizer or an interrupt included."""
     B, n, stops, on = len(seqs), plan.samples_per_prompt, plan.stops, plan.settings
     reused = 0
@@ -45,6 +47,10 @@ def open_cache(model, plan, seqs, feats, kv_reuse_key):
         if reused < len(model._reuse[3]):
             model.kv_truncate(kv, 0, reused)
         _kv, nxt, _ = model.prefill([seqs[0][reused:]], None, 0, append_to=kv, **on.prefill_kwargs())
+    elif plan.guidance is not None:
+        negs = [list(x) for x in plan.negatives]
+        both = stack_features(feats, plan.guidance.negative_feats, negs, getattr(model.model.vision_config, "vid_patch_token", None))
+        kv, nxt, _ = model.prefill(list(seqs) + negs, both, plan.max_seq, **on.prefill_kwargs())
     else:
         kv, nxt, _ = model.prefill(seqs, feats, plan.max_seq, **({"capacity": B * n} if n > 1 else {}), **on.prefill_kwargs())
     try:
@@ -60,14 +66,19 @@ def open_cache(model, plan, seqs, feats, kv_reuse_key):
 
 def first_pick(model, plan, kv, nxt, B: int, generator):
     """-> (the call's uniforms [max_new_tokens, B] or None, first tokens [B] on the device, the log-probability blocks so far).  A sampled call
-    draws; greedy under a penalty or bans re-picks over the processed logits (the prefill's argmax knows neither; first index on ties)."""
+    draws; greedy under a penalty, bans or guidance re-picks over the processed logits (the prefill's argmax knows none of them; first index on
+    ties).  Under guidance the group is 2B wide: the uniforms are the B columns of the call padded to that width (the twins' columns are never
+    read), and the tokens come back 2B long, rows [B, 2B) repeating rows [0, B)."""
     u, lp_parts = None, []              # lp_parts: [2, B, steps] blocks in generation order (first token, then every chunk)
+    W = 2 * B if plan.guidance is not None else B
     if plan.max_new_tokens >= 1:
         if plan.do_sample:
             u = torch.rand(plan.max_new_tokens, B, device=model.device_, dtype=torch.float32, generator=generator)
+            if W != B:
+                u = torch.nn.functional.pad(u, (0, W - B))
             nxt = model.sample_last(kv, u[0], plan.temperature, plan.top_k, **plan.warp)
-        elif plan.repetition_penalty != 1.0 or plan.bans_on:
-            nxt = model.greedy_last(kv, B, **plan.pen)
+        elif plan.repetition_penalty != 1.0 or plan.bans_on or W != B:
+            nxt = model.greedy_last(kv, W, **plan.pen)
         if plan.output_logprobs:
             lp_parts.append(model.logprobs_last(kv, B)[:, :, None])
     return u, nxt, lp_parts
@@ -125,6 +136,8 @@ class PlainStep:
             toks = m.decode_greedy(kv, nxt, n, p.eos_id, **p.pen)
         if p.output_logprobs:
             self.lp_parts.append(m.logprobs_steps(kv, self.B, n))
+        if p.guidance is not None:          # the group is 2B wide; the twins' rows repeat the answers' and stay on the device
+            return toks[:self.B].cpu().numpy(), np.full(self.B, n), toks[:, n - 1].contiguous()
         return toks.cpu().numpy(), np.full(self.B, n), toks[:, n - 1].contiguous()
 
     def steps(self, n_gen: int, stop: bool, taken: int, answers) -> int:
@@ -169,7 +182,7 @@ def generate_chunks(model, plan, seqs, feats, generator, tokenizer, timings, kv_
         step = LookupStep(model, plan, kv, u) if plan.lookup[0] else PlainStep(model, plan, kv, B, u, lp_parts)
         n_gen, t1 = 0, t0
         if plan.max_new_tokens >= 1:
-            stop, _ = answers.absorb(nxt.cpu().numpy()[:, None], np.ones(B, dtype=np.int64))
+            stop, _ = answers.absorb(nxt[:B].cpu().numpy()[:, None], np.ones(B, dtype=np.int64))
             t1, n_gen = time.perf_counter(), 1
             while not stop and n_gen < step.limit:
                 h, runs, nxt = step(nxt, n_gen, answers)

@@ -13,6 +13,7 @@ import os
 from dataclasses import dataclass
 from typing import Any, Dict, Optional, Sequence, Tuple
 
+from .guidance import check_guidance
 from .logit_bans import LogitBans, check_bans
 from .sample_filters import check_filters
 
@@ -310,12 +311,14 @@ def step_kwargs(top_p: float, repetition_penalty: float) -> Tuple[dict, dict]:
 class CacheSettings:
     """What a KV cache is switched to for the length of ONE call, and the one scope that does it: `apply` (or the prefill, for what it takes)
     switches on what is on, `clear` switches off exactly that.  logprobs: True records log-probabilities (False: `apply` turns the switch off, None
-    leaves it).  bans: a checked LogitBans with the `eos_id` its length rules ban; filters: a checked SampleFilters; lookup: (D, n).  None: off."""
+    leaves it).  bans: a checked LogitBans with the `eos_id` its length rules ban; filters: a checked SampleFilters; lookup: (D, n); guidance:
+    (scale, pairs), switched on behind the prefill of prompts + negatives (no prefill takes it: its own first token is not a covered pick).  None: off."""
     logprobs: Optional[bool] = None
     bans: Any = None
     eos_id: int = -1
     filters: Any = None
     lookup: Optional[Tuple[int, int]] = None
+    guidance: Optional[Tuple[float, int]] = None
 
     def prefill_kwargs(self) -> dict:
         """The keywords of model.prefill that are on: it sets them before the prompt runs, so that the first pick and the id record see them."""
@@ -337,6 +340,8 @@ class CacheSettings:
                 model.set_lookup(kv, *self.lookup)
         if self.filters is not None:
             model.set_filters(kv, self.filters)
+        if self.guidance is not None:
+            model.set_guidance(kv, *self.guidance)
 
     def clear(self, model, kv):
         if self.logprobs:
@@ -347,6 +352,8 @@ class CacheSettings:
             model.set_filters(kv, None)
         if self.lookup is not None:
             model.set_lookup(kv, 0)
+        if self.guidance is not None:
+            model.set_guidance(kv, 1.0, 0)
 
 
 @dataclass(frozen=True)
@@ -377,6 +384,8 @@ class GenerationPlan:
     lookup_sample: bool
     criteria: tuple = ()
     stops: Optional[list] = None
+    guidance: Any = None            # the checked guidance.Guidance of a guided call (None: off) and its negatives, one id list per prompt
+    negatives: Optional[tuple] = None
 
     @property
     def warp(self) -> dict:
@@ -389,13 +398,14 @@ class GenerationPlan:
     @property
     def settings(self) -> CacheSettings:
         return CacheSettings(True if self.output_logprobs else None, self.bans if self.bans_on else None, self.eos_id,
-                             self.filters if self.filters_on else None, self.lookup if self.lookup[0] else None)
+                             self.filters if self.filters_on else None, self.lookup if self.lookup[0] else None,
+                             (self.guidance.scale, len(self.negatives)) if self.guidance is not None else None)
 
 
 def plan_generate(model, seqs, do_sample=False, temperature=None, max_new_tokens=1024, stopping_criteria=None, eos_token_id="config", chunk=32,
                   top_k=None, stop_strings=None, tokenizer=None, kv_reuse_key=None, top_p=None, repetition_penalty=None, output_logprobs=False,
                   samples_per_prompt=1, beams=1, length_penalty=None, early_stopping=None, output_beam_scores=False, bans=None, filters=None,
-                  lookup=0, lookup_ngram=2, lookup_sample=False, unused=None) -> GenerationPlan:
+                  lookup=0, lookup_ngram=2, lookup_sample=False, unused=None, guidance=None) -> GenerationPlan:
     """The plan of generate(seqs, ...) -- its keywords under their own names, `unused` what fell into **_unused -- or the first ValueError of the
     call: every check in the order generate() has always made them, on the host.  Of `model` only generation_config, config and (under `bans`)
     vocab_size are read."""
@@ -434,6 +444,15 @@ def plan_generate(model, seqs, do_sample=False, temperature=None, max_new_tokens
             if len(stops) != B or tokenizer is None:
                 raise ValueError("stop_strings needs one entry per sequence and the tokenizer that decodes them")
             stops = stops if any(stops) else None
+    # guidance: after every other check, so that the first error of a faulty call stays what it has always been
+    guide = check_guidance(guidance, seqs, None if guidance is None else model.vocab_size, K, look[0], n_samples, reuse, bool(output_logprobs))
+    negatives = None
+    if guide is not None:
+        negatives = tuple(tuple(n) for n in guide.negatives(seqs))
+        longest = max(len(n) for n in negatives) + max_new_tokens
+        if longest > model.config.max_position_embeddings:
+            raise ValueError(f"`guidance` negative + max_new_tokens = {longest} exceeds max_position_embeddings {model.config.max_position_embeddings}")
+        max_seq = max(max_seq, (longest + 63) // 64 * 64)
     return GenerationPlan(sample, temperature, top_k, top_p, rep_pen, max_new_tokens, eos_i, chunk, max_seq, K, length_penalty, early_stopping,
                           bool(output_beam_scores), n_samples, bool(output_logprobs), ban, ban_on, filt, sample and not filt.neutral, look,
-                          bool(lookup_sample), tuple(criteria), stops)
+                          bool(lookup_sample), tuple(criteria), stops, guide, negatives)

@@ -31,9 +31,12 @@ def get_spatio_temporal_features_torch(features: torch.Tensor) -> torch.Tensor:
     return _lib.Context.get(features.device).st_pool(features, NUM_TEMPORAL_TOKENS, torch.float16)
 
 
-def build_prompt(question: str, conv_mode: str, video_token_len: int, use_vid_start_end: bool, transcript=None):
-    """Prompt string + stop string exactly as video_chatgpt_infer assembles them (inference.py:66-80,101)."""
-    if use_vid_start_end:
+def build_prompt(question: str, conv_mode: str, video_token_len: int, use_vid_start_end: bool, transcript=None, video: bool = True):
+    """Prompt string + stop string exactly as video_chatgpt_infer assembles them (inference.py:66-80,101).  video=False: the same conversation
+    without the video tokens -- the "no_video" negative prompt of classifier-free guidance (guidance_for)."""
+    if not video:
+        qs = question + "\n"
+    elif use_vid_start_end:
         qs = question + "\n" + DEFAULT_VID_START_TOKEN + DEFAULT_VIDEO_PATCH_TOKEN * video_token_len + DEFAULT_VID_END_TOKEN
     else:
         qs = question + "\n" + DEFAULT_VIDEO_PATCH_TOKEN * video_token_len
@@ -44,6 +47,26 @@ def build_prompt(question: str, conv_mode: str, video_token_len: int, use_vid_st
     conv.append_message(conv.roles[1], None)
     stop_str = conv.sep if conv.sep_style != SeparatorStyle.TWO else conv.sep2
     return conv.get_prompt(), stop_str
+
+
+def guidance_for(guidance_scale, guidance_negative, question: str, conv_mode: str, tokenizer, video_token_len: int, use_vid_start_end: bool,
+                 transcript=None):
+    """`guidance_scale` / `guidance_negative` of the single-clip entry points as the `guidance` argument of model.generate (None: off -- no scale,
+    or scale 1).  guidance_negative: "no_video" (default) -- the same conversation prompt built without the video tokens, i.e. contrast decoding
+    against what the language model would say without the clip; "last_token" -- HF's default, the prompt's last id; any other string -- a
+    negative prompt text, tokenised as it is."""
+    from .guidance import Guidance
+    if guidance_scale is None or float(guidance_scale) == 1.0:
+        return None
+    if not isinstance(guidance_negative, str):
+        raise ValueError(f"`guidance_negative` has to be \"no_video\", \"last_token\" or a negative prompt text, but is {guidance_negative!r}")
+    if guidance_negative == "last_token":
+        return Guidance(float(guidance_scale), "last_token")
+    if guidance_negative == "no_video":
+        text, _ = build_prompt(question, conv_mode, video_token_len, use_vid_start_end, transcript, video=False)
+    else:
+        text = guidance_negative
+    return Guidance(float(guidance_scale), [list(tokenizer([text]).input_ids[0])])
 
 
 def frames_to_pixels(video_frames, image_processor, vision_tower) -> torch.Tensor:
@@ -144,8 +167,15 @@ def video_features_batch(clips, vision_tower, image_processor, timings=None):
 
 def _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len, transcript, do_sample,
                     temperature, max_new_tokens, features, generate_kwargs):
-    """The generate() call of `video_chatgpt_infer` -> (what generate returned, its sequences, prompt length, stop string)."""
-    prompt, stop_str = build_prompt(question, conv_mode, video_token_len, model.get_model().vision_config.use_vid_start_end, transcript)
+    """The generate() call of `video_chatgpt_infer` -> (what generate returned, its sequences, prompt length, stop string).  The keywords
+    `guidance_scale` / `guidance_negative` among generate_kwargs become generate's `guidance` (guidance_for)."""
+    use_se = model.get_model().vision_config.use_vid_start_end
+    prompt, stop_str = build_prompt(question, conv_mode, video_token_len, use_se, transcript)
+    generate_kwargs = dict(generate_kwargs)
+    scale, negative = generate_kwargs.pop("guidance_scale", None), generate_kwargs.pop("guidance_negative", "no_video")
+    guide = guidance_for(scale, negative, question, conv_mode, tokenizer, video_token_len, use_se, transcript)
+    if guide is not None:
+        generate_kwargs["guidance"] = guide
     inputs = tokenizer([prompt])
     feats = features if features is not None else video_features(video_frames, vision_tower, image_processor)
     input_ids = torch.as_tensor(inputs.input_ids)
@@ -172,9 +202,16 @@ def video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tow
     return output_ids[0, n_in:].tolist(), stop_str
 
 
+def guidance_kwargs(guidance_scale, guidance_negative) -> dict:
+    """The two guidance keywords as _infer_generate takes them: {} when no scale asks anything, so that a plain call stays the call it has always been."""
+    if guidance_scale is None or float(guidance_scale) == 1.0:
+        return {}
+    return {"guidance_scale": guidance_scale, "guidance_negative": guidance_negative}
+
+
 def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                         transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, bans=None, filters=None, lookup=0,
-                        lookup_ngram=2, lookup_sample=False):
+                        lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video"):
     """Answer `question` about one clip.  Same positional signature and defaults as the reference
     (video_chatgpt/inference.py:47; do_sample=True, temperature=0.2, max_new_tokens=1024 at :109-111); pass
     do_sample=False for deterministic greedy decoding.  `features`: pooled features computed earlier (skips the tower).  `bans`
@@ -183,24 +220,30 @@ def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, 
     behind top_p -- min_p, typical_p, epsilon_cutoff, eta_cutoff -- passed to model.generate(filters=) as it is.  `lookup` = D > 0 (needs
     do_sample=False): prompt-lookup speculative decoding, model.generate(lookup=D, lookup_ngram=n) -- the same answer in fewer passes over the weights.
     `lookup_sample=True` (with lookup = D > 0 and do_sample=True): the sampled form, model.generate(lookup_sample=True) -- bit for bit the sampled
-    answer of the call without the two keywords for the same generator state."""
+    answer of the call without the two keywords for the same generator state.  `guidance_scale` = s (None or 1: off): classifier-free guidance,
+    model.generate(guidance=) -- every pick reads s * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond), `uncond` the logits of
+    `guidance_negative`: "no_video" (the same conversation prompt without the video tokens: contrast decoding against the language prior),
+    "last_token" (HF's default negative) or a negative prompt text."""
     new_ids, stop_str = video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                                 transcript, do_sample, temperature, max_new_tokens, features,
-                                                **given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample))
+                                                **given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample),
+                                                **guidance_kwargs(guidance_scale, guidance_negative))
     outputs = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0]
     return outputs.strip().rstrip(stop_str).strip()
 
 
 def video_chatgpt_infer_logprobs(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                  transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, bans=None, filters=None, lookup=0,
-                                 lookup_ngram=2, lookup_sample=False, **generate_kwargs):
+                                 lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video", **generate_kwargs):
     """`video_chatgpt_infer` that also says how probable the answer it produced was (model.generate(output_logprobs=True): recorded on the device
     at pick time, no second prefill).  Returns a dict: "text" (what video_chatgpt_infer returns), "ids" (the generated token ids),
     "token_logprobs" (per id, the model's own log-probability: HF's compute_transition_scores on the raw logits -- what video_chatgpt_score
     gives for the same ids), "transition_scores" (per id, the log of the probability the pick used, after repetition penalty / temperature /
     top-k / top-p) and "logprob" (the fp64 sum of token_logprobs).  `lookup` / `lookup_sample` keep the signature of
-    video_chatgpt_infer; lookup steps record no log-probabilities, so anything but 0 / False is refused by generate()."""
-    asked = given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample)
+    video_chatgpt_infer; lookup steps record no log-probabilities, so anything but 0 / False is refused by generate().  `guidance_scale` /
+    `guidance_negative` likewise: a guided pick records none, so a scale other than None / 1 is refused by generate()."""
+    asked = dict(given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample),
+                 **guidance_kwargs(guidance_scale, guidance_negative))
     out, output_ids, n_in, stop_str = _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                                       transcript, do_sample, temperature, max_new_tokens, features,
                                                       dict(generate_kwargs, output_logprobs=True, **asked))

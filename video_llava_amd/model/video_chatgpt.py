@@ -519,6 +519,16 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         cfg = _lib.BanConfig.from_bans(bans, -1 if eos_id is None else int(eos_id))
         _lib.check(self.ctx.lib.pgv_kv_set_bans(kv, C.byref(cfg)), "pgv_kv_set_bans")
 
+    def set_guidance(self, kv, scale: float = 1.0, pairs: int = 0):
+        """pgv_kv_set_guidance: classifier-free guidance for every later covered pick on this cache -- slots [0, pairs) of a live group of 2 * pairs are
+        the conditional sequences, slot pairs + p the unconditional twin of p (prefill prompts + negatives as one batch).  scale 1 or pairs 0: off."""
+        _lib.check(self.ctx.lib.pgv_kv_set_guidance(kv, float(scale), int(pairs)), "pgv_kv_set_guidance")
+
+    def guidance_logits(self, cond: torch.Tensor, uncond: torch.Tensor, scale: float) -> torch.Tensor:
+        """pgv_guidance_logits: scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond) on fp32 logits [P, vocab] -> [P, vocab], the
+        kernel a guided pick reads its rows from (guidance.guided_scores is the rule in fp64)."""
+        return self.ctx.guidance_logits(cond.to(device=self.device_, dtype=torch.float32), uncond.to(device=self.device_, dtype=torch.float32), scale)
+
     def ids_peek(self, kv, slot: int, n: int):
         """pgv_kv_ids_peek (test read-back): (the first n ids of the slot's record as a list, the slot's prompt length)."""
         out = torch.empty(int(n) + 1, dtype=torch.int32, device=self.device_)
@@ -762,7 +772,8 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  stop_strings: Optional[Sequence[Optional[str]]] = None, tokenizer=None, timings: Optional[dict] = None,
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  samples_per_prompt: int = 1, beams: int = 1, length_penalty: Optional[float] = None, early_stopping=None,
-                 output_beam_scores: bool = False, bans=None, filters=None, lookup: int = 0, lookup_ngram: int = 2, lookup_sample: bool = False, **_unused):
+                 output_beam_scores: bool = False, bans=None, filters=None, lookup: int = 0, lookup_ngram: int = 2, lookup_sample: bool = False,
+                 guidance=None, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -840,11 +851,21 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         token (pgv.h: pgv_llm_decode_lookup_sample), and a draft is kept exactly when it equals that pick.  The returned tensor is therefore bit for
         bit the one of generate(do_sample=True) with the same generator -- not merely equal in distribution -- under any temperature, top_k, top_p
         and `filters`.  A draft x is kept with the probability p(x) the pick gives it, which is HF's speculative acceptance min(1, p / q) for a
-        one-hot draft distribution q; how often that happens on real answers is unmeasured.  The other refusals of `lookup` stay."""
+        one-hot draft distribution q; how often that happens on real answers is unmeasured.  The other refusals of `lookup` stay.
+        `guidance` (a keyword of this package: guidance.Guidance, a scale, a dict of its fields, or None; HF's `guidance_scale` /
+        `negative_prompt_ids` name the same two things and are not arguments here): classifier-free guidance, HF's
+        UnbatchedClassifierFreeGuidanceLogitsProcessor -- every pick reads scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond),
+        `uncond` the logits of a negative prompt ("last_token" / None: HF's default, each prompt's last id; or one id list per prompt, e.g. the same
+        question without the video: contrast decoding against the language prior).  The negatives are prefilled with the prompts as one ragged
+        batch and run as B more rows of every token step; the mix is a kernel between the lm_head and the pick (pgv.h: pgv_kv_set_guidance), at
+        HF's place in the chain: in front of the repetition penalty, the bans and the warpers, which all see the guided scores.  Combines with
+        sampling, temperature, top_k, top_p, `filters`, repetition_penalty, `bans`, `stop_strings` and `stopping_criteria`; the uniforms stay
+        torch.rand(max_new_tokens, B).  Refused with beams > 1, lookup, samples_per_prompt > 1, kv_reuse_key, output_logprobs and B > 32
+        (guidance.check_guidance).  None or scale 1 is the call without the keyword, bit for bit."""
         seqs = [row.tolist() for row in input_ids.cpu()] if torch.is_tensor(input_ids) else [list(s) for s in input_ids]
         plan = plan_generate(self, seqs, do_sample, temperature, max_new_tokens, stopping_criteria, eos_token_id, chunk, top_k, stop_strings, tokenizer,
                              kv_reuse_key, top_p, repetition_penalty, output_logprobs, samples_per_prompt, beams, length_penalty, early_stopping,
-                             output_beam_scores, bans, filters, lookup, lookup_ngram, lookup_sample, unused=_unused)
+                             output_beam_scores, bans, filters, lookup, lookup_ngram, lookup_sample, unused=_unused, guidance=guidance)
         if plan.beams > 1:
             return generate_loop.generate_beams(self, plan, seqs, video_spatio_temporal_features, timings)
         return generate_loop.generate_chunks(self, plan, seqs, video_spatio_temporal_features, generator, tokenizer, timings, kv_reuse_key)
