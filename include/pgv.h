@@ -596,6 +596,75 @@ int pgv_guidance_logits(pgv_ctx *ctx, const float *d_cond, const float *d_uncond
 int pgv_kv_set_guidance(pgv_kv *kv, float scale, int pairs);
 int pgv_kv_guidance(const pgv_kv *kv);
 
+/* Constrained decoding: HF's PrefixConstrainedLogitsProcessor (generation/logits_process.py; generate(prefix_allowed_tokens_fn = fn), built by
+ * GenerationMixin._get_logits_processor behind the bans and in front of the warpers), with the Python callback replaced by a deterministic token
+ * AUTOMATON that the device follows.  It writes -inf or nothing, like every ban, so its order against the bans and the repetition penalty does not
+ * change the result: it runs at the bans' place, between the lm_head and the pick.
+ * The automaton: states 0 .. S - 1; the edges of state s are entries [row_ptr[s], row_ptr[s + 1]) of edge_token / edge_next, their tokens in
+ * [0, vocab), strictly rising within a state (sorted, distinct), their targets states; accept[s] != 0 marks a state in which the answer may end.
+ * DEAD is the state -1.  With P the prompt length of a slot (the length after its last prefill; for pgv_llm_prefill_append the total after the
+ * append, so the next answer starts at the root again), r its root and g the ids at cache positions [P, L) -- every token a covered pick returned
+ * and a later step consumed:
+ *  - the walk: q = r; for every t of g: q = the target of t's edge in q, DEAD when q has none; DEAD stays DEAD.
+ *  - the allowed set of the pick at length L: the tokens of q's edges, plus eos_id when q accepts; when q is DEAD or has no edge: {eos_id} alone
+ *    (the answer ends; HF raises for an empty list instead).  Every score outside the set becomes -inf; a score inside it keeps its bits, NaN
+ *    and -inf included.
+ * Limits (PGV_EINVAL, the message names the value): 1 <= S <= PGV_ALLOW_MAX_STATES, 0 <= E <= PGV_ALLOW_MAX_EDGES, eos_id in [0, vocab) -- the rule
+ * needs it --, every root in [0, S), a vocabulary of at most 65536 (the allowed set is an LDS bitmap), and the shape above (row_ptr rising from 0 to
+ * E, tokens sorted and distinct, targets in range): the kernel then reads inside the arrays whatever the record holds.
+ *
+ * pgv_kv_set_allowed (modelled on pgv_kv_set_bans): the automaton of every later COVERED pick on this cache; NULL turns the feature off, and every
+ *   launch, captured graph and token is then what it is without this call.  h_roots [batch]: the root of every slot (NULL: all 0), written when
+ *   the call is made.  Set it before the prefill of the sequences it is meant for: while it is on, the prefill calls write each slot's prompt length
+ *   (and ids) to the record of pgv_kv_set_bans, which it shares.  The state record int32 [batch][max_seq], indexed by cache position like the id record
+ *   (entry pos >= P: the state after the ids at [P, pos]; so pgv_kv_truncate needs no action), the roots [batch] and the device copy of the automaton
+ *   are allocated by the first configuration that asks; the copy grows with the automaton.  The kernel of a decode step does ONE edge lookup: it reads
+ *   the state before the step's position (the root at P), follows the edge of the token the step consumes and stores the new state at the position;
+ *   a pick that advances nothing (pgv_llm_sample, pgv_llm_pick_greedy, the first token of a refill) reads the state and stores nothing.  No walk from
+ *   the root, no host round trip; inside the captured decode graphs, whose key carries a generation counter that moves when the uploaded automaton
+ *   changes.  Synchronises the device.
+ *   pgv_kv_fork copies a source's state rows [0, len) and root to its destinations; pgv_llm_prefill_slots / _slots_n give every slot they fill
+ *   root 0 (one automaton for every task of a refill run).
+ *   Covered picks: pgv_llm_sample, pgv_llm_pick_greedy, every step of pgv_llm_decode_greedy / _sample, and the first token of
+ *   pgv_llm_prefill_slots / _slots_n.  Greedy picks then take the route of a greedy pick under a repetition penalty (the lm_head's arg-max candidates
+ *   know no constraint).  NOT covered, exactly as for the penalty and the bans: the greedy d_next of pgv_llm_prefill / _append (re-pick with
+ *   pgv_llm_pick_greedy) and plain pgv_llm_decode steps, which neither mask nor record the state of the token they consume.
+ *   With pgv_kv_set_bans also on, the result is the union of the two -inf sets: this kernel writes the pick's copy of the row, logit_ban_kernel runs
+ *   in place behind it.  Under guidance the input is the guided row and the record is the conditional slot's.
+ *   PGV_ESTATE, and nothing changes: a beam run in flight or pgv_kv_set_lookup on; in turn pgv_beam_begin, pgv_kv_set_lookup (D > 0) and the lookup
+ *   calls are refused while it is on.
+ *   RE-PICKED ROWS: as under bans, the pick reads a COPY of the row; the cache's own logits (d_logits, what pgv_kv_fork copies, what a second pick
+ *   reads) stay raw, `model` log-probabilities are the raw row's, `pick` is normalised over what survives.
+ *   Measured on one MI355X at 7B shapes, 8 sequences, 461-token prompt, 256 steps (scripts/bench_allowed.py; LAB.md): the kernel takes 6 - 7 us for
+ *   a narrow state and 20 us for a cyclic state of 30000 edges (the ban kernel: 13 us): sampled 2.500 -> 2.520 ms per token step with the latter
+ *   (+0.020 ms).  A state with fewer edges than top_k costs more in the PICK: sample_kernel at top_k 50 takes 153 us instead of 83 us over a row with
+ *   fewer than 50 finite entries, so sampled 2.500 -> 2.577 ms (+0.077 ms) with a live 10-edge state or behind the end of a 1000-answer trie.  Greedy
+ *   2.422 -> 2.512 - 2.518 ms (+0.089 - 0.096 ms, of which 0.072 ms is the pick route that greedy under a repetition penalty already pays).  Off: the
+ *   steps of the commit before, within the process-to-process spread.
+ * pgv_allow_logits: the same kernel on caller buffers, in place: d_logits [B, V] fp32 (row stride V), row b in state d_states[b] (-1, or anything
+ *   outside [0, S): DEAD); eos_id as an argument (cfg->eos_id and cfg->h_roots are not read).  Every entry is written by at most one thread: the
+ *   result does not depend on B or on the row's index.  Synchronises the stream.
+ * pgv_allow_logits_copy: its out-of-place form, the launch kv_pick makes: rows of d_src [B, V] -> d_dst [B, V], d_src unchanged; d_dst == d_src is
+ *   pgv_allow_logits, any other overlap is refused.
+ * pgv_kv_allow_peek (test read-back): the first n <= max_seq entries of slot's state record -> d_out [n] int32 (may be NULL), the slot's root ->
+ *   d_root [1] (may be NULL).  PGV_ESTATE while the cache has no record. */
+#define PGV_ALLOW_MAX_STATES (1 << 20)
+#define PGV_ALLOW_MAX_EDGES (1 << 22)
+typedef struct {
+    const int32_t *h_row_ptr;            /* [n_states + 1] */
+    const int32_t *h_edge_token;         /* [n_edges] sorted and distinct within a state */
+    const int32_t *h_edge_next;          /* [n_edges] */
+    const uint8_t *h_accept;             /* [n_states] */
+    int n_states, n_edges;
+    const int32_t *h_roots;              /* [batch] or NULL = all 0 */
+    int eos_id;
+} pgv_allow_config;
+int pgv_kv_set_allowed(pgv_kv *kv, const pgv_allow_config *cfg);
+int pgv_allow_logits(pgv_ctx *ctx, float *d_logits, int V, int B, const int32_t *d_states, int eos_id, const pgv_allow_config *cfg, void *stream);
+int pgv_allow_logits_copy(pgv_ctx *ctx, const float *d_src, float *d_dst, int V, int B, const int32_t *d_states, int eos_id,
+                          const pgv_allow_config *cfg, void *stream);
+int pgv_kv_allow_peek(pgv_kv *kv, int slot, int n, int32_t *d_out, int32_t *d_root, void *stream);
+
 /* current length (tokens in cache) of sequence b, host-side bookkeeping */
 int pgv_kv_len(const pgv_kv *kv, int b);
 

@@ -73,6 +73,28 @@ class FilterConfig(C.Structure):
         return cls(0.0 if f.min_p is None else float(f.min_p), float(f.typical_p), float(f.epsilon_cutoff), float(f.eta_cutoff))
 
 
+ALLOW_MAX_STATES, ALLOW_MAX_EDGES = 1 << 20, 1 << 22      # PGV_ALLOW_MAX_* of include/pgv.h
+
+
+class AllowConfig(C.Structure):
+    """pgv_allow_config of include/pgv.h (pgv_kv_set_allowed, pgv_allow_logits).  `from_automaton` keeps the host arrays alive as attributes."""
+    _fields_ = [("h_row_ptr", C.POINTER(C.c_int32)), ("h_edge_token", C.POINTER(C.c_int32)), ("h_edge_next", C.POINTER(C.c_int32)),
+                ("h_accept", C.POINTER(C.c_uint8)), ("n_states", _i), ("n_edges", _i), ("h_roots", C.POINTER(C.c_int32)), ("eos_id", _i)]
+
+    @classmethod
+    def from_automaton(cls, automaton, roots=None, eos_id: int = -1) -> "AllowConfig":
+        """`automaton`: allowed.TokenAutomaton; `roots`: one state per slot of the cache (None: all 0)."""
+        import numpy as np
+        arrs = [np.ascontiguousarray(automaton.row_ptr, dtype=np.int32), np.ascontiguousarray(automaton.edge_token, dtype=np.int32),
+                np.ascontiguousarray(automaton.edge_next, dtype=np.int32), np.ascontiguousarray(automaton.accept, dtype=np.uint8)]
+        if roots is not None:
+            arrs.append(np.ascontiguousarray(roots, dtype=np.int32))
+        ptr = [a.ctypes.data_as(C.POINTER(C.c_uint8 if a.dtype == np.uint8 else C.c_int32)) if a.size else None for a in arrs]
+        cfg = cls(ptr[0], ptr[1], ptr[2], ptr[3], int(automaton.n_states), int(automaton.n_edges), ptr[4] if roots is not None else None, int(eos_id))
+        cfg._keep = arrs
+        return cfg
+
+
 def beam_state_words(K: int) -> int:
     """PGV_BEAM_STATE_WORDS(K): 32-bit words of one prompt's beam state."""
     return 6 * int(K) + 2
@@ -166,6 +188,10 @@ PROTOTYPES = {
     "pgv_kv_set_bans": (_i, [_vp, C.POINTER(BanConfig)]),
     "pgv_ban_logits": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _i, C.POINTER(BanConfig), _vp]),
     "pgv_kv_ids_peek": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "pgv_kv_set_allowed": (_i, [_vp, C.POINTER(AllowConfig)]),
+    "pgv_allow_logits": (_i, [_vp, _vp, _i, _i, _vp, _i, C.POINTER(AllowConfig), _vp]),
+    "pgv_allow_logits_copy": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, C.POINTER(AllowConfig), _vp]),
+    "pgv_kv_allow_peek": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "pgv_guidance_logits": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _i, _vp]),
     "pgv_kv_set_guidance": (_i, [_vp, _f, _i]),
     "pgv_kv_guidance": (_i, [_vp]),
@@ -428,6 +454,23 @@ class Context:
         check(self.lib.pgv_guidance_logits(self.handle, cond.data_ptr(), uncond.data_ptr(), ld, V, P, float(scale), out.data_ptr(),
                                            max(out.stride(0), out.shape[1]) if P > 1 else out.shape[1], stream_ptr(cond.device)), "pgv_guidance_logits")
         return out
+
+    def allow_logits(self, logits: torch.Tensor, states: torch.Tensor, automaton, eos_id: int, out: "torch.Tensor | None" = None) -> torch.Tensor:
+        """pgv_allow_logits: the token automaton's mask (allowed.TokenAutomaton) on `logits` [B, V] fp32 IN PLACE, row b in state states[b]
+        (int32 [B]; -1: DEAD).  Returns `logits`.  `out` [B, V] fp32: pgv_allow_logits_copy -- the masked rows go there, `logits` stays as it is (the
+        launch a pick on a cache makes); returns `out`."""
+        assert logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+        B = logits.shape[0]
+        assert states.is_cuda and states.dtype == torch.int32 and states.is_contiguous() and states.numel() == B
+        cfg = AllowConfig.from_automaton(automaton, None, int(eos_id))
+        if out is not None:
+            assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == logits.shape
+            check(self.lib.pgv_allow_logits_copy(self.handle, logits.data_ptr(), out.data_ptr(), logits.shape[1], B, states.data_ptr(), int(eos_id),
+                                                 C.byref(cfg), stream_ptr(logits.device)), "pgv_allow_logits_copy")
+            return out
+        check(self.lib.pgv_allow_logits(self.handle, logits.data_ptr(), logits.shape[1], B, states.data_ptr(), int(eos_id), C.byref(cfg),
+                                        stream_ptr(logits.device)), "pgv_allow_logits")
+        return logits
 
     def sample_logits_lp(self, logits: torch.Tensor, u: "torch.Tensor | None", temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                          repetition_penalty: float = 1.0, seen_ids: "torch.Tensor | None" = None, seen_lens: "torch.Tensor | None" = None,

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(HERE, "libpgv.so")
-SOURCES = ["api.hip", "gemm.hip", "elementwise.hip", "vit_attn.hip", "weights.hip", "fp8.hip", "w12.hip", "vit.hip", "llm_prefill.hip", "kv_fork.hip", "beam.hip", "gemv.hip", "decode_attn.hip", "sampling.hip", "lookup.hip", "logit_ban.hip", "score.hip", "guidance.hip", "llm.hip"]
+SOURCES = ["api.hip", "gemm.hip", "elementwise.hip", "vit_attn.hip", "weights.hip", "fp8.hip", "w12.hip", "vit.hip", "llm_prefill.hip", "kv_fork.hip", "beam.hip", "gemv.hip", "decode_attn.hip", "sampling.hip", "lookup.hip", "logit_ban.hip", "logit_allow.hip", "score.hip", "guidance.hip", "llm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          "-ffp-contract=fast"]
 # Attention kernels run VALU softmax on the MFMA results every chunk: keep their accumulators in the VGPR file (hipcc otherwise puts

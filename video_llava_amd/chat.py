@@ -25,7 +25,7 @@ from .video_conversation import SeparatorStyle, conv_templates, default_conversa
 class VideoChatGPTInterface:
     def __init__(self, args_model_name, args_projection_path, use_asr=False, conv_mode="pg-video-llava", temperature=0.2,
                  max_output_tokens=1024, components=None, do_sample=True, reuse_kv=True, top_p=None, repetition_penalty=None, lookup=0,
-                 lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video") -> None:
+                 lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video", answer_choices=None) -> None:
         if use_asr:
             raise NotImplementedError("--use_asr needs the WhisperX transcript stack, which is outside this package's hot path")
         self.use_asr = use_asr
@@ -48,6 +48,12 @@ class VideoChatGPTInterface:
         self.guidance_scale = guidance_from_flags(guidance_scale, guidance_negative, lookup=self.lookup[0], who="VideoChatGPTInterface")
         self.guidance_negative = guidance_negative
         self.reuse_kv = reuse_kv and self.guidance_scale is None
+        # constrained decoding (generate(allowed=)): every answer is one of `answer_choices` (a list of strings), followed on the device as a token
+        # automaton compiled once here; such a turn runs the full prefill (generate's own fall-back under `kv_reuse_key`)
+        if answer_choices and self.lookup[0]:
+            raise ValueError(f"VideoChatGPTInterface: answer_choices cannot be combined with lookup={self.lookup[0]} (the drafts are verified against the "
+                             f"unconstrained pick)")
+        self.allowed = allowed_from_choices(tokenizer, answer_choices)
         self.frame_size = (image_processor.crop_size["height"], image_processor.crop_size["width"])
         if self.model.get_model().vision_config.use_vid_start_end:
             self.replace_token = DEFAULT_VID_START_TOKEN + DEFAULT_VIDEO_PATCH_TOKEN * video_token_len + DEFAULT_VID_END_TOKEN
@@ -132,7 +138,8 @@ class VideoChatGPTInterface:
                                              max_new_tokens=min(int(self.max_new_tokens), 1536), stopping_criteria=[stopping_criteria],
                                              kv_reuse_key=self.kv_key, timings=self.last_timings, top_p=self.top_p,
                                              repetition_penalty=self.repetition_penalty,
-                                             **given(lookup=self.lookup[0], lookup_ngram=self.lookup[1], lookup_sample=self.lookup_sample), **guide)
+                                             **given(lookup=self.lookup[0], lookup_ngram=self.lookup[1], lookup_sample=self.lookup_sample, allowed=self.allowed),
+                                             **guide)
         n_in = input_ids.shape[1]
         n_diff = int((input_ids.to(output_ids.device) != output_ids[:, :n_in]).sum())
         if n_diff > 0:
@@ -201,6 +208,48 @@ def guidance_from_flags(scale, negative, lookup=0, beams=1, samples_per_prompt=1
     return scale
 
 
+def answer_choices_from_flags(choices, choices_file, lookup=0, beams=1):
+    """--answer_choices "yes,no" / --answer_choices_file F (one answer per line) of a command line -> the answers as a list of strings, or None when
+    neither flag is given; ValueError names what is wrong, or the flag constrained decoding cannot run with, as generate() would refuse it."""
+    if choices is None and choices_file is None:
+        return None
+    if choices is not None and choices_file is not None:
+        raise ValueError("--answer_choices and --answer_choices_file are two ways to give the same list: pass one of them")
+    if choices is not None:
+        texts = [t.strip() for t in str(choices).split(",")]
+    else:
+        with open(choices_file, encoding="utf-8") as fh:
+            texts = [line.strip() for line in fh]
+    texts = [t for t in texts if t]
+    if not texts:
+        raise ValueError("--answer_choices / --answer_choices_file: no answer given")
+    if int(beams or 1) > 1:
+        raise ValueError(f"--answer_choices cannot be combined with --beams {beams} (the beam pick applies no logits processor)")
+    if int(lookup or 0) > 0:
+        raise ValueError(f"--answer_choices cannot be combined with --lookup {lookup} (the drafts are verified against the unconstrained pick)")
+    return texts
+
+
+def allowed_from_choices(tokenizer, texts):
+    """The answers of answer_choices_from_flags as generate()'s `allowed`: allowed.TokenAutomaton.from_texts (None: no constraint).  The tokenizer
+    is asked for each answer on its own, without special tokens.  ASSUMPTION, not checked against a real tokenizer or checkpoint: that these ids are
+    the ones the model produces behind its prompt -- for LLaMA's sentencepiece the answer with its leading-space piece -- and that the model writes the
+    answer as it is spelled here ("Yes" and "yes" are different tokens: list both where either may come).  Where that does not hold, build the
+    automaton from id lists (TokenAutomaton.from_sequences) or give from_texts a `prefix`."""
+    if not texts:
+        return None
+    from .allowed import TokenAutomaton
+    return TokenAutomaton.from_texts(tokenizer, list(texts))
+
+
+def add_answer_choice_flags(parser):
+    parser.add_argument("--answer_choices", default=None, metavar="A,B,...",
+                        help="constrained decoding (generate(allowed=); HF: prefix_allowed_tokens_fn): every answer is one of these comma-separated "
+                             "strings, e.g. \"yes,no\" or \"A,B,C,D\" -- compiled once into a token automaton that the device follows; not with --beams "
+                             "or --lookup")
+    parser.add_argument("--answer_choices_file", default=None, metavar="F", help="--answer_choices from a file, one answer per line")
+
+
 def add_guidance_flags(parser):
     parser.add_argument("--guidance_scale", type=float, default=None, metavar="S",
                         help="classifier-free guidance (generate(guidance=); HF: guidance_scale): every pick reads S * (log_softmax(cond) - "
@@ -226,6 +275,7 @@ def parse_args(argv=None):
     parser.add_argument("--lookup_sample", action="store_true",
                         help="--lookup D --do_sample: lookup steps for the sampled run (generate(lookup_sample=True)): bit for bit the answer of --do_sample alone")
     add_guidance_flags(parser)
+    add_answer_choice_flags(parser)
     args = parser.parse_args(argv)
     if args.lookup_sample and not args.do_sample:
         parser.error("--lookup_sample needs --do_sample (greedy lookup is --lookup D alone)")
@@ -236,7 +286,8 @@ def parse_args(argv=None):
     try:
         check_lookup(args.lookup, args.lookup_ngram, 1, who="chat.py")
         guidance_from_flags(args.guidance_scale, args.guidance_negative, lookup=args.lookup)
-    except ValueError as e:
+        args.answer_choice_list = answer_choices_from_flags(args.answer_choices, args.answer_choices_file, lookup=args.lookup)
+    except (ValueError, OSError) as e:
         parser.error(str(e))
     return args
 
@@ -247,4 +298,5 @@ if __name__ == "__main__":
         raise NotImplementedError("the grounding stack (GroundingDINO / SAM / DEVA / RAM) is outside this package's hot path")
     VideoChatGPTInterface(args_model_name=args.model_name, args_projection_path=args.projection_path, use_asr=args.use_asr,
                           conv_mode=args.conv_mode, do_sample=args.lookup_sample or not args.lookup, lookup=args.lookup, lookup_ngram=args.lookup_ngram,
-                          lookup_sample=args.lookup_sample, guidance_scale=args.guidance_scale, guidance_negative=args.guidance_negative).interact()
+                          lookup_sample=args.lookup_sample, guidance_scale=args.guidance_scale, guidance_negative=args.guidance_negative,
+                          answer_choices=args.answer_choice_list).interact()

@@ -88,7 +88,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
                         prompt_slack: int = 128, eos_token_id="config", seed: int = 0,
                         on_error: Callable[[Any, Exception], None] = _default_on_error,
                         timings: Optional[dict] = None, top_p: float = 1.0, repetition_penalty: float = 1.0,
-                        logprobs: Optional[dict] = None, bans=None, filters=None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
+                        logprobs: Optional[dict] = None, bans=None, filters=None, allowed=None) -> Iterator[Tuple[Any, Optional[List[int]]]]:
     """Yield (task_id, new_ids) as each task finishes; new_ids is None for a task that failed (`on_error(task_id, exc)` is told why) -- a failed
     task costs only itself.
 
@@ -119,7 +119,9 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     `generate`; a task's sequence is its own prompt and answer -- a refilled slot's id record starts from its prompt (pgv_kv_set_bans).
     filters (sample_filters.SampleFilters, a dict of its fields, or None): HF's min_p / typical_p / epsilon_cutoff / eta_cutoff warpers behind top_p,
     one record for every sampled pick of the call -- the opening draw, every refill's first-token draw and every decode step (pgv_kv_set_filters);
-    fields not given come from the model's generation config, as in `generate`.  Inert with do_sample=False."""
+    fields not given come from the model's generation config, as in `generate`.  Inert with do_sample=False.
+    allowed (allowed.TokenAutomaton or None): constrained decoding as in `generate`, ONE automaton shared by every task of the call -- every slot,
+    the refilled ones included, starts its answer at state 0 (pgv_kv_set_allowed).  An automaton per task is not implemented: a list is refused."""
     if not 1 <= width <= 64:
         raise ValueError(f"width {width} outside [1, 64]")
     if do_sample and not float(temperature) > 0.0:
@@ -136,9 +138,14 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
     ban_on = not ban.effective_neutral(eos_i)
     from .sample_filters import check_filters
     filt = check_filters(filters, getattr(model, "generation_config", None), who="generate_continuous()")
+    from .allowed import TokenAutomaton, check_allowed
+    if allowed is not None and not isinstance(allowed, TokenAutomaton):
+        raise ValueError(f"generate_continuous(): `allowed` has to be ONE TokenAutomaton shared by every task or None, but is {allowed!r} (an automaton per "
+                         f"task is not implemented in the refill runner)")
+    allow = check_allowed(allowed, 1, model.vocab_size, eos_i if eos_i >= 0 else None, who="generate_continuous()")      # roots: 0 for every slot
     want_lp = logprobs is not None
     # on for this call only: cleared in the finally below, also when the generator is closed early
-    on = CacheSettings(True if want_lp else None, ban if ban_on else None, eos_i, filt if do_sample and not filt.neutral else None)
+    on = CacheSettings(True if want_lp else None, ban if ban_on else None, eos_i, filt if do_sample and not filt.neutral else None, allowed=allow)
     dev = model.device_
 
     source = iter(tasks)
@@ -255,7 +262,7 @@ def generate_continuous(model, tasks: Iterable[Task], width: int, max_new_tokens
         if do_sample:
             idle = torch.full((), 0.5, dtype=torch.float32, device=dev)
             nxt = model.sample_last(kv, torch.stack([u[0] if u is not None else idle for u in us]), temperature, top_k, **warp)
-        elif rep_pen != 1.0 or ban_on:
+        elif rep_pen != 1.0 or ban_on or allow is not None:
             nxt = model.greedy_last(kv, W, **pen)                  # greedy over the penalised / banned logits (as generate does)
         cur = nxt.clone()
         first_lp = model.logprobs_last(kv, W).cpu().numpy() if want_lp else None

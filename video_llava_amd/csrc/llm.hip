@@ -101,6 +101,15 @@ struct pgv_kv {
     std::vector<int> ban_host;          // the list words the device copy holds
     bool ban_on = false;
     int ban_gen = 0;                    // bumped by every pgv_kv_set_bans that changes the device copy: part of the decode graphs' key
+    // constrained decoding (pgv_kv_set_allowed): the state record [B][max_seq] (indexed by cache position) and the roots [B], one allocation by the
+    // first configuration that asks; the device copy of the automaton (al_auto binds it), which grows with the configuration.  It shares the prompt
+    // lengths and the pick's logits copy of the bans (kv_ids_alloc).
+    char* al_blob = nullptr; int *al_state = nullptr, *al_root = nullptr;
+    int* al_dev = nullptr; size_t al_cap = 0;      // device words of the automaton and how many are allocated
+    AllowAuto al_auto; int al_eos = -1;
+    std::vector<int> al_host;           // the automaton words the device copy holds
+    bool al_on = false;
+    int al_gen = 0;                     // bumped by every pgv_kv_set_allowed that changes the device copy: part of the decode graphs' key
     // classifier-free guidance (pgv_kv_set_guidance): slots [0, g_pairs) of a live group of 2 * g_pairs are conditional, slot g_pairs + p is the
     // unconditional twin of p.  g_logits [B / 2][vocab] (row stride vocab) holds the guided rows the pick reads; allocated when guidance is first
     // switched on.  g_pairs 0: off
@@ -437,6 +446,8 @@ extern "C" void pgv_kv_destroy(pgv_kv* kv) {
     if (kv->blob) (void)hipFree(kv->blob);
     if (kv->bm_blob) (void)hipFree(kv->bm_blob);
     if (kv->ban_blob) (void)hipFree(kv->ban_blob);
+    if (kv->al_blob) (void)hipFree(kv->al_blob);
+    if (kv->al_dev) (void)hipFree(kv->al_dev);
     if (kv->lk_blob) (void)hipFree(kv->lk_blob);
     if (kv->g_logits) (void)hipFree(kv->g_logits);
     delete kv;
@@ -512,6 +523,60 @@ extern "C" int pgv_kv_ids_peek(pgv_kv* kv, int slot, int n, int32_t* d_out, int3
     PGV_CHECK(n >= 0 && n <= kv->max_seq, "pgv_kv_ids_peek: %d entries outside the cache's %d", n, kv->max_seq);
     if (d_out && n > 0) PGV_HIP(hipMemcpyAsync(d_out, kv->ban_ids + (size_t)slot * kv->max_seq, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (d_prompt_len) PGV_HIP(hipMemcpyAsync(d_prompt_len, kv->ban_plen + slot, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PGV_OK;
+}
+
+// Constrained decoding (pgv.h).  As for the bans, the automaton goes to device memory owned by the cache, outside any capture: a captured decode
+// step bakes in its addresses and sizes, and the graphs' key carries the generation counter.  The roots are per-slot state (pgv_kv_fork and the
+// refills move them), so they are written by every call that switches the feature on.
+extern "C" int pgv_kv_set_allowed(pgv_kv* kv, const pgv_allow_config* cfg) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_set_allowed: null cache");
+    if (!cfg) { kv->al_on = false; return PGV_OK; }
+    PGV_TRY(pgv_allow_check("pgv_kv_set_allowed", cfg, kv->llm->cfg.vocab, kv->B));
+    if (kv->bm_K > 0) { pgv_set_error("pgv_kv_set_allowed: a beam run is in flight in this cache (the beam pick applies no logits processor)"); return PGV_ESTATE; }
+    if (kv->lk_D > 0) { pgv_set_error("pgv_kv_set_allowed: pgv_kv_set_lookup is on in this cache (lookup steps verify drafts against the unconstrained pick)"); return PGV_ESTATE; }
+    PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_allowed"));          // the prompt lengths and the pick's copy of the logits
+    const size_t B = kv->B;
+    if (!kv->al_blob) {
+        const size_t b_state = pgv_align(B * kv->max_seq * 4), b_root = pgv_align(B * 4);
+        hipError_t e = hipMalloc((void**)&kv->al_blob, b_state + b_root);
+        if (e != hipSuccess) { kv->al_blob = nullptr; pgv_set_error("pgv_kv_set_allowed: hipMalloc(%zu KiB): %s", (b_state + b_root) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
+        kv->al_state = (int*)kv->al_blob; kv->al_root = (int*)(kv->al_blob + b_state);
+        PGV_HIP(hipMemset(kv->al_blob, 0xff, b_state));       // DEAD until a step stores a state
+    }
+    std::vector<int> blob;
+    pgv_allow_pack(cfg, blob);
+    PGV_HIP(hipDeviceSynchronize());              // a pick in flight may still read the automaton and the roots of the configuration before
+    // the automaton the device copy already holds (a caller that sets and clears it around every run): nothing to upload, the graphs stay valid
+    const bool same = kv->al_gen > 0 && cfg->eos_id == kv->al_eos && cfg->n_states == kv->al_auto.n_states && cfg->n_edges == kv->al_auto.n_edges && blob == kv->al_host;
+    if (!same) {
+        if (blob.size() > kv->al_cap) {
+            if (kv->al_dev) (void)hipFree(kv->al_dev);
+            kv->al_dev = nullptr; kv->al_cap = 0; kv->al_host.clear();       // (the counter moves below: graphs that baked the old address in never match again)
+            hipError_t e = hipMalloc((void**)&kv->al_dev, blob.size() * 4);
+            if (e != hipSuccess) { kv->al_dev = nullptr; kv->al_on = false; pgv_set_error("pgv_kv_set_allowed: hipMalloc(%zu KiB): %s", (blob.size() * 4) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
+            kv->al_cap = blob.size();
+        }
+        PGV_HIP(hipMemcpy(kv->al_dev, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+        kv->al_auto = allow_auto(kv->al_dev, cfg->n_states, cfg->n_edges);
+        kv->al_host.swap(blob);
+        kv->al_eos = cfg->eos_id;
+        kv->al_gen += 1;
+    }
+    std::vector<int> roots(B, 0);
+    for (size_t b = 0; cfg->h_roots && b < B; ++b) roots[b] = cfg->h_roots[b];
+    PGV_HIP(hipMemcpy(kv->al_root, roots.data(), B * 4, hipMemcpyHostToDevice));
+    kv->al_on = true;
+    return PGV_OK;
+}
+
+extern "C" int pgv_kv_allow_peek(pgv_kv* kv, int slot, int n, int32_t* d_out, int32_t* d_root, void* stream) {
+    PGV_CHECK(kv != nullptr, "pgv_kv_allow_peek: null cache");
+    if (!kv->al_state) { pgv_set_error("pgv_kv_allow_peek: this cache has no state record (pgv_kv_set_allowed allocates it)"); return PGV_ESTATE; }
+    PGV_CHECK(slot >= 0 && slot < kv->B, "pgv_kv_allow_peek: slot %d outside the %d of the cache", slot, kv->B);
+    PGV_CHECK(n >= 0 && n <= kv->max_seq, "pgv_kv_allow_peek: %d entries outside the cache's %d", n, kv->max_seq);
+    if (d_out && n > 0) PGV_HIP(hipMemcpyAsync(d_out, kv->al_state + (size_t)slot * kv->max_seq, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_root) PGV_HIP(hipMemcpyAsync(d_root, kv->al_root + slot, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PGV_OK;
 }
 
@@ -620,7 +685,10 @@ static PickState kv_state(pgv_kv* kv, int eos, int advance) { return {kv->d_cur,
 // processors applied, made by logit_ban_kernel behind the row statistics: kv->logits itself stays raw for the statistics, a re-pick, a fork and the
 // d_logits outputs.  Row b's sequence is the record of its slot at length ban_lens[b] (null: the cache's positions) -- plus, for the pick of a decode
 // step (AM_INC_POS), the token that step consumed, which the kernel appends to the record.
-static bool kv_greedy_sampled(const pgv_kv* kv) { return kv->warpers.penalty != 1.f || kv->ban_on || kv->g_pairs > 0; }
+// With pgv_kv_set_allowed on, logit_allow_kernel makes that copy -- the row with -inf outside what the slot's automaton state allows, the state
+// advanced by the token the step consumed -- and logit_ban_kernel, where bans are on too, runs in place behind it: the union of the two -inf sets.
+// With only bans on, the ban kernel's launch is the one it has always been.
+static bool kv_greedy_sampled(const pgv_kv* kv) { return kv->warpers.penalty != 1.f || kv->ban_on || kv->g_pairs > 0 || kv->al_on; }
 static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u, bool u_by_step, const PickState& st, const int* slot_map, hipStream_t s,
                    const int* ban_lens = nullptr) {
     const int V = kv->llm->cfg.vocab;
@@ -640,6 +708,17 @@ static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u,
         PGV_CHECK(B == 2 * P && st.next == kv->d_cur, "kv_pick: a guided pick runs on the cache's own state at width 2 x pairs");
         PGV_TRY(pgv_launch_guidance_mix(kv->logits, kv->logits + (size_t)P * V, V, V, P, kv->g_scale, kv->g_logits, V, s));
         logits = kv->g_logits;
+    }
+    if (kv->al_on) {
+        AllowArgs a;
+        a.src = logits; a.dst = kv->ban_logits; a.V = V;
+        a.au = kv->al_auto; a.state = kv->al_state; a.state_stride = kv->max_seq; a.root = kv->al_root;
+        a.slot_map = slot_map; a.lens = ban_lens ? ban_lens : kv->d_pos; a.prompt_lens = kv->ban_plen;
+        a.cur = kv->d_cur; a.inc = (st.advance & AM_INC_POS) ? 1 : 0;
+        a.done = (st.advance & AM_RECORD) ? st.done : nullptr;       // as for the bans below
+        a.eos = kv->al_eos;
+        PGV_TRY(pgv_launch_logit_allow(a, rows, s));
+        logits = kv->ban_logits; lp.banned = 1;
     }
     if (kv->ban_on) {
         BanArgs a;
@@ -828,7 +907,10 @@ static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefi
     // (and every sample of a prompt starts from the prompt's ids alone: the pick adds its own token to the set of its own slot)
     PGV_TRY(pgv_launch_seen_mark(w.d.raw_ids, w.d.cu, w.t_slots, T, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s, q.h_counts ? w.d.samp_seq : nullptr));
     // the ordered twin of the seen-set (pgv_kv_set_bans): each slot's ids at their cache positions and its prompt length, same indirection
-    if (kv->ban_on || kv->lk_D > 0) PGV_TRY(pgv_launch_ids_write(w.d.raw_ids, w.d.cu, w.d.offs, w.t_slots, q.h_counts ? w.d.samp_seq : nullptr, T, kv->ban_ids, kv->max_seq, kv->ban_plen, s));
+    if (kv->ban_on || kv->lk_D > 0 || kv->al_on) PGV_TRY(pgv_launch_ids_write(w.d.raw_ids, w.d.cu, w.d.offs, w.t_slots, q.h_counts ? w.d.samp_seq : nullptr, T, kv->ban_ids, kv->max_seq, kv->ban_plen, s));
+    // pgv_kv_set_allowed: a refilled slot starts at root 0 (one automaton for every task of a refill run); its state rows need no action, the
+    // first pick reads the root and every later step stores the entry the next one reads
+    if (kv->al_on && slots) PGV_TRY(pgv_launch_allow_root_zero(w.t_slots, T, kv->al_root, s));
     if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
         PGV_HIP(hipMemcpyAsync(kv->d_pos, w.d.lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
         PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
@@ -1071,6 +1153,13 @@ extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* 
             PGV_HIP(hipMemcpyAsync(kv->ban_ids + (size_t)(base + i) * kv->max_seq, kv->ban_ids + (size_t)p * kv->max_seq, (size_t)kv->h_len[p] * 4, hipMemcpyDeviceToDevice, s));
             PGV_HIP(hipMemcpyAsync(kv->ban_plen + base + i, kv->ban_plen + p, 4, hipMemcpyDeviceToDevice, s));
         }
+        // likewise the state record of pgv_kv_set_allowed and the slot's root (the prompt length went with the loop above when bans are on)
+        for (int i = 0; kv->al_on && i < c; ++i) {
+            if (base + i == p) continue;
+            PGV_HIP(hipMemcpyAsync(kv->al_state + (size_t)(base + i) * kv->max_seq, kv->al_state + (size_t)p * kv->max_seq, (size_t)kv->h_len[p] * 4, hipMemcpyDeviceToDevice, s));
+            PGV_HIP(hipMemcpyAsync(kv->al_root + base + i, kv->al_root + p, 4, hipMemcpyDeviceToDevice, s));
+            if (!kv->ban_on) PGV_HIP(hipMemcpyAsync(kv->ban_plen + base + i, kv->ban_plen + p, 4, hipMemcpyDeviceToDevice, s));
+        }
     }
     for (int i = 0; i < (int)W; ++i) kv->h_len[i] = len[i];
     kv->active = (int)W;
@@ -1187,7 +1276,7 @@ static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int fla
 // lookup: the captured steps are lookup steps (pgv_llm_decode_lookup, with AM_SAMPLE pgv_llm_decode_lookup_sample) with the cache's D and n, which join the key
 static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s, bool lookup = false) {
     const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K, kv->ban_on ? kv->ban_gen : 0, lookup ? kv->lk_D : 0,
-                                                lookup ? kv->lk_n : 0, kv->g_pairs, kv->g_scale);
+                                                lookup ? kv->lk_n : 0, kv->g_pairs, kv->g_scale, kv->al_on ? kv->al_gen : 0);
     if (!(kv->gkey == key)) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->gkey = key;
@@ -1366,6 +1455,7 @@ extern "C" int pgv_beam_begin(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const pgv_be
     PGV_TRY(guidance_refuses(kv, "pgv_beam_begin"));
     if (kv->active < 1) { pgv_set_error("pgv_beam_begin: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
     if (kv->ban_on) { pgv_set_error("pgv_beam_begin: logit bans are set on this cache (pgv_kv_set_bans); the beam pick applies no logits processor"); return PGV_ESTATE; }
+    if (kv->al_on) { pgv_set_error("pgv_beam_begin: a token automaton is set on this cache (pgv_kv_set_allowed); the beam pick applies no logits processor"); return PGV_ESTATE; }
     const int P = kv->active, K = cfg->beams, N = cfg->max_new_tokens, B = kv->B;
     PGV_CHECK((long long)P * K <= B, "pgv_beam_begin: %d prompts x %d beams exceed the %d sequences the cache was created with", P, K, B);
     PGV_CHECK(N <= kv->max_seq, "pgv_beam_begin: max_new_tokens %d exceeds the cache's %d positions", N, kv->max_seq);
@@ -1510,6 +1600,7 @@ extern "C" int pgv_kv_set_lookup(pgv_kv* kv, int D, int n) {
     PGV_CHECK(D >= 0 && D <= 15, "pgv_kv_set_lookup: %d draft rows per slot outside [0,15]", D);
     if (D == 0) { kv->lk_D = 0; kv->lk_valid = false; return PGV_OK; }
     PGV_TRY(guidance_refuses(kv, "pgv_kv_set_lookup"));
+    if (kv->al_on) { pgv_set_error("pgv_kv_set_lookup: a token automaton is set on this cache (pgv_kv_set_allowed); lookup steps verify drafts against the unconstrained pick"); return PGV_ESTATE; }
     PGV_CHECK(n >= 1 && n <= 4, "pgv_kv_set_lookup: ngram size %d outside [1,4]", n);
     PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_lookup"));
     if (!kv->lk_blob) {
@@ -1578,6 +1669,7 @@ static int check_lookup_run(pgv_llm* m, pgv_kv* kv, int steps, int eos_id, const
     if (!kv->lk_valid) { pgv_set_error("%s: the cache's id record does not cover its sequences: set pgv_kv_set_lookup before pgv_llm_prefill and step with pgv_llm_decode_lookup only", who); return PGV_ESTATE; }
     if (kv->warpers.penalty != 1.f) { pgv_set_error("%s: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
     if (kv->ban_on) { pgv_set_error("%s: logit bans are set on this cache (pgv_kv_set_bans); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
+    if (kv->al_on) { pgv_set_error("%s: a token automaton is set on this cache (pgv_kv_set_allowed); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
     if (kv->lp_on) { pgv_set_error("%s: log-probabilities are on (pgv_kv_set_logprobs); lookup steps record none", who); return PGV_ESTATE; }
     if (kv->bm_K > 0) { pgv_set_error("%s: a beam run is in flight on this cache", who); return PGV_ESTATE; }
     PGV_CHECK(B * W <= kv->lk_rows && B * W <= kMaxBatch, "%s: %d sequences x %d rows exceed the %d rows of a step", who, B, W, kv->lk_rows < kMaxBatch ? kv->lk_rows : kMaxBatch);

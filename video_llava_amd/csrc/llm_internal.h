@@ -188,6 +188,42 @@ inline BanLists ban_lists(const BanPacked& at, const int* d_blob) {
     return l;
 }
 
+// logit_allow.hip: constrained decoding by a token automaton (pgv.h: pgv_kv_set_allowed).
+// The automaton in DEVICE memory, CSR: the edges of state s are [row_ptr[s], row_ptr[s + 1]), their tokens sorted and distinct.  One blob of
+// allow_words(S, E) ints holds row_ptr [S + 1] | edge_token [E] | edge_next [E] | accept [S] bytes (allow_auto binds the pointers).
+struct AllowAuto {
+    const int *row_ptr = nullptr, *edge_token = nullptr, *edge_next = nullptr; const unsigned char* accept = nullptr;
+    int n_states = 0, n_edges = 0;
+};
+inline size_t allow_words(int S, int E) { return (size_t)S + 1 + 2 * (size_t)E + ((size_t)S + 3) / 4; }
+inline AllowAuto allow_auto(const int* d_blob, int S, int E) {
+    AllowAuto a;
+    a.row_ptr = d_blob; a.edge_token = d_blob + S + 1; a.edge_next = a.edge_token + E; a.accept = (const unsigned char*)(a.edge_next + E);
+    a.n_states = S; a.n_edges = E;
+    return a;
+}
+// One workgroup per logits row b: dst[b] = src[b] with -inf outside the tokens the row's state allows (src == dst: only those entries are written).
+// The state: direct[b] (pgv_allow_logits; -1: DEAD), or that of the cache row -- slot = slot_map[b] (null: b), at = lens[b], and with
+// prev = (at == prompt_lens[slot]) ? root[slot] : state[slot * state_stride + at - 1]: with `inc` (the pick of a decode step, AM_INC_POS) the target
+// of cur[b]'s edge in prev (none: DEAD), which is first stored at state[slot * state_stride + at]; without it prev itself, nothing stored.
+// done (may be null): rows whose flag is set are copied as they are.
+struct AllowArgs {
+    const float* src = nullptr; float* dst = nullptr; int V = 0;
+    AllowAuto au;
+    const int* direct = nullptr;
+    int* state = nullptr; int state_stride = 0; const int* root = nullptr;
+    const int *slot_map = nullptr, *lens = nullptr, *prompt_lens = nullptr, *cur = nullptr; int inc = 0;
+    const int* done = nullptr;
+    int eos = -1;
+};
+int pgv_launch_logit_allow(const AllowArgs& a, int B, hipStream_t s);
+// root[slots[t]] = 0 for the n slots of a DEVICE list (a refill's slots start at the root of the shared automaton)
+int pgv_launch_allow_root_zero(const int* slots, int n, int* root, hipStream_t s);
+// validate a pgv_allow_config against the limits of pgv.h, the vocabulary and the shape of a CSR automaton (n_roots entries of h_roots, where given);
+// pack its arrays into the blob layout above
+int pgv_allow_check(const char* who, const pgv_allow_config* c, int V, int n_roots);
+void pgv_allow_pack(const pgv_allow_config* c, std::vector<int>& blob);
+
 // guidance.hip: classifier-free guidance (pgv.h: pgv_kv_set_guidance).
 // mix: pair p of P reads cond[p * ld ..) and uncond[p * ld ..) over columns [0, V) and writes out[p * ld_out ..) = scale * (lc - lu) + lu with lc / lu
 // the rows' log-softmax (row_lse_kernel's statistics, bit for bit).  Any strides >= V, 4-byte alignment.

@@ -30,13 +30,14 @@ struct DecodeGraphKey {
     int bans = 0;           // pgv_kv_set_bans: the generation counter of the cache's ban configuration (0: none) -- the ban kernel's launch and its list lengths are baked in
     int lookup_D = 0, lookup_n = 0;      // pgv_llm_decode_lookup: drafts per slot and ngram size of the captured lookup steps (0: plain token steps)
     int guide_pairs = 0; float guide_scale = 1.f;      // pgv_kv_set_guidance: the mix and follow launches bake in the pair count and the scale (0, 1: off)
+    int allowed = 0;        // pgv_kv_set_allowed: the generation counter of the cache's token automaton (0: none) -- the allow kernel's launch and the automaton's addresses are baked in
     bool operator==(const DecodeGraphKey& o) const {
         return B == o.B && eos == o.eos && flags == o.flags && generation == o.generation && logprobs == o.logprobs && pick == o.pick && beams == o.beams && bans == o.bans &&
-               lookup_D == o.lookup_D && lookup_n == o.lookup_n && guide_pairs == o.guide_pairs && guide_scale == o.guide_scale;
+               lookup_D == o.lookup_D && lookup_n == o.lookup_n && guide_pairs == o.guide_pairs && guide_scale == o.guide_scale && allowed == o.allowed;
     }
 };
 inline DecodeGraphKey decode_graph_key(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight, int beams = 0, int bans = 0,
-                                       int lookup_D = 0, int lookup_n = 0, int guide_pairs = 0, float guide_scale = 1.f) {
+                                       int lookup_D = 0, int lookup_n = 0, int guide_pairs = 0, float guide_scale = 1.f, int allowed = 0) {
     return {B, eos, flags, generation, logprobs, (flags & AM_SAMPLE) ? in_flight : PickParams{}, (flags & AM_BEAM) ? beams : 0, bans, lookup_D, lookup_n,
-            guide_pairs, guide_pairs > 0 ? guide_scale : 1.f};
+            guide_pairs, guide_pairs > 0 ? guide_scale : 1.f, allowed};
 }

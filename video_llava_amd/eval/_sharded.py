@@ -81,7 +81,8 @@ def add_runtime_arguments(parser):
                         help="--lookup D --do_sample: lookup steps for the sampled run (generate(lookup_sample=True)) -- every draft is verified against the "
                              "pick from the uniform the plain run draws for that token, so the answers are bit for bit those of --do_sample alone; lifts "
                              "only the --do_sample refusal of --lookup")
-    from ..chat import add_guidance_flags
+    from ..chat import add_answer_choice_flags, add_guidance_flags
+    add_answer_choice_flags(parser)     # --answer_choices "yes,no" / --answer_choices_file F: generate(allowed=), every schedule
     add_guidance_flags(parser)          # --guidance_scale S / --guidance_negative: --batch and --batch auto count two rows per clip
     parser.add_argument("--timings", default=None, metavar="OUT.jsonl",
                         help="append one JSON line per answered task (rank-local file `OUT.jsonl.rank<r>` when world > 1): frame load, upload + ingest, "
@@ -106,10 +107,11 @@ def add_runtime_arguments(parser):
             K, _, _ = check_beam_args(ns)
             lookup_from_args(ns)
             guidance_scale_from_args(ns)
+            answer_choices_from_args(ns)
             if bans_from_args(ns) and K > 1:        # validates the three flags, HF's wording
                 raise ValueError(f"--beams {K} cannot be combined with --no_repeat_ngram / --min_new_tokens / --suppress_tokens (the beam pick applies "
                                  f"no logits processor)")
-        except ValueError as e:
+        except (ValueError, OSError) as e:
             parser.error(str(e))
         return ns, rest
 
@@ -151,6 +153,22 @@ def lookup_from_args(ns) -> dict:
     if batch != "auto" and batch * (1 + D) > MAX_BATCH:
         raise ValueError(f"--batch {batch} clips x (1 + --lookup {D}) rows exceed the {MAX_BATCH} rows of a decode step")
     return {"lookup": D, "lookup_ngram": n, **({"lookup_sample": True} if sampled else {})}
+
+
+def answer_choices_from_args(ns):
+    """--answer_choices / --answer_choices_file of a parsed command line -> the answers as a list of strings (None: no constraint); ValueError names
+    the flag constrained decoding cannot run with."""
+    from ..chat import answer_choices_from_flags
+    return answer_choices_from_flags(getattr(ns, "answer_choices", None), getattr(ns, "answer_choices_file", None), getattr(ns, "lookup", 0),
+                                     getattr(ns, "beams", 1))
+
+
+def allowed_from_args(ns, tokenizer) -> dict:
+    """The same two flags as generate() / generate_continuous() keywords: {} when neither is given, else {"allowed": TokenAutomaton} -- ONE automaton
+    for every question of the run, compiled once per call site from the run's tokenizer (TokenAutomaton.from_texts)."""
+    from ..chat import allowed_from_choices
+    texts = answer_choices_from_args(ns)
+    return {} if texts is None else {"allowed": allowed_from_choices(tokenizer, texts)}
 
 
 def guidance_scale_from_args(ns):
@@ -322,6 +340,7 @@ class _Runner:
         self.args, self.tasks, self.load_frames, self.rank, self.tfile, self.sfile = args, tasks, load_frames, rank, tfile, sfile
         self.model, self.vision_tower, self.tokenizer, self.image_processor, self.video_token_len = components
         self.use_se = self.model.get_model().vision_config.use_vid_start_end
+        self.allowed_kw = allowed_from_args(args, self.tokenizer)      # --answer_choices: one automaton for the run, compiled once ({}: off)
         self.cache = FeatureCache(getattr(args, "feature_cache", FEATURE_CACHE_CLIPS))
         self.ring = PinnedRing()
         self.stop_strs = {}             # task -> the stop string of its prompt
@@ -475,7 +494,7 @@ class _Runner:
                                            early_stopping=early, **self.warpers()).cpu()
             return self.model.generate([ids for _, ids, _, _ in part], video_spatio_temporal_features=torch.stack([f for _, _, f, _ in part]),
                                        do_sample=False, max_new_tokens=self.args.max_new_tokens, stop_strings=[s for _, _, _, s in part],
-                                       tokenizer=self.tokenizer, timings=timings, **self.warpers(), **bans_from_args(self.args),
+                                       tokenizer=self.tokenizer, timings=timings, **self.warpers(), **bans_from_args(self.args), **self.allowed_kw,
                                        **lookup_from_args(self.args), **self.guidance([indices[j] for j, _, _, _ in part])).cpu()
 
         def record(part, out):
@@ -544,7 +563,7 @@ class _Runner:
         lps = {} if many else None                                    # the samples are ranked by their log-probabilities
         for idx, new in generate_continuous(self.model, stream(), W, args.max_new_tokens, do_sample=args.do_sample, temperature=0.2, top_k=50,
                                             tokenizer=self.tokenizer, on_error=self.failed, timings=tm, **warp, **({"logprobs": lps} if many else {}),
-                                            **bans_from_args(args), **filters_from_args(args)):
+                                            **bans_from_args(args), **filters_from_args(args), **self.allowed_kw):
             if new is not None and many:
                 new = self.pick_sample(idx, new, lps.pop(idx))
             if new is not None:
@@ -594,7 +613,7 @@ class _Runner:
                     raise clips[t["path"]]
                 new, stop = video_chatgpt_infer_ids(None, t["question"], self.args.conv_mode, self.model, self.vision_tower, self.tokenizer,
                                                     self.image_processor, self.video_token_len, None, max_new_tokens=self.args.max_new_tokens,
-                                                    features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args), **filters_from_args(self.args),
+                                                    features=feat_of[t["path"]], **self.warpers(), **bans_from_args(self.args), **filters_from_args(self.args), **self.allowed_kw,
                                                     **lookup_from_args(self.args),      # --lookup D --lookup_sample: the same ids in fewer passes
                                                     **guidance_kwargs(guidance_scale_from_args(self.args), getattr(self.args, "guidance_negative", "no_video")))
                 self.stop_strs[idx] = stop

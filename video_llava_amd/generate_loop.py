@@ -38,9 +38,10 @@ def open_cache(model, plan, seqs, feats, kv_reuse_key):
     prefill, off again however the call ends -- a refused fork, a criterion, the tokenizer or an interrupt included."""
     B, n, stops, on = len(seqs), plan.samples_per_prompt, plan.stops, plan.settings
     reused = 0
-    if kv_reuse_key is not None and B == 1 and plan.repetition_penalty == 1.0 and not plan.bans_on and not plan.lookup[0]:
+    if kv_reuse_key is not None and B == 1 and plan.repetition_penalty == 1.0 and not plan.bans_on and not plan.lookup[0] and plan.allowed is None:
         # under a repetition penalty the slot's seen-set has to be exactly prompt + answer: the surplus steps a kept cache carries past a stop
-        # string would stay in it, so such a turn runs the full prefill; under bans or lookup the slot's id record, for the same reason
+        # string would stay in it, so such a turn runs the full prefill; under bans or lookup the slot's id record, under `allowed` its state record, for
+        # the same reason
         reused = model._reusable_prefix(kv_reuse_key, seqs[0], plan.max_new_tokens)
     if reused:
         kv = model._reuse[1]
@@ -66,7 +67,7 @@ def open_cache(model, plan, seqs, feats, kv_reuse_key):
 
 def first_pick(model, plan, kv, nxt, B: int, generator):
     """-> (the call's uniforms [max_new_tokens, B] or None, first tokens [B] on the device, the log-probability blocks so far).  A sampled call
-    draws; greedy under a penalty, bans or guidance re-picks over the processed logits (the prefill's argmax knows none of them; first index on
+    draws; greedy under a penalty, bans, an automaton (`allowed`) or guidance re-picks over the processed logits (the prefill's argmax knows none of them; first index on
     ties).  Under guidance the group is 2B wide: the uniforms are the B columns of the call padded to that width (the twins' columns are never
     read), and the tokens come back 2B long, rows [B, 2B) repeating rows [0, B)."""
     u, lp_parts = None, []              # lp_parts: [2, B, steps] blocks in generation order (first token, then every chunk)
@@ -77,7 +78,7 @@ def first_pick(model, plan, kv, nxt, B: int, generator):
             if W != B:
                 u = torch.nn.functional.pad(u, (0, W - B))
             nxt = model.sample_last(kv, u[0], plan.temperature, plan.top_k, **plan.warp)
-        elif plan.repetition_penalty != 1.0 or plan.bans_on or W != B:
+        elif plan.repetition_penalty != 1.0 or plan.bans_on or plan.allowed is not None or W != B:
             nxt = model.greedy_last(kv, W, **plan.pen)
         if plan.output_logprobs:
             lp_parts.append(model.logprobs_last(kv, B)[:, :, None])

@@ -14,6 +14,7 @@ from dataclasses import dataclass
 from typing import Any, Dict, Optional, Sequence, Tuple
 
 from .guidance import check_guidance
+from .allowed import check_allowed
 from .logit_bans import LogitBans, check_bans
 from .sample_filters import check_filters
 
@@ -54,6 +55,7 @@ REFUSED = {
     "epsilon_cutoff": _positive,
     "eta_cutoff": _positive,
     "encoder_repetition_penalty": lambda v: v is not None and v != 1.0,
+    "prefix_allowed_tokens_fn": lambda v: v is not None,
 }
 
 
@@ -117,6 +119,8 @@ def check_generate_kwargs(kwargs: Dict[str, Any], generation_config=None, who: s
                     "num_beams": "; beam search: this package's own keyword `beams`",
                     **{hf: f"; HF's -inf processors: this package's own keyword `bans` (logit_bans.LogitBans({field}=...))"
                        for hf, field in BANS_HINT.items()},
+                    "prefix_allowed_tokens_fn": "; a callback cannot run on the device -- constrained decoding: this package's own keyword `allowed` "
+                                                "(allowed.TokenAutomaton.from_sequences / from_texts / from_edges)",
                     **{hf: f"; HF's sampling warpers behind top_p: this package's own keyword `filters` (sample_filters.SampleFilters({hf}=...))"
                        for hf in FILTERS_HINT}}.get(name, "")
             raise ValueError(f"{who}: {where} `{name}`={v!r} is not implemented by this package (it would change the result of HF's generate()); "
@@ -312,13 +316,15 @@ class CacheSettings:
     """What a KV cache is switched to for the length of ONE call, and the one scope that does it: `apply` (or the prefill, for what it takes)
     switches on what is on, `clear` switches off exactly that.  logprobs: True records log-probabilities (False: `apply` turns the switch off, None
     leaves it).  bans: a checked LogitBans with the `eos_id` its length rules ban; filters: a checked SampleFilters; lookup: (D, n); guidance:
-    (scale, pairs), switched on behind the prefill of prompts + negatives (no prefill takes it: its own first token is not a covered pick).  None: off."""
+    (scale, pairs), switched on behind the prefill of prompts + negatives (no prefill takes it: its own first token is not a covered pick); allowed:
+    a checked allowed.Allowed (automaton, one root per prompt), which also uses `eos_id`.  None: off."""
     logprobs: Optional[bool] = None
     bans: Any = None
     eos_id: int = -1
     filters: Any = None
     lookup: Optional[Tuple[int, int]] = None
     guidance: Optional[Tuple[float, int]] = None
+    allowed: Any = None
 
     def prefill_kwargs(self) -> dict:
         """The keywords of model.prefill that are on: it sets them before the prompt runs, so that the first pick and the id record see them."""
@@ -327,6 +333,8 @@ class CacheSettings:
             kw.update(bans=self.bans, eos_id=self.eos_id)
         if self.lookup is not None:
             kw.update(lookup=self.lookup)
+        if self.allowed is not None:
+            kw.update(allowed=self.allowed, eos_id=self.eos_id)
         return kw
 
     def apply(self, model, kv, prefilled: bool = False):
@@ -338,6 +346,8 @@ class CacheSettings:
                 model.set_bans(kv, self.bans, self.eos_id)
             if self.lookup is not None:
                 model.set_lookup(kv, *self.lookup)
+            if self.allowed is not None:
+                model.set_allowed(kv, self.allowed.automaton, self.allowed.roots, self.eos_id)
         if self.filters is not None:
             model.set_filters(kv, self.filters)
         if self.guidance is not None:
@@ -354,6 +364,8 @@ class CacheSettings:
             model.set_lookup(kv, 0)
         if self.guidance is not None:
             model.set_guidance(kv, 1.0, 0)
+        if self.allowed is not None:
+            model.set_allowed(kv, None)
 
 
 @dataclass(frozen=True)
@@ -386,6 +398,7 @@ class GenerationPlan:
     stops: Optional[list] = None
     guidance: Any = None            # the checked guidance.Guidance of a guided call (None: off) and its negatives, one id list per prompt
     negatives: Optional[tuple] = None
+    allowed: Any = None             # the checked allowed.Allowed of a constrained call (None: off)
 
     @property
     def warp(self) -> dict:
@@ -399,16 +412,16 @@ class GenerationPlan:
     def settings(self) -> CacheSettings:
         return CacheSettings(True if self.output_logprobs else None, self.bans if self.bans_on else None, self.eos_id,
                              self.filters if self.filters_on else None, self.lookup if self.lookup[0] else None,
-                             (self.guidance.scale, len(self.negatives)) if self.guidance is not None else None)
+                             (self.guidance.scale, len(self.negatives)) if self.guidance is not None else None, self.allowed)
 
 
 def plan_generate(model, seqs, do_sample=False, temperature=None, max_new_tokens=1024, stopping_criteria=None, eos_token_id="config", chunk=32,
                   top_k=None, stop_strings=None, tokenizer=None, kv_reuse_key=None, top_p=None, repetition_penalty=None, output_logprobs=False,
                   samples_per_prompt=1, beams=1, length_penalty=None, early_stopping=None, output_beam_scores=False, bans=None, filters=None,
-                  lookup=0, lookup_ngram=2, lookup_sample=False, unused=None, guidance=None) -> GenerationPlan:
+                  lookup=0, lookup_ngram=2, lookup_sample=False, unused=None, guidance=None, allowed=None) -> GenerationPlan:
     """The plan of generate(seqs, ...) -- its keywords under their own names, `unused` what fell into **_unused -- or the first ValueError of the
-    call: every check in the order generate() has always made them, on the host.  Of `model` only generation_config, config and (under `bans`)
-    vocab_size are read."""
+    call: every check in the order generate() has always made them, on the host.  Of `model` only generation_config, config and (under `bans`,
+    `allowed` or `guidance`) vocab_size are read."""
     gc, B = model.generation_config, len(seqs)       # `model.config` is read where it is needed: a call refused before that needs none
     check_generate_kwargs(unused or {}, gc, filters_given=filters is not None)
     temperature, top_k, top_p, rep_pen = resolve_sampling(temperature, top_k, top_p, repetition_penalty, gc)
@@ -424,6 +437,7 @@ def plan_generate(model, seqs, do_sample=False, temperature=None, max_new_tokens
     ban_on = not ban.effective_neutral(eos_i)
     look = check_lookup(lookup, lookup_ngram, B, sample, K, n_samples, rep_pen, ban_on, bool(output_logprobs), lookup_sample=bool(lookup_sample))
     filt = check_filters(filters, gc, K)
+    allow = None if allowed is None else check_allowed(allowed, B, model.vocab_size, eos_i if eos_i >= 0 else None, K, look[0])      # None: the call as it has always been
     max_seq = max(len(s) for s in seqs) + max_new_tokens
     if max_seq > model.config.max_position_embeddings:
         raise ValueError(f"prompt + max_new_tokens = {max_seq} exceeds max_position_embeddings {model.config.max_position_embeddings}")
@@ -455,4 +469,4 @@ def plan_generate(model, seqs, do_sample=False, temperature=None, max_new_tokens
         max_seq = max(max_seq, (longest + 63) // 64 * 64)
     return GenerationPlan(sample, temperature, top_k, top_p, rep_pen, max_new_tokens, eos_i, chunk, max_seq, K, length_penalty, early_stopping,
                           bool(output_beam_scores), n_samples, bool(output_logprobs), ban, ban_on, filt, sample and not filt.neutral, look,
-                          bool(lookup_sample), tuple(criteria), stops, guide, negatives)
+                          bool(lookup_sample), tuple(criteria), stops, guide, negatives, allow)

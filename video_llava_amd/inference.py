@@ -211,7 +211,7 @@ def guidance_kwargs(guidance_scale, guidance_negative) -> dict:
 
 def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                         transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, bans=None, filters=None, lookup=0,
-                        lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video"):
+                        lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video", allowed=None):
     """Answer `question` about one clip.  Same positional signature and defaults as the reference
     (video_chatgpt/inference.py:47; do_sample=True, temperature=0.2, max_new_tokens=1024 at :109-111); pass
     do_sample=False for deterministic greedy decoding.  `features`: pooled features computed earlier (skips the tower).  `bans`
@@ -223,10 +223,11 @@ def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, 
     answer of the call without the two keywords for the same generator state.  `guidance_scale` = s (None or 1: off): classifier-free guidance,
     model.generate(guidance=) -- every pick reads s * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond), `uncond` the logits of
     `guidance_negative`: "no_video" (the same conversation prompt without the video tokens: contrast decoding against the language prior),
-    "last_token" (HF's default negative) or a negative prompt text."""
+    "last_token" (HF's default negative) or a negative prompt text.  `allowed` (allowed.TokenAutomaton): constrained decoding,
+    model.generate(allowed=) -- the answer is a path of the automaton, e.g. TokenAutomaton.from_texts(tokenizer, ["yes", "no"])."""
     new_ids, stop_str = video_chatgpt_infer_ids(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                                 transcript, do_sample, temperature, max_new_tokens, features,
-                                                **given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample),
+                                                **given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample, allowed=allowed),
                                                 **guidance_kwargs(guidance_scale, guidance_negative))
     outputs = tokenizer.batch_decode([new_ids], skip_special_tokens=True)[0]
     return outputs.strip().rstrip(stop_str).strip()
@@ -234,15 +235,16 @@ def video_chatgpt_infer(video_frames, question, conv_mode, model, vision_tower, 
 
 def video_chatgpt_infer_logprobs(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                  transcript=None, do_sample=True, temperature=0.2, max_new_tokens=1024, features=None, bans=None, filters=None, lookup=0,
-                                 lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video", **generate_kwargs):
+                                 lookup_ngram=2, lookup_sample=False, guidance_scale=None, guidance_negative="no_video", allowed=None, **generate_kwargs):
     """`video_chatgpt_infer` that also says how probable the answer it produced was (model.generate(output_logprobs=True): recorded on the device
     at pick time, no second prefill).  Returns a dict: "text" (what video_chatgpt_infer returns), "ids" (the generated token ids),
     "token_logprobs" (per id, the model's own log-probability: HF's compute_transition_scores on the raw logits -- what video_chatgpt_score
     gives for the same ids), "transition_scores" (per id, the log of the probability the pick used, after repetition penalty / temperature /
     top-k / top-p) and "logprob" (the fp64 sum of token_logprobs).  `lookup` / `lookup_sample` keep the signature of
     video_chatgpt_infer; lookup steps record no log-probabilities, so anything but 0 / False is refused by generate().  `guidance_scale` /
-    `guidance_negative` likewise: a guided pick records none, so a scale other than None / 1 is refused by generate()."""
-    asked = dict(given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample),
+    `guidance_negative` likewise: a guided pick records none, so a scale other than None / 1 is refused by generate().  `allowed`
+    (allowed.TokenAutomaton): constrained decoding, as in video_chatgpt_infer -- "transition_scores" are then normalised over the allowed tokens."""
+    asked = dict(given(bans=bans, filters=filters, lookup=lookup, lookup_ngram=lookup_ngram, lookup_sample=lookup_sample, allowed=allowed),
                  **guidance_kwargs(guidance_scale, guidance_negative))
     out, output_ids, n_in, stop_str = _infer_generate(video_frames, question, conv_mode, model, vision_tower, tokenizer, image_processor, video_token_len,
                                                       transcript, do_sample, temperature, max_new_tokens, features,

@@ -22,7 +22,7 @@ import torch.nn as nn
 from .. import _lib, generate_loop
 from ..constants import CLIP_WIDTH
 from ..beam_reference import early_code
-from ..generation import CacheSettings, fork_sources, load_generation_config, plan_generate
+from ..generation import MAX_GROUP, CacheSettings, fork_sources, load_generation_config, plan_generate
 from ..logit_bans import LogitBans
 from ..sample_filters import SampleFilters
 from ..scoring import ScoreOutput, id_rows, shift_labels
@@ -367,7 +367,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
 
     def prefill(self, seqs: Sequence[Sequence[int]], video_spatio_temporal_features: Optional[torch.Tensor], max_seq: int,
                 want_logits: bool = False, want_all_logits: bool = False, append_to=None, logprobs: Optional[bool] = None,
-                capacity: Optional[int] = None, bans=None, eos_id: int = -1, lookup=None):
+                capacity: Optional[int] = None, bans=None, eos_id: int = -1, lookup=None, allowed=None):
         """Run the prompt(s); returns (kv handle, next-token ids [B] int32 on device, logits [B, vocab] or None) -- with want_all_logits a fourth
         entry: the logits of EVERY position, [sum of lengths, vocab] fp32 (what the reference's forward returns, model/video_chatgpt.py:225-226).
         `append_to` = a kv handle this model filled before: the rows continue its sequences (pgv_llm_prefill_append; `max_seq` is ignored).
@@ -376,7 +376,9 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         `capacity`: the cache is created for max(B, capacity) sequences, so that fork() has slots to grow into (ignored with `append_to`).
         `bans` (logit_bans.LogitBans, checked) with `eos_id`: set the cache's logit bans (set_bans) before the prompt runs, so that the slots' id
         record holds it -- on the `append_to` path too; None leaves the cache's configuration as it is.
-        `lookup` (D, n): set_lookup before the prompt runs, for the same reason; None leaves the setting as it is."""
+        `lookup` (D, n): set_lookup before the prompt runs, for the same reason; None leaves the setting as it is.
+        `allowed` (allowed.Allowed, checked: an automaton and one root per prompt) with `eos_id`: set_allowed before the prompt runs, so that the
+        slots' prompt lengths are recorded; None leaves the cache's automaton as it is."""
         B = len(seqs)
         lens = [len(s) for s in seqs]
         feats = video_spatio_temporal_features
@@ -391,7 +393,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             self._reuse = None
         else:
             kv = append_to
-        on = CacheSettings(logprobs, bans, eos_id, lookup=lookup)
+        on = CacheSettings(logprobs, bans, eos_id, lookup=lookup, allowed=allowed)
         on.apply(self, kv)
         flat = np.concatenate([np.asarray(s, dtype=np.int32) for s in seqs])
         h_lens = (C.c_int32 * B)(*lens)
@@ -518,6 +520,27 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
             return
         cfg = _lib.BanConfig.from_bans(bans, -1 if eos_id is None else int(eos_id))
         _lib.check(self.ctx.lib.pgv_kv_set_bans(kv, C.byref(cfg)), "pgv_kv_set_bans")
+
+    def set_allowed(self, kv, automaton=None, roots=None, eos_id: int = -1):
+        """pgv_kv_set_allowed: constrained decoding by a token automaton (allowed.TokenAutomaton; None: off) for every later covered pick on this
+        cache.  `roots`: the start state of every slot (None: all 0; a shorter list is padded with 0).  `eos_id`: the token that ends an answer --
+        the rule needs one.  Set it before the prefill of the sequences it is meant for (prefill(..., allowed=) does)."""
+        if automaton is None:
+            _lib.check(self.ctx.lib.pgv_kv_set_allowed(kv, None), "pgv_kv_set_allowed")
+            return
+        full = np.zeros(MAX_GROUP, dtype=np.int32)
+        if roots is not None:
+            full[:len(roots)] = np.asarray(roots, dtype=np.int32)
+        cfg = _lib.AllowConfig.from_automaton(automaton, full, -1 if eos_id is None else int(eos_id))
+        _lib.check(self.ctx.lib.pgv_kv_set_allowed(kv, C.byref(cfg)), "pgv_kv_set_allowed")
+
+    def allow_peek(self, kv, slot: int, n: int):
+        """pgv_kv_allow_peek (test read-back): (the first n entries of the slot's state record as a list, the slot's root)."""
+        out = torch.empty(int(n) + 1, dtype=torch.int32, device=self.device_)
+        _lib.check(self.ctx.lib.pgv_kv_allow_peek(kv, int(slot), int(n), out.data_ptr(), out[int(n):].data_ptr(), _lib.stream_ptr(self.device_)),
+                   "pgv_kv_allow_peek")
+        h = out.cpu().tolist()
+        return h[:int(n)], h[int(n)]
 
     def set_guidance(self, kv, scale: float = 1.0, pairs: int = 0):
         """pgv_kv_set_guidance: classifier-free guidance for every later covered pick on this cache -- slots [0, pairs) of a live group of 2 * pairs are
@@ -773,7 +796,7 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
                  kv_reuse_key=None, top_p: Optional[float] = None, repetition_penalty: Optional[float] = None, output_logprobs: bool = False,
                  samples_per_prompt: int = 1, beams: int = 1, length_penalty: Optional[float] = None, early_stopping=None,
                  output_beam_scores: bool = False, bans=None, filters=None, lookup: int = 0, lookup_ngram: int = 2, lookup_sample: bool = False,
-                 guidance=None, **_unused):
+                 guidance=None, allowed=None, **_unused):
         """Returns LongTensor [B, S + n_new] on the device, prompt echoed (checked by inference.py:115-117).
         `output_logprobs=True` (a keyword of this package): returns generation.GenerateLogprobsOutput instead -- `.sequences` is that tensor,
         `.token_logprobs` / `.transition_scores` [B, n_new] fp32 on the host are each new token's log-probability under the model's own
@@ -861,11 +884,21 @@ class VideoChatGPTLlamaForCausalLM(nn.Module):
         HF's place in the chain: in front of the repetition penalty, the bans and the warpers, which all see the guided scores.  Combines with
         sampling, temperature, top_k, top_p, `filters`, repetition_penalty, `bans`, `stop_strings` and `stopping_criteria`; the uniforms stay
         torch.rand(max_new_tokens, B).  Refused with beams > 1, lookup, samples_per_prompt > 1, kv_reuse_key, output_logprobs and B > 32
-        (guidance.check_guidance).  None or scale 1 is the call without the keyword, bit for bit."""
+        (guidance.check_guidance).  None or scale 1 is the call without the keyword, bit for bit.
+        `allowed` (a keyword of this package: allowed.TokenAutomaton for all prompts, a list with one per prompt, or None; HF's
+        `prefix_allowed_tokens_fn` is refused -- a callback cannot run on the device): constrained decoding, HF's PrefixConstrainedLogitsProcessor
+        with the callback compiled into a token automaton (TokenAutomaton.from_sequences / from_texts: a closed set of answers; from_edges: the
+        general form) that the device follows inside the captured decode graphs (pgv.h: pgv_kv_set_allowed), at the bans' place in the chain.  Only
+        the tokens of the reached state's edges may come next, plus EOS where the state accepts; a walk that leaves the automaton, or a state
+        without edges, allows EOS alone (allowed.allowed_ids is the rule).  Needs an EOS token.  Greedy decoding takes the route of greedy under a
+        repetition penalty.  Combines with sampling, temperature, top_k, top_p, `filters`, repetition_penalty, `bans`, `guidance`,
+        samples_per_prompt (a sample starts at its prompt's root), output_logprobs (token_logprobs stay the raw model's, transition_scores are
+        normalised over what survives), stop_strings and stopping_criteria; `kv_reuse_key` falls back to the full prefill; `beams` > 1 and `lookup`
+        are refused.  None is the call without the keyword, bit for bit; the cache's automaton is cleared when the call ends."""
         seqs = [row.tolist() for row in input_ids.cpu()] if torch.is_tensor(input_ids) else [list(s) for s in input_ids]
         plan = plan_generate(self, seqs, do_sample, temperature, max_new_tokens, stopping_criteria, eos_token_id, chunk, top_k, stop_strings, tokenizer,
                              kv_reuse_key, top_p, repetition_penalty, output_logprobs, samples_per_prompt, beams, length_penalty, early_stopping,
-                             output_beam_scores, bans, filters, lookup, lookup_ngram, lookup_sample, unused=_unused, guidance=guidance)
+                             output_beam_scores, bans, filters, lookup, lookup_ngram, lookup_sample, unused=_unused, guidance=guidance, allowed=allowed)
         if plan.beams > 1:
             return generate_loop.generate_beams(self, plan, seqs, video_spatio_temporal_features, timings)
         return generate_loop.generate_chunks(self, plan, seqs, video_spatio_temporal_features, generator, tokenizer, timings, kv_reuse_key)
