@@ -608,3 +608,115 @@ def test_library_refusals(ctx):
             m.set_allowed(kv, A.trie, [0], 2)
     finally:
         m.set_lookup(kv, 0)
+
+
+# ---- 6. one cache through every feature ----------------------------------------------------------------------------------------------------------
+def test_one_cache_object_through_every_feature(ctx):
+    """ONE cache object (2 prompts, max_seq 128, capacity 4) runs, a first token and 10 decode steps each (on a used cache one 8-step graph and two 1-step graphs) and every feature switched off again behind its run: plain
+    greedy; bans; plain greedy; an automaton; automaton + bans; sampled with fixed uniforms; greedy with log-probabilities; guidance with 1 pair (the
+    2 slots are a prompt and its negative); lookup D = 3, n = 2; beam K = 2; plain greedy.  Every run's tokens -- and log-probabilities, beam scores
+    and lookup counts where there are any -- equal bit for bit the same run on a freshly created cache, and the three plain runs equal each other:
+    the decode graphs' key and the per-kind eager-first flags separate every configuration (a stale graph would replay another run's launches)."""
+    from video_llava_amd.logit_bans import LogitBans
+    cfg, m = _tiny(seed=8)
+    eos, n, W = 2, 10, 2
+    A = _automata(cfg)
+    p0 = [1] + np.random.default_rng(21).integers(3, cfg.vocab - 3, 14).tolist()
+    prompts = [p0, p0[-4:]]                                  # the second prompt is the first one's negative: its last tokens without the context
+    bans = LogitBans(no_repeat_ngram=2, min_new_tokens=4).check(cfg.vocab, eos)
+    al = check_allowed(A.cyc, W, cfg.vocab, eos)
+    u = torch.rand(n + 1, W, generator=torch.Generator().manual_seed(7))
+    seen = []                                                # the cache handle of every run
+
+    def prefill(**kw):
+        kv, nxt, _ = m.prefill(prompts, None, 128, capacity=4, **kw)
+        seen.append(kv.value)
+        return kv, nxt
+
+    def greedy(kv, nxt, repick):
+        if repick:
+            nxt = m.greedy_last(kv, W)                       # the prefill's arg-max knows no processor (generate_loop.first_pick)
+        return [nxt.cpu(), m.decode_greedy(kv, nxt, n, eos).cpu()]
+
+    def plain():
+        return greedy(*prefill(), False)
+
+    def banned():
+        kv, nxt = prefill(bans=bans, eos_id=eos)
+        try:
+            return greedy(kv, nxt, True)
+        finally:
+            m.set_bans(kv, None)
+
+    def constrained(with_bans):
+        kv, nxt = prefill(allowed=al, eos_id=eos, **({"bans": bans} if with_bans else {}))
+        try:
+            return greedy(kv, nxt, True)
+        finally:
+            m.set_allowed(kv, None)
+            m.set_bans(kv, None)
+
+    def sampled():
+        kv, _nxt = prefill()
+        first = m.sample_last(kv, u[0], 0.9, 50, top_p=0.9)
+        out = [first.cpu(), m.decode_sample(kv, first, n, eos, 0.9, 50, u[1:], top_p=0.9).cpu()]
+        m.set_warpers(kv)
+        return out
+
+    def logprobs():
+        kv, nxt = prefill(logprobs=True)
+        try:
+            out = [bits(m.logprobs_last(kv, W).cpu())] + greedy(kv, nxt, False)
+            return out + [bits(m.logprobs_steps(kv, W, n).cpu())]
+        finally:
+            m.set_logprobs(kv, False)
+
+    def guided():
+        kv, nxt = prefill()
+        m.set_guidance(kv, 1.5, 1)
+        try:
+            return greedy(kv, nxt, True)
+        finally:
+            m.set_guidance(kv, 1.0, 0)
+
+    def lookup():
+        kv, nxt = prefill(lookup=(3, 2))
+        try:
+            toks, counts = m.decode_lookup(kv, nxt, n, eos, [n] * W)
+            return [nxt.cpu(), toks.cpu(), torch.from_numpy(counts)]
+        finally:
+            m.set_lookup(kv, 0)
+
+    def beam():
+        kv, _nxt = prefill()
+        m.beam_begin(kv, 2, n + 1, eos)                      # the first pick, then n steps: the budget ends the run
+        m.decode_beam(kv, n)
+        out = []
+        for p in range(W):
+            toks, score, fin = m.beam_result(kv, p, 0)
+            out += [torch.tensor(toks), bits(torch.tensor([score])), torch.tensor([fin])]
+        return out
+
+    runs = [("plain", plain), ("bans", banned), ("plain again", plain), ("automaton", lambda: constrained(False)), ("automaton + bans", lambda: constrained(True)),
+            ("sampled", sampled), ("logprobs", logprobs), ("guidance", guided), ("lookup", lookup), ("beam", beam), ("plain last", plain)]
+
+    def fresh_cache():
+        for kv in m._kv.values():
+            m.ctx.lib.pgv_kv_destroy(kv)
+        m._kv.clear()
+
+    want = []
+    for _name, run in runs:
+        fresh_cache()
+        want.append(run())
+    fresh_cache()
+    seen.clear()
+    got = [run() for _name, run in runs]
+    assert len(set(seen)) == 1 and len(seen) == len(runs), "the runs did not share one cache object"
+    for (name, _run), g, w in zip(runs, got, want):
+        assert len(g) == len(w) and all(a.shape == b.shape and torch.equal(a, b) for a, b in zip(g, w)), (name, g, w)
+    for i in (2, 10):
+        assert all(torch.equal(a, b) for a, b in zip(got[0], got[i])), runs[i][0]
+    tokens = {name: torch.cat([g[0][:, None], g[1]], 1) for (name, _r), g in zip(runs, got) if name in ("plain", "bans", "automaton", "sampled", "guidance")}
+    print({k: not torch.equal(tokens["plain"], v) for k, v in tokens.items()}, "<- which features changed the plain answers")
+    assert not torch.equal(tokens["plain"], tokens["automaton"]), "the automaton left the answers as they were: the run pins nothing"

@@ -764,19 +764,39 @@ int main(int argc, char** argv) {
 
 
 def test_pick_params_and_decode_graph_key(tmp_path):
-    """csrc/pick_params.h, compiled on its own with g++ (it must need no HIP header): (1) pick_greedy(p) is temperature 1, top_k 1, top_p 1,
-    penalty p, greedy; (2) two decode-graph keys that differ in exactly one of B, eos, flags, generation, the log-probability switch or one of the
-    five PickParams fields compare unequal -- a field left out of the comparison would replay a stale graph; (3) the keys of two runs without
-    AM_SAMPLE compare equal whatever sampled parameters an earlier run left in flight, and differ from the key of a sampled run.  Where g++ has the
-    sanitizer runtimes the same stand-alone program runs a second time under ASan + UBSan."""
+    """csrc/pick_params.h and csrc/kv_features.h, each compiled on its own with g++ (they must need no HIP header): (1) pick_greedy(p) is
+    temperature 1, top_k 1, top_p 1, penalty p, greedy; (2) two decode-graph keys, built by the ONE builder llm.hip uses (KvFeatures + the per-call
+    values), that differ in exactly one of the key's 21 fields -- B, eos, flags, generation, the log-probability switch, the nine PickParams fields,
+    beams, bans, lookup_D, lookup_n, guide_pairs, guide_scale, allowed -- compare unequal: a field left out of the comparison would replay a stale
+    graph; (3) the builder's five normalisations, one by one: the keys of two runs without AM_SAMPLE compare equal whatever sampled parameters an
+    earlier run left in flight (and differ from a sampled run's), beams is 0 without AM_BEAM, guide_scale is 1 without pairs, lookup_D / lookup_n
+    are 0 unless the steps are lookup steps, and bans / allowed are 0 when off; (4) the rule table: for every operation and every single feature
+    switched on in an otherwise neutral KvFeatures, refused or not and with which message, against the literal list below, and the three orderings
+    (set_guidance: logprobs before beam before lookup; beam_begin: bans before allowed; lookup run: penalty before bans).  Where g++ has the
+    sanitizer runtimes the same stand-alone program runs a second time under ASan + UBSan.  llm.hip holds no second copy of a rule text or of
+    the key assembly."""
     import shutil
     gxx = shutil.which("g++")
     assert gxx, "g++ is part of the image"
     csrc = os.path.join(ROOT, "video_llava_amd", "csrc")
     prog = r"""#include <cstdio>
-#include "pick_params.h"
+#include <cstring>
+#include "kv_features.h"
 static int bad = 0;
 #define EXPECT(c) do { if (!(c)) { printf("FAILED line %d: %s\n", __LINE__, #c); bad = 1; } } while (0)
+// a cache with nothing on but (maybe) the log-probabilities, stepping plain steps: the six values the key had before the features
+static DecodeGraphKey key6(int B, int eos, int flags, int generation, bool logprobs, const PickParams& in_flight) {
+    KvFeatures f;
+    f.logprobs = logprobs;
+    return decode_graph_key(f, B, eos, flags, generation, in_flight, false);
+}
+// the first refusal of an operation, phase 0 before phase 1, "" for none
+static const char* first(KvOp op, const KvFeatures& f) {
+    static char msg[512];
+    if (kv_refusal(op, 0, f, "W", "X", msg, sizeof(msg)) || kv_refusal(op, 1, f, "W", "X", msg, sizeof(msg))) return msg;
+    return "";
+}
+struct Want { KvOp op; KvFeature on; const char* msg; };
 int main() {
     const PickParams d;
     EXPECT(d.temperature == 1.f && d.top_k == 0 && d.top_p == 1.f && d.penalty == 1.f && !d.greedy);
@@ -785,32 +805,150 @@ int main() {
     EXPECT((g == PickParams{1.f, 1, 1.f, 1.3f, true}) && !(g == pick_greedy(1.2f)));
     const PickParams p{0.7f, 50, 0.9f, 1.2f, false};
     const int F = AM_INC_POS | AM_RECORD | AM_SAMPLE;
-    const DecodeGraphKey k = decode_graph_key(2, 7, F, 3, false, p);
-    EXPECT(k == decode_graph_key(2, 7, F, 3, false, p));
+    const DecodeGraphKey k = key6(2, 7, F, 3, false, p);
+    EXPECT(k == key6(2, 7, F, 3, false, p));
     EXPECT(k.B == 2 && k.eos == 7 && k.flags == F && k.generation == 3 && !k.logprobs && k.pick == p);
     EXPECT(!(DecodeGraphKey{} == k) && DecodeGraphKey{}.generation == -1);
     int differ = 0;
-    differ += !(k == decode_graph_key(3, 7, F, 3, false, p));
-    differ += !(k == decode_graph_key(2, -1, F, 3, false, p));
-    differ += !(k == decode_graph_key(2, 7, F & ~AM_RECORD, 3, false, p));
-    differ += !(k == decode_graph_key(2, 7, F, 4, false, p));
-    differ += !(k == decode_graph_key(2, 7, F, 3, true, p));
-    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.8f, 50, 0.9f, 1.2f, false}));
-    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 49, 0.9f, 1.2f, false}));
-    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 50, 0.8f, 1.2f, false}));
-    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 50, 0.9f, 1.3f, false}));
-    differ += !(k == decode_graph_key(2, 7, F, 3, false, {0.7f, 50, 0.9f, 1.2f, true}));
+    differ += !(k == key6(3, 7, F, 3, false, p));
+    differ += !(k == key6(2, -1, F, 3, false, p));
+    differ += !(k == key6(2, 7, F & ~AM_RECORD, 3, false, p));
+    differ += !(k == key6(2, 7, F, 4, false, p));
+    differ += !(k == key6(2, 7, F, 3, true, p));
+    differ += !(k == key6(2, 7, F, 3, false, {0.8f, 50, 0.9f, 1.2f, false}));
+    differ += !(k == key6(2, 7, F, 3, false, {0.7f, 49, 0.9f, 1.2f, false}));
+    differ += !(k == key6(2, 7, F, 3, false, {0.7f, 50, 0.8f, 1.2f, false}));
+    differ += !(k == key6(2, 7, F, 3, false, {0.7f, 50, 0.9f, 1.3f, false}));
+    differ += !(k == key6(2, 7, F, 3, false, {0.7f, 50, 0.9f, 1.2f, true}));
     EXPECT(differ == 10);
     const int G = AM_INC_POS | AM_RECORD;
-    const DecodeGraphKey a = decode_graph_key(2, 7, G, 3, false, p), b = decode_graph_key(2, 7, G, 3, false, pick_greedy(2.f));
+    const DecodeGraphKey a = key6(2, 7, G, 3, false, p), b = key6(2, 7, G, 3, false, pick_greedy(2.f));
     EXPECT(a == b && a.pick == PickParams{} && !(a == k));
-    if (!bad) printf("OK %d\n", differ);
+
+    // (2) all 21 fields, from a key in which none is normalised away: a sampled beam flag set, lookup steps, every feature on
+    KvFeatures on;
+    on.bans = 4; on.allowed = 6; on.guide_pairs = 3; on.guide_scale = 1.5f; on.lookup_D = 3; on.lookup_n = 2; on.beams = 2; on.penalty = 1.2f;
+    const PickParams q{0.7f, 50, 0.9f, 1.2f, false, 0.05f, 0.9f, 1e-3f, 2e-3f};
+    const int FB = F | AM_BEAM;
+    const DecodeGraphKey full = decode_graph_key(on, 4, 7, FB, 3, q, true);
+    EXPECT(full == decode_graph_key(on, 4, 7, FB, 3, q, true));
+    EXPECT(full.beams == 2 && full.bans == 4 && full.allowed == 6 && full.guide_pairs == 3 && full.guide_scale == 1.5f && full.lookup_D == 3 && full.lookup_n == 2 && full.pick == q);
+    int all = 0;
+    all += !(full == decode_graph_key(on, 5, 7, FB, 3, q, true));
+    all += !(full == decode_graph_key(on, 4, -1, FB, 3, q, true));
+    all += !(full == decode_graph_key(on, 4, 7, FB & ~AM_RECORD, 3, q, true));
+    all += !(full == decode_graph_key(on, 4, 7, FB, 4, q, true));
+    { KvFeatures f = on; f.logprobs = true; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    const PickParams qs[9] = {{0.8f, 50, 0.9f, 1.2f, false, 0.05f, 0.9f, 1e-3f, 2e-3f}, {0.7f, 49, 0.9f, 1.2f, false, 0.05f, 0.9f, 1e-3f, 2e-3f},
+                              {0.7f, 50, 0.8f, 1.2f, false, 0.05f, 0.9f, 1e-3f, 2e-3f}, {0.7f, 50, 0.9f, 1.3f, false, 0.05f, 0.9f, 1e-3f, 2e-3f},
+                              {0.7f, 50, 0.9f, 1.2f, true, 0.05f, 0.9f, 1e-3f, 2e-3f},  {0.7f, 50, 0.9f, 1.2f, false, 0.06f, 0.9f, 1e-3f, 2e-3f},
+                              {0.7f, 50, 0.9f, 1.2f, false, 0.05f, 0.8f, 1e-3f, 2e-3f}, {0.7f, 50, 0.9f, 1.2f, false, 0.05f, 0.9f, 2e-3f, 2e-3f},
+                              {0.7f, 50, 0.9f, 1.2f, false, 0.05f, 0.9f, 1e-3f, 3e-3f}};
+    for (const PickParams& x : qs) all += !(full == decode_graph_key(on, 4, 7, FB, 3, x, true));
+    { KvFeatures f = on; f.beams = 3; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    { KvFeatures f = on; f.bans = 5; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    { KvFeatures f = on; f.lookup_D = 4; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    { KvFeatures f = on; f.lookup_n = 3; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    { KvFeatures f = on; f.guide_pairs = 2; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    { KvFeatures f = on; f.guide_scale = 2.5f; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    { KvFeatures f = on; f.allowed = 7; all += !(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    EXPECT(all == 21);
+    { KvFeatures f = on; f.penalty = 1.3f; EXPECT(full == decode_graph_key(f, 4, 7, FB, 3, q, true)); }      // the penalty reaches a step through the PickParams in flight only
+
+    // (3) the normalisations, one by one
+    EXPECT(decode_graph_key(on, 4, 7, FB & ~AM_SAMPLE, 3, q, true).pick == PickParams{});                    // without AM_SAMPLE: default PickParams
+    EXPECT(decode_graph_key(on, 4, 7, FB & ~AM_SAMPLE, 3, q, true) == decode_graph_key(on, 4, 7, FB & ~AM_SAMPLE, 3, qs[0], true));
+    EXPECT(decode_graph_key(on, 4, 7, F, 3, q, true).beams == 0);                                            // without AM_BEAM: beams 0
+    { KvFeatures f = on; f.beams = 3; EXPECT(decode_graph_key(on, 4, 7, F, 3, q, true) == decode_graph_key(f, 4, 7, F, 3, q, true)); }
+    { KvFeatures f = on; f.guide_pairs = 0; f.guide_scale = 2.5f;                                            // without pairs: scale 1
+      const DecodeGraphKey x = decode_graph_key(f, 4, 7, FB, 3, q, true);
+      EXPECT(x.guide_pairs == 0 && x.guide_scale == 1.f);
+      f.guide_scale = 1.5f; EXPECT(x == decode_graph_key(f, 4, 7, FB, 3, q, true)); }
+    { const DecodeGraphKey x = decode_graph_key(on, 4, 7, FB, 3, q, false);                                  // plain steps: D and n stay out
+      EXPECT(x.lookup_D == 0 && x.lookup_n == 0 && !(x == full));
+      KvFeatures f = on; f.lookup_D = 7; f.lookup_n = 4; EXPECT(x == decode_graph_key(f, 4, 7, FB, 3, q, false)); }
+    { KvFeatures f = on; f.bans = 0; f.allowed = 0;                                                          // off: 0, and 0 is what a neutral cache gives
+      const DecodeGraphKey x = decode_graph_key(f, 4, 7, FB, 3, q, true);
+      EXPECT(x.bans == 0 && x.allowed == 0 && key6(2, 7, F, 3, false, p).bans == 0 && key6(2, 7, F, 3, false, p).allowed == 0); }
+
+    // (4) the rule table: every (operation, single feature) that refuses, with its text; every other pair passes
+    const Want want[] = {
+        {KV_SET_ALLOWED, KF_BEAM, "W: a beam run is in flight in this cache (the beam pick applies no logits processor)"},
+        {KV_SET_ALLOWED, KF_LOOKUP, "W: pgv_kv_set_lookup is on in this cache (lookup steps verify drafts against the unconstrained pick)"},
+        {KV_SET_LOGPROBS, KF_GUIDANCE, "W: guidance is on in this cache (a guided pick records no log-probabilities)"},
+        {KV_SET_GUIDANCE, KF_LOGPROBS, "W: pgv_kv_set_logprobs is on in this cache (a guided pick records no log-probabilities)"},
+        {KV_SET_GUIDANCE, KF_BEAM, "W: a beam run is in flight in this cache"},
+        {KV_SET_GUIDANCE, KF_LOOKUP, "W: pgv_kv_set_lookup is on in this cache (lookup steps verify drafts against the unguided pick)"},
+        {KV_SET_LOOKUP, KF_GUIDANCE, "W: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)"},
+        {KV_SET_LOOKUP, KF_ALLOWED, "W: a token automaton is set on this cache (pgv_kv_set_allowed); lookup steps verify drafts against the unconstrained pick"},
+        {KV_PREFILL_SLOTS, KF_GUIDANCE, "W: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)"},
+        {KV_FORK, KF_GUIDANCE, "W: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)"},
+        {KV_BEAM_BEGIN, KF_GUIDANCE, "W: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)"},
+        {KV_BEAM_BEGIN, KF_BANS, "W: logit bans are set on this cache (pgv_kv_set_bans); the beam pick applies no logits processor"},
+        {KV_BEAM_BEGIN, KF_ALLOWED, "W: a token automaton is set on this cache (pgv_kv_set_allowed); the beam pick applies no logits processor"},
+        {KV_LOOKUP_RUN, KF_GUIDANCE, "W: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)"},
+        {KV_LOOKUP_RUN, KF_PENALTY, "W: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify X"},
+        {KV_LOOKUP_RUN, KF_BANS, "W: logit bans are set on this cache (pgv_kv_set_bans); lookup steps verify X"},
+        {KV_LOOKUP_RUN, KF_ALLOWED, "W: a token automaton is set on this cache (pgv_kv_set_allowed); lookup steps verify X"},
+        {KV_LOOKUP_RUN, KF_LOGPROBS, "W: log-probabilities are on (pgv_kv_set_logprobs); lookup steps record none"},
+        {KV_LOOKUP_RUN, KF_BEAM, "W: a beam run is in flight on this cache"},
+    };
+    const KvOp ops[] = {KV_SET_ALLOWED, KV_SET_LOGPROBS, KV_SET_GUIDANCE, KV_SET_LOOKUP, KV_PREFILL_SLOTS, KV_FORK, KV_BEAM_BEGIN, KV_LOOKUP_RUN};
+    const KvFeature feats[] = {KF_LOGPROBS, KF_BANS, KF_ALLOWED, KF_GUIDANCE, KF_LOOKUP, KF_BEAM, KF_PENALTY};
+    int refused = 0;
+    for (KvOp op : ops) {
+        EXPECT(!strcmp(first(op, KvFeatures{}), ""));                     // a neutral cache: nothing refuses
+        for (KvFeature x : feats) {
+            KvFeatures f;
+            if (x == KF_LOGPROBS) f.logprobs = true;
+            if (x == KF_BANS) f.bans = 1;
+            if (x == KF_ALLOWED) f.allowed = 1;
+            if (x == KF_GUIDANCE) { f.guide_pairs = 1; f.guide_scale = 2.f; }
+            if (x == KF_LOOKUP) { f.lookup_D = 3; f.lookup_n = 2; }
+            if (x == KF_BEAM) f.beams = 2;
+            if (x == KF_PENALTY) f.penalty = 1.2f;
+            const char* expect = "";
+            for (const Want& w : want) if (w.op == op && w.on == x) expect = w.msg;
+            const char* got = first(op, f);
+            if (strcmp(got, expect)) { printf("FAILED op %d feature %d: got '%s', want '%s'\n", (int)op, (int)x, got, expect); bad = 1; }
+            refused += got[0] != 0;
+        }
+    }
+    EXPECT(refused == 19);
+    // the phases: the rules behind an operation's own state checks are not reported before them
+    { KvFeatures f; f.bans = 1; f.allowed = 1; char m[512];
+      EXPECT(!kv_refusal(KV_BEAM_BEGIN, 0, f, "W", "X", m, sizeof(m)) && kv_refusal(KV_BEAM_BEGIN, 1, f, "W", "X", m, sizeof(m)));
+      f.penalty = 1.2f; f.logprobs = true; f.beams = 2;
+      EXPECT(!kv_refusal(KV_LOOKUP_RUN, 0, f, "W", "X", m, sizeof(m)) && kv_refusal(KV_LOOKUP_RUN, 1, f, "W", "X", m, sizeof(m))); }
+    // the orderings
+    { KvFeatures f; f.logprobs = true; f.beams = 2; f.lookup_D = 3; f.lookup_n = 2;
+      EXPECT(!strcmp(first(KV_SET_GUIDANCE, f), "W: pgv_kv_set_logprobs is on in this cache (a guided pick records no log-probabilities)"));
+      f.logprobs = false; EXPECT(!strcmp(first(KV_SET_GUIDANCE, f), "W: a beam run is in flight in this cache")); }
+    { KvFeatures f; f.bans = 1; f.allowed = 1;
+      EXPECT(!strcmp(first(KV_BEAM_BEGIN, f), "W: logit bans are set on this cache (pgv_kv_set_bans); the beam pick applies no logits processor")); }
+    { KvFeatures f; f.penalty = 1.2f; f.bans = 1;
+      EXPECT(!strcmp(first(KV_LOOKUP_RUN, f), "W: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify X")); }
+    { KvFeatures f; f.guide_pairs = 1; f.guide_scale = 2.f; f.bans = 1; f.penalty = 1.2f;                   // guidance is reported before everything
+      EXPECT(!strcmp(first(KV_LOOKUP_RUN, f), "W: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)"));
+      EXPECT(!strcmp(first(KV_BEAM_BEGIN, f), "W: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)")); }
+    { char m[64];                                                        // the caller's name and the verify tail are substituted
+      KvFeatures f; f.penalty = 1.2f;
+      char big[512];
+      EXPECT(kv_refusal(KV_LOOKUP_RUN, 1, f, "pgv_llm_decode_lookup", "the plain arg-max", big, sizeof(big)));
+      EXPECT(!strcmp(big, "pgv_llm_decode_lookup: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify the plain arg-max"));
+      EXPECT(kv_refusal(KV_LOOKUP_RUN, 1, f, "pgv_llm_decode_lookup", "the plain arg-max", m, sizeof(m)) && strlen(m) == sizeof(m) - 1); }   // a short buffer truncates
+    if (!bad) printf("OK %d\n", all);
     return bad;
 }
 """
     cpp, exe, exe_san = tmp_path / "pick.cpp", tmp_path / "pick", tmp_path / "pick_san"
     cpp.write_text(prog)
-    base = [gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", csrc, str(cpp)]
+    base = [gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", csrc]
+    for header in ("pick_params.h", "kv_features.h"):                  # each header alone: no HIP header, nothing it forgot to include
+        alone = tmp_path / (header + ".cpp")
+        alone.write_text(f'#include "{header}"\nint main() {{ return 0; }}\n')
+        subprocess.run([*base, "-fsyntax-only", str(alone)], check=True)
+    base.append(str(cpp))
     subprocess.run([*base, "-o", str(exe)], check=True)
     exes = [exe]
     san = subprocess.run([*base, "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", str(exe_san)], capture_output=True, text=True)
@@ -821,7 +959,17 @@ int main() {
         print("g++ has no sanitizer runtimes here: plain build only")
     for x in exes:
         r = subprocess.run([str(x)], capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr and r.stdout == "OK 10\n", (x, r.returncode, r.stdout, r.stderr[-2000:])
+        assert r.returncode == 0 and not r.stderr and r.stdout == "OK 21\n", (x, r.returncode, r.stdout, r.stderr[-2000:])
+    # the header is what the library uses: llm.hip includes it, builds its key from the cache's snapshot alone, and holds no rule text of its own
+    users = [f for f in sorted(os.listdir(csrc)) if '#include "kv_features.h"' in open(os.path.join(csrc, f)).read()]
+    assert users == ["llm.hip"], users
+    llm, table = open(os.path.join(csrc, "llm.hip")).read(), open(os.path.join(csrc, "kv_features.h")).read()
+    for phrase in ("is on in this cache", "are set on this cache", "in flight"):
+        assert phrase not in llm and phrase in table, phrase
+    assert llm.count("decode_graph_key(") == 1 and "decode_graph_key(kv_features(kv), " in llm
+    assert llm.count("kv_features(kv)") == 2 and llm.count("static KvFeatures kv_features(const pgv_kv* kv)") == 1      # the key and kv_allows
+    for read in ("kv->ban.gen : 0", "kv->allow.gen : 0"):
+        assert llm.count(read) == 1, read
 
 
 def test_prefill_plan_row_maps_and_refusals(tmp_path):

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "kv_features.h"
 #include "llm_internal.h"
 #include "llm_weights.h"
 #include "prefill_plan.h"
@@ -46,27 +47,79 @@ struct pgv_llm {
 };
 static const LlmMat& layer_mat(const pgv_llm* m, int layer, int kind) { return m->mats[llm_mat_index(layer, kind)]; }
 
-// The fixed-address buffers one decode step works in, one entry per ROW of the step: the cache's own (kv_scratch: row b is slot b) or the row
-// scratch of pgv_kv_set_lookup, whose rows are (slot, offset) pairs.  What pgv_kv documents for its members of these names holds here.
+// The fixed-address buffers one decode step works in (so a step can be captured into a hipGraph), one entry per ROW of the step: the cache's own
+// (pgv_kv::sc: row b is slot b) or the row scratch of pgv_kv_set_lookup, whose rows are (slot, offset) pairs.
 struct DecodeScratch {
     float* resid = nullptr; void *xn = nullptr, *qkv = nullptr, *ao = nullptr, *act = nullptr; float* logits = nullptr;
-    float* amax_val = nullptr; int* amax_idx = nullptr; float* ssq = nullptr; int ssq_ts = 0, amax_ts = 0;
-    void* k8_part = nullptr; float* dattn_part = nullptr; unsigned* dattn_ticket = nullptr;
+    float* amax_val = nullptr; int* amax_idx = nullptr;     // greedy candidates of the lm_head GEMV, tile-major: [ceil(rows / 16)][vocab_cap / 16][16]
+    float* ssq = nullptr;                                   // sum-of-squares partials of the folded RMSNorm, tile-major: [ceil(rows / 16)][hidden / 16][16] (see GemvArgs in gemv.hip)
+    int ssq_ts = 0, amax_ts = 0;                            // their tile strides in elements: hidden, vocab_cap
+    void* k8_part = nullptr;                                // 8-phase residual producers (gemv.hip gemv_k8_kernel): phase tiles [hidden / 16][8][column tiles][64] float4
+    float* dattn_part = nullptr; unsigned* dattn_ticket = nullptr;   // context-split decode attention: partial states [rows * heads][8][130], arrival tickets [rows * heads] (zero between launches)
 };
+
+// A device block its owner allocates on first use and frees with itself.  unit: 10 reports KiB, 20 MiB.
+struct DevBlock {
+    char* p = nullptr;
+    DevBlock() = default; DevBlock(const DevBlock&) = delete;
+    ~DevBlock() { drop(); }
+    void drop() { if (p) (void)hipFree(p); p = nullptr; }
+    int alloc(const char* who, size_t bytes, int unit = 10) {
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) { p = nullptr; pgv_set_error("%s: hipMalloc(%zu %s): %s", who, bytes >> unit, unit == 10 ? "KiB" : "MiB", hipGetErrorString(e)); return PGV_ENOMEM; }
+        return PGV_OK;
+    }
+};
+// A configuration that lives in device memory, outside any capture: a captured decode step bakes in its addresses and sizes, and the graphs' key
+// carries gen (config_upload).  host: the words the device copy holds; gen: bumped by every call that changes the device copy
+struct DevConfig { std::vector<int> host; int eos = -1; bool on = false; int gen = 0; };
+// The id record of a cache: each slot's ids at their cache positions [B][max_seq], its prompt length [B] and the copy of the logits that the -inf
+// processors of a pick write to [B][vocab_cap].  Shared by the bans, lookup and the automaton; the first of them allocates it (kv_ids_alloc).
+struct KvIds { DevBlock blob; int *ids = nullptr, *plen = nullptr; float* logits = nullptr; };
+// logit bans (pgv_kv_set_bans): the lists of the configuration, in the id record's block
+struct KvBan : DevConfig { int* lists = nullptr; BanLists cfg; };
+// constrained decoding (pgv_kv_set_allowed): the state record [B][max_seq] (indexed by cache position) and the roots [B], one allocation by the
+// first configuration that asks; the device copy of the automaton (au binds it; cap words allocated), which grows with the configuration
+struct KvAllow : DevConfig { DevBlock blob, dev; int *state = nullptr, *root = nullptr; size_t cap = 0; AllowAuto au; };
+// classifier-free guidance (pgv_kv_set_guidance): slots [0, pairs) of a live group of 2 * pairs are conditional, slot pairs + p is the unconditional
+// twin of p.  logits [B / 2][vocab] (row stride vocab) holds the guided rows the pick reads; allocated when guidance is first switched on.  pairs 0: off
+struct KvGuide { DevBlock logits; int pairs = 0; float scale = 1.f; };
+// pgv_kv_set_logprobs: the two log-probabilities of every pick.  stat [B][2] row statistics (row_lse_kernel), last [2][B] the values of each
+// slot's latest pick (model | pick), hist [2][B][max_seq] those of the stepping calls, parallel to d_hist
+struct KvLogprobs {
+    bool on = false; float *stat = nullptr, *last = nullptr, *hist = nullptr;
+    int steps = -1;                     // steps of the last pgv_llm_decode_greedy / _sample call that ran with the switch on (-1: it was off)
+};
+// beam search (pgv_beam_begin): one allocation on first use, sized for the cache's batch -- state words [B][PGV_BEAM_STATE_WORDS(8)], gather map [B],
+// prompt lengths row0 [B], step counters t [B], the run parameters, the length-penalty table denom [max_seq] and the per-step history of tokens
+// and parents, hist [2][max_seq][B]
+struct KvBeam {
+    DevBlock blob; unsigned* state = nullptr; int *map = nullptr, *row0 = nullptr, *t = nullptr, *hist = nullptr; BeamParams* prm = nullptr; float* denom = nullptr;
+    std::vector<unsigned> stage;        // host staging of the initial state (kept alive across the async copy)
+    int K = 0, P = 0, N = 0, steps = 0; // the current run (K 0: none): width K, prompts, token budget, picks done
+};
+// row-wise steps (pgv_kv_set_lookup): one allocation by the first call that asks -- a second DecodeScratch for up to `rows` rows that are
+// (slot, offset) pairs, and the row maps (slot [rows] | j [rows])
+struct KvLookup {
+    DevBlock blob; DecodeScratch sc;
+    int *slot = nullptr, *j = nullptr, rows = 0, D = 0, n = 0;
+    std::vector<int> stage;             // host staging of the row maps / the budgets (kept alive across the async copy)
+    // prompt-lookup steps (pgv_llm_decode_lookup): row tokens and row arg-max [rows], drafts and budget per slot [B], the run's step counter and the
+    // emit counts [max_seq][B]
+    int *tok = nullptr, *t = nullptr, *ndraft = nullptr, *budget = nullptr, *k = nullptr, *counts = nullptr;
+    // their sampled form (pgv_llm_decode_lookup_sample): the uniform of every row [rows], tokens emitted before the call per slot [B] (behind budget)
+    float* u = nullptr; int* ubase = nullptr;
+    bool valid = false;                 // the id record holds exactly the ids behind cache rows [0, len) of every live slot (a plain prefill wrote it, only lookup steps since)
+};
+enum StepKind { STEP_PLAIN, STEP_LOOKUP, STEP_LOOKUP_SAMPLED, STEP_KINDS };      // what run_steps runs: token steps, prompt-lookup steps, their sampled form
 
 struct pgv_kv {
     pgv_llm* llm;
     int B, max_seq;
-    char* blob = nullptr;
+    DevBlock blob;
     std::vector<void*> Kc, Vc;          // per layer [B][heads][max_seq][128]
     size_t plane_bytes = 0;             // Kc[0], Vc[0], Kc[1], ... sit this far apart in the blob (pgv_kv_fork covers them in one launch)
-    // fixed-address decode buffers (so a decode step can be captured into a hipGraph)
-    float* resid; void* xn; void* qkv; void* ao; void* act; float* logits;
-    float* amax_val; int* amax_idx;     // greedy candidates of the lm_head GEMV, tile-major: [ceil(B / 16)][vocab_cap / 16][16]
-    float* ssq;                         // sum-of-squares partials of the folded RMSNorm, tile-major: [ceil(B / 16)][hidden / 16][16] (see GemvArgs in gemv.hip)
-    int ssq_ts, amax_ts;                // their tile strides in elements: hidden, vocab_cap
-    void* k8_part;                      // 8-phase residual producers (gemv.hip gemv_k8_kernel): phase tiles [hidden / 16][8][column tiles][64] float4
-    float* dattn_part; unsigned* dattn_ticket;   // context-split decode attention: partial states [B * heads][8][130], arrival tickets [B * heads] (zero between launches)
+    DecodeScratch sc;
     int *d_pos, *d_cur, *d_step, *d_done, *d_hist;
     std::vector<int> h_len;
     std::vector<int> h_meta;           // staging for prefill row maps (kept alive across the async copy)
@@ -75,71 +128,29 @@ struct pgv_kv {
     // tokens and step counters live in device memory and are advanced by the argmax kernel)
     hipGraphExec_t gexec[2] = {nullptr, nullptr};      // [0]: one token step, [1]: kGraphSteps consecutive steps
     DecodeGraphKey gkey;                // what they baked in
+    bool warmed[STEP_KINDS] = {};       // a step of the kind has run eagerly (code objects loaded) before the first capture
     float* d_u = nullptr;               // uniforms of a sampled decode run: [max_seq][B], indexed by the device-side step counter
     PickParams warpers;                 // pgv_kv_set_warpers: the top_p and penalty every later pick on this cache runs with (the other fields stay neutral)
-    PickParams run;                     // the stepping run in flight (AM_SAMPLE)
+    PickParams run;                     // the current stepping run (AM_SAMPLE)
     unsigned* d_seen = nullptr;         // seen-set of every slot (repetition penalty): [B][seen_words] bitmaps over the vocabulary
     int seen_words = 0;
-    // pgv_kv_set_logprobs: the two log-probabilities of every pick.  lp_stat [B][2] row statistics (row_lse_kernel), lp_last [2][B] the values of each
-    // slot's latest pick (model | pick), lp_hist [2][B][max_seq] those of the stepping calls, parallel to d_hist
-    bool lp_on = false;
-    float *lp_stat = nullptr, *lp_last = nullptr, *lp_hist = nullptr;
-    int lp_steps = -1;                  // steps of the last pgv_llm_decode_greedy / _sample call that ran with the switch on (-1: it was off)
-    bool warmed = false;
-    // beam search (pgv_beam_begin): one allocation on first use, sized for the cache's batch -- state words [B][PGV_BEAM_STATE_WORDS(8)], gather map [B],
-    // prompt lengths row0 [B], step counters t [B], the run parameters, the length-penalty table denom [max_seq] and the per-step history of tokens
-    // and parents, hist [2][max_seq][B]
-    char* bm_blob = nullptr;
-    unsigned* bm_state = nullptr; int *bm_map = nullptr, *bm_row0 = nullptr, *bm_t = nullptr, *bm_hist = nullptr; BeamParams* bm_prm = nullptr; float* bm_denom = nullptr;
-    std::vector<unsigned> bm_stage;     // host staging of the initial state (kept alive across the async copy)
-    int bm_K = 0, bm_P = 0, bm_N = 0, bm_steps = 0;      // the run in flight (bm_K 0: none): width K, prompts, token budget, picks done
-    // logit bans (pgv_kv_set_bans): one allocation by the first configuration that asks something -- the id record [B][max_seq] (indexed by cache
-    // position), the prompt lengths [B], the logits copy the bans are written to [B][vocab_cap] and the lists of the configuration
-    char* ban_blob = nullptr;
-    int *ban_ids = nullptr, *ban_plen = nullptr, *ban_lists = nullptr; float* ban_logits = nullptr;
-    BanLists ban_cfg; int ban_eos = -1;
-    std::vector<int> ban_host;          // the list words the device copy holds
-    bool ban_on = false;
-    int ban_gen = 0;                    // bumped by every pgv_kv_set_bans that changes the device copy: part of the decode graphs' key
-    // constrained decoding (pgv_kv_set_allowed): the state record [B][max_seq] (indexed by cache position) and the roots [B], one allocation by the
-    // first configuration that asks; the device copy of the automaton (al_auto binds it), which grows with the configuration.  It shares the prompt
-    // lengths and the pick's logits copy of the bans (kv_ids_alloc).
-    char* al_blob = nullptr; int *al_state = nullptr, *al_root = nullptr;
-    int* al_dev = nullptr; size_t al_cap = 0;      // device words of the automaton and how many are allocated
-    AllowAuto al_auto; int al_eos = -1;
-    std::vector<int> al_host;           // the automaton words the device copy holds
-    bool al_on = false;
-    int al_gen = 0;                     // bumped by every pgv_kv_set_allowed that changes the device copy: part of the decode graphs' key
-    // classifier-free guidance (pgv_kv_set_guidance): slots [0, g_pairs) of a live group of 2 * g_pairs are conditional, slot g_pairs + p is the
-    // unconditional twin of p.  g_logits [B / 2][vocab] (row stride vocab) holds the guided rows the pick reads; allocated when guidance is first
-    // switched on.  g_pairs 0: off
-    float* g_logits = nullptr;
-    int g_pairs = 0; float g_scale = 1.f;
-    // row-wise steps (pgv_kv_set_lookup): one allocation by the first call that asks -- a second set of the per-row decode buffers above for up to
-    // lk_rows rows that are (slot, offset) pairs, and the row maps (slot [lk_rows] | offset [lk_rows])
-    char* lk_blob = nullptr;
-    DecodeScratch lk;
-    int *lk_slot = nullptr, *lk_j = nullptr;
-    int lk_rows = 0, lk_D = 0, lk_n = 0;
-    std::vector<int> lk_stage;          // host staging of the row maps / the budgets (kept alive across the async copy)
-    // prompt-lookup steps (pgv_llm_decode_lookup): row tokens and row arg-max [lk_rows], drafts and budget per slot [B], the run's step counter and the
-    // emit counts [max_seq][B]
-    int *lk_tok = nullptr, *lk_t = nullptr, *lk_ndraft = nullptr, *lk_budget = nullptr, *lk_k = nullptr, *lk_counts = nullptr;
-    // their sampled form (pgv_llm_decode_lookup_sample): the uniform of every row [lk_rows], tokens emitted before the call per slot [B] (behind lk_budget)
-    float* lk_u = nullptr; int* lk_ubase = nullptr;
-    bool lk_warmed = false;             // a lookup step has run eagerly (code objects loaded) before the first capture
-    bool lk_warmed_s = false;           // likewise a sampled lookup step
-    bool lk_valid = false;              // the id record holds exactly the ids behind cache rows [0, len) of every live slot (a plain prefill wrote it, only lookup steps since)
+    KvIds ids; KvBan ban; KvAllow allow; KvGuide guide; KvLogprobs lp; KvBeam beam; KvLookup lookup;
 };
-static DecodeScratch kv_scratch(const pgv_kv* kv) {
-    DecodeScratch sc;
-    sc.resid = kv->resid; sc.xn = kv->xn; sc.qkv = kv->qkv; sc.ao = kv->ao; sc.act = kv->act; sc.logits = kv->logits;
-    sc.amax_val = kv->amax_val; sc.amax_idx = kv->amax_idx; sc.ssq = kv->ssq; sc.ssq_ts = kv->ssq_ts; sc.amax_ts = kv->amax_ts;
-    sc.k8_part = kv->k8_part; sc.dattn_part = kv->dattn_part; sc.dattn_ticket = kv->dattn_ticket;
-    return sc;
+// THE place that reads the switches off a cache (kv_features.h): the graph key and every cross-feature refusal go through this snapshot
+static KvFeatures kv_features(const pgv_kv* kv) {
+    KvFeatures f;
+    f.logprobs = kv->lp.on; f.bans = kv->ban.on ? kv->ban.gen : 0; f.allowed = kv->allow.on ? kv->allow.gen : 0; f.guide_pairs = kv->guide.pairs; f.guide_scale = kv->guide.scale;
+    f.lookup_D = kv->lookup.D; f.lookup_n = kv->lookup.n; f.beams = kv->beam.K; f.penalty = kv->warpers.penalty;
+    return f;
+}
+// PGV_OK, or the first refusal the rule table holds for the call in the cache's state (a null cache: the caller's own check reports it)
+static int kv_allows(const pgv_kv* kv, KvOp op, const char* who, int phase = 0, const char* verifies = "") {
+    char msg[384];
+    if (!kv || !kv_refusal(op, phase, kv_features(kv), who, verifies, msg, sizeof(msg))) return PGV_OK;
+    pgv_set_error("%s", msg); return PGV_ESTATE;
 }
 // every call that changes what the slots of the live group hold ends a beam run
-static void beam_drop(pgv_kv* kv) { kv->bm_K = 0; }
+static void beam_drop(pgv_kv* kv) { kv->beam.K = 0; }
 
 extern "C" int pgv_llm_create(pgv_ctx* ctx, const pgv_llm_config* cfg, int dtype, pgv_llm** out) {
     PGV_CHECK(ctx && cfg && out, "pgv_llm_create: null argument");
@@ -417,24 +428,21 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
     if ((size_t)kv->seen_words * 32 < V) kv->seen_words += 1;
     const size_t o_seen = take(B * (size_t)kv->seen_words * 4);
     const size_t n_lp = 4 * B + 2 * B * (size_t)max_seq, o_lp = take(n_lp * 4);
-    hipError_t e = hipMalloc((void**)&kv->blob, off);
-    if (e != hipSuccess) { delete kv; pgv_set_error("pgv_kv_create: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
-    char* b = kv->blob;
+    if (kv->blob.alloc("pgv_kv_create", off, 20) != PGV_OK) { delete kv; return PGV_ENOMEM; }
+    char* b = kv->blob.p;
     for (size_t i = 0; i < L; ++i) { kv->Kc.push_back(b + o_cache + per * 2 * i); kv->Vc.push_back(b + o_cache + per * (2 * i + 1)); }
     kv->plane_bytes = per;
-    const DecodeScratch sc = scratch_bind(b, so, llm);
-    kv->resid = sc.resid; kv->xn = sc.xn; kv->qkv = sc.qkv; kv->ao = sc.ao; kv->act = sc.act; kv->logits = sc.logits; kv->ssq = sc.ssq; kv->amax_val = sc.amax_val; kv->amax_idx = sc.amax_idx;
-    kv->ssq_ts = sc.ssq_ts; kv->amax_ts = sc.amax_ts; kv->dattn_part = sc.dattn_part; kv->dattn_ticket = sc.dattn_ticket; kv->k8_part = sc.k8_part;
+    kv->sc = scratch_bind(b, so, llm);
     int* ints = (int*)(b + o_ints);
     kv->d_pos = ints; kv->d_cur = ints + B; kv->d_step = ints + 2 * B; kv->d_done = ints + 3 * B; kv->d_hist = ints + 4 * B;
     kv->d_u = (float*)(b + o_u);
     kv->d_seen = (unsigned*)(b + o_seen);
-    kv->lp_stat = (float*)(b + o_lp); kv->lp_last = kv->lp_stat + 2 * B; kv->lp_hist = kv->lp_last + 2 * B;
-    e = hipMemset(ints, 0, (4 * B + B * (size_t)max_seq) * 4);
+    kv->lp.stat = (float*)(b + o_lp); kv->lp.last = kv->lp.stat + 2 * B; kv->lp.hist = kv->lp.last + 2 * B;
+    hipError_t e = hipMemset(ints, 0, (4 * B + B * (size_t)max_seq) * 4);
     if (e == hipSuccess) e = hipMemset(kv->d_seen, 0, B * (size_t)kv->seen_words * 4);
-    if (e == hipSuccess) e = hipMemset(kv->lp_stat, 0, n_lp * 4);
-    if (e == hipSuccess) e = scratch_clear(sc, so);
-    if (e != hipSuccess) { (void)hipFree(kv->blob); delete kv; pgv_set_error("pgv_kv_create: memset: %s", hipGetErrorString(e)); return PGV_EHIP; }
+    if (e == hipSuccess) e = hipMemset(kv->lp.stat, 0, n_lp * 4);
+    if (e == hipSuccess) e = scratch_clear(kv->sc, so);
+    if (e != hipSuccess) { delete kv; pgv_set_error("pgv_kv_create: memset: %s", hipGetErrorString(e)); return PGV_EHIP; }
     kv->h_len.assign(batch, 0);
     *out = kv;
     return PGV_OK;
@@ -443,14 +451,7 @@ extern "C" int pgv_kv_create(pgv_ctx* ctx, pgv_llm* llm, int batch, int max_seq,
 extern "C" void pgv_kv_destroy(pgv_kv* kv) {
     if (!kv) return;
     for (auto g : kv->gexec) if (g) (void)hipGraphExecDestroy(g);
-    if (kv->blob) (void)hipFree(kv->blob);
-    if (kv->bm_blob) (void)hipFree(kv->bm_blob);
-    if (kv->ban_blob) (void)hipFree(kv->ban_blob);
-    if (kv->al_blob) (void)hipFree(kv->al_blob);
-    if (kv->al_dev) (void)hipFree(kv->al_dev);
-    if (kv->lk_blob) (void)hipFree(kv->lk_blob);
-    if (kv->g_logits) (void)hipFree(kv->g_logits);
-    delete kv;
+    delete kv;                          // every device block is freed by its owner (DevBlock)
 }
 
 extern "C" int pgv_kv_set_warpers(pgv_kv* kv, float top_p, float repetition_penalty) {
@@ -464,15 +465,14 @@ extern "C" int pgv_kv_set_warpers(pgv_kv* kv, float top_p, float repetition_pena
 // logits copy behind it: one allocation by the first configuration that needs the record (pgv_kv_set_bans, pgv_kv_set_lookup)
 constexpr size_t kBanListWords = PGV_BAN_MAX_IDS + PGV_BAN_MAX_WORDS + 1;
 static int kv_ids_alloc(pgv_kv* kv, const char* who) {
-    if (kv->ban_blob) return PGV_OK;
+    if (kv->ids.blob.p) return PGV_OK;
     const size_t B = kv->B;
     const size_t b_ids = pgv_align(B * kv->max_seq * 4), b_plen = pgv_align(B * 4), b_lists = pgv_align(kBanListWords * 4),
                  b_logits = pgv_align(B * (size_t)kv->llm->vocab_cap * 4);
-    hipError_t e = hipMalloc((void**)&kv->ban_blob, b_ids + b_plen + b_lists + b_logits);
-    if (e != hipSuccess) { kv->ban_blob = nullptr; pgv_set_error("%s: hipMalloc(%zu KiB): %s", who, (b_ids + b_plen + b_lists + b_logits) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
-    kv->ban_ids = (int*)kv->ban_blob; kv->ban_plen = (int*)(kv->ban_blob + b_ids); kv->ban_lists = (int*)(kv->ban_blob + b_ids + b_plen);
-    kv->ban_logits = (float*)(kv->ban_blob + b_ids + b_plen + b_lists);
-    PGV_HIP(hipMemset(kv->ban_blob, 0, b_ids + b_plen + b_lists));
+    PGV_TRY(kv->ids.blob.alloc(who, b_ids + b_plen + b_lists + b_logits));
+    char* b = kv->ids.blob.p;
+    kv->ids.ids = (int*)b; kv->ids.plen = (int*)(b + b_ids); kv->ban.lists = (int*)(b + b_ids + b_plen); kv->ids.logits = (float*)(b + b_ids + b_plen + b_lists);
+    PGV_HIP(hipMemset(b, 0, b_ids + b_plen + b_lists));
     return PGV_OK;
 }
 
@@ -486,98 +486,92 @@ extern "C" int pgv_kv_set_filters(pgv_kv* kv, const pgv_filter_config* cfg) {
     return PGV_OK;
 }
 
-// HF's -inf processors (pgv.h).  The lists go to device memory owned by the cache, outside any capture: a captured decode step bakes in their
-// addresses and lengths, and the graphs' key carries the generation counter.
+// The upload protocol of a device-resident configuration.  The one the device copy already holds (a caller that sets and clears it around every
+// run): nothing to upload, the graphs stay valid.  Anything else waits for the picks that may still read the copy before (sync; false: the caller
+// has waited), uploads, and moves the counter in the graphs' key.
+template <class Upload>
+static int config_upload(DevConfig& c, std::vector<int>& words, int eos, bool same_shape, bool sync, Upload&& upload) {
+    if (c.gen > 0 && same_shape && eos == c.eos && words == c.host) return PGV_OK;
+    if (sync) PGV_HIP(hipDeviceSynchronize());
+    PGV_TRY(upload());
+    c.host.swap(words); c.eos = eos; c.gen += 1;
+    return PGV_OK;
+}
+
+// HF's -inf processors (pgv.h): the lists are a DevConfig of the cache.
 extern "C" int pgv_kv_set_bans(pgv_kv* kv, const pgv_ban_config* cfg) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_bans: null cache");
-    if (!cfg) { kv->ban_on = false; return PGV_OK; }
+    if (!cfg) { kv->ban.on = false; return PGV_OK; }
     std::vector<int> blob;
     BanPacked at;
     PGV_TRY(pgv_ban_pack("pgv_kv_set_bans", cfg, kv->llm->cfg.vocab, blob, at));
     PGV_CHECK(cfg->eos_id < kv->llm->cfg.vocab, "pgv_kv_set_bans: eos_id %d outside the vocabulary (%d)", cfg->eos_id, kv->llm->cfg.vocab);
-    if (pgv_ban_neutral(cfg, cfg->eos_id)) { kv->ban_on = false; return PGV_OK; }
+    if (pgv_ban_neutral(cfg, cfg->eos_id)) { kv->ban.on = false; return PGV_OK; }
     const size_t n_lists = kBanListWords;
     PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_bans"));
     PGV_CHECK(blob.size() <= n_lists, "pgv_kv_set_bans: %zu list words exceed the %zu reserved", blob.size(), n_lists);
-    // the configuration the device copy already holds (a caller that sets and clears it around every run): nothing to upload, the graphs stay valid
-    const BanLists& o = kv->ban_cfg;
+    const BanLists& o = kv->ban.cfg;
     const BanLists& n = at.cfg;
-    const bool same = kv->ban_gen > 0 && blob == kv->ban_host && cfg->eos_id == kv->ban_eos && n.ngram == o.ngram && n.n_sup == o.n_sup && n.n_beg == o.n_beg &&
-                      n.n_words == o.n_words && n.min_length == o.min_length && n.min_new == o.min_new;
-    if (!same) {
-        PGV_HIP(hipDeviceSynchronize());          // a pick in flight may still read the lists of the configuration before
-        PGV_HIP(hipMemcpy(kv->ban_lists, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
-        kv->ban_cfg = ban_lists(at, kv->ban_lists);
-        kv->ban_host = blob;
-        kv->ban_eos = cfg->eos_id;
-        kv->ban_gen += 1;
-    }
-    kv->ban_on = true;
+    const bool same = n.ngram == o.ngram && n.n_sup == o.n_sup && n.n_beg == o.n_beg && n.n_words == o.n_words && n.min_length == o.min_length && n.min_new == o.min_new;
+    PGV_TRY(config_upload(kv->ban, blob, cfg->eos_id, same, true, [&]() -> int {
+        PGV_HIP(hipMemcpy(kv->ban.lists, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+        kv->ban.cfg = ban_lists(at, kv->ban.lists); return PGV_OK;
+    }));
+    kv->ban.on = true;
     return PGV_OK;
 }
 
+// `n` entries of slot `slot` of a per-slot record [B][max_seq] and the slot's word of `one` [B], device to device
+static int record_peek(pgv_kv* kv, const char* who, const char* what, const char* by, const int* rec, const int* one, int slot, int n, int32_t* d_out, int32_t* d_one, void* stream) {
+    PGV_CHECK(kv != nullptr, "%s: null cache", who);
+    if (!rec) { pgv_set_error("%s: this cache has no %s record (%s allocates it)", who, what, by); return PGV_ESTATE; }
+    PGV_CHECK(slot >= 0 && slot < kv->B, "%s: slot %d outside the %d of the cache", who, slot, kv->B);
+    PGV_CHECK(n >= 0 && n <= kv->max_seq, "%s: %d entries outside the cache's %d", who, n, kv->max_seq);
+    if (d_out && n > 0) PGV_HIP(hipMemcpyAsync(d_out, rec + (size_t)slot * kv->max_seq, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_one) PGV_HIP(hipMemcpyAsync(d_one, one + slot, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return PGV_OK;
+}
 extern "C" int pgv_kv_ids_peek(pgv_kv* kv, int slot, int n, int32_t* d_out, int32_t* d_prompt_len, void* stream) {
-    PGV_CHECK(kv != nullptr, "pgv_kv_ids_peek: null cache");
-    if (!kv->ban_ids) { pgv_set_error("pgv_kv_ids_peek: this cache has no id record (pgv_kv_set_bans allocates it)"); return PGV_ESTATE; }
-    PGV_CHECK(slot >= 0 && slot < kv->B, "pgv_kv_ids_peek: slot %d outside the %d of the cache", slot, kv->B);
-    PGV_CHECK(n >= 0 && n <= kv->max_seq, "pgv_kv_ids_peek: %d entries outside the cache's %d", n, kv->max_seq);
-    if (d_out && n > 0) PGV_HIP(hipMemcpyAsync(d_out, kv->ban_ids + (size_t)slot * kv->max_seq, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (d_prompt_len) PGV_HIP(hipMemcpyAsync(d_prompt_len, kv->ban_plen + slot, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return PGV_OK;
+    return record_peek(kv, "pgv_kv_ids_peek", "id", "pgv_kv_set_bans", kv ? kv->ids.ids : nullptr, kv ? kv->ids.plen : nullptr, slot, n, d_out, d_prompt_len, stream);
 }
 
-// Constrained decoding (pgv.h).  As for the bans, the automaton goes to device memory owned by the cache, outside any capture: a captured decode
-// step bakes in its addresses and sizes, and the graphs' key carries the generation counter.  The roots are per-slot state (pgv_kv_fork and the
+// Constrained decoding (pgv.h): the automaton is a DevConfig of the cache, as the ban lists are.  The roots are per-slot state (pgv_kv_fork and the
 // refills move them), so they are written by every call that switches the feature on.
 extern "C" int pgv_kv_set_allowed(pgv_kv* kv, const pgv_allow_config* cfg) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_allowed: null cache");
-    if (!cfg) { kv->al_on = false; return PGV_OK; }
+    if (!cfg) { kv->allow.on = false; return PGV_OK; }
     PGV_TRY(pgv_allow_check("pgv_kv_set_allowed", cfg, kv->llm->cfg.vocab, kv->B));
-    if (kv->bm_K > 0) { pgv_set_error("pgv_kv_set_allowed: a beam run is in flight in this cache (the beam pick applies no logits processor)"); return PGV_ESTATE; }
-    if (kv->lk_D > 0) { pgv_set_error("pgv_kv_set_allowed: pgv_kv_set_lookup is on in this cache (lookup steps verify drafts against the unconstrained pick)"); return PGV_ESTATE; }
+    PGV_TRY(kv_allows(kv, KV_SET_ALLOWED, "pgv_kv_set_allowed"));
     PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_allowed"));          // the prompt lengths and the pick's copy of the logits
     const size_t B = kv->B;
-    if (!kv->al_blob) {
+    KvAllow& al = kv->allow;
+    if (!al.blob.p) {
         const size_t b_state = pgv_align(B * kv->max_seq * 4), b_root = pgv_align(B * 4);
-        hipError_t e = hipMalloc((void**)&kv->al_blob, b_state + b_root);
-        if (e != hipSuccess) { kv->al_blob = nullptr; pgv_set_error("pgv_kv_set_allowed: hipMalloc(%zu KiB): %s", (b_state + b_root) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
-        kv->al_state = (int*)kv->al_blob; kv->al_root = (int*)(kv->al_blob + b_state);
-        PGV_HIP(hipMemset(kv->al_blob, 0xff, b_state));       // DEAD until a step stores a state
+        PGV_TRY(al.blob.alloc("pgv_kv_set_allowed", b_state + b_root));
+        al.state = (int*)al.blob.p; al.root = (int*)(al.blob.p + b_state);
+        PGV_HIP(hipMemset(al.blob.p, 0xff, b_state));         // DEAD until a step stores a state
     }
     std::vector<int> blob;
     pgv_allow_pack(cfg, blob);
-    PGV_HIP(hipDeviceSynchronize());              // a pick in flight may still read the automaton and the roots of the configuration before
-    // the automaton the device copy already holds (a caller that sets and clears it around every run): nothing to upload, the graphs stay valid
-    const bool same = kv->al_gen > 0 && cfg->eos_id == kv->al_eos && cfg->n_states == kv->al_auto.n_states && cfg->n_edges == kv->al_auto.n_edges && blob == kv->al_host;
-    if (!same) {
-        if (blob.size() > kv->al_cap) {
-            if (kv->al_dev) (void)hipFree(kv->al_dev);
-            kv->al_dev = nullptr; kv->al_cap = 0; kv->al_host.clear();       // (the counter moves below: graphs that baked the old address in never match again)
-            hipError_t e = hipMalloc((void**)&kv->al_dev, blob.size() * 4);
-            if (e != hipSuccess) { kv->al_dev = nullptr; kv->al_on = false; pgv_set_error("pgv_kv_set_allowed: hipMalloc(%zu KiB): %s", (blob.size() * 4) >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
-            kv->al_cap = blob.size();
+    PGV_HIP(hipDeviceSynchronize());              // a pick not yet done may still read the automaton and the roots of the configuration before
+    PGV_TRY(config_upload(al, blob, cfg->eos_id, cfg->n_states == al.au.n_states && cfg->n_edges == al.au.n_edges, false, [&]() -> int {
+        if (blob.size() > al.cap) {
+            al.dev.drop();
+            al.cap = 0; al.host.clear();          // (the counter moves behind this: graphs that baked the old address in never match again)
+            if (al.dev.alloc("pgv_kv_set_allowed", blob.size() * 4) != PGV_OK) { al.on = false; return PGV_ENOMEM; }
+            al.cap = blob.size();
         }
-        PGV_HIP(hipMemcpy(kv->al_dev, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
-        kv->al_auto = allow_auto(kv->al_dev, cfg->n_states, cfg->n_edges);
-        kv->al_host.swap(blob);
-        kv->al_eos = cfg->eos_id;
-        kv->al_gen += 1;
-    }
+        PGV_HIP(hipMemcpy(al.dev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+        al.au = allow_auto((const int*)al.dev.p, cfg->n_states, cfg->n_edges); return PGV_OK;
+    }));
     std::vector<int> roots(B, 0);
     for (size_t b = 0; cfg->h_roots && b < B; ++b) roots[b] = cfg->h_roots[b];
-    PGV_HIP(hipMemcpy(kv->al_root, roots.data(), B * 4, hipMemcpyHostToDevice));
-    kv->al_on = true;
+    PGV_HIP(hipMemcpy(al.root, roots.data(), B * 4, hipMemcpyHostToDevice));
+    al.on = true;
     return PGV_OK;
 }
-
 extern "C" int pgv_kv_allow_peek(pgv_kv* kv, int slot, int n, int32_t* d_out, int32_t* d_root, void* stream) {
-    PGV_CHECK(kv != nullptr, "pgv_kv_allow_peek: null cache");
-    if (!kv->al_state) { pgv_set_error("pgv_kv_allow_peek: this cache has no state record (pgv_kv_set_allowed allocates it)"); return PGV_ESTATE; }
-    PGV_CHECK(slot >= 0 && slot < kv->B, "pgv_kv_allow_peek: slot %d outside the %d of the cache", slot, kv->B);
-    PGV_CHECK(n >= 0 && n <= kv->max_seq, "pgv_kv_allow_peek: %d entries outside the cache's %d", n, kv->max_seq);
-    if (d_out && n > 0) PGV_HIP(hipMemcpyAsync(d_out, kv->al_state + (size_t)slot * kv->max_seq, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (d_root) PGV_HIP(hipMemcpyAsync(d_root, kv->al_root + slot, 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return PGV_OK;
+    return record_peek(kv, "pgv_kv_allow_peek", "state", "pgv_kv_set_allowed", kv ? kv->allow.state : nullptr, kv ? kv->allow.root : nullptr, slot, n, d_out, d_root, stream);
 }
 
 // a sampled pick on this cache: the caller's temperature and top_k, the cache's warpers
@@ -589,8 +583,8 @@ static PickParams kv_sampled(const pgv_kv* kv, float temperature, int top_k) {
 
 extern "C" int pgv_kv_set_logprobs(pgv_kv* kv, int on) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_logprobs: null cache");
-    if (on && kv->g_pairs > 0) { pgv_set_error("pgv_kv_set_logprobs: guidance is on in this cache (a guided pick records no log-probabilities)"); return PGV_ESTATE; }
-    if (kv->lp_on != (on != 0)) { kv->lp_on = on != 0; kv->lp_steps = -1; }
+    if (on) PGV_TRY(kv_allows(kv, KV_SET_LOGPROBS, "pgv_kv_set_logprobs"));
+    if (kv->lp.on != (on != 0)) { kv->lp.on = on != 0; kv->lp.steps = -1; }
     return PGV_OK;
 }
 
@@ -599,57 +593,47 @@ extern "C" int pgv_kv_set_guidance(pgv_kv* kv, float scale, int pairs) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_guidance: null cache");
     PGV_CHECK(scale == scale && scale - scale == 0.f, "pgv_kv_set_guidance: scale %g is not finite", (double)scale);
     PGV_CHECK(pairs >= 0 && 2 * (long long)pairs <= kv->B, "pgv_kv_set_guidance: %d pairs need %lld slots, outside the cache's %d", pairs, 2 * (long long)pairs, kv->B);
-    if (pairs == 0 || scale == 1.f) { kv->g_pairs = 0; kv->g_scale = 1.f; return PGV_OK; }
-    if (kv->lp_on) { pgv_set_error("pgv_kv_set_guidance: pgv_kv_set_logprobs is on in this cache (a guided pick records no log-probabilities)"); return PGV_ESTATE; }
-    if (kv->bm_K > 0) { pgv_set_error("pgv_kv_set_guidance: a beam run is in flight in this cache"); return PGV_ESTATE; }
-    if (kv->lk_D > 0) { pgv_set_error("pgv_kv_set_guidance: pgv_kv_set_lookup is on in this cache (lookup steps verify drafts against the unguided pick)"); return PGV_ESTATE; }
-    if (!kv->g_logits) {
-        const size_t bytes = (size_t)(kv->B / 2) * kv->llm->vocab_cap * 4;
-        hipError_t e = hipMalloc((void**)&kv->g_logits, bytes);
-        if (e != hipSuccess) { kv->g_logits = nullptr; pgv_set_error("pgv_kv_set_guidance: hipMalloc(%zu KiB): %s", bytes >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
-    }
-    kv->g_pairs = pairs; kv->g_scale = scale;
+    if (pairs == 0 || scale == 1.f) { kv->guide.pairs = 0; kv->guide.scale = 1.f; return PGV_OK; }
+    PGV_TRY(kv_allows(kv, KV_SET_GUIDANCE, "pgv_kv_set_guidance"));
+    if (!kv->guide.logits.p) PGV_TRY(kv->guide.logits.alloc("pgv_kv_set_guidance", (size_t)(kv->B / 2) * kv->llm->vocab_cap * 4));
+    kv->guide.pairs = pairs; kv->guide.scale = scale;
     return PGV_OK;
 }
-extern "C" int pgv_kv_guidance(const pgv_kv* kv) { return kv ? kv->g_pairs : -1; }
-// a covered call under guidance needs the live group to be exactly the pairs; a call that guidance does not cover is refused outright
+extern "C" int pgv_kv_guidance(const pgv_kv* kv) { return kv ? kv->guide.pairs : -1; }
+// a covered call under guidance needs the live group to be exactly the pairs; a call that guidance does not cover is refused outright (kv_features.h)
 static int guidance_width(const pgv_kv* kv, const char* who) {
-    if (kv->g_pairs > 0 && kv->active != 2 * kv->g_pairs) {
-        pgv_set_error("%s: guidance is on for %d pairs, the live group has %d sequences (need %d)", who, kv->g_pairs, kv->active, 2 * kv->g_pairs);
+    if (kv->guide.pairs > 0 && kv->active != 2 * kv->guide.pairs) {
+        pgv_set_error("%s: guidance is on for %d pairs, the live group has %d sequences (need %d)", who, kv->guide.pairs, kv->active, 2 * kv->guide.pairs);
         return PGV_ESTATE;
     }
-    return PGV_OK;
-}
-static int guidance_refuses(const pgv_kv* kv, const char* who) {
-    if (kv && kv->g_pairs > 0) { pgv_set_error("%s: guidance is on in this cache (pgv_kv_set_guidance(kv, 1, 0) turns it off)", who); return PGV_ESTATE; }
     return PGV_OK;
 }
 
 extern "C" int pgv_kv_logprobs_last(pgv_kv* kv, float* d_model, float* d_pick, void* stream) {
     PGV_CHECK(kv != nullptr, "pgv_kv_logprobs_last: null cache");
-    if (!kv->lp_on || kv->active < 1) { pgv_set_error("pgv_kv_logprobs_last: %s", kv->lp_on ? "no prefilled sequences in this cache" : "pgv_kv_set_logprobs is off"); return PGV_ESTATE; }
-    if (d_model) PGV_HIP(hipMemcpyAsync(d_model, kv->lp_last, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (d_pick) PGV_HIP(hipMemcpyAsync(d_pick, kv->lp_last + kv->B, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (!kv->lp.on || kv->active < 1) { pgv_set_error("pgv_kv_logprobs_last: %s", kv->lp.on ? "no prefilled sequences in this cache" : "pgv_kv_set_logprobs is off"); return PGV_ESTATE; }
+    if (d_model) PGV_HIP(hipMemcpyAsync(d_model, kv->lp.last, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_pick) PGV_HIP(hipMemcpyAsync(d_pick, kv->lp.last + kv->B, (size_t)kv->active * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PGV_OK;
 }
 
 extern "C" int pgv_kv_logprobs_steps(pgv_kv* kv, int n, float* d_model, float* d_pick, void* stream) {
     PGV_CHECK(kv != nullptr, "pgv_kv_logprobs_steps: null cache");
-    if (!kv->lp_on || kv->lp_steps < 0) { pgv_set_error("pgv_kv_logprobs_steps: pgv_kv_set_logprobs was off during the last pgv_llm_decode_greedy / _sample call"); return PGV_ESTATE; }
-    PGV_CHECK(n >= 1 && n <= kv->lp_steps, "pgv_kv_logprobs_steps: %d steps asked for, the last call ran %d", n, kv->lp_steps);
+    if (!kv->lp.on || kv->lp.steps < 0) { pgv_set_error("pgv_kv_logprobs_steps: pgv_kv_set_logprobs was off during the last pgv_llm_decode_greedy / _sample call"); return PGV_ESTATE; }
+    PGV_CHECK(n >= 1 && n <= kv->lp.steps, "pgv_kv_logprobs_steps: %d steps asked for, the last call ran %d", n, kv->lp.steps);
     const size_t row = (size_t)kv->max_seq * 4;
-    if (d_model) PGV_HIP(hipMemcpy2DAsync(d_model, (size_t)n * 4, kv->lp_hist, row, (size_t)n * 4, kv->active, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (d_model) PGV_HIP(hipMemcpy2DAsync(d_model, (size_t)n * 4, kv->lp.hist, row, (size_t)n * 4, kv->active, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (d_pick)
-        PGV_HIP(hipMemcpy2DAsync(d_pick, (size_t)n * 4, kv->lp_hist + (size_t)kv->B * kv->max_seq, row, (size_t)n * 4, kv->active, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        PGV_HIP(hipMemcpy2DAsync(d_pick, (size_t)n * 4, kv->lp.hist + (size_t)kv->B * kv->max_seq, row, (size_t)n * 4, kv->active, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PGV_OK;
 }
 
 extern "C" int pgv_kv_len(const pgv_kv* kv, int b) { return (kv && b >= 0 && b < kv->B) ? kv->h_len[b] : -1; }
 
 // ---------------------------------------------------------------------------------------------
-// shared tail: final norm + lm_head + argmax on kv->resid [B,H]
+// shared tail: final norm + lm_head + argmax on kv->sc.resid [B,H]
 // ---------------------------------------------------------------------------------------------
-// kv->xn holds round16(resid * norm_g) and kv->ssq the `nparts` sum-of-squares partials of resid (folded final RMSNorm): lm_head scales its
+// kv->sc.xn holds round16(resid * norm_g) and kv->sc.ssq the `nparts` sum-of-squares partials of resid (folded final RMSNorm): lm_head scales its
 // fp32 accumulators by rstd.
 // PGV_LLM_NORM_FOLD=0: decode with a standalone RMSNorm launch in front of every consumer GEMV (HF's order of operations: normalise, round
 // to 16 bits, multiply) instead of the folded form -- a bisect switch for real-checkpoint regressions, not a fallback: both paths
@@ -675,60 +659,60 @@ static int lm_head_rows(pgv_ctx* ctx, pgv_llm* m, const DecodeScratch& sc, int B
     if (greedy) { nm.amax_val = sc.amax_val; nm.amax_idx = sc.amax_idx; }
     return gemv_mat(ctx, m, GV_F32, m->mats[0], sc.xn, sc.logits, V, B, s, &nm);
 }
-static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hipStream_t s, int nparts) { return lm_head_rows(ctx, m, kv_scratch(kv), B, greedy, s, nparts); }
+static int lm_head(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int B, bool greedy, hipStream_t s, int nparts) { return lm_head_rows(ctx, m, kv->sc, B, greedy, s, nparts); }
 
-// Every pick on rows [0, B) of kv->logits.  `sampled` null: the arg-max of the candidates lm_head left; else the sampled pick with those parameters
+// Every pick on rows [0, B) of kv->sc.logits.  `sampled` null: the arg-max of the candidates lm_head left; else the sampled pick with those parameters
 // and the uniforms u [B], or u [steps][B] indexed by the device-side step counter (u_by_step).  `st`: the cache's own state (kv_state) or a refill's
 // scratch.  Row b reads the seen-set of slot slot_map[b] (null: b) and, with pgv_kv_set_logprobs on, records its log-probabilities there.
 static PickState kv_state(pgv_kv* kv, int eos, int advance) { return {kv->d_cur, kv->d_pos, kv->d_step, kv->d_hist, kv->max_seq, kv->d_done, eos, advance}; }
 // With pgv_kv_set_bans on, a sampled pick (the greedy ones take that route then, kv_greedy_sampled) reads a copy of the logits with HF's -inf
-// processors applied, made by logit_ban_kernel behind the row statistics: kv->logits itself stays raw for the statistics, a re-pick, a fork and the
+// processors applied, made by logit_ban_kernel behind the row statistics: kv->sc.logits itself stays raw for the statistics, a re-pick, a fork and the
 // d_logits outputs.  Row b's sequence is the record of its slot at length ban_lens[b] (null: the cache's positions) -- plus, for the pick of a decode
 // step (AM_INC_POS), the token that step consumed, which the kernel appends to the record.
 // With pgv_kv_set_allowed on, logit_allow_kernel makes that copy -- the row with -inf outside what the slot's automaton state allows, the state
 // advanced by the token the step consumed -- and logit_ban_kernel, where bans are on too, runs in place behind it: the union of the two -inf sets.
 // With only bans on, the ban kernel's launch is the one it has always been.
-static bool kv_greedy_sampled(const pgv_kv* kv) { return kv->warpers.penalty != 1.f || kv->ban_on || kv->g_pairs > 0 || kv->al_on; }
+static bool kv_greedy_sampled(const pgv_kv* kv) { return kv->warpers.penalty != 1.f || kv->ban.on || kv->guide.pairs > 0 || kv->allow.on; }
 static int kv_pick(pgv_kv* kv, int B, const PickParams* sampled, const float* u, bool u_by_step, const PickState& st, const int* slot_map, hipStream_t s,
                    const int* ban_lens = nullptr) {
     const int V = kv->llm->cfg.vocab;
     PickLp lp;
-    if (kv->lp_on) {
-        lp.stat = kv->lp_stat; lp.last_model = kv->lp_last; lp.last_pick = kv->lp_last + kv->B; lp.slot = slot_map;
-        if (st.advance & AM_RECORD) { lp.hist_model = kv->lp_hist; lp.hist_pick = kv->lp_hist + (size_t)kv->B * kv->max_seq; lp.hist_stride = kv->max_seq; }
-        PGV_TRY(pgv_launch_row_lse(kv->logits, V, V, B, kv->lp_stat, s));
+    if (kv->lp.on) {
+        lp.stat = kv->lp.stat; lp.last_model = kv->lp.last; lp.last_pick = kv->lp.last + kv->B; lp.slot = slot_map;
+        if (st.advance & AM_RECORD) { lp.hist_model = kv->lp.hist; lp.hist_pick = kv->lp.hist + (size_t)kv->B * kv->max_seq; lp.hist_stride = kv->max_seq; }
+        PGV_TRY(pgv_launch_row_lse(kv->sc.logits, V, V, B, kv->lp.stat, s));
     }
-    if (!sampled) return pgv_launch_argmax_parts(kv->amax_val, kv->amax_idx, (V + 15) / 16, kv->amax_ts, V, B, st, s, kv->logits, &lp);
-    const float* logits = kv->logits;
+    if (!sampled) return pgv_launch_argmax_parts(kv->sc.amax_val, kv->sc.amax_idx, (V + 15) / 16, kv->sc.amax_ts, V, B, st, s, kv->sc.logits, &lp);
+    const float* logits = kv->sc.logits;
     // Guidance: the B = 2P rows of the group become P guided rows -- scale * (log_softmax(row p) - log_softmax(row P + p)) + log_softmax(row P + p) --
-    // in a buffer of their own (kv->logits stays raw); bans, penalty and pick run over those P rows with the conditional slots' records and
+    // in a buffer of their own (kv->sc.logits stays raw); bans, penalty and pick run over those P rows with the conditional slots' records and
     // seen-sets, the uniforms keep the group's width as their stride, and the follow kernel hands the outcome to the twins.
-    const int P = (kv->g_pairs > 0 && !slot_map) ? kv->g_pairs : 0, rows = P > 0 ? P : B;
+    const int P = (kv->guide.pairs > 0 && !slot_map) ? kv->guide.pairs : 0, rows = P > 0 ? P : B;
     if (P > 0) {
         PGV_CHECK(B == 2 * P && st.next == kv->d_cur, "kv_pick: a guided pick runs on the cache's own state at width 2 x pairs");
-        PGV_TRY(pgv_launch_guidance_mix(kv->logits, kv->logits + (size_t)P * V, V, V, P, kv->g_scale, kv->g_logits, V, s));
-        logits = kv->g_logits;
+        PGV_TRY(pgv_launch_guidance_mix(kv->sc.logits, kv->sc.logits + (size_t)P * V, V, V, P, kv->guide.scale, (float*)kv->guide.logits.p, V, s));
+        logits = (const float*)kv->guide.logits.p;
     }
-    if (kv->al_on) {
+    if (kv->allow.on) {
         AllowArgs a;
-        a.src = logits; a.dst = kv->ban_logits; a.V = V;
-        a.au = kv->al_auto; a.state = kv->al_state; a.state_stride = kv->max_seq; a.root = kv->al_root;
-        a.slot_map = slot_map; a.lens = ban_lens ? ban_lens : kv->d_pos; a.prompt_lens = kv->ban_plen;
+        a.src = logits; a.dst = kv->ids.logits; a.V = V;
+        a.au = kv->allow.au; a.state = kv->allow.state; a.state_stride = kv->max_seq; a.root = kv->allow.root;
+        a.slot_map = slot_map; a.lens = ban_lens ? ban_lens : kv->d_pos; a.prompt_lens = kv->ids.plen;
         a.cur = kv->d_cur; a.inc = (st.advance & AM_INC_POS) ? 1 : 0;
         a.done = (st.advance & AM_RECORD) ? st.done : nullptr;       // as for the bans below
-        a.eos = kv->al_eos;
+        a.eos = kv->allow.eos;
         PGV_TRY(pgv_launch_logit_allow(a, rows, s));
-        logits = kv->ban_logits; lp.banned = 1;
+        logits = kv->ids.logits; lp.banned = 1;
     }
-    if (kv->ban_on) {
+    if (kv->ban.on) {
         BanArgs a;
-        a.src = logits; a.dst = kv->ban_logits; a.V = V;
-        a.ids = kv->ban_ids; a.ids_stride = kv->max_seq; a.slot_map = slot_map; a.lens = ban_lens ? ban_lens : kv->d_pos; a.prompt_lens = kv->ban_plen;
-        a.rec = kv->ban_ids; a.cur = kv->d_cur; a.inc = (st.advance & AM_INC_POS) ? 1 : 0;
+        a.src = logits; a.dst = kv->ids.logits; a.V = V;
+        a.ids = kv->ids.ids; a.ids_stride = kv->max_seq; a.slot_map = slot_map; a.lens = ban_lens ? ban_lens : kv->d_pos; a.prompt_lens = kv->ids.plen;
+        a.rec = kv->ids.ids; a.cur = kv->d_cur; a.inc = (st.advance & AM_INC_POS) ? 1 : 0;
         a.done = (st.advance & AM_RECORD) ? st.done : nullptr;       // a pick that does not record must not look at a flag an earlier run left set
-        a.eos = kv->ban_eos; a.cfg = kv->ban_cfg;
+        a.eos = kv->ban.eos; a.cfg = kv->ban.cfg;
         PGV_TRY(pgv_launch_logit_ban(a, rows, s));
-        logits = kv->ban_logits; lp.banned = 1;
+        logits = kv->ids.logits; lp.banned = 1;
     }
     SampleWarp w;
     w.seen_bits = kv->d_seen; w.seen_words = kv->seen_words; w.seen_slot = slot_map;
@@ -742,27 +726,27 @@ static KvGatherArgs kv_gather_args(pgv_kv* kv, int K, int groups, const int* map
     const pgv_llm* m = kv->llm;
     const int heads = m->cfg.heads, L = m->cfg.layers;
     KvGatherArgs g{};
-    g.cache = L > 0 ? (char*)kv->Kc[0] : kv->blob;
+    g.cache = L > 0 ? (char*)kv->Kc[0] : kv->blob.p;
     g.head_stride = (size_t)kv->max_seq * kHD * 2; g.slot_stride = g.head_stride * heads; g.plane_stride = kv->plane_bytes;
     g.heads = heads; g.nrun = 2 * L * heads; g.K = K; g.groups = groups; g.max_seq = kv->max_seq;
     g.map = map; g.row0 = row0; g.len = kv->d_pos; g.cur = cur;
     return g;
 }
 static int beam_pick_and_gather(pgv_ctx* ctx, pgv_kv* kv, bool advance, hipStream_t s) {
-    const int V = kv->llm->cfg.vocab, K = kv->bm_K, P = kv->bm_P;
+    const int V = kv->llm->cfg.vocab, K = kv->beam.K, P = kv->beam.P;
     pgv_prof_begin(ctx, 6, s);
-    PGV_TRY(pgv_launch_row_lse(kv->logits, V, V, P * K, kv->lp_stat, s));
+    PGV_TRY(pgv_launch_row_lse(kv->sc.logits, V, V, P * K, kv->lp.stat, s));
     BeamPickArgs a{};
-    a.logits = kv->logits; a.ld = V; a.V = V; a.K = K; a.stat = kv->lp_stat;
-    a.state = kv->bm_state; a.state_stride = PGV_BEAM_STATE_WORDS(K);
-    a.t_dev = kv->bm_t; a.prm_dev = kv->bm_prm; a.denom = kv->bm_denom;
-    a.cur = kv->d_cur; a.map = kv->bm_map; a.pos = kv->d_pos; a.advance = advance ? 1 : 0;
-    a.hist_tok = kv->bm_hist; a.hist_par = kv->bm_hist + (size_t)kv->max_seq * kv->B; a.hist_stride = kv->B; a.hist_steps = kv->max_seq;
+    a.logits = kv->sc.logits; a.ld = V; a.V = V; a.K = K; a.stat = kv->lp.stat;
+    a.state = kv->beam.state; a.state_stride = PGV_BEAM_STATE_WORDS(K);
+    a.t_dev = kv->beam.t; a.prm_dev = kv->beam.prm; a.denom = kv->beam.denom;
+    a.cur = kv->d_cur; a.map = kv->beam.map; a.pos = kv->d_pos; a.advance = advance ? 1 : 0;
+    a.hist_tok = kv->beam.hist; a.hist_par = kv->beam.hist + (size_t)kv->max_seq * kv->B; a.hist_stride = kv->B; a.hist_steps = kv->max_seq;
     PGV_TRY(pgv_launch_beam_pick(a, P, s));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     if (K > 1 && advance) {
         pgv_prof_begin(ctx, 5, s);
-        PGV_TRY(pgv_launch_kv_gather(kv_gather_args(kv, K, P, kv->bm_map, kv->bm_row0, nullptr), s));
+        PGV_TRY(pgv_launch_kv_gather(kv_gather_args(kv, K, P, kv->beam.map, kv->beam.row0, nullptr), s));
         pgv_prof_end(ctx, 5, s, 0.0, 0.0);
     }
     return PGV_OK;
@@ -877,7 +861,7 @@ static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefi
     const int M = w.plan.M, nscore = w.plan.nscore, T = w.T = q.h_counts ? w.plan.S : B;
     // arrival tickets of the context-split decode attention: a launch re-arms its own, but an ABORTED decode launch (device fault, process kill
     // between launches) would leave one non-zero for the next user of this cache -- every prefill starts from zeros
-    PGV_HIP(hipMemsetAsync(kv->dattn_ticket, 0, (size_t)kv->B * m->cfg.heads * sizeof(unsigned), s));
+    PGV_HIP(hipMemsetAsync(kv->sc.dattn_ticket, 0, (size_t)kv->B * m->cfg.heads * sizeof(unsigned), s));
 
     const size_t b_meta = pgv_align(meta.size() * 4), b_resid = pgv_align((size_t)M * H * 4), b_xn = pgv_align((size_t)M * H * 2),
                  b_qkv = pgv_align((size_t)M * 3 * H * 2), b_ao = pgv_align((size_t)M * H * 2), b_act = pgv_align((size_t)M * I * 2);
@@ -907,10 +891,10 @@ static int prefill_plan_upload(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefi
     // (and every sample of a prompt starts from the prompt's ids alone: the pick adds its own token to the set of its own slot)
     PGV_TRY(pgv_launch_seen_mark(w.d.raw_ids, w.d.cu, w.t_slots, T, vocab, kv->d_seen, kv->seen_words, append ? 0 : 1, s, q.h_counts ? w.d.samp_seq : nullptr));
     // the ordered twin of the seen-set (pgv_kv_set_bans): each slot's ids at their cache positions and its prompt length, same indirection
-    if (kv->ban_on || kv->lk_D > 0 || kv->al_on) PGV_TRY(pgv_launch_ids_write(w.d.raw_ids, w.d.cu, w.d.offs, w.t_slots, q.h_counts ? w.d.samp_seq : nullptr, T, kv->ban_ids, kv->max_seq, kv->ban_plen, s));
+    if (kv->ban.on || kv->lookup.D > 0 || kv->allow.on) PGV_TRY(pgv_launch_ids_write(w.d.raw_ids, w.d.cu, w.d.offs, w.t_slots, q.h_counts ? w.d.samp_seq : nullptr, T, kv->ids.ids, kv->max_seq, kv->ids.plen, s));
     // pgv_kv_set_allowed: a refilled slot starts at root 0 (one automaton for every task of a refill run); its state rows need no action, the
     // first pick reads the root and every later step stores the entry the next one reads
-    if (kv->al_on && slots) PGV_TRY(pgv_launch_allow_root_zero(w.t_slots, T, kv->al_root, s));
+    if (kv->allow.on && slots) PGV_TRY(pgv_launch_allow_root_zero(w.t_slots, T, kv->allow.root, s));
     if (!slots) {       // a refill sets the state of its own slots only, after the pick (pgv_launch_slot_scatter)
         PGV_HIP(hipMemcpyAsync(kv->d_pos, w.d.lens, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
         PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)2 * kv->B * 4, s));      // step + done
@@ -983,10 +967,10 @@ static int prefill_score(pgv_ctx* ctx, pgv_llm* m, const ScoreReq& sc, const Pre
 static int prefill_last_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& q, const PrefillWork& w, hipStream_t s) {
     const bool slots = q.mode == PREFILL_SLOTS;
     const int B = w.T, H = m->cfg.hidden;          // rows of the tail: the samples
-    PGV_TRY(pgv_launch_gather_rows(w.resid, w.t_last, kv->resid, B, H, s));
+    PGV_TRY(pgv_launch_gather_rows(w.resid, w.t_last, kv->sc.resid, B, H, s));
     const int nparts = norm_fold_enabled() ? 1 : 0;
-    if (nparts) PGV_TRY(pgv_launch_final_prep(m->dtype, kv->resid, m->norm_g, kv->xn, kv->ssq, B, H, s, true));
-    else PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->resid, m->norm_g, m->cfg.eps, kv->xn, B, H, s));
+    if (nparts) PGV_TRY(pgv_launch_final_prep(m->dtype, kv->sc.resid, m->norm_g, kv->sc.xn, kv->sc.ssq, B, H, s, true));
+    else PGV_TRY(pgv_launch_rmsnorm(m->dtype, kv->sc.resid, m->norm_g, m->cfg.eps, kv->sc.xn, B, H, s));
     if (!slots) {
         PGV_TRY(lm_head_and_pick(ctx, m, kv, B, -1, 0, s, nparts));
     } else {
@@ -998,7 +982,7 @@ static int prefill_last_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const Prefill
         PGV_TRY(pgv_launch_slot_scatter(w.t_slots, w.d_pick, w.t_lens, B, kv->d_cur, kv->d_pos, kv->d_step, kv->d_done, s));
         pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     }
-    if (q.d_logits) PGV_HIP(hipMemcpyAsync(q.d_logits, kv->logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
+    if (q.d_logits) PGV_HIP(hipMemcpyAsync(q.d_logits, kv->sc.logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
     if (q.d_next) PGV_HIP(hipMemcpyAsync(q.d_next, slots ? w.d_pick : kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     if (slots) {
         for (int b = 0; b < B; ++b) kv->h_len[q.h_slots[b]] = w.ht_lens[b];
@@ -1014,14 +998,14 @@ static int prefill_impl(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const PrefillReq& 
     PrefillWork w;
     PGV_TRY(prefill_check(ctx, m, kv, q));
     beam_drop(kv);
-    kv->lk_valid = false;
+    kv->lookup.valid = false;
     PGV_TRY(prefill_plan_upload(ctx, m, kv, q, w, s));
     PGV_TRY(prefill_trunk(ctx, m, kv, q, w, s));
     if (q.h_counts) PGV_TRY(prefill_fork_runs(m, kv, q, w, s));
     if (q.d_all_logits) PGV_TRY(prefill_all_logits(ctx, m, q, w, s));
     if (q.mode == PREFILL_SCORE) PGV_TRY(prefill_score(ctx, m, q.score, w, s));
     PGV_TRY(prefill_last_rows(ctx, m, kv, q, w, s));
-    kv->lk_valid = kv->lk_D > 0 && q.mode == PREFILL_PLAIN;
+    kv->lookup.valid = kv->lookup.D > 0 && q.mode == PREFILL_PLAIN;
     PGV_HIP(hipGetLastError());
     PGV_TRY(pgv_ws_release(ctx, s));
     return PGV_OK;
@@ -1051,7 +1035,7 @@ extern "C" int pgv_llm_prefill_slots(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const
                                      const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k, const float* d_u, float* d_logits,
                                      int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots, "pgv_llm_prefill_slots: null slot list");
-    PGV_TRY(guidance_refuses(kv, "pgv_llm_prefill_slots"));
+    PGV_TRY(kv_allows(kv, KV_PREFILL_SLOTS, "pgv_llm_prefill_slots"));
     // uniforms: sampled; none: greedy, from the lm_head candidates unless a penalty or a ban applies (prefill_check refuses a null cache)
     const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);
     PrefillReq q;
@@ -1067,7 +1051,7 @@ extern "C" int pgv_llm_prefill_slots_n(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, con
                                        const int32_t* h_seq_lens, const void* d_video, int Vt, const int32_t* h_vid_pos, float temperature, int top_k,
                                        const float* d_u, float* d_logits, int32_t* d_next, void* stream) {
     PGV_CHECK(h_slots && h_counts, "pgv_llm_prefill_slots_n: null slot or count list");
-    PGV_TRY(guidance_refuses(kv, "pgv_llm_prefill_slots_n"));
+    PGV_TRY(kv_allows(kv, KV_PREFILL_SLOTS, "pgv_llm_prefill_slots_n"));
     const PickParams p = !kv ? PickParams{} : d_u ? kv_sampled(kv, temperature, top_k) : pick_greedy(kv->warpers.penalty);       // as pgv_llm_prefill_slots
     PrefillReq q;
     q.who = "pgv_llm_prefill_slots_n"; q.mode = PREFILL_SLOTS;
@@ -1114,10 +1098,25 @@ extern "C" int pgv_kv_truncate(pgv_kv* kv, int b, int len, void* stream) {
 // read.  Inside a launch the source slot itself is skipped as a destination, so no launch reads what it writes.  The result is as if every
 // read preceded every write.  (counts [2,2,2]: slot 1 is source 1 and second destination of source 0 -- source 2 -> slots 4, 5; then source
 // 1 -> slots 2, 3; only then source 0 -> slot 1.)
+// The feature records of slot src, rows [0, len), go to slots [d0, d0 + nd) (src itself skipped).  Id rows are copied iff bans are on; automaton
+// state rows and the root iff the automaton is on; the prompt length iff either is on (once: with the id rows if there are any, else with the root).
+static int slot_records_copy(pgv_kv* kv, int src, int d0, int nd, int len, hipStream_t s) {
+    const bool ids = kv->ban.on, states = kv->allow.on;
+    auto rows = [&](int* rec, int dst) { return hipMemcpyAsync(rec + (size_t)dst * kv->max_seq, rec + (size_t)src * kv->max_seq, (size_t)len * 4, hipMemcpyDeviceToDevice, s); };
+    auto word = [&](int* rec, int dst) { return hipMemcpyAsync(rec + dst, rec + src, 4, hipMemcpyDeviceToDevice, s); };
+    for (int dst = d0; ids && dst < d0 + nd; ++dst)
+        if (dst != src) { PGV_HIP(rows(kv->ids.ids, dst)); PGV_HIP(word(kv->ids.plen, dst)); }
+    for (int dst = d0; states && dst < d0 + nd; ++dst) {
+        if (dst != src) { PGV_HIP(rows(kv->allow.state, dst)); PGV_HIP(word(kv->allow.root, dst)); }
+        if (dst != src && !ids) PGV_HIP(word(kv->ids.plen, dst));
+    }
+    return PGV_OK;
+}
+
 extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_counts, int P, void* stream) {
     PGV_CHECK(ctx && m && kv && h_counts, "pgv_kv_fork: null argument");
     PGV_CHECK(kv->llm == m, "pgv_kv_fork: kv cache belongs to another model");
-    PGV_TRY(guidance_refuses(kv, "pgv_kv_fork"));
+    PGV_TRY(kv_allows(kv, KV_FORK, "pgv_kv_fork"));
     if (kv->active < 1) { pgv_set_error("pgv_kv_fork: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
     PGV_CHECK(P == kv->active, "pgv_kv_fork: %d counts for a live group of %d sequences", P, kv->active);
     long long W = 0;
@@ -1128,15 +1127,15 @@ extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* 
     PGV_CHECK(W <= kv->B, "pgv_kv_fork: new width %lld exceeds the %d sequences the cache was created with", W, kv->B);
     if (W == P) return PGV_OK;            // every count is 1: the group is its own fork
     beam_drop(kv);
-    kv->lk_valid = false;
+    kv->lookup.valid = false;
     hipStream_t s = (hipStream_t)stream;
     const int heads = m->cfg.heads, L = m->cfg.layers;
     KvForkArgs a;
-    a.cache = L > 0 ? (char*)kv->Kc[0] : kv->blob;
+    a.cache = L > 0 ? (char*)kv->Kc[0] : kv->blob.p;
     a.head_stride = (size_t)kv->max_seq * kHD * 2; a.slot_stride = a.head_stride * heads; a.plane_stride = kv->plane_bytes;
     a.heads = heads; a.nrun = 2 * L * heads;
-    a.pos = kv->d_pos; a.cur = kv->d_cur; a.done = kv->d_done; a.lp_last = kv->lp_last; a.lp_stride = kv->B;
-    a.seen = kv->d_seen; a.seen_words = kv->seen_words; a.logits = kv->logits; a.vocab = m->cfg.vocab;
+    a.pos = kv->d_pos; a.cur = kv->d_cur; a.done = kv->d_done; a.lp_last = kv->lp.last; a.lp_stride = kv->B;
+    a.seen = kv->d_seen; a.seen_words = kv->seen_words; a.logits = kv->sc.logits; a.vocab = m->cfg.vocab;
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
     std::vector<int> len((size_t)W);
     int base = (int)W;
@@ -1147,19 +1146,7 @@ extern "C" int pgv_kv_fork(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* 
         if (c == 1 && base == p) continue;                 // the slot stays where it is
         a.src = p; a.d0 = base; a.nd = c; a.run_pieces = (unsigned)kv->h_len[p] * (kHD * 2 / 16);
         PGV_TRY(pgv_launch_kv_fork(a, s));
-        // the id record of pgv_kv_set_bans moves with the slot: rows [0, len) and the prompt length, in the same order as the cache rows
-        for (int i = 0; kv->ban_on && i < c; ++i) {
-            if (base + i == p) continue;
-            PGV_HIP(hipMemcpyAsync(kv->ban_ids + (size_t)(base + i) * kv->max_seq, kv->ban_ids + (size_t)p * kv->max_seq, (size_t)kv->h_len[p] * 4, hipMemcpyDeviceToDevice, s));
-            PGV_HIP(hipMemcpyAsync(kv->ban_plen + base + i, kv->ban_plen + p, 4, hipMemcpyDeviceToDevice, s));
-        }
-        // likewise the state record of pgv_kv_set_allowed and the slot's root (the prompt length went with the loop above when bans are on)
-        for (int i = 0; kv->al_on && i < c; ++i) {
-            if (base + i == p) continue;
-            PGV_HIP(hipMemcpyAsync(kv->al_state + (size_t)(base + i) * kv->max_seq, kv->al_state + (size_t)p * kv->max_seq, (size_t)kv->h_len[p] * 4, hipMemcpyDeviceToDevice, s));
-            PGV_HIP(hipMemcpyAsync(kv->al_root + base + i, kv->al_root + p, 4, hipMemcpyDeviceToDevice, s));
-            if (!kv->ban_on) PGV_HIP(hipMemcpyAsync(kv->ban_plen + base + i, kv->ban_plen + p, 4, hipMemcpyDeviceToDevice, s));
-        }
+        PGV_TRY(slot_records_copy(kv, p, base, c, kv->h_len[p], s));       // in the same order as the cache rows
     }
     for (int i = 0; i < (int)W; ++i) kv->h_len[i] = len[i];
     kv->active = (int)W;
@@ -1256,7 +1243,7 @@ static int decode_trunk(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const DecodeScratc
 // a plain token step: the trunk over the live slots on the cache's own scratch, then lm_head and the pick
 static int decode_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s) {
     int nparts = 0;
-    PGV_TRY(decode_trunk(ctx, m, kv, kv_scratch(kv), kv->d_cur, kv->active, RowMap{}, s, &nparts));
+    PGV_TRY(decode_trunk(ctx, m, kv, kv->sc, kv->d_cur, kv->active, RowMap{}, s, &nparts));
     return lm_head_and_pick(ctx, m, kv, kv->active, eos, flags, s, nparts);
 }
 
@@ -1273,10 +1260,13 @@ static bool graphs_enabled() {
 constexpr int kGraphSteps = 8;
 
 static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s);      // below: one prompt-lookup step
-// lookup: the captured steps are lookup steps (pgv_llm_decode_lookup, with AM_SAMPLE pgv_llm_decode_lookup_sample) with the cache's D and n, which join the key
-static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int which, int steps, hipStream_t s, bool lookup = false) {
-    const DecodeGraphKey key = decode_graph_key(kv->active, eos, flags, m->generation, kv->lp_on, kv->run, kv->bm_K, kv->ban_on ? kv->ban_gen : 0, lookup ? kv->lk_D : 0,
-                                                lookup ? kv->lk_n : 0, kv->g_pairs, kv->g_scale, kv->al_on ? kv->al_gen : 0);
+// one step of the kind on the stream: a plain token step, or a lookup step (pgv_llm_decode_lookup, with AM_SAMPLE pgv_llm_decode_lookup_sample)
+static int step_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, StepKind kind, int eos, int flags, hipStream_t s) {
+    return kind == STEP_PLAIN ? decode_enqueue(ctx, m, kv, eos, flags, s) : lookup_enqueue(ctx, m, kv, eos, flags, s);
+}
+// captured lookup steps bake in the cache's D and n, which join the key
+static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, StepKind kind, int eos, int flags, int which, int steps, hipStream_t s) {
+    const DecodeGraphKey key = decode_graph_key(kv_features(kv), kv->active, eos, flags, m->generation, kv->run, kind != STEP_PLAIN);
     if (!(kv->gkey == key)) {
         for (auto& g : kv->gexec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
         kv->gkey = key;
@@ -1288,7 +1278,7 @@ static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags
         if (!ctx->cap_stream) PGV_HIP(hipStreamCreateWithFlags(&ctx->cap_stream, hipStreamNonBlocking));
         PGV_HIP(hipStreamBeginCapture(ctx->cap_stream, hipStreamCaptureModeRelaxed));
         int rc = PGV_OK;
-        for (int i = 0; i < steps && rc == PGV_OK; ++i) rc = lookup ? lookup_enqueue(ctx, m, kv, eos, flags, ctx->cap_stream) : decode_enqueue(ctx, m, kv, eos, flags, ctx->cap_stream);
+        for (int i = 0; i < steps && rc == PGV_OK; ++i) rc = step_enqueue(ctx, m, kv, kind, eos, flags, ctx->cap_stream);
         hipError_t e = hipStreamEndCapture(ctx->cap_stream, &graph);
         if (rc != PGV_OK) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess) { pgv_set_error("decode graph capture failed: %s", hipGetErrorString(e)); return PGV_EHIP; }
@@ -1300,24 +1290,28 @@ static int decode_graph(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags
     return PGV_OK;
 }
 
-static int decode_steps(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int n, hipStream_t s) {
-    const int B = kv->active;
-    kv->lk_valid = false;               // a plain step appends nothing to the id record
+// n steps of one kind: eager while the kind has not run eagerly on this cache, under profiling or with PGV_NO_GRAPH=1; else the kGraphSteps-step
+// graph while that many remain; else the one-step graph.  Only plain steps advance the host's lengths (a lookup step's live on the device).
+static int run_steps(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, StepKind kind, int eos, int flags, int n, hipStream_t s) {
     while (n > 0) {
         int k = 1;
-        if (ctx->prof || !graphs_enabled() || !kv->warmed) {
-            kv->warmed = true;
-            PGV_TRY(decode_enqueue(ctx, m, kv, eos, flags, s));
+        if (ctx->prof || !graphs_enabled() || !kv->warmed[kind]) {
+            kv->warmed[kind] = true;
+            PGV_TRY(step_enqueue(ctx, m, kv, kind, eos, flags, s));
         } else if (n >= kGraphSteps) {
             k = kGraphSteps;
-            PGV_TRY(decode_graph(ctx, m, kv, eos, flags, 1, kGraphSteps, s));
+            PGV_TRY(decode_graph(ctx, m, kv, kind, eos, flags, 1, kGraphSteps, s));
         } else {
-            PGV_TRY(decode_graph(ctx, m, kv, eos, flags, 0, 1, s));
+            PGV_TRY(decode_graph(ctx, m, kv, kind, eos, flags, 0, 1, s));
         }
-        for (int b = 0; b < B; ++b) kv->h_len[b] += k;
+        for (int b = 0; kind == STEP_PLAIN && b < kv->active; ++b) kv->h_len[b] += k;
         n -= k;
     }
     return PGV_OK;
+}
+static int decode_steps(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, int n, hipStream_t s) {
+    kv->lookup.valid = false;               // a plain step appends nothing to the id record
+    return run_steps(ctx, m, kv, STEP_PLAIN, eos, flags, n, s);
 }
 
 static int check_decode(pgv_llm* m, pgv_kv* kv, int steps, const char* who) {
@@ -1336,7 +1330,7 @@ extern "C" int pgv_llm_decode(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_
     beam_drop(kv);
     if (d_last != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_last, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_TRY(decode_steps(ctx, m, kv, -1, AM_INC_POS, 1, s));
-    if (d_logits) PGV_HIP(hipMemcpyAsync(d_logits, kv->logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
+    if (d_logits) PGV_HIP(hipMemcpyAsync(d_logits, kv->sc.logits, (size_t)B * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
     if (d_next) PGV_HIP(hipMemcpyAsync(d_next, kv->d_cur, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
@@ -1350,7 +1344,7 @@ static int decode_run(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_fir
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
     if (run) kv->run = *run;
     PGV_TRY(decode_steps(ctx, m, kv, eos_id, AM_INC_POS | AM_RECORD | (run ? AM_SAMPLE : 0), n, s));
-    kv->lp_steps = kv->lp_on ? n : -1;
+    kv->lp.steps = kv->lp.on ? n : -1;
     PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)n * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)n * 4, B, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
@@ -1452,10 +1446,9 @@ extern "C" int pgv_beam_begin(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const pgv_be
     PGV_CHECK(ctx && m && kv, "pgv_beam_begin: null argument");
     PGV_CHECK(kv->llm == m, "pgv_beam_begin: kv cache belongs to another model");
     PGV_TRY(beam_check_config("pgv_beam_begin", cfg, m->cfg.vocab));
-    PGV_TRY(guidance_refuses(kv, "pgv_beam_begin"));
+    PGV_TRY(kv_allows(kv, KV_BEAM_BEGIN, "pgv_beam_begin"));
     if (kv->active < 1) { pgv_set_error("pgv_beam_begin: no live group in this cache (run pgv_llm_prefill first)"); return PGV_ESTATE; }
-    if (kv->ban_on) { pgv_set_error("pgv_beam_begin: logit bans are set on this cache (pgv_kv_set_bans); the beam pick applies no logits processor"); return PGV_ESTATE; }
-    if (kv->al_on) { pgv_set_error("pgv_beam_begin: a token automaton is set on this cache (pgv_kv_set_allowed); the beam pick applies no logits processor"); return PGV_ESTATE; }
+    PGV_TRY(kv_allows(kv, KV_BEAM_BEGIN, "pgv_beam_begin", 1));
     const int P = kv->active, K = cfg->beams, N = cfg->max_new_tokens, B = kv->B;
     PGV_CHECK((long long)P * K <= B, "pgv_beam_begin: %d prompts x %d beams exceed the %d sequences the cache was created with", P, K, B);
     PGV_CHECK(N <= kv->max_seq, "pgv_beam_begin: max_new_tokens %d exceeds the cache's %d positions", N, kv->max_seq);
@@ -1463,20 +1456,19 @@ extern "C" int pgv_beam_begin(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const pgv_be
         PGV_CHECK(kv->h_len[p] + N - 1 <= kv->max_seq, "pgv_beam_begin: sequence %d would grow to %d tokens (cache holds %d)", p, kv->h_len[p] + N - 1, kv->max_seq);
     hipStream_t s = (hipStream_t)stream;
     const size_t SW = PGV_BEAM_STATE_WORDS(8);
-    if (!kv->bm_blob) {
+    if (!kv->beam.blob.p) {
         size_t off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
         const size_t o_state = take((size_t)B * SW * 4), o_map = take((size_t)B * 4), o_row0 = take((size_t)B * 4), o_t = take((size_t)B * 4), o_prm = take(sizeof(BeamParams)),
                      o_den = take((size_t)kv->max_seq * 4), o_hist = take((size_t)2 * kv->max_seq * B * 4);
-        hipError_t e = hipMalloc((void**)&kv->bm_blob, off);
-        if (e != hipSuccess) { kv->bm_blob = nullptr; pgv_set_error("pgv_beam_begin: hipMalloc(%zu KiB): %s", off >> 10, hipGetErrorString(e)); return PGV_ENOMEM; }
-        char* b = kv->bm_blob;
-        kv->bm_state = (unsigned*)(b + o_state); kv->bm_map = (int*)(b + o_map); kv->bm_row0 = (int*)(b + o_row0); kv->bm_t = (int*)(b + o_t);
-        kv->bm_prm = (BeamParams*)(b + o_prm); kv->bm_denom = (float*)(b + o_den); kv->bm_hist = (int*)(b + o_hist);
+        PGV_TRY(kv->beam.blob.alloc("pgv_beam_begin", off));
+        char* b = kv->beam.blob.p;
+        kv->beam.state = (unsigned*)(b + o_state); kv->beam.map = (int*)(b + o_map); kv->beam.row0 = (int*)(b + o_row0); kv->beam.t = (int*)(b + o_t);
+        kv->beam.prm = (BeamParams*)(b + o_prm); kv->beam.denom = (float*)(b + o_den); kv->beam.hist = (int*)(b + o_hist);
     }
     // host staging: state words of the P prompts | row0 [P] | parameters | denom [N]
     const int S = PGV_BEAM_STATE_WORDS(K);
-    std::vector<unsigned>& st = kv->bm_stage;
+    std::vector<unsigned>& st = kv->beam.stage;
     st.assign((size_t)P * S + P + 4 + N, 0u);
     auto fbits = [](float f) { unsigned u; memcpy(&u, &f, 4); return u; };
     for (int p = 0; p < P; ++p) {
@@ -1492,23 +1484,23 @@ extern "C" int pgv_beam_begin(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const pgv_be
         std::vector<int32_t> counts((size_t)P, K);
         PGV_TRY(pgv_kv_fork(ctx, m, kv, counts.data(), P, stream));
     }
-    PGV_HIP(hipMemcpyAsync(kv->bm_state, st.data(), (size_t)P * S * 4, hipMemcpyHostToDevice, s));
-    PGV_HIP(hipMemcpyAsync(kv->bm_row0, st.data() + (size_t)P * S, (size_t)P * 4, hipMemcpyHostToDevice, s));
-    PGV_HIP(hipMemcpyAsync(kv->bm_prm, hp, sizeof(BeamParams), hipMemcpyHostToDevice, s));
-    PGV_HIP(hipMemcpyAsync(kv->bm_denom, hp + 4, (size_t)N * 4, hipMemcpyHostToDevice, s));
-    PGV_HIP(hipMemsetAsync(kv->bm_t, 0, (size_t)B * 4, s));
-    kv->bm_K = K; kv->bm_P = P; kv->bm_N = N; kv->bm_steps = 0;
+    PGV_HIP(hipMemcpyAsync(kv->beam.state, st.data(), (size_t)P * S * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->beam.row0, st.data() + (size_t)P * S, (size_t)P * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->beam.prm, hp, sizeof(BeamParams), hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->beam.denom, hp + 4, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemsetAsync(kv->beam.t, 0, (size_t)B * 4, s));
+    kv->beam.K = K; kv->beam.P = P; kv->beam.N = N; kv->beam.steps = 0;
     // the first pick, on the logits of the prefill (pgv_kv_fork copied the row of every prompt to its K slots); nothing to gather yet
     int rc = beam_pick_and_gather(ctx, kv, false, s);
     if (rc == PGV_OK) { hipError_t e = hipGetLastError(); if (e != hipSuccess) { pgv_set_error("pgv_beam_begin: %s", hipGetErrorString(e)); rc = PGV_EHIP; } }
     if (rc != PGV_OK) { beam_drop(kv); return rc; }
-    kv->bm_steps = 1;
+    kv->beam.steps = 1;
     return PGV_OK;
 }
 
 static int beam_live(const pgv_kv* kv, const char* who) {
     PGV_CHECK(kv != nullptr, "%s: null cache", who);
-    if (kv->bm_K < 1 || kv->active != kv->bm_P * kv->bm_K) { pgv_set_error("%s: no beam run on this cache (pgv_beam_begin starts one; any other call that moves its slots ends it)", who); return PGV_ESTATE; }
+    if (kv->beam.K < 1 || kv->active != kv->beam.P * kv->beam.K) { pgv_set_error("%s: no beam run on this cache (pgv_beam_begin starts one; any other call that moves its slots ends it)", who); return PGV_ESTATE; }
     return PGV_OK;
 }
 
@@ -1517,9 +1509,9 @@ extern "C" int pgv_llm_decode_beam(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int n, 
     PGV_CHECK(n >= 1, "pgv_llm_decode_beam: n must be positive");
     PGV_TRY(check_decode(m, kv, n, "pgv_llm_decode_beam"));
     PGV_TRY(beam_live(kv, "pgv_llm_decode_beam"));
-    PGV_CHECK(kv->bm_steps + n <= kv->bm_N, "pgv_llm_decode_beam: %d picks done + %d steps exceed max_new_tokens %d", kv->bm_steps, n, kv->bm_N);
+    PGV_CHECK(kv->beam.steps + n <= kv->beam.N, "pgv_llm_decode_beam: %d picks done + %d steps exceed max_new_tokens %d", kv->beam.steps, n, kv->beam.N);
     PGV_TRY(decode_steps(ctx, m, kv, -1, AM_INC_POS | AM_BEAM, n, (hipStream_t)stream));
-    kv->bm_steps += n;
+    kv->beam.steps += n;
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
@@ -1527,24 +1519,24 @@ extern "C" int pgv_llm_decode_beam(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int n, 
 extern "C" int pgv_beam_open(pgv_kv* kv, int32_t* h_open, void* stream) {
     PGV_TRY(beam_live(kv, "pgv_beam_open"));
     PGV_CHECK(h_open != nullptr, "pgv_beam_open: null argument");
-    const int K = kv->bm_K, S = PGV_BEAM_STATE_WORDS(K);
-    PGV_HIP(hipMemcpy2DAsync(h_open, 4, kv->bm_state + 6 * K + 1, (size_t)S * 4, 4, kv->bm_P, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    const int K = kv->beam.K, S = PGV_BEAM_STATE_WORDS(K);
+    PGV_HIP(hipMemcpy2DAsync(h_open, 4, kv->beam.state + 6 * K + 1, (size_t)S * 4, 4, kv->beam.P, hipMemcpyDeviceToHost, (hipStream_t)stream));
     PGV_HIP(hipStreamSynchronize((hipStream_t)stream));
     return PGV_OK;
 }
 
 extern "C" int pgv_beam_result(pgv_kv* kv, int p, int rank, int32_t* h_tokens, int cap, int32_t* n_out, float* score_out, int32_t* finished_out, void* stream) {
     PGV_TRY(beam_live(kv, "pgv_beam_result"));
-    const int K = kv->bm_K, S = PGV_BEAM_STATE_WORDS(K);
-    PGV_CHECK(p >= 0 && p < kv->bm_P && rank >= 0 && rank < K, "pgv_beam_result: prompt %d / rank %d outside the run's %d prompts x %d beams", p, rank, kv->bm_P, K);
+    const int K = kv->beam.K, S = PGV_BEAM_STATE_WORDS(K);
+    PGV_CHECK(p >= 0 && p < kv->beam.P && rank >= 0 && rank < K, "pgv_beam_result: prompt %d / rank %d outside the run's %d prompts x %d beams", p, rank, kv->beam.P, K);
     hipStream_t s = (hipStream_t)stream;
     std::vector<unsigned> st((size_t)S);
-    PGV_HIP(hipMemcpyAsync(st.data(), kv->bm_state + (size_t)p * S, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+    PGV_HIP(hipMemcpyAsync(st.data(), kv->beam.state + (size_t)p * S, (size_t)S * 4, hipMemcpyDeviceToHost, s));
     PGV_HIP(hipStreamSynchronize(s));
     float score; memcpy(&score, &st[K + rank], 4);
     const int n = (int)st[2 * K + rank], flag = (int)st[5 * K + rank];
     int par = (int)st[3 * K + rank];
-    PGV_CHECK(n >= 0 && n <= kv->bm_steps, "pgv_beam_result: the state holds a hypothesis of %d tokens after %d picks", n, kv->bm_steps);
+    PGV_CHECK(n >= 0 && n <= kv->beam.steps, "pgv_beam_result: the state holds a hypothesis of %d tokens after %d picks", n, kv->beam.steps);
     if (n_out) *n_out = n;
     if (score_out) *score_out = score;
     if (finished_out) *finished_out = flag;
@@ -1555,8 +1547,8 @@ extern "C" int pgv_beam_result(pgv_kv* kv, int p, int rank, int32_t* h_tokens, i
     // the tokens before the last: back through the parents of picks n - 2 .. 0 (the group's K columns of the history)
     std::vector<int> hist((size_t)2 * (n - 1) * K);
     const size_t pitch = (size_t)kv->B * 4;
-    PGV_HIP(hipMemcpy2DAsync(hist.data(), (size_t)K * 4, kv->bm_hist + p * K, pitch, (size_t)K * 4, n - 1, hipMemcpyDeviceToHost, s));
-    PGV_HIP(hipMemcpy2DAsync(hist.data() + (size_t)(n - 1) * K, (size_t)K * 4, kv->bm_hist + (size_t)kv->max_seq * kv->B + p * K, pitch, (size_t)K * 4, n - 1, hipMemcpyDeviceToHost, s));
+    PGV_HIP(hipMemcpy2DAsync(hist.data(), (size_t)K * 4, kv->beam.hist + p * K, pitch, (size_t)K * 4, n - 1, hipMemcpyDeviceToHost, s));
+    PGV_HIP(hipMemcpy2DAsync(hist.data() + (size_t)(n - 1) * K, (size_t)K * 4, kv->beam.hist + (size_t)kv->max_seq * kv->B + p * K, pitch, (size_t)K * 4, n - 1, hipMemcpyDeviceToHost, s));
     PGV_HIP(hipStreamSynchronize(s));
     for (int u = n - 2; u >= 0; --u) {
         PGV_CHECK(par >= 0 && par < K, "pgv_beam_result: parent %d outside the group at pick %d", par, u + 1);
@@ -1598,63 +1590,61 @@ extern "C" int pgv_beam_pick_logits(pgv_ctx* ctx, const float* d_logits, int V, 
 extern "C" int pgv_kv_set_lookup(pgv_kv* kv, int D, int n) {
     PGV_CHECK(kv != nullptr, "pgv_kv_set_lookup: null cache");
     PGV_CHECK(D >= 0 && D <= 15, "pgv_kv_set_lookup: %d draft rows per slot outside [0,15]", D);
-    if (D == 0) { kv->lk_D = 0; kv->lk_valid = false; return PGV_OK; }
-    PGV_TRY(guidance_refuses(kv, "pgv_kv_set_lookup"));
-    if (kv->al_on) { pgv_set_error("pgv_kv_set_lookup: a token automaton is set on this cache (pgv_kv_set_allowed); lookup steps verify drafts against the unconstrained pick"); return PGV_ESTATE; }
+    if (D == 0) { kv->lookup.D = 0; kv->lookup.valid = false; return PGV_OK; }
+    PGV_TRY(kv_allows(kv, KV_SET_LOOKUP, "pgv_kv_set_lookup"));
     PGV_CHECK(n >= 1 && n <= 4, "pgv_kv_set_lookup: ngram size %d outside [1,4]", n);
     PGV_TRY(kv_ids_alloc(kv, "pgv_kv_set_lookup"));
-    if (!kv->lk_blob) {
+    if (!kv->lookup.blob.p) {
         // sized once for the most rows any setting can ask of this cache: the per-row decode buffers for R rows, then the lookup ints
         const size_t B = kv->B, R = kMaxBatch < kv->B * 16 ? kMaxBatch : kv->B * 16;
         size_t off = 0;
         auto take = [&](size_t bytes) { size_t o = off; off += pgv_align(bytes); return o; };
         const ScratchLayout so = scratch_layout(kv->llm, R, take);
         const size_t o_ints = take((5 * R + 3 * B + 1 + B * (size_t)kv->max_seq) * 4);
-        char* b = nullptr;
-        hipError_t e = hipMalloc((void**)&b, off);
-        if (e != hipSuccess) { pgv_set_error("pgv_kv_set_lookup: hipMalloc(%zu MiB): %s", off >> 20, hipGetErrorString(e)); return PGV_ENOMEM; }
-        e = hipMemset(b, 0, off);                 // beyond scratch_clear: rows no step has written yet are read by the GEMVs of a step with absent rows
-        if (e != hipSuccess) { (void)hipFree(b); pgv_set_error("pgv_kv_set_lookup: memset: %s", hipGetErrorString(e)); return PGV_EHIP; }
-        kv->lk = scratch_bind(b, so, kv->llm);
+        PGV_TRY(kv->lookup.blob.alloc("pgv_kv_set_lookup", off, 20));
+        char* b = kv->lookup.blob.p;
+        const hipError_t e = hipMemset(b, 0, off);       // beyond scratch_clear: rows no step has written yet are read by the GEMVs of a step with absent rows
+        if (e != hipSuccess) { kv->lookup.blob.drop(); pgv_set_error("pgv_kv_set_lookup: memset: %s", hipGetErrorString(e)); return PGV_EHIP; }
+        kv->lookup.sc = scratch_bind(b, so, kv->llm);
         int* ints = (int*)(b + o_ints);
-        kv->lk_slot = ints; kv->lk_j = ints + R; kv->lk_tok = ints + 2 * R; kv->lk_t = ints + 3 * R;
-        kv->lk_u = (float*)(ints + 4 * R);
-        kv->lk_ndraft = ints + 5 * R; kv->lk_budget = kv->lk_ndraft + B; kv->lk_ubase = kv->lk_budget + B; kv->lk_k = kv->lk_ubase + B; kv->lk_counts = kv->lk_k + 1;
-        kv->lk_blob = b; kv->lk_rows = (int)R;
+        kv->lookup.slot = ints; kv->lookup.j = ints + R; kv->lookup.tok = ints + 2 * R; kv->lookup.t = ints + 3 * R;
+        kv->lookup.u = (float*)(ints + 4 * R);
+        kv->lookup.ndraft = ints + 5 * R; kv->lookup.budget = kv->lookup.ndraft + B; kv->lookup.ubase = kv->lookup.budget + B; kv->lookup.k = kv->lookup.ubase + B; kv->lookup.counts = kv->lookup.k + 1;
+        kv->lookup.rows = (int)R;
     }
-    kv->lk_D = D; kv->lk_n = n;
+    kv->lookup.D = D; kv->lookup.n = n;
     return PGV_OK;
 }
 
-extern "C" int pgv_kv_lookup(const pgv_kv* kv) { return kv ? kv->lk_D : -1; }
+extern "C" int pgv_kv_lookup(const pgv_kv* kv) { return kv ? kv->lookup.D : -1; }
 
 // One prompt-lookup step over the live slots: draft -> row-wise trunk -> lm_head -> row-wise pick -> accept.  The pick is the arg-max of the lm_head
 // candidates, or with AM_SAMPLE the sampled pick with kv->run over the full logits of every row, fed the uniform the draft kernel gathered for the
 // row (pgv.h: u[u_base + step + j][b]).  Either pick writes the row's token and nothing else: the accept kernel keeps the slots' state.
 static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int flags, hipStream_t s) {
-    const int B = kv->active, R = B * (1 + kv->lk_D), V = m->cfg.vocab;
+    const int B = kv->active, R = B * (1 + kv->lookup.D), V = m->cfg.vocab;
     const bool sampled = flags & AM_SAMPLE;
     LookupArgs a;
-    a.D = kv->lk_D; a.n = kv->lk_n; a.eos = eos; a.max_seq = kv->max_seq;
+    a.D = kv->lookup.D; a.n = kv->lookup.n; a.eos = eos; a.max_seq = kv->max_seq;
     a.pos = kv->d_pos; a.cur = kv->d_cur; a.step = kv->d_step; a.done = kv->d_done; a.hist = kv->d_hist; a.hist_stride = kv->max_seq;
-    a.rec = kv->ban_ids; a.budget = kv->lk_budget;
-    a.tok = kv->lk_tok; a.row_slot = kv->lk_slot; a.row_j = kv->lk_j; a.n_draft = kv->lk_ndraft; a.t = kv->lk_t;
-    a.counts = kv->lk_counts; a.counts_stride = kv->B; a.k = kv->lk_k;
+    a.rec = kv->ids.ids; a.budget = kv->lookup.budget;
+    a.tok = kv->lookup.tok; a.row_slot = kv->lookup.slot; a.row_j = kv->lookup.j; a.n_draft = kv->lookup.ndraft; a.t = kv->lookup.t;
+    a.counts = kv->lookup.counts; a.counts_stride = kv->B; a.k = kv->lookup.k;
     if (sampled) {
-        a.u = kv->d_u; a.u_stride = B; a.u_base = kv->lk_ubase; a.u_row = kv->lk_u;
+        a.u = kv->d_u; a.u_stride = B; a.u_base = kv->lookup.ubase; a.u_row = kv->lookup.u;
         // a plain sampled step marks the token it returns in the slot's seen-set in the instantiations that carry the set (pgv_launch_sample)
         if (kv->run.filtered() || kv->run.top_p < 1.f) { a.seen = kv->d_seen; a.seen_words = kv->seen_words; a.vocab = V; }
     }
     pgv_prof_begin(ctx, 6, s);
     PGV_TRY(pgv_launch_lookup_draft(a, B, s));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
-    RowMap rm; rm.d_slot = kv->lk_slot; rm.d_j = kv->lk_j;
+    RowMap rm; rm.d_slot = kv->lookup.slot; rm.d_j = kv->lookup.j;
     int nparts = 0;
-    PGV_TRY(decode_trunk(ctx, m, kv, kv->lk, kv->lk_tok, R, rm, s, &nparts));
-    PGV_TRY(lm_head_rows(ctx, m, kv->lk, R, !sampled, s, nparts));
+    PGV_TRY(decode_trunk(ctx, m, kv, kv->lookup.sc, kv->lookup.tok, R, rm, s, &nparts));
+    PGV_TRY(lm_head_rows(ctx, m, kv->lookup.sc, R, !sampled, s, nparts));
     pgv_prof_begin(ctx, 6, s);
-    if (sampled) PGV_TRY(pgv_launch_sample(kv->lk.logits, V, R, kv->run, kv->lk_u, R, false, PickState{kv->lk_t}, s));
-    else PGV_TRY(pgv_launch_argmax_parts(kv->lk.amax_val, kv->lk.amax_idx, (V + 15) / 16, kv->lk.amax_ts, V, R, PickState{kv->lk_t}, s));
+    if (sampled) PGV_TRY(pgv_launch_sample(kv->lookup.sc.logits, V, R, kv->run, kv->lookup.u, R, false, PickState{kv->lookup.t}, s));
+    else PGV_TRY(pgv_launch_argmax_parts(kv->lookup.sc.amax_val, kv->lookup.sc.amax_idx, (V + 15) / 16, kv->lookup.sc.amax_ts, V, R, PickState{kv->lookup.t}, s));
     PGV_TRY(pgv_launch_lookup_accept(a, B, s));
     pgv_prof_end(ctx, 6, s, 0.0, 0.0);
     return PGV_OK;
@@ -1663,16 +1653,12 @@ static int lookup_enqueue(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, int eos, int fla
 // what both lookup entries refuse, before any device work
 static int check_lookup_run(pgv_llm* m, pgv_kv* kv, int steps, int eos_id, const int32_t* h_budget, const char* who, const char* verifies) {
     PGV_TRY(check_decode(m, kv, 0, who));
-    PGV_TRY(guidance_refuses(kv, who));
-    const int B = kv->active, D = kv->lk_D, W = 1 + D;
+    PGV_TRY(kv_allows(kv, KV_LOOKUP_RUN, who));
+    const int B = kv->active, D = kv->lookup.D, W = 1 + D;
     if (D < 1) { pgv_set_error("%s: lookup is off on this cache (pgv_kv_set_lookup)", who); return PGV_ESTATE; }
-    if (!kv->lk_valid) { pgv_set_error("%s: the cache's id record does not cover its sequences: set pgv_kv_set_lookup before pgv_llm_prefill and step with pgv_llm_decode_lookup only", who); return PGV_ESTATE; }
-    if (kv->warpers.penalty != 1.f) { pgv_set_error("%s: a repetition penalty is set on this cache (pgv_kv_set_warpers); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
-    if (kv->ban_on) { pgv_set_error("%s: logit bans are set on this cache (pgv_kv_set_bans); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
-    if (kv->al_on) { pgv_set_error("%s: a token automaton is set on this cache (pgv_kv_set_allowed); lookup steps verify %s", who, verifies); return PGV_ESTATE; }
-    if (kv->lp_on) { pgv_set_error("%s: log-probabilities are on (pgv_kv_set_logprobs); lookup steps record none", who); return PGV_ESTATE; }
-    if (kv->bm_K > 0) { pgv_set_error("%s: a beam run is in flight on this cache", who); return PGV_ESTATE; }
-    PGV_CHECK(B * W <= kv->lk_rows && B * W <= kMaxBatch, "%s: %d sequences x %d rows exceed the %d rows of a step", who, B, W, kv->lk_rows < kMaxBatch ? kv->lk_rows : kMaxBatch);
+    if (!kv->lookup.valid) { pgv_set_error("%s: the cache's id record does not cover its sequences: set pgv_kv_set_lookup before pgv_llm_prefill and step with pgv_llm_decode_lookup only", who); return PGV_ESTATE; }
+    PGV_TRY(kv_allows(kv, KV_LOOKUP_RUN, who, 1, verifies));
+    PGV_CHECK(B * W <= kv->lookup.rows && B * W <= kMaxBatch, "%s: %d sequences x %d rows exceed the %d rows of a step", who, B, W, kv->lookup.rows < kMaxBatch ? kv->lookup.rows : kMaxBatch);
     PGV_CHECK(steps >= 1 && steps <= kv->max_seq, "%s: %d steps outside [1,%d]", who, steps, kv->max_seq);
     PGV_CHECK(eos_id < m->cfg.vocab, "%s: eos_id %d outside the vocabulary (%d)", who, eos_id, m->cfg.vocab);
     for (int b = 0; b < B; ++b)
@@ -1685,39 +1671,26 @@ static int check_lookup_run(pgv_llm* m, pgv_kv* kv, int steps, int eos_id, const
 // (copied into the cache's) at the rows h_u_base counts from.
 static int lookup_run(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* d_first, int steps, int eos_id, const int32_t* h_budget, const int32_t* h_u_base,
                       const PickParams* run, const float* d_u, int u_rows, int32_t* d_tokens, int32_t* d_counts, hipStream_t s) {
-    const int B = kv->active, W = 1 + kv->lk_D;
+    const int B = kv->active, W = 1 + kv->lookup.D;
     const int flags = AM_INC_POS | AM_RECORD | (run ? AM_SAMPLE : 0);
-    PGV_HIP(hipStreamSynchronize(s));             // an earlier call's copy of the staging may still be in flight
-    kv->lk_stage.assign(h_budget, h_budget + B);
-    if (run) kv->lk_stage.insert(kv->lk_stage.end(), h_u_base, h_u_base + B);
-    PGV_HIP(hipMemcpyAsync(kv->lk_budget, kv->lk_stage.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipStreamSynchronize(s));             // an earlier call's copy of the staging may still be pending
+    kv->lookup.stage.assign(h_budget, h_budget + B);
+    if (run) kv->lookup.stage.insert(kv->lookup.stage.end(), h_u_base, h_u_base + B);
+    PGV_HIP(hipMemcpyAsync(kv->lookup.budget, kv->lookup.stage.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
     if (run) {
-        PGV_HIP(hipMemcpyAsync(kv->lk_ubase, kv->lk_stage.data() + B, (size_t)B * 4, hipMemcpyHostToDevice, s));
+        PGV_HIP(hipMemcpyAsync(kv->lookup.ubase, kv->lookup.stage.data() + B, (size_t)B * 4, hipMemcpyHostToDevice, s));
         PGV_HIP(hipMemcpyAsync(kv->d_u, d_u, (size_t)u_rows * B * 4, hipMemcpyDeviceToDevice, s));      // u_rows <= max_seq (checked by the entry)
         kv->run = *run;
     }
     if (d_first && d_first != kv->d_cur) PGV_HIP(hipMemcpyAsync(kv->d_cur, d_first, (size_t)B * 4, hipMemcpyDeviceToDevice, s));      // null: the cache's current tokens
     PGV_HIP(hipMemsetAsync(kv->d_step, 0, (size_t)kv->B * 4, s));
-    PGV_HIP(hipMemsetAsync(kv->lk_k, 0, 4, s));
-    PGV_HIP(hipMemsetAsync(kv->lk.dattn_ticket, 0, (size_t)B * W * m->cfg.heads * sizeof(unsigned), s));
-    bool& warmed = run ? kv->lk_warmed_s : kv->lk_warmed;
-    for (int n = steps; n > 0;) {
-        int k = 1;
-        if (ctx->prof || !graphs_enabled() || !warmed) {
-            warmed = true;
-            PGV_TRY(lookup_enqueue(ctx, m, kv, eos_id, flags, s));
-        } else if (n >= kGraphSteps) {
-            k = kGraphSteps;
-            PGV_TRY(decode_graph(ctx, m, kv, eos_id, flags, 1, kGraphSteps, s, true));
-        } else {
-            PGV_TRY(decode_graph(ctx, m, kv, eos_id, flags, 0, 1, s, true));
-        }
-        n -= k;
-    }
-    kv->lp_steps = -1;
+    PGV_HIP(hipMemsetAsync(kv->lookup.k, 0, 4, s));
+    PGV_HIP(hipMemsetAsync(kv->lookup.sc.dattn_ticket, 0, (size_t)B * W * m->cfg.heads * sizeof(unsigned), s));
+    PGV_TRY(run_steps(ctx, m, kv, run ? STEP_LOOKUP_SAMPLED : STEP_LOOKUP, eos_id, flags, steps, s));
+    kv->lp.steps = -1;
     const int cap = steps * W < kv->max_seq ? steps * W : kv->max_seq;
     PGV_HIP(hipMemcpy2DAsync(d_tokens, (size_t)steps * W * 4, kv->d_hist, (size_t)kv->max_seq * 4, (size_t)cap * 4, B, hipMemcpyDeviceToDevice, s));
-    PGV_HIP(hipMemcpy2DAsync(d_counts, (size_t)B * 4, kv->lk_counts, (size_t)kv->B * 4, (size_t)B * 4, steps, hipMemcpyDeviceToDevice, s));
+    PGV_HIP(hipMemcpy2DAsync(d_counts, (size_t)B * 4, kv->lookup.counts, (size_t)kv->B * 4, (size_t)B * 4, steps, hipMemcpyDeviceToDevice, s));
     // the lengths now live on the device only: one blocking copy makes h_len true again (the caller reads the tokens at this point anyway)
     PGV_HIP(hipMemcpyAsync(kv->h_len.data(), kv->d_pos, (size_t)B * 4, hipMemcpyDeviceToHost, s));
     PGV_HIP(hipStreamSynchronize(s));
@@ -1750,30 +1723,30 @@ extern "C" int pgv_llm_decode_lookup_sample(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv
 extern "C" int pgv_llm_decode_rows(pgv_ctx* ctx, pgv_llm* m, pgv_kv* kv, const int32_t* h_slots, const int32_t* d_tokens, int R, float* d_logits, void* stream) {
     PGV_CHECK(ctx && h_slots && d_tokens && d_logits, "pgv_llm_decode_rows: null argument");
     PGV_TRY(check_decode(m, kv, 0, "pgv_llm_decode_rows"));
-    if (kv->lk_D < 1) { pgv_set_error("pgv_llm_decode_rows: this cache has no row scratch (pgv_kv_set_lookup allocates it)"); return PGV_ESTATE; }
-    PGV_CHECK(R >= 1 && R <= kv->lk_rows, "pgv_llm_decode_rows: %d rows outside [1,%d]", R, kv->lk_rows);
+    if (kv->lookup.D < 1) { pgv_set_error("pgv_llm_decode_rows: this cache has no row scratch (pgv_kv_set_lookup allocates it)"); return PGV_ESTATE; }
+    PGV_CHECK(R >= 1 && R <= kv->lookup.rows, "pgv_llm_decode_rows: %d rows outside [1,%d]", R, kv->lookup.rows);
     // rows are listed per slot in order: row j of a slot's run sits at position h_len + j
-    std::vector<int>& map = kv->lk_stage;
+    std::vector<int>& map = kv->lookup.stage;
     std::vector<int> count((size_t)kv->active, 0);
     map.assign((size_t)2 * R, 0);
     for (int r = 0; r < R; ++r) {
         const int b = h_slots[r];
         PGV_CHECK(b >= 0 && b < kv->active, "pgv_llm_decode_rows: slot %d of row %d outside the %d prefilled sequences", b, r, kv->active);
         PGV_CHECK(count[b] == 0 || h_slots[r - 1] == b, "pgv_llm_decode_rows: the rows of slot %d are not consecutive (row %d)", b, r);
-        PGV_CHECK(count[b] <= kv->lk_D, "pgv_llm_decode_rows: more than the %d rows per slot pgv_kv_set_lookup set (slot %d)", 1 + kv->lk_D, b);
+        PGV_CHECK(count[b] <= kv->lookup.D, "pgv_llm_decode_rows: more than the %d rows per slot pgv_kv_set_lookup set (slot %d)", 1 + kv->lookup.D, b);
         PGV_CHECK(kv->h_len[b] + count[b] < kv->max_seq, "pgv_llm_decode_rows: sequence %d would grow to %d tokens (cache holds %d)", b, kv->h_len[b] + count[b] + 1, kv->max_seq);
         map[r] = b; map[(size_t)R + r] = count[b]++;
     }
     hipStream_t s = (hipStream_t)stream;
-    PGV_HIP(hipStreamSynchronize(s));             // an earlier call's copy of the staging may still be in flight
-    PGV_HIP(hipMemcpyAsync(kv->lk_slot, map.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
-    PGV_HIP(hipMemcpyAsync(kv->lk_j, map.data() + R, (size_t)R * 4, hipMemcpyHostToDevice, s));
-    PGV_HIP(hipMemsetAsync(kv->lk.dattn_ticket, 0, (size_t)R * m->cfg.heads * sizeof(unsigned), s));      // as every prefill does for the cache's own
-    RowMap rm; rm.d_slot = kv->lk_slot; rm.d_j = kv->lk_j; rm.h_slot = map.data(); rm.h_j = map.data() + R;
+    PGV_HIP(hipStreamSynchronize(s));             // an earlier call's copy of the staging may still be pending
+    PGV_HIP(hipMemcpyAsync(kv->lookup.slot, map.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemcpyAsync(kv->lookup.j, map.data() + R, (size_t)R * 4, hipMemcpyHostToDevice, s));
+    PGV_HIP(hipMemsetAsync(kv->lookup.sc.dattn_ticket, 0, (size_t)R * m->cfg.heads * sizeof(unsigned), s));      // as every prefill does for the cache's own
+    RowMap rm; rm.d_slot = kv->lookup.slot; rm.d_j = kv->lookup.j; rm.h_slot = map.data(); rm.h_j = map.data() + R;
     int nparts = 0;
-    PGV_TRY(decode_trunk(ctx, m, kv, kv->lk, d_tokens, R, rm, s, &nparts));
-    PGV_TRY(lm_head_rows(ctx, m, kv->lk, R, false, s, nparts));
-    PGV_HIP(hipMemcpyAsync(d_logits, kv->lk.logits, (size_t)R * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
+    PGV_TRY(decode_trunk(ctx, m, kv, kv->lookup.sc, d_tokens, R, rm, s, &nparts));
+    PGV_TRY(lm_head_rows(ctx, m, kv->lookup.sc, R, false, s, nparts));
+    PGV_HIP(hipMemcpyAsync(d_logits, kv->lookup.sc.logits, (size_t)R * m->cfg.vocab * 4, hipMemcpyDeviceToDevice, s));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
